@@ -14,7 +14,10 @@ handle (tgp_create_multi: RCCL inside the library); under the driver's torchrun 
 (`--scaling weak` keeps --T points per GPU instead; `--workload/--T` override the series).
 `--workload cfg5` runs BASELINE config 5 (Separable space-time, 256 spatial points, dense d = 768 / p = 256 recursion on the
 fp64 MFMA kernels; sequential in time: N > 1 means N independent replicas).
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0). A plain run does only what that line's headline needs: set-up, W warm-up steps, the K timed steps.
+`--full` adds everything else the bench measures: per-kernel hipEvent profiles and rooflines, the other engines, layouts and
+configurations, the CPU baselines, the single-GPU reference of N > 1. `--dump-outputs DIR` writes what the last timed step
+returned (logpdf; posterior mean and variance, a fixed seeded sample of them at the default T) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -472,6 +475,32 @@ def valu_utilisation(prof, d, layout):
 
 MFMA_F64_PEAK_TFS = 78.6     # MI355X datasheet fp64 matrix peak; v_mfma_f64_16x16x4_f64 measured at 64 cycles / SIMD = 77.7 TF/s (scripts/ubench_mfma_f64.hip)
 
+# --dump-outputs: a per-step output longer than this is written as this many elements at fixed, seeded positions (2 x 8 MB for mean, var)
+DUMP_SAMPLE = 1 << 20
+
+
+def dump_sample(T, parts):
+    """The --dump-outputs sample of a length-T output held as segments [(offset, device tensor or host array), ...]: the elements at
+    DUMP_SAMPLE positions drawn once from a fixed seed (all T of them when T <= DUMP_SAMPLE), in order, as float64 on the host.
+    Segments that hold none of the positions contribute an empty array (a rank of a sharded series)."""
+    idx = np.arange(T) if T <= DUMP_SAMPLE else np.sort(np.random.default_rng(20240607).choice(T, DUMP_SAMPLE, replace=False))
+    vals = []
+    for lo, a in parts:
+        sel = idx[(idx >= lo) & (idx < lo + a.shape[0])] - lo
+        if hasattr(a, "index_select"):
+            import torch
+            vals.append(a.index_select(0, torch.from_numpy(sel).to(a.device)).cpu().numpy())
+        else:
+            vals.append(np.asarray(a)[sel])
+    return np.concatenate(vals).astype(np.float64)
+
+
+def write_outputs(dirname, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy in float64."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(np.atleast_1d(a), dtype=np.float64))
+
 
 def respawn_under_torchrun(n):
     """`python bench.py --gpus N` as the driver calls it: become `python -m torch.distributed.run ... bench.py <same args>`."""
@@ -527,11 +556,14 @@ def run_cfg5(args, torch, tgp, world, rank, local, emit=True):
     if world > 1:
         dist.barrier()
     dt_s = time.perf_counter() - t0
-    hd.set_option(tgp._lib.OPT_PROFILE, 1)
-    hd.profile_reset()
-    tgp.logpdf(model, Y)
-    hd.set_option(tgp._lib.OPT_PROFILE, 0)
-    prof = hd.profile()
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, dict(logpdf=float(lp)))
+    if args.full:
+        hd.set_option(tgp._lib.OPT_PROFILE, 1)
+        hd.profile_reset()
+        tgp.logpdf(model, Y)
+        hd.set_option(tgp._lib.OPT_PROFILE, 0)
+        prof = hd.profile()
     if world > 1:
         tmax = torch.tensor([dt_s], dtype=torch.float64, device=f"cuda:{local}")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -539,11 +571,24 @@ def run_cfg5(args, torch, tgp, world, rank, local, emit=True):
     if rank != 0:
         return
     d, p = 3 * Nr, Nr
+    sec_per_step = dt_s / args.steps / T
+    out = dict(
+        metric="Kalman steps/sec (logpdf), separable space-time 256 spatial x T, dense d=768 p=256", value=world * T / (dt_s / args.steps),
+        unit="Kalman steps/s", n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=dt_s / args.steps * 1e3,
+        higher_is_better=True, scaling="weak", vs_baseline=None, dtype="f64", data="synthetic",
+        config=dict(workload=f"cfg5: Separable(SE, Matern52), 256 spatial points x RegularSpacing(0,0.01,T={T}), sigma2_obs=0.1, "
+                             f"ArrayStorage-equivalent dense model d=768 p=256; one logpdf pass per step; "
+                             + ("dense A / H products (the reference's arithmetic)" if args.dense_products else "A = I (x) A_t, H = I (x) H_t applied in sparse form"),
+                    T=T, d=d, p=p, parallelism=f"replicas x{world} (sequential in time: the dense path does not time-shard)",
+                    us_per_kalman_step=sec_per_step * 1e6, logpdf=lp))
+    if not args.full:
+        if emit:
+            print(json.dumps(out))
+        return out
     # algorithmic flops of the reference's dense step: predict 2 x 2 d^3, update 2 p d^2 + 2 p^2 d + p^3 / 3 + p^2 d + 2 p d^2
     flops = {"dk_gemm<A P>": 2.0 * d ** 3, "dk_gemm<(A P) A' + Q>": 2.0 * d ** 3, "dk_gemm<H Pp>": 2.0 * p * d * d,
              "dk_gemm<V H' + R>": 2.0 * p * p * d, "dk_chol": p ** 3 / 3.0, "dk_trsm": 1.0 * p * p * d, "dk_gemm<Pp - B'B>": 2.0 * p * d * d}
     step_flops = 2 * 2.0 * d ** 3 + 2.0 * p * d * d + 2.0 * p * p * d + p ** 3 / 3.0 + p * p * d + 2.0 * p * d * d
-    sec_per_step = dt_s / args.steps / T
     kernels = {kn: dict(avg_us=v["total_ms"] / max(1, v["calls"]) * 1e3, calls=v["calls"],
                         tflops=(flops[kn] / (v["total_ms"] / max(1, v["calls"]) * 1e-3) / 1e12) if kn in flops else None)
                for kn, v in prof.items()}
@@ -556,15 +601,7 @@ def run_cfg5(args, torch, tgp, world, rank, local, emit=True):
     # 0.364 GF counted on the device (SQ_INSTS_VALU_MFMA_MOPS_F64 x 512: profiles/r05_sq_counters_cfg5.txt); the dense-products run executes step_flops
     exec_flops = step_flops if args.dense_products else (2 * 2.0 * 3 * d * d + 2.0 * 3 * p * d + 2.0 * 3 * p * p + p ** 3 / 3.0 + 1.0 * p * p * d + 2.0 * p * d * d)
     ach_exec = exec_flops / sec_per_step / 1e12
-    out = dict(
-        metric="Kalman steps/sec (logpdf), separable space-time 256 spatial x T, dense d=768 p=256", value=world * T / (dt_s / args.steps),
-        unit="Kalman steps/s", n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=dt_s / args.steps * 1e3,
-        higher_is_better=True, scaling="weak", vs_baseline=None, dtype="f64", data="synthetic",
-        config=dict(workload=f"cfg5: Separable(SE, Matern52), 256 spatial points x RegularSpacing(0,0.01,T={T}), sigma2_obs=0.1, "
-                             f"ArrayStorage-equivalent dense model d=768 p=256; one logpdf pass per step; "
-                             + ("dense A / H products (the reference's arithmetic)" if args.dense_products else "A = I (x) A_t, H = I (x) H_t applied in sparse form"),
-                    T=T, d=d, p=p, parallelism=f"replicas x{world} (sequential in time: the dense path does not time-shard)",
-                    us_per_kalman_step=sec_per_step * 1e6, logpdf=lp),
+    out.update(
         roofline=dict(bound="mfma", kernel="whole time step (kernel chain)", achieved=ach, peak=MFMA_F64_PEAK_TFS, unit="TFLOP/s", frac=ach / MFMA_F64_PEAK_TFS,
                       traffic=None, algorithmic_flops_per_step=step_flops,
                       executed_flops_per_step=exec_flops, executed_achieved=ach_exec, executed_frac=ach_exec / MFMA_F64_PEAK_TFS,
@@ -702,7 +739,7 @@ def other_config_legs(args, torch, tgp, local):
         legs["wide_d9"] = dict(error=repr(ex))
     try:
         a5 = copy.copy(args)
-        a5.T, a5.steps, a5.warmup, a5.no_cpu_baseline, a5.dense_products = 2000, 1, 1, True, False
+        a5.T, a5.steps, a5.warmup, a5.no_cpu_baseline, a5.dense_products, a5.dump_outputs = 2000, 1, 1, True, False, None
         o5 = run_cfg5(a5, torch, tgp, 1, 0, local, emit=False)
         legs["cfg5"] = dict(workload=o5["config"]["workload"], T=2000, ms_per_step=o5["ms_per_step"], steps_per_s=o5["value"],
                             us_per_kalman_step=o5["config"]["us_per_kalman_step"], roofline=o5["roofline"],
@@ -747,18 +784,23 @@ def run_multi_inprocess(args):
     for dv in set(devices):
         torch.cuda.synchronize(dv)
     dt_s = time.perf_counter() - t0
-    ms.mh.set_option(tgp._lib.OPT_PROFILE, 1)
-    step()
-    ms.mh.set_option(tgp._lib.OPT_PROFILE, 0)
-    prof = ms.mh.rank_profile(0)
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, dict(logpdf=lp, mean=dump_sample(T, [(lo, m) for (lo, _), m in zip(ms.bounds, mean)]),
+                                              var=dump_sample(T, [(lo, v) for (lo, _), v in zip(ms.bounds, var)])))
     out = dict(metric="Kalman steps/sec (logpdf + posterior marginals), T=10^7 Matern32 d=3", value=T / (dt_s / args.steps), unit="Kalman steps/s",
                n_gpus=W, steps=args.steps, warmup=args.warmup, ms_per_step=dt_s / args.steps * 1e3, higher_is_better=True, scaling=args.scaling,
                vs_baseline=None, dtype="f64", data="synthetic",
                config=dict(workload=f"{'cfg4' if name == 'sum52_12_d4' else 'cfg2'}: {name}, RegularSpacing(0,0.1,T={T}), sigma2_obs=0.1, layout={args.layout}; per step: "
                                     "logpdf AND posterior marginals of the series (one combined call: tgp_multi_logpdf_and_posterior_marginals)",
                            T=T, T_per_gpu=T // W, d=d, layout=args.layout, devices=devices,
-                           parallelism=f"time-shard x{W} in ONE process (tgp_create_multi), {args.scaling}", ranks=W, backend=ms.transport, logpdf=lp),
-               kernels_rank0={kk: dict(avg_ms=v["total_ms"] / max(1, v["calls"]), calls=v["calls"]) for kk, v in prof.items()})
+                           parallelism=f"time-shard x{W} in ONE process (tgp_create_multi), {args.scaling}", ranks=W, backend=ms.transport, logpdf=lp))
+    if not args.full:
+        print(json.dumps(out))
+        return
+    ms.mh.set_option(tgp._lib.OPT_PROFILE, 1)
+    step()
+    ms.mh.set_option(tgp._lib.OPT_PROFILE, 0)
+    out["kernels_rank0"] = {kk: dict(avg_ms=v["total_ms"] / max(1, v["calls"]), calls=v["calls"]) for kk, v in ms.mh.rank_profile(0).items()}
     if not args.no_single_gpu_reference and args.scaling == "strong":
         try:
             full = lti_sde.build_lgssm(lti_sde.to_kernel(k), lti_sde.RegularSpacing(0.0, dt, T), s2, device=devices[0])
@@ -845,6 +887,10 @@ def main():
     ap.add_argument("--devices", default=None, help="in-process multi-GPU path: comma-separated device ordinals, one per rank (repeat one to share a GPU)")
     ap.add_argument("--engine-factory", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--no-bind", action="store_true", help="leave the process on whatever CPUs it was started on (A/B: tgp_bind_host_thread)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: per-kernel hipEvent profiles and rooflines, the other engines, "
+                    "layouts and configurations, the CPU baselines and the single-GPU reference of N > 1 (off: set-up, warm-up, the timed steps, the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned as "
+                    f"DIR/<name>.npy (float64; an output longer than {DUMP_SAMPLE} elements as a fixed, seeded sample of that many)")
     args = ap.parse_args()
     # the headline is T / (t_logpdf + t_post), the two calls the reference's API has (lti_sde.jl:60-68, posterior_lti_sde.jl:27-36)
     args.separate_calls = not args.combined_call
@@ -945,11 +991,59 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt_s = time.perf_counter() - t0
+    if world > 1:
+        tmax = torch.tensor([dt_s], dtype=torch.float64, device=f"cuda:{local}")
+        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+        dt_s = float(tmax.item())
+    if args.dump_outputs:
+        # (logpdf of the whole series; mean, var: this rank's segment -> rank 0)
+        lp, mean, var = last
+        mv = (dump_sample(T, [(seg[0], mean)]), dump_sample(T, [(seg[0], var)]))
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, mv)
+            mv = tuple(np.concatenate([p[i] for p in parts]) for i in (0, 1))
+        if rank == 0:
+            write_outputs(args.dump_outputs, dict(logpdf=float(lp), mean=mv[0], var=mv[1]))
+
+    def steady_steps():
+        # how many of the series' steps passes 2 / 3 of the last call ran in the mean-only form (TGP_OPT_STEADY; decided at run time, bit for bit)
+        import ctypes as _ct
+        st_fast, st_total = _ct.c_int64(0), _ct.c_int64(0)
+        hd.check(hd.lib.tgp_steady_steps(hd.h, _ct.byref(st_fast), _ct.byref(st_total)))
+        return int(st_fast.value), int(st_total.value)
+
+    mean_only, total = steady_steps()
+    out = dict(
+        metric="Kalman steps/sec (logpdf + posterior marginals), T=10^7 Matern32 d=3",
+        value=T / (dt_s / args.steps), unit="Kalman steps/s", n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=dt_s / args.steps * 1e3,
+        higher_is_better=True, scaling=args.scaling, vs_baseline=None, dtype="f64", data="synthetic",
+        config=dict(workload=f"{'cfg4' if (world > 1 and name == 'sum52_12_d4') else 'cfg2'}: {name}, RegularSpacing(0,0.1,T={T}), sigma2_obs=0.1, "
+                             f"layout={args.layout}; per step: logpdf AND posterior marginals of the series "
+                             + ("(the reference's two calls: logpdf(fx, y), then marginals(posterior(fx, y)(x)) -- value = T / (t_logpdf + t_post), SURVEY.md 8d)"
+                                if args.separate_calls else "(one combined call: tgp_logpdf_and_posterior_marginals)"),
+                    T=T, T_per_gpu=Tseg, d=d, calls=("separate" if args.separate_calls else "combined"),
+                    layout=args.layout, host_thread_bound_to_gpu_socket=bool(host_bound),
+                    parallelism=f"time-shard x{world} ({args.scaling}: {'T per GPU fixed' if args.scaling == 'weak' else 'total T fixed'})",
+                    ranks=world, backend=("rccl" if world > 1 else "none"), exchange=shard.transport,
+                    hip_graph_replays=int(hd.lib.tgp_graph_replays(hd.h)),
+                    stationary_covariance_steps=dict(
+                        mean_only=mean_only, total=total,
+                        note="steps served with the stationary gains: every step behind the head of n0 steps over which the filter covariance "
+                             "is iterated until it no longer changes (on the host, inside every timed call: tgp_steady_plan.hpp; nothing is carried "
+                             "over between calls). `with_five_launch_engine`: round 3's form of the same engine; `with_general_engine` / "
+                             "`with_full_steps`: the same steps on the general engine (--full)")))
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # per-kernel durations: the SAME K steps once more with every launch bracketed by hipEvents on the
     # handle's stream (kept out of the timed region above: two event records per launch slow the host
     # enqueue enough to open gaps between the ~20-300 us kernels).
@@ -994,10 +1088,8 @@ def main():
         fused = dict(value=T / dt_f, ms_per_step=dt_f * 1e3,
                      note="ONE tgp_logpdf_and_posterior_marginals call per step: the log marginal likelihood is a by-product of the filter the posterior "
                           "needs anyway (a convenience the reference's API does not have; rounds 1-4 quoted this as `value`)")
-    # how many of the series' steps passes 2 / 3 ran in the mean-only form (TGP_OPT_STEADY; decided at run time, bit for bit)
-    import ctypes as _ct
-    st_fast, st_total = _ct.c_int64(0), _ct.c_int64(0)
-    hd.check(hd.lib.tgp_steady_steps(hd.h, _ct.byref(st_fast), _ct.byref(st_total)))
+    mean_only, total = steady_steps()
+    out["config"]["stationary_covariance_steps"].update(mean_only=mean_only, total=total)
     prof = prof_all
     steady_engine = any(k.startswith("k_steady") for k in prof)
 
@@ -1024,7 +1116,7 @@ def main():
         return dict(value=T / (dt_n / args.steps), ms_per_step=dt_n / args.steps * 1e3)
 
     general, no_steady, five = None, None, None
-    if st_fast.value > 0 and args.layout == "lti":
+    if mean_only > 0 and args.layout == "lti":
         if any(k.startswith("k_steady_one") for k in prof):
             five = dict(timed_leg(2), note="TGP_OPT_STEADY = 2: round 3's form of the stationary-gain engine (set-up kernel, two passes over y, carry "
                                            "and reduction kernels: five launches)")
@@ -1035,14 +1127,9 @@ def main():
                                             "noise or missing data gets)")
         hd.set_option(tgp._lib.OPT_STEADY, 3)
     reuse = None
-    if world > 1:
-        tmax = torch.tensor([dt_s], dtype=torch.float64, device=f"cuda:{local}")
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        dt_s = float(tmax.item())
 
     if rank == 0:
-        ms_per_step = dt_s / args.steps * 1e3
-        value = T / (dt_s / args.steps)
+        value = out["value"]
         # roofline of the dominant kernel (by accumulated hipEvent time in the timed region)
         dom = max(prof.items(), key=lambda kv: kv[1]["total_ms"]) if prof else None
         lti = args.layout == "lti"
@@ -1103,32 +1190,13 @@ def main():
                            note="the logpdf call's ONE kernel: reads y once (8 B/step), writes nothing of size T; 80 MB per launch -- a launch this short "
                                 "is bound by its fp64 instruction stream and its ramps as much as by HBM (DESIGN 3.19)")
         net_of_bracket(roof_lp, 8 * Tseg)
-        out = dict(
-            metric="Kalman steps/sec (logpdf + posterior marginals), T=10^7 Matern32 d=3",
-            value=value, unit="Kalman steps/s", n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=ms_per_step,
-            higher_is_better=True, scaling=args.scaling, vs_baseline=None, dtype="f64", data="synthetic",
-            config=dict(workload=f"{'cfg4' if (world > 1 and name == 'sum52_12_d4') else 'cfg2'}: {name}, RegularSpacing(0,0.1,T={T}), sigma2_obs=0.1, "
-                                 f"layout={args.layout}; per step: logpdf AND posterior marginals of the series "
-                                 + ("(the reference's two calls: logpdf(fx, y), then marginals(posterior(fx, y)(x)) -- value = T / (t_logpdf + t_post), SURVEY.md 8d)"
-                                    if args.separate_calls else "(one combined call: tgp_logpdf_and_posterior_marginals)"),
-                        T=T, T_per_gpu=Tseg, d=d, calls=("separate" if args.separate_calls else "combined"),
-                        layout=args.layout, host_thread_bound_to_gpu_socket=bool(host_bound),
-                        parallelism=f"time-shard x{world} ({args.scaling}: {'T per GPU fixed' if args.scaling == 'weak' else 'total T fixed'})",
-                        ranks=world, backend=("rccl" if world > 1 else "none"), exchange=shard.transport,
-                        hip_graph_replays=int(hd.lib.tgp_graph_replays(hd.h)),
-                        stationary_covariance_steps=dict(
-                            mean_only=int(st_fast.value), total=int(st_total.value),
-                            note="steps served with the stationary gains: every step behind the head of n0 steps over which the filter covariance "
-                                 "is iterated until it no longer changes (on the host, inside every timed call: tgp_steady_plan.hpp; nothing is carried "
-                                 "over between calls). `with_five_launch_engine`: round 3's form of the same engine; `with_general_engine` / "
-                                 "`with_full_steps`: the same steps on the general engine"),
-                        pass1=("shared matrix parts (TGP_OPT_SHARED_PARTS): the observation-independent half of the chunk recursion is tabulated "
-                               "once per bound model -- on a side stream, launched by the second call, 1.4 ms at d = 3 -- and reused by later "
-                               "calls on the same model; the warm-up steps bind and warm the model, the timed steps reuse the table"
-                               if any("shared parts" in k for k in prof) else "general")),
-            roofline=roof,
-            kernels={k: dict(avg_ms=v["total_ms"] / max(1, v["calls"]), calls=v["calls"]) for k, v in prof.items()},
-        )
+        out["config"]["hip_graph_replays"] = int(hd.lib.tgp_graph_replays(hd.h))
+        out["config"]["pass1"] = ("shared matrix parts (TGP_OPT_SHARED_PARTS): the observation-independent half of the chunk recursion is tabulated "
+                                  "once per bound model -- on a side stream, launched by the second call, 1.4 ms at d = 3 -- and reused by later "
+                                  "calls on the same model; the warm-up steps bind and warm the model, the timed steps reuse the table"
+                                  if any("shared parts" in k for k in prof) else "general")
+        out["roofline"] = roof
+        out["kernels"] = {k: dict(avg_ms=v["total_ms"] / max(1, v["calls"]), calls=v["calls"]) for k, v in prof.items()}
         if roof_lp is not None:
             out["roofline_logpdf_kernel"] = roof_lp
         if fused is not None:

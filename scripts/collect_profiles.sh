@@ -17,12 +17,12 @@ case $CLASS in
   lti)
     WL=${1:-matern52_d3}; SUF=""; [ "$WL" != matern52_d3 ] && SUF="_$WL"
     OUT=$ROOT/gpurun_out/prof_${TAG}_lti$SUF; mkdir -p $OUT
-    B="python $ROOT/bench.py --workload $WL --no-cpu-baseline --no-general-leg ${@:2}"
+    B="python $ROOT/bench.py --full --workload $WL --no-cpu-baseline --no-general-leg ${@:2}"
     FULL="$B --steps 10 --warmup 2"; SHORT="$B --steps 3 --warmup 1" ;;
   per_step)
     WL=${1:-matern52_d3}; SUF=""; [ "$WL" != matern52_d3 ] && SUF="_$WL"
     OUT=$ROOT/gpurun_out/prof_${TAG}_per_step$SUF; mkdir -p $OUT
-    B="python $ROOT/bench.py --workload $WL --layout per_step --no-cpu-baseline --no-general-leg ${@:2}"
+    B="python $ROOT/bench.py --full --workload $WL --layout per_step --no-cpu-baseline --no-general-leg ${@:2}"
     FULL="$B --steps 6 --warmup 2"; SHORT="$B --steps 2 --warmup 1" ;;
   sweep)
     OUT=$ROOT/gpurun_out/prof_${TAG}_sweep; mkdir -p $OUT
@@ -34,8 +34,8 @@ case $CLASS in
   cfg5)
     T5=${1:-20000}
     OUT=$ROOT/gpurun_out/prof_${TAG}_cfg5; mkdir -p $OUT
-    FULL="python $ROOT/bench.py --workload cfg5 --T $T5 --steps 1 --warmup 1 --no-cpu-baseline"
-    SHORT="python $ROOT/bench.py --workload cfg5 --T 2000 --steps 1 --warmup 1 --no-cpu-baseline"
+    FULL="python $ROOT/bench.py --full --workload cfg5 --T $T5 --steps 1 --warmup 1 --no-cpu-baseline"
+    SHORT="python $ROOT/bench.py --full --workload cfg5 --T 2000 --steps 1 --warmup 1 --no-cpu-baseline"
     SQ="SQ_WAVES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_INSTS_MFMA" ;;
   *) echo "unknown class $CLASS"; exit 1 ;;
 esac

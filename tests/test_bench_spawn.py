@@ -39,3 +39,16 @@ def test_bench_weak_scaling_is_an_option():
     out = _run(2, ("--scaling", "weak", "--workload", "matern32_d2"))
     assert out["scaling"] == "weak" and out["config"]["workload"] == "matern32_d2"
     assert np.isfinite(out["value"]) and out["value"] > 0
+
+
+def test_dump_sample_is_fixed_and_independent_of_the_sharding():
+    """`--dump-outputs`: the sample of a long output is the same positions whichever segments hold it (one GPU, N ranks)"""
+    import bench
+    T = 3 * bench.DUMP_SAMPLE + 7
+    full = np.arange(T, dtype=np.float64)
+    one = bench.dump_sample(T, [(0, full)])
+    assert one.dtype == np.float64 and one.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(one) > 0)
+    cut = [0, 1000, T // 2, T]
+    assert np.array_equal(bench.dump_sample(T, [(lo, full[lo:hi]) for lo, hi in zip(cut[:-1], cut[1:])]), one)
+    assert np.array_equal(bench.dump_sample(T, [(0, full)]), one)
+    assert np.array_equal(bench.dump_sample(10, [(0, full[:10])]), full[:10])      # a short output: all of it

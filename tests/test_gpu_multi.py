@@ -147,13 +147,14 @@ def test_unsupported_models_are_refused():
 
 
 def test_bench_launched_directly_with_several_gpus_uses_the_in_library_handle():
-    """`python bench.py --gpus 2` without a torch.distributed environment: ONE process, tgp_create_multi (here both ranks on cuda:0)."""
+    """`python bench.py --gpus 2` without a torch.distributed environment: ONE process, tgp_create_multi (here both ranks on cuda:0);
+    `--full` adds the whole series on one GPU (`single_gpu_reference`)."""
     import json
     import os
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(U.ROOT, "bench.py"), "--gpus", "2", "--devices", "0,0", "--steps", "2", "--warmup", "1", "--T", "400000"]
+    cmd = [sys.executable, os.path.join(U.ROOT, "bench.py"), "--gpus", "2", "--devices", "0,0", "--steps", "2", "--warmup", "1", "--T", "400000", "--full"]
     res = subprocess.run(cmd, env=env, cwd=U.ROOT, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
