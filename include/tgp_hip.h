@@ -153,7 +153,7 @@ typedef struct tgp_handle tgp_handle;
 #define TGP_OPT_STREAM_MIN_T 18 /* series length from which the STREAMING kernels of the stationary-gain engine serve a call: persistent
                                    waves with ~7 us more fixed latency and 1.3 - 2.7 x the throughput of k_steady_one.  -1 (default): the measured
                                    crossovers (logpdf 5e6, posterior marginals 3e6 steps at d = 3); 0: always (the tests); a length: from there on */
-#define TGP_OPT_WIDE 19 /* 1 (default): logpdf of a Forward LTI model with 16 < d <= 63 and scalar observations on the stationary closed loop across the
+#define TGP_OPT_WIDE 19 /* 1 (default): logpdf (and tgp_logpdf_adjoint) of a Forward LTI model with 16 < d <= 63 and scalar observations on the stationary closed loop across the
                            chip (tgp_wide.hip: k_wide_lml); 0: the dense engine's sequential passes (the A/B of the tests) */
 #define TGP_OPT_TIMING 6 /* 1: record the hipEvents behind tgp_last_timing (off by default: ~30 us of host time per call) */
 #define TGP_OPT_FUSE_SCAN 4 /* 1 (default): the level-0 scan reduce / apply of the forward scan run inside the chunk kernels;
@@ -249,7 +249,9 @@ int tgp_logpdf_grad_sde(tgp_handle* h, const double* y, const uint8_t* missing, 
 
 /* ---- logpdf and its gradient with respect to the MODEL BLOCKS by one adjoint (reverse-time) pass -------------------
  * Forward LTI models (every block shared: the reference's Fill layout of RegularSpacing inputs, lti_sde.jl:148-160) with
- * one noise variance, scalar observations, no missing data, d <= 8 -- the models of the stationary-gain engine. One
+ * one noise variance, scalar observations, no missing data, d <= 8 -- the models of the stationary-gain engine -- and
+ * 8 < d <= 63 with a shared emission offset where the wide-state engine's plan applies (tgp_wide.hip; TGP_OPT_WIDE = 1 and no
+ * chunk engine requested: its forward kernel, the backward kernel in adjoint form, the sums on the f64 MFMA). One
  * forward and one backward mean recursion over the series (the cost of a posterior-marginals call, whatever the number
  * of hyper-parameters) leave the sums behind d logpdf / d (A, a, Q, H, h, R, x0m, x0P); the host finishes with the head's
  * steps and a reverse sweep through the ~n0 steps of the covariance recursion. The caller contracts the block gradients
@@ -257,7 +259,8 @@ int tgp_logpdf_grad_sde(tgp_handle* h, const double* y, const uint8_t* missing, 
  * gA, gQ, gx0P [d*d] column-major (gQ, gx0P symmetrised), ga, gH, gx0m [d], ghh, gR [1]; all host pointers.
  * Replaces Mooncake's reverse mode over the sequential loop (bench/single_output_gps.jl:149-156, test/gp/lti_sde.jl:203-206).
  * d <= 6 (TGP_OPT_STEADY = 3, the default): plan and head on the host, ONE kernel behind the head.
- * TGP_EUNSUPPORTED when the engine does not apply (use tgp_logpdf_grad). */
+ * 8 < d <= 63: device scratch of 2 T d + T doubles, kept by the handle.
+ * TGP_EUNSUPPORTED when no engine applies (use tgp_logpdf_grad). */
 int tgp_logpdf_adjoint(tgp_handle* h, const double* y, uint32_t flags, double* lml_out, double* gA, double* ga,
                        double* gQ, double* gH, double* ghh, double* gR, double* gx0m, double* gx0P);
 /* The plan of the stationary-gain engine's ONE-LAUNCH path (TGP_OPT_STEADY = 3, the default), a pure host function: what
@@ -305,6 +308,12 @@ int tgp_segment_logpdf_and_posterior_marginals(tgp_handle* h, int64_t T_total, i
 int tgp_adjoint_record_size(int d);
 int tgp_adjoint_finish(int d, const double* rec, const double* y_head, int64_t n_head, double* gA, double* ga, double* gQ,
                        double* gH, double* ghh, double* gR, double* gx0m, double* gx0P);
+/* ... for 1 <= d <= 63, the host half of the wide models' adjoint pass (csrc/tgp_wide_adjoint_host.hpp: the same algorithm, its d^3 work
+ * vectorised; the covariance recursion re-iterated from the record's model): rec_len = 3 d^2 + 8 d + 8 + d (d + 1) / 2 doubles in the
+ * same layout, whose head-tile word is ignored -- the head is head_steps long (<= n_head), the record's n0 the index of the settled gain.
+ * TGP_EINVAL: the record does not fit; TGP_EUNSUPPORTED: the CPU lacks AVX2 / FMA. */
+int tgp_adjoint_finish_wide(int d, const double* rec, int64_t rec_len, const double* y_head, int64_t n_head, int64_t head_steps,
+                            double* gA, double* ga, double* gQ, double* gH, double* ghh, double* gR, double* gx0m, double* gx0P);
 
 /* ---- _filter(model, y): lgssm.jl:171-187. m_out [T][d], P_out [T][d*d] (either may be NULL);
  *      lml_out (host, may be NULL) receives the log marginal likelihood as a by-product.

@@ -348,7 +348,8 @@ function logpdf_and_directional_derivatives(m::DeviceLGSSM{Forward}, y::Abstract
 end
 
 """`logpdf` and its gradient with respect to the packed model blocks by ONE adjoint pass (tgp_logpdf_adjoint: Forward models whose
-blocks are all shared, one noise variance, scalar outputs, no missing data, d <= 8) -- the pullback a ChainRules / Mooncake rule for
+blocks are all shared, one noise variance, scalar outputs, no missing data, d <= 8 -- or 8 < d <= 63 on the wide-state engine where its
+plan applies: products of kernels such as ApproxPeriodicKernel() * Matern32Kernel()) -- the pullback a ChainRules / Mooncake rule for
 `logpdf(::DeviceLGSSM, y)` needs: the rule returns `lml` and contracts the named tuple with the cotangent (the reference differentiates
 the sequential loop itself, bench/single_output_gps.jl:149-156). Matrices come back d x d (column-major, as Julia stores them)."""
 function logpdf_and_block_gradients(m::DeviceLGSSM{Forward}, y::AbstractVector{<:Real})

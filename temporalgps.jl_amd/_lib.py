@@ -58,6 +58,7 @@ _SIGS = {
     "tgp_segment_plan": (ctypes.c_int, [_vp, _i64, ctypes.c_int, _vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "tgp_segment_logpdf_and_posterior_marginals": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _dp]),
     "tgp_adjoint_finish": (ctypes.c_int, [ctypes.c_int, _vp, _vp, _i64] + [_vp] * 8),
+    "tgp_adjoint_finish_wide": (ctypes.c_int, [ctypes.c_int, _vp, _i64, _vp, _i64, _i64] + [_vp] * 8),
     "tgp_filter": (ctypes.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _dp]),
     "tgp_posterior": (ctypes.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "tgp_posterior_marginals": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _dp]),

@@ -99,6 +99,61 @@ static int adjoint_lti_call(tgp_handle* h, const double* y, uint32_t flags, doub
     return TGP_OK;
 }
 
+// The adjoint pass of a wide LTI model (8 < d <= 63, every block shared, one noise variance, no per-step emission offsets; tgp_wide::adjoint): the
+// wide-state engine's forward kernel, its backward kernel in the ADJ form and the sums k_wide_gram on the device, the head and the host half of the
+// gradient (tgp_wide_adjoint_host.hpp) on the host.  *served = false: the engine does not apply (nothing the caller must undo).
+static int wide_adjoint_call(tgp_handle* h, const double* y, uint32_t flags, double* lml_out, const tgp_adjoint::Out& o, bool* served) {
+    *served = false;
+    static const bool env_on = [] {
+        const char* s = std::getenv("TGP_WIDE");
+        return !(s && s[0] == '0');
+    }();
+    if (!env_on || !h->opt_wide || chunk_engine_requested(h) || h->widem.empty() || h->wide_ht != nullptr || y == nullptr || h->ordering != 0) return TGP_OK;
+    if (!h->wide) h->wide = tgp_wide::create();
+    const int d = h->d;
+    const size_t dd = (size_t)d * d;
+    const double* q = h->widem.data();
+    tgp_wide::ModelHost mh;
+    mh.d = d;
+    mh.A = q; mh.a = q + dd; mh.Q = q + dd + d; mh.H = q + 2 * dd + d; mh.hh = q[2 * dd + 2 * d]; mh.R = q[2 * dd + 2 * d + 1];
+    mh.x0m = h->x0m.data();
+    mh.x0P = h->x0P.data();
+    if (!tgp_wide::plan(h->wide, mh, h->T)) {
+        h->wide_state = -1;
+        return TGP_OK;
+    }
+    // (the observations are about to change: no later TGP_REUSE_REDUCE call may read an earlier call's reduction, whatever becomes of this one)
+    h->reduce_valid = false;
+    h->smoother_valid = false;
+    h->modal_last = false;
+    h->steady2_last = false;
+    CallTimer tm(h, /*clear=*/false);
+    TRY(set_obs(h, y, nullptr, flags));
+    tm.inputs_done();
+    std::string err;
+    double lml = 0.0;
+    bool declined = true;
+    {
+        const std::string nm_k = std::string("k_wide_adjoint: ") + tgp_wide::kernel_name(h->wide) + " + k_wide_bwd + k_wide_gram";
+        LaunchScope ls(h, nm_k.c_str());
+        if (tgp_wide::adjoint(h->wide, h->stream, mh, h->T, h->mv.y, &lml, o, &declined, &err) != 0) return h->fail(TGP_EHIP, err);
+    }
+    if (declined) return TGP_OK;
+    if (h->profile) HIPCHK(hipStreamSynchronize(h->stream));      // (the bracket's closing event)
+    resolve_profile(h);
+    if (getenv("TGP_STEADY_DEBUG") != nullptr) {
+        const tgp_wide::Info& in = tgp_wide::last_plan(h->wide);
+        fprintf(stderr, "[tgp wide adjoint] n0 %d halo %d chunks %lld x %lld steps, plan %.3f ms, host finish %.3f ms\n", in.n0, in.halo, in.chunks, in.chunk_len, in.plan_ms,
+                in.finish_ms);
+    }
+    for (int i = 0; i < 8; ++i) h->host_result[i] = 0.0;
+    h->host_result[0] = lml;
+    if (lml_out) *lml_out = lml;
+    h->dense_last_n0 = tgp_wide::last_plan(h->wide).n0;
+    *served = true;
+    return TGP_OK;
+}
+
 int tgp_logpdf_adjoint(tgp_handle* h, const double* y, uint32_t flags, double* lml_out, double* gA, double* ga, double* gQ, double* gH,
                        double* ghh, double* gR, double* gx0m, double* gx0P) {
     StreamGuard stream_guard_(h);
@@ -116,9 +171,16 @@ int tgp_logpdf_adjoint(tgp_handle* h, const double* y, uint32_t flags, double* l
     h->steady2_state = 0;            // (an earlier "does not apply" verdict of a posterior call -- series shorter than head + tail -- does not bind this one)
     const bool ok = steady2_eligible(h, nullptr, flags);
     h->steady2_state = keep_state;
+    if (!ok && y != nullptr && tgp_wide::supports(h->d)) {
+        bool served = false;
+        const tgp_adjoint::Out ow{gA, ga, gQ, gH, ghh, gR, gx0m, gx0P};
+        TRY(wide_adjoint_call(h, y, flags, lml_out, ow, &served));
+        if (served) return TGP_OK;
+    }
     if (!ok)
         return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint: Forward LTI models (every block shared), one noise variance, scalar observations, d <= 8 "
-                                         "(the stationary-gain engine); use tgp_logpdf_grad otherwise");
+                                         "(the stationary-gain engine) or 8 < d <= 63 (the wide-state engine, no per-step emission offsets); use "
+                                         "tgp_logpdf_grad otherwise");
     constexpr int64_t kHead = (int64_t)tgp_steady::kHeadMaxTiles * tgp_steady::kTile;
     const size_t nrec = tgp_steady::grad_record_size(h->d);
     const int64_t nyh = h->T < kHead ? h->T : kHead;

@@ -191,4 +191,12 @@ int tgp_adjoint_finish(int d, const double* rec, const double* y_head, int64_t n
     return tgp_adjoint::finish(d, rec, y_head, n_head, o) == 0 ? TGP_OK : TGP_EINVAL;
 }
 
+int tgp_adjoint_finish_wide(int d, const double* rec, int64_t rec_len, const double* y_head, int64_t n_head, int64_t head_steps, double* gA, double* ga, double* gQ,
+                            double* gH, double* ghh, double* gR, double* gx0m, double* gx0P) {
+    if (d < 1 || d > tgp_wide::kMaxD || !rec || !y_head || rec_len != tgp_adjoint::record_size(d)) return TGP_EINVAL;
+    const tgp_adjoint::Out o{gA, ga, gQ, gH, ghh, gR, gx0m, gx0P};
+    const int rc = tgp_wide::adjoint_finish_host(d, rec, y_head, n_head, head_steps, o);
+    return rc == 0 ? TGP_OK : (rc < 0 ? TGP_EUNSUPPORTED : TGP_EINVAL);
+}
+
 // the pinned host buffer of the head-on-the-host paths (head observations in, head outputs and the workgroups' partial sums out)

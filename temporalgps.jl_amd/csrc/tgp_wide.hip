@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "tgp_alloc.hpp"
+#include "tgp_wide_adjoint_host.hpp"
 
 namespace tgp_wide {
 
@@ -99,11 +100,13 @@ __global__ __launch_bounds__(64) void k_wide_lml(const double* __restrict__ tab,
 // mean_t = y_t - (R / S) r_t + gw . lam_(t+1), gw = R A K; var_t = (S - R) R / S - gw' Lam_(t+1) gw + Rnew_t, where the quadratic form is a constant
 // behind the last n1 steps (qtab: its partial sums at the series' end).  tab: [DP + 1][64] -- column j of the lanes' rows (lane i < d: row i of Psi;
 // lane d, the observer: gw), then the gains on r_t (h_i / S; observer: -R / S).  A chunk starts `halo` steps behind its end from lam = 0 (exact at T).
-template <int DP>
+// ADJ (the adjoint pass of logpdf, tgp_wide::adjoint): lam_t of the chunk's own steps to lamT [T][d] instead of the means and variances -- lam_t is
+// d logpdf / d mu_t, mu_t the predicted mean (the observer's row is not used).
+template <int DP, bool ADJ = false>
 __global__ __launch_bounds__(64) void k_wide_bwd(const double* __restrict__ tab, const double* __restrict__ y, const double* __restrict__ r,
                                                   const double* __restrict__ Rnew, int rnew_per_step, const double* __restrict__ qtab, long long n1, double vbase,
                                                   double qinf, long long T, long long t_head, long long chunk_len, long long halo, int obs_lane, int d,
-                                                  double* __restrict__ mean, double* __restrict__ var, double* __restrict__ lam_out) {
+                                                  double* __restrict__ mean, double* __restrict__ var, double* __restrict__ lam_out, double* __restrict__ lamT) {
     __shared__ __attribute__((aligned(16))) double zb[64];
     const int lane = threadIdx.x;
     const long long chunk = blockIdx.x;
@@ -145,13 +148,15 @@ __global__ __launch_bounds__(64) void k_wide_bwd(const double* __restrict__ tab,
             lds_sync();
             zb[lane] = acc;
             lds_sync();
-            if (own) {
+            if constexpr (ADJ) {
+                if (tb - l < s1 && lane < d) lamT[(tb - l) * d + lane] = acc;
+            } else if (own) {
                 const double mm = readlane_d(acc, obs_lane);
                 outm = lane == l ? mm : outm;
             }
         }
         const long long t = tb - lane;
-        if (own && lane < nb && t < s1) {
+        if (!ADJ && own && lane < nb && t < s1) {
             mean[t] = y[t] + outm;
             const long long jt = T - 1 - t;
             const double q = jt < n1 ? qtab[jt] : qinf;
@@ -272,9 +277,9 @@ __global__ __launch_bounds__(64) void k_wide_lml4(const double* __restrict__ tab
     if (is_obs && g.valid) part[chunk] = ssq;
 }
 
-template <int L, int NB>
+template <int L, int NB, bool ADJ>
 __device__ __forceinline__ void bwd_step4(double& rv, double& yv, double& zlo, double& zhi, const double (&pA)[32], const double (&pB)[32], double kA, double kB, double yA, double yB,
-                                          long long t, const RowGeom& g, bool obsB, bool is_obs, double* __restrict__ mean) {
+                                          long long t, const RowGeom& g, bool obsB, bool is_obs, double* __restrict__ mean, double* __restrict__ lamT, int d, int p) {
     asm volatile("s_nop 4" : "+v"(zlo), "+v"(zhi), "+v"(rv), "+v"(yv) : : "memory");
     Acc4 a{{0.0, 0.0, 0.0, 0.0}}, b{{0.0, 0.0, 0.0, 0.0}};
     fmac_bc<L>(a.v[3], rv, kA);
@@ -291,19 +296,27 @@ __device__ __forceinline__ void bwd_step4(double& rv, double& yv, double& zlo, d
     const bool live = t >= g.s0;
     zlo = live ? nA : zlo;
     zhi = live ? nB : zhi;
-    if (is_obs && live && t < g.s1) mean[t] = obsB ? nB : nA;
+    if constexpr (ADJ) {      // (lam_t of the row's own steps: see k_wide_bwd)
+        if (live && t < g.s1) {
+            if (p < d) lamT[t * d + p] = nA;
+            if (NB == 2 && 16 + p < d) lamT[t * d + 16 + p] = nB;
+        }
+    } else {
+        if (is_obs && live && t < g.s1) mean[t] = obsB ? nB : nA;
+    }
 }
-template <int NB, int... Ls>
+template <int NB, bool ADJ, int... Ls>
 __device__ __forceinline__ void bwd_block4(double& rv, double& yv, double& zlo, double& zhi, const double (&pA)[32], const double (&pB)[32], double kA, double kB, double yA, double yB,
-                                           long long t0, const RowGeom& g, bool obsB, bool is_obs, double* __restrict__ mean, std::integer_sequence<int, Ls...>) {
-    (bwd_step4<Ls, NB>(rv, yv, zlo, zhi, pA, pB, kA, kB, yA, yB, t0 - Ls, g, obsB, is_obs, mean), ...);
+                                           long long t0, const RowGeom& g, bool obsB, bool is_obs, double* __restrict__ mean, double* __restrict__ lamT, int d, int p,
+                                           std::integer_sequence<int, Ls...>) {
+    (bwd_step4<Ls, NB, ADJ>(rv, yv, zlo, zhi, pA, pB, kA, kB, yA, yB, t0 - Ls, g, obsB, is_obs, mean, lamT, d, p), ...);
 }
 
-template <int NB>
+template <int NB, bool ADJ = false>
 __global__ __launch_bounds__(64) void k_wide_bwd4(const double* __restrict__ tab, const double* __restrict__ y, const double* __restrict__ r, const double* __restrict__ Rnew,
                                                    int rnew_per_step, const double* __restrict__ qtab, long long n1, double vbase, double qinf, long long T, long long t_head,
                                                    long long chunk_len, long long halo, long long chunks, int d, double* __restrict__ mean, double* __restrict__ var,
-                                                   double* __restrict__ lam_out) {
+                                                   double* __restrict__ lam_out, double* __restrict__ lamT) {
     const int lane = threadIdx.x, p = lane & 15, row = lane >> 4;
     const long long chunk = (long long)blockIdx.x * 4 + row;
     RowGeom g;
@@ -339,9 +352,9 @@ __global__ __launch_bounds__(64) void k_wide_bwd4(const double* __restrict__ tab
         const long long tl = top - kb - p;
         rn = (tl - 16 >= g.s0) ? r[tl - 16] : 0.0;
         const bool mine = tl >= g.s0 && tl < g.s1;
-        double yv = mine ? y[tl] : 0.0;
-        bwd_block4<NB>(rv, yv, zlo, zhi, pA, pB, kA, kB, yA, yB, top - kb, g, obsB, is_obs, mean, Seq16{});
-        if (mine) {
+        double yv = (!ADJ && mine) ? y[tl] : 0.0;
+        bwd_block4<NB, ADJ>(rv, yv, zlo, zhi, pA, pB, kA, kB, yA, yB, top - kb, g, obsB, is_obs, mean, lamT, d, p, Seq16{});
+        if (!ADJ && mine) {
             const long long jt = T - 1 - tl;
             const double q = jt < n1 ? qtab[jt] : qinf;
             var[tl] = vbase - q + (rnew_per_step ? Rnew[tl] : Rnew[0]);
@@ -513,9 +526,9 @@ __global__ __launch_bounds__(64) void k_wide_lml43(const double* __restrict__ ta
     if (is_obs && g.valid) part[chunk] = ssq;
 }
 
-template <int L>
+template <int L, bool ADJ>
 __device__ __forceinline__ void bwd_step43(double& rv, double& yv, double (&z)[3], const double (&P)[3][48], const double (&kin)[3], const double (&yin)[3], long long t,
-                                           const RowGeom& g, int obs_o, bool is_obs, double* __restrict__ mean) {
+                                           const RowGeom& g, int obs_o, bool is_obs, double* __restrict__ mean, double* __restrict__ lamT, int d, int p) {
     asm volatile("s_nop 4" : "+v"(z[0]), "+v"(z[1]), "+v"(z[2]), "+v"(rv), "+v"(yv) : : "memory");
     double n[3];
 #pragma unroll
@@ -531,17 +544,27 @@ __device__ __forceinline__ void bwd_step43(double& rv, double& yv, double (&z)[3
     const bool live = t >= g.s0;
 #pragma unroll
     for (int o = 0; o < 3; ++o) z[o] = live ? n[o] : z[o];
-    if (is_obs && live && t < g.s1) mean[t] = obs_o == 0 ? n[0] : (obs_o == 1 ? n[1] : n[2]);
+    if constexpr (ADJ) {      // (lam_t of the row's own steps: see k_wide_bwd)
+        if (live && t < g.s1) {
+#pragma unroll
+            for (int o = 0; o < 3; ++o)
+                if (16 * o + p < d) lamT[t * d + 16 * o + p] = n[o];
+        }
+    } else {
+        if (is_obs && live && t < g.s1) mean[t] = obs_o == 0 ? n[0] : (obs_o == 1 ? n[1] : n[2]);
+    }
 }
-template <int... Ls>
+template <bool ADJ, int... Ls>
 __device__ __forceinline__ void bwd_block43(double& rv, double& yv, double (&z)[3], const double (&P)[3][48], const double (&kin)[3], const double (&yin)[3], long long t0,
-                                            const RowGeom& g, int obs_o, bool is_obs, double* __restrict__ mean, std::integer_sequence<int, Ls...>) {
-    (bwd_step43<Ls>(rv, yv, z, P, kin, yin, t0 - Ls, g, obs_o, is_obs, mean), ...);
+                                            const RowGeom& g, int obs_o, bool is_obs, double* __restrict__ mean, double* __restrict__ lamT, int d, int p,
+                                            std::integer_sequence<int, Ls...>) {
+    (bwd_step43<Ls, ADJ>(rv, yv, z, P, kin, yin, t0 - Ls, g, obs_o, is_obs, mean, lamT, d, p), ...);
 }
+template <bool ADJ = false>
 __global__ __launch_bounds__(64) void k_wide_bwd43(const double* __restrict__ tab, const double* __restrict__ y, const double* __restrict__ r, const double* __restrict__ Rnew,
                                                     int rnew_per_step, const double* __restrict__ qtab, long long n1, double vbase, double qinf, long long T, long long t_head,
                                                     long long chunk_len, long long halo, long long chunks, int d, double* __restrict__ mean, double* __restrict__ var,
-                                                    double* __restrict__ lam_out) {
+                                                    double* __restrict__ lam_out, double* __restrict__ lamT) {
     const int lane = threadIdx.x, p = lane & 15, row = lane >> 4;
     const long long chunk = (long long)blockIdx.x * 4 + row;
     RowGeom g;
@@ -578,9 +601,9 @@ __global__ __launch_bounds__(64) void k_wide_bwd43(const double* __restrict__ ta
         const long long tl = top - kb - p;
         rn = (tl - 16 >= g.s0) ? r[tl - 16] : 0.0;
         const bool mine = tl >= g.s0 && tl < g.s1;
-        double yv = mine ? y[tl] : 0.0;
-        bwd_block43(rv, yv, z, P, kin, yin, top - kb, g, obs_o, is_obs, mean, Seq16{});
-        if (mine) {
+        double yv = (!ADJ && mine) ? y[tl] : 0.0;
+        bwd_block43<ADJ>(rv, yv, z, P, kin, yin, top - kb, g, obs_o, is_obs, mean, lamT, d, p, Seq16{});
+        if (!ADJ && mine) {
             const long long jt = T - 1 - tl;
             const double q = jt < n1 ? qtab[jt] : qinf;
             var[tl] = vbase - q + (rnew_per_step ? Rnew[tl] : Rnew[0]);
@@ -599,6 +622,67 @@ __global__ __launch_bounds__(256) void k_wide_fill_cov(double* __restrict__ P, l
     const long long n = (T - n0) * dd;
     double* __restrict__ dst = P + n0 * dd;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) dst[i] = src[i % dd];
+}
+
+// ---- the adjoint pass's sums: G = sum_t u_t w_t' over the steps behind the head, u_t = (lam_(t+1), r_t, 1), w_t = (m_(t-1), r_t, 1) -- lam from the
+// ADJ backward kernels (lamT [T][d], lam_T = 0), m the filtered means from the forward kernel (m [T][d], row n0 - 1 the head's end state), r its
+// innovations.  A tall-skinny split-K product on v_mfma_f64_16x16x4_f64: a wave takes `span` consecutive steps, four per MFMA (k = lane >> 4 the
+// step, lane & 15 the component within a 16-wide tile), and keeps the (16 NT)^2 sums in NT^2 accumulator tiles (C/D of the f64 form:
+// row = (lane >> 4) + 4 reg, col = lane & 15); its partial goes to part [wave][16 NT][16 NT], summed in wave order by k_wide_gram_sum.
+typedef double d4v __attribute__((ext_vector_type(4)));
+template <int NT>
+__global__ __launch_bounds__(256) void k_wide_gram(const double* __restrict__ lamT, const double* __restrict__ m, const double* __restrict__ r, long long t_head,
+                                                   long long T, long long span, int d, double* __restrict__ part) {
+    constexpr int NG = 16 * NT;
+    const int lane = threadIdx.x & 63, kq = lane >> 4, c15 = lane & 15;
+    const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long a0 = t_head + w * span;
+    long long a1 = a0 + span;
+    if (a1 > T) a1 = T;
+    d4v acc[NT][NT];
+#pragma unroll
+    for (int I = 0; I < NT; ++I)
+#pragma unroll
+        for (int J = 0; J < NT; ++J) acc[I][J] = d4v{0.0, 0.0, 0.0, 0.0};
+    for (long long tb = a0; tb < a1; tb += 4) {
+        const long long t = tb + kq;
+        const bool in = t < a1;
+        const double rt = in ? r[t] : 0.0;
+        double u[NT], v[NT];
+#pragma unroll
+        for (int I = 0; I < NT; ++I) {
+            const int c = 16 * I + c15;
+            const double tail = c == d ? rt : (c == d + 1 ? 1.0 : 0.0);
+            u[I] = !in ? 0.0 : (c < d ? (t + 1 < T ? lamT[(t + 1) * d + c] : 0.0) : tail);
+            v[I] = !in ? 0.0 : (c < d ? m[(t - 1) * d + c] : tail);
+        }
+#pragma unroll
+        for (int I = 0; I < NT; ++I)
+#pragma unroll
+            for (int J = 0; J < NT; ++J) acc[I][J] = __builtin_amdgcn_mfma_f64_16x16x4f64(u[I], v[J], acc[I][J], 0, 0, 0);
+    }
+    double* out = part + w * (NG * NG);
+#pragma unroll
+    for (int I = 0; I < NT; ++I)
+#pragma unroll
+        for (int J = 0; J < NT; ++J)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) out[(16 * I + kq + 4 * q) * NG + 16 * J + c15] = acc[I][J][q];
+}
+// G [ng2] = sum over the waves' partials in wave order: 64 entries per block, its four waves a quarter of the partials each, combined in a fixed order
+__global__ __launch_bounds__(256) void k_wide_gram_sum(const double* __restrict__ part, long long nw, int ng2, double* __restrict__ G) {
+    __shared__ double red[4][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int e = blockIdx.x * 64 + lane;
+    const long long q = (nw + 3) / 4, w0 = wv * q, w1 = w0 + q < nw ? w0 + q : nw;
+    double s = 0.0;
+    if (e < ng2) {
+#pragma unroll 8
+        for (long long w = w0; w < w1; ++w) s += part[w * ng2 + e];
+    }
+    red[wv][lane] = s;
+    __syncthreads();
+    if (wv == 0 && e < ng2) G[e] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
 }
 
 // ---- host: small dense linear algebra, row-major ---------------------------------------------------------------------------------------
@@ -654,6 +738,14 @@ struct Engine {
     std::vector<double> Pf_head;          // the head's filtered covariances [n0][d d] (row-major = column-major: symmetric), for _filter; empty: too large
     double* rand_dev = nullptr;           // device: k_wide_rand's table
     size_t rand_cap = 0;
+    // the adjoint pass (built by its first call of a planned model): the backward table of the ADJ kernels, the per-step scratch of the pass
+    bool adj_ready = false;
+    int adj_halo = -1;                     // -1: Psi does not forget within 2^20 steps
+    std::vector<double> taba_host;         // [DP + 1][64]: rows of Psi, gains h / S (no observer)
+    double *adj_dev = nullptr, *adj_pin = nullptr;      // device: forward table | backward table | G; pinned: G | the head's end state
+    size_t adj_cap = 0;
+    double *mbuf = nullptr, *lbuf = nullptr, *gpart = nullptr;      // device: m [T][d], lam [T][d], partial sums of G
+    size_t mbuf_cap = 0, gpart_cap = 0;
 };
 
 namespace {
@@ -672,6 +764,9 @@ void destroy(Engine* e) {
     if (e->rbuf) (void)tgp_alloc::dev_free(e->rbuf);
     if (e->rand_dev) (void)tgp_alloc::dev_free(e->rand_dev);
     if (e->pinned) (void)tgp_alloc::host_free(e->pinned);
+    for (double* p : {e->adj_dev, e->mbuf, e->lbuf, e->gpart})
+        if (p) (void)tgp_alloc::dev_free(p);
+    if (e->adj_pin) (void)tgp_alloc::host_free(e->adj_pin);
     delete e;
 }
 const Info& last_plan(const Engine* e) { return e->info; }
@@ -749,6 +844,7 @@ bool plan(Engine* e, const ModelHost& m, long long T) {
     e->have = false;
     e->dev_current = false;
     e->post_ready = false;
+    e->adj_ready = false;
     e->info = Info{};
     const int d = m.d;
     const size_t dd = (size_t)d * d;
@@ -1143,20 +1239,20 @@ int run(Engine* e, hipStream_t stream, const Call& c, double* lml_out, std::stri
     if (rc != hipSuccess) return fail(rc, "launch");
     if (post) {
         if (three)
-            hipLaunchKernelGGL(k_wide_bwd43, dim3(grid4), dim3(64), 0, stream, tab_b, c.y, e->rbuf, c.Rnew, c.rnew_per_step, qtab_d, (long long)e->info.n1, e->vbase, e->qinf, T,
-                               (long long)n0, e->info.chunk_len, (long long)e->info.halo_back, chunks, d, c.mean, c.var, lam);
+            hipLaunchKernelGGL(k_wide_bwd43<false>, dim3(grid4), dim3(64), 0, stream, tab_b, c.y, e->rbuf, c.Rnew, c.rnew_per_step, qtab_d, (long long)e->info.n1, e->vbase, e->qinf, T,
+                               (long long)n0, e->info.chunk_len, (long long)e->info.halo_back, chunks, d, c.mean, c.var, lam, nullptr);
         else if (four && one)
             hipLaunchKernelGGL(k_wide_bwd4<1>, dim3(grid4), dim3(64), 0, stream, tab_b, c.y, e->rbuf, c.Rnew, c.rnew_per_step, qtab_d, (long long)e->info.n1, e->vbase, e->qinf, T,
-                               (long long)n0, e->info.chunk_len, (long long)e->info.halo_back, chunks, d, c.mean, c.var, lam);
+                               (long long)n0, e->info.chunk_len, (long long)e->info.halo_back, chunks, d, c.mean, c.var, lam, nullptr);
         else if (four)
             hipLaunchKernelGGL(k_wide_bwd4<2>, dim3(grid4), dim3(64), 0, stream, tab_b, c.y, e->rbuf, c.Rnew, c.rnew_per_step, qtab_d, (long long)e->info.n1, e->vbase, e->qinf, T,
-                               (long long)n0, e->info.chunk_len, (long long)e->info.halo_back, chunks, d, c.mean, c.var, lam);
+                               (long long)n0, e->info.chunk_len, (long long)e->info.halo_back, chunks, d, c.mean, c.var, lam, nullptr);
         else if (DP == 32)
             hipLaunchKernelGGL(k_wide_bwd<32>, dim3((unsigned)chunks), dim3(64), 0, stream, tab_b, c.y, e->rbuf, c.Rnew, c.rnew_per_step, qtab_d, (long long)e->info.n1, e->vbase,
-                               e->qinf, T, (long long)n0, e->info.chunk_len, (long long)e->info.halo_back, d, d, c.mean, c.var, lam);
+                               e->qinf, T, (long long)n0, e->info.chunk_len, (long long)e->info.halo_back, d, d, c.mean, c.var, lam, nullptr);
         else
             hipLaunchKernelGGL(k_wide_bwd<64>, dim3((unsigned)chunks), dim3(64), 0, stream, tab_b, c.y, e->rbuf, c.Rnew, c.rnew_per_step, qtab_d, (long long)e->info.n1, e->vbase,
-                               e->qinf, T, (long long)n0, e->info.chunk_len, (long long)e->info.halo_back, d, d, c.mean, c.var, lam);
+                               e->qinf, T, (long long)n0, e->info.chunk_len, (long long)e->info.halo_back, d, d, c.mean, c.var, lam, nullptr);
         rc = hipGetLastError();
         if (rc != hipSuccess) return fail(rc, "launch");
     }
@@ -1194,6 +1290,233 @@ int run(Engine* e, hipStream_t stream, const Call& c, double* lml_out, std::stri
     const double kLog2Pi = 1.8378770664093454835606594728112;
     *lml_out = -0.5 * ((double)T * kLog2Pi + e->sum_logS_head + (double)(T - n0) * std::log(e->Sss) + quad + ssq / e->Sss);
     return 0;
+}
+
+int adjoint(Engine* e, hipStream_t stream, const ModelHost& m, long long T, const double* y, double* lml_out, const tgp_adjoint::Out& out, bool* declined,
+            std::string* err) {
+    *declined = true;
+    auto fail = [&](hipError_t rc, const char* what) {
+        if (err) *err = std::string("tgp_wide adjoint: ") + what + ": " + hipGetErrorString(rc);
+        return (int)rc;
+    };
+    if (!e->have || e->info.why != kOk || e->d != m.d) return 0;
+    const int d = e->d, DP = e->dp, n0 = e->info.n0;
+    const size_t dd = (size_t)d * d;
+    const double *A = e->A.data(), *h = e->hvec.data();
+    // ---- the backward table: Psi = (I - h K') A' of the stationary step, gains h / S; the halo of Psi
+    if (!e->adj_ready) {
+        const double* K = e->Kt.data() + (size_t)(n0 - 1) * d;
+        std::vector<double> AK(d), Psi(dd);
+        for (int j = 0; j < d; ++j) {
+            double s = 0.0;
+            for (int k = 0; k < d; ++k) s += A[(size_t)j * d + k] * K[k];
+            AK[j] = s;
+        }
+        for (int i = 0; i < d; ++i)
+            for (int j = 0; j < d; ++j) Psi[(size_t)i * d + j] = A[(size_t)j * d + i] - h[i] * AK[j];
+        const long long hb = halo_of(d, Psi);
+        e->adj_halo = hb < 0 ? -1 : (int)hb;
+        e->taba_host.assign((size_t)(DP + 1) * 64, 0.0);
+        for (int i = 0; i < d; ++i) {
+            for (int j = 0; j < d; ++j) e->taba_host[(size_t)j * 64 + i] = Psi[(size_t)i * d + j];
+            e->taba_host[(size_t)DP * 64 + i] = h[i] / e->Sss;
+        }
+        e->adj_ready = true;
+        if (e->adj_dev) {      // (tables of an earlier model)
+            (void)tgp_alloc::dev_free(e->adj_dev);
+            e->adj_dev = nullptr;
+            e->adj_cap = 0;
+        }
+    }
+    if (e->adj_halo < 0) return 0;
+    const int NT = (d + 2 + 15) / 16;
+    const int NG = 16 * NT, ng2 = NG * NG;
+    hipError_t rc;
+    // ---- buffers: tables and G (device), G and the head's end state (pinned), the per-step scratch (2 T d + T doubles), the waves' partials of G
+    const size_t nf = e->tab_host.size(), nb = e->taba_host.size();
+    if (!e->adj_dev) {
+        rc = tgp_alloc::dev_malloc(reinterpret_cast<void**>(&e->adj_dev), (nf + nb + (size_t)ng2) * sizeof(double));
+        if (rc != hipSuccess) return fail(rc, "tables");
+        rc = hipMemcpyAsync(e->adj_dev, e->tab_host.data(), nf * sizeof(double), hipMemcpyHostToDevice, stream);
+        if (rc == hipSuccess) rc = hipMemcpyAsync(e->adj_dev + nf, e->taba_host.data(), nb * sizeof(double), hipMemcpyHostToDevice, stream);
+        if (rc != hipSuccess) return fail(rc, "table upload");
+    }
+    double *tab_f = e->adj_dev, *tab_b = tab_f + nf, *G_dev = tab_b + nb;
+    if (!e->adj_pin) {
+        rc = tgp_alloc::host_malloc(reinterpret_cast<void**>(&e->adj_pin), (size_t)(80 * 80 + 64) * sizeof(double), hipHostMallocDefault);
+        if (rc != hipSuccess) return fail(rc, "pinned buffer");
+    }
+    if (!e->pinned) {
+        rc = tgp_alloc::host_malloc(reinterpret_cast<void**>(&e->pinned), (size_t)(5 * kHeadMax + 64 + 65536) * sizeof(double), hipHostMallocDefault);
+        if (rc != hipSuccess) return fail(rc, "pinned buffer");
+    }
+    const size_t nTd = (size_t)T * d * sizeof(double);
+    if (nTd > e->mbuf_cap) {
+        for (double** p : {&e->mbuf, &e->lbuf}) {
+            if (*p) (void)tgp_alloc::dev_free(*p);
+            *p = nullptr;
+        }
+        e->mbuf_cap = 0;
+        rc = tgp_alloc::dev_malloc(reinterpret_cast<void**>(&e->mbuf), nTd);
+        if (rc == hipSuccess) rc = tgp_alloc::dev_malloc(reinterpret_cast<void**>(&e->lbuf), nTd);
+        if (rc != hipSuccess) return fail(rc, "per-step scratch");
+        e->mbuf_cap = nTd;
+    }
+    if ((size_t)T * sizeof(double) > e->rbuf_cap) {
+        if (e->rbuf) (void)tgp_alloc::dev_free(e->rbuf);
+        e->rbuf = nullptr;
+        e->rbuf_cap = 0;
+        rc = tgp_alloc::dev_malloc(reinterpret_cast<void**>(&e->rbuf), (size_t)T * sizeof(double));
+        if (rc != hipSuccess) return fail(rc, "innovation buffer");
+        e->rbuf_cap = (size_t)T * sizeof(double);
+    }
+    // the reduction's waves: at most 2048, none with fewer than 256 steps (a multiple of four: four waves per block)
+    const long long Tb = T - n0;
+    long long nw = std::min<long long>(2048, std::max<long long>(1, (Tb + 255) / 256));
+    nw = (nw + 3) / 4 * 4;
+    long long span = (Tb + nw - 1) / nw;
+    span = (span + 3) / 4 * 4;
+    const size_t gneed = (size_t)nw * ng2 * sizeof(double);
+    if (gneed > e->gpart_cap) {
+        if (e->gpart) (void)tgp_alloc::dev_free(e->gpart);
+        e->gpart = nullptr;
+        e->gpart_cap = 0;
+        rc = tgp_alloc::dev_malloc(reinterpret_cast<void**>(&e->gpart), gneed);
+        if (rc != hipSuccess) return fail(rc, "partial sums");
+        e->gpart_cap = gneed;
+    }
+    double *yh = e->pinned, *lam = yh + 5 * kHeadMax, *part = lam + 64;
+    double *Gh = e->adj_pin, *zend = Gh + 80 * 80;
+    rc = hipMemcpyAsync(yh, y, (size_t)n0 * sizeof(double), hipMemcpyDeviceToHost, stream);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(stream);
+    if (rc != hipSuccess) return fail(rc, "head observations");
+    // ---- the head forward (as tgp_wide::run): its end state m_(n0 - 1) starts chunk 0 and is the reduction's m row n0 - 1
+    ZArg z0;
+    for (int i = 0; i < 64; ++i) z0.z[i] = 0.0;
+    double quad = 0.0;
+    {
+        std::vector<double> mcur(e->x0m), mp(d);
+        for (int t = 0; t < n0; ++t) {
+            double pred = e->hh;
+            for (int i = 0; i < d; ++i) {
+                double s = e->avec[i];
+                const double* ai = A + (size_t)i * d;
+                for (int k = 0; k < d; ++k) s += ai[k] * mcur[k];
+                mp[i] = s;
+                pred += h[i] * s;
+            }
+            const double r = yh[t] - pred;
+            quad += r * r / e->St[t];
+            const double* K = e->Kt.data() + (size_t)t * d;
+            for (int i = 0; i < d; ++i) mcur[i] = mp[i] + K[i] * r;
+        }
+        for (int i = 0; i < d; ++i) z0.z[i] = zend[i] = mcur[i];
+    }
+    rc = hipMemcpyAsync(e->mbuf + (size_t)(n0 - 1) * d, zend, (size_t)d * sizeof(double), hipMemcpyHostToDevice, stream);
+    if (rc != hipSuccess) return fail(rc, "head's end state");
+    // ---- forward (innovations and filtered means of the steps behind the head), backward (lam_t), the sums
+    const long long chunks = e->info.chunks, len = e->info.chunk_len;
+    const unsigned grid4 = (unsigned)((chunks + 3) / 4);
+    const bool four = DP == 32 && dpp_enabled(), three = DP == 64 && d <= 47 && dpp_enabled(), one = d <= 15;
+    const long long hf = e->info.halo, hb = e->adj_halo;
+    double *rb = e->rbuf, *mb = e->mbuf, *lb = e->lbuf;
+    if (three) {
+        hipLaunchKernelGGL(k_wide_lml43<true>, dim3(grid4), dim3(64), 0, stream, tab_f, y, e->hh, T, (long long)n0, len, hf, chunks, d, z0, part, rb, nullptr, mb);
+        hipLaunchKernelGGL(k_wide_bwd43<true>, dim3(grid4), dim3(64), 0, stream, tab_b, y, rb, nullptr, 0, nullptr, 0ll, 0.0, 0.0, T, (long long)n0, len, hb, chunks, d, nullptr,
+                           nullptr, lam, lb);
+    } else if (four && one) {
+        hipLaunchKernelGGL((k_wide_lml4<true, 1>), dim3(grid4), dim3(64), 0, stream, tab_f, y, e->hh, T, (long long)n0, len, hf, chunks, d, z0, part, rb, nullptr, mb);
+        hipLaunchKernelGGL((k_wide_bwd4<1, true>), dim3(grid4), dim3(64), 0, stream, tab_b, y, rb, nullptr, 0, nullptr, 0ll, 0.0, 0.0, T, (long long)n0, len, hb, chunks, d, nullptr,
+                           nullptr, lam, lb);
+    } else if (four) {
+        hipLaunchKernelGGL((k_wide_lml4<true, 2>), dim3(grid4), dim3(64), 0, stream, tab_f, y, e->hh, T, (long long)n0, len, hf, chunks, d, z0, part, rb, nullptr, mb);
+        hipLaunchKernelGGL((k_wide_bwd4<2, true>), dim3(grid4), dim3(64), 0, stream, tab_b, y, rb, nullptr, 0, nullptr, 0ll, 0.0, 0.0, T, (long long)n0, len, hb, chunks, d, nullptr,
+                           nullptr, lam, lb);
+    } else if (DP == 32) {
+        hipLaunchKernelGGL(k_wide_lml<32>, dim3((unsigned)chunks), dim3(64), 0, stream, tab_f, y, e->hh, T, (long long)n0, len, hf, d, z0, part, rb, nullptr, mb, d);
+        hipLaunchKernelGGL((k_wide_bwd<32, true>), dim3((unsigned)chunks), dim3(64), 0, stream, tab_b, y, rb, nullptr, 0, nullptr, 0ll, 0.0, 0.0, T, (long long)n0, len, hb, d, d,
+                           nullptr, nullptr, lam, lb);
+    } else {
+        hipLaunchKernelGGL(k_wide_lml<64>, dim3((unsigned)chunks), dim3(64), 0, stream, tab_f, y, e->hh, T, (long long)n0, len, hf, d, z0, part, rb, nullptr, mb, d);
+        hipLaunchKernelGGL((k_wide_bwd<64, true>), dim3((unsigned)chunks), dim3(64), 0, stream, tab_b, y, rb, nullptr, 0, nullptr, 0ll, 0.0, 0.0, T, (long long)n0, len, hb, d, d,
+                           nullptr, nullptr, lam, lb);
+    }
+    const unsigned gblocks = (unsigned)(nw / 4);
+    switch (NT) {
+        case 1: hipLaunchKernelGGL(k_wide_gram<1>, dim3(gblocks), dim3(256), 0, stream, lb, mb, rb, (long long)n0, T, span, d, e->gpart); break;
+        case 2: hipLaunchKernelGGL(k_wide_gram<2>, dim3(gblocks), dim3(256), 0, stream, lb, mb, rb, (long long)n0, T, span, d, e->gpart); break;
+        case 3: hipLaunchKernelGGL(k_wide_gram<3>, dim3(gblocks), dim3(256), 0, stream, lb, mb, rb, (long long)n0, T, span, d, e->gpart); break;
+        case 4: hipLaunchKernelGGL(k_wide_gram<4>, dim3(gblocks), dim3(256), 0, stream, lb, mb, rb, (long long)n0, T, span, d, e->gpart); break;
+        default: hipLaunchKernelGGL(k_wide_gram<5>, dim3(gblocks), dim3(256), 0, stream, lb, mb, rb, (long long)n0, T, span, d, e->gpart); break;
+    }
+    hipLaunchKernelGGL(k_wide_gram_sum, dim3((unsigned)((ng2 + 63) / 64)), dim3(256), 0, stream, e->gpart, nw, ng2, G_dev);
+    rc = hipGetLastError();
+    if (rc != hipSuccess) return fail(rc, "launch");
+    rc = hipMemcpyAsync(Gh, G_dev, (size_t)ng2 * sizeof(double), hipMemcpyDeviceToHost, stream);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(stream);
+    if (rc != hipSuccess) return fail(rc, "kernel");
+    // ---- the record of tgp_adjoint_host.hpp: SA = Glm A' + Sa a', Srm = A Grm + Sr a (mu_t = A m_(t-1) + a); psi and mu at the head's end
+    const int DD = d * d, NS = DD + 3 * d + 2;
+    std::vector<double> rec((size_t)3 * DD + 8 * d + 8 + d * (d + 1) / 2, 0.0);
+    double *SA = rec.data(), *Sa = SA + DD, *Sk = Sa + d, *Srm = Sk + d;
+    auto Gat = [&](int i, int j) { return Gh[(size_t)i * NG + j]; };
+    const double Sr = Gat(d, d + 1);
+    for (int i = 0; i < d; ++i) {
+        Sa[i] = Gat(i, d + 1);
+        Sk[i] = Gat(i, d);
+        double x = Sr * e->avec[i];
+        for (int j = 0; j < d; ++j) x += A[(size_t)i * d + j] * Gat(d, j);
+        Srm[i] = x;
+        for (int k = 0; k < d; ++k) {
+            double s = Sa[i] * e->avec[k];
+            for (int j = 0; j < d; ++j) s += Gat(i, j) * A[(size_t)k * d + j];
+            SA[(size_t)i * d + k] = s;
+        }
+    }
+    rec[DD + 3 * d] = Sr;
+    rec[DD + 3 * d + 1] = Gat(d, d);
+    for (int i = 0; i < d; ++i) {
+        rec[NS + i] = lam[i];
+        double x = e->avec[i];
+        for (int k = 0; k < d; ++k) x += A[(size_t)i * d + k] * zend[k];
+        rec[NS + d + i] = x;
+    }
+    double* meta = rec.data() + NS + 2 * d;
+    meta[0] = (double)(n0 - 1);      // (the settled gain's index: step n0 - 1 already runs with it)
+    meta[1] = 0.0;
+    meta[2] = (double)T;
+    meta[3] = 1.0;
+    double* md = meta + 4;
+    std::memcpy(md, m.A, dd * sizeof(double));
+    std::memcpy(md + dd, m.a, d * sizeof(double));
+    std::memcpy(md + dd + d, m.Q, dd * sizeof(double));
+    std::memcpy(md + 2 * dd + d, m.H, d * sizeof(double));
+    md[2 * dd + 2 * d] = m.hh;
+    md[2 * dd + 2 * d + 1] = m.R;
+    double* x0 = md + 2 * dd + 2 * d + 2;
+    for (int i = 0; i < d; ++i) x0[i] = m.x0m[i];
+    for (int c = 0; c < d; ++c)
+        for (int r = 0; r <= c; ++r) x0[d + c * (c + 1) / 2 + r] = m.x0P[r + (size_t)c * d];
+    const auto t_fin = std::chrono::steady_clock::now();
+    tgp_wide_adjoint::Head hd;
+    hd.K = e->Kt.data();
+    hd.S = e->St.data();
+    hd.Pf = e->Pf_head.size() == (size_t)n0 * dd ? e->Pf_head.data() : nullptr;
+    hd.n = n0;
+    if (tgp_wide_adjoint::finish(d, rec.data(), yh, n0, n0, out, &hd) != 0) return fail(hipErrorInvalidValue, "inconsistent record");
+    e->info.finish_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_fin).count();
+    double ssq = 0.0;
+    for (long long k = 0; k < chunks; ++k) ssq += part[k];
+    const double kLog2Pi = 1.8378770664093454835606594728112;
+    *lml_out = -0.5 * ((double)T * kLog2Pi + e->sum_logS_head + (double)(T - n0) * std::log(e->Sss) + quad + ssq / e->Sss);
+    *declined = false;
+    return 0;
+}
+
+int adjoint_finish_host(int d, const double* rec, const double* yh, long long nyh, long long head_steps, const tgp_adjoint::Out& out) {
+    static const bool cpu_ok = __builtin_cpu_supports("avx2") && __builtin_cpu_supports("fma");      // (this object's host code is built with both)
+    if (!cpu_ok) return -1;
+    return tgp_wide_adjoint::finish(d, rec, yh, nyh, head_steps, out, nullptr);
 }
 
 int rand(Engine* e, hipStream_t stream, const ModelHost& m, long long T, const double* x0_host, const double* eps_t, const double* eps_e, double* y_out, bool* declined,

@@ -15,11 +15,19 @@
 //               kernel keeps its innovations (8 B per step), a second kernel of the same shape runs lam_t = h r_t / S + Psi lam_(t+1) backwards
 //               (Psi = (I - h K') A'), its observer row gw = R A K gives mean_t = y_t - (R / S) r_t + gw . lam_(t+1); the variance is a constant
 //               between the head (host, from Lam_inf backwards through the head's steps) and the last n1 steps (a data-free table).
+//   adjoint     logpdf and its gradient with respect to the model blocks (the record of tgp_adjoint_host.hpp): the forward kernel keeps its innovations
+//               and filtered means m_t, an ADJ variant of the backward kernel runs lam_t = d logpdf / d mu_t = h r_t / S + Psi lam_(t+1) -- the same
+//               recursion -- and writes lam_t; k_wide_gram sums G = sum_t (lam_(t+1), r_t, 1) (m_(t-1), r_t, 1)' on the f64 MFMA; the host turns G
+//               into the record (mu_t = A m_(t-1) + a) and runs tgp_wide_adjoint_host.hpp's finish on the plan's kept head.  Device scratch, kept
+//               by the engine between calls: m and lam whole, 2 T d doubles (T = 1e7, d = 28: 4.5 GB), the innovations (T doubles) and the waves'
+//               partial sums of G (2048 (16 ceil((d + 2) / 16))^2 doubles at most: 8 MB at d = 28).
 // Before this engine such models ran on ONE compute unit (tgp_dense_fused.hpp: a persistent kernel, sequential in time).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <string>
+
+#include "tgp_adjoint_host.hpp"
 
 namespace tgp_wide {
 
@@ -43,6 +51,7 @@ struct Info {
     int why_post = kOk, n1 = -1, halo_back = 0;
     long long chunks = 0, chunk_len = 0;
     double plan_ms = 0.0, plan_post_ms = 0.0;      // 0 when the plan of the previous call was kept
+    double finish_ms = 0.0;                        // the host half of the last adjoint call
 };
 
 struct Call {      // device pointers; mean == nullptr: logpdf only
@@ -71,6 +80,13 @@ const char* kernel_name(const Engine* e);
 bool filter_ready(const Engine* e);
 // the planned model's stationary gain K [d], innovation variance S, and (behind plan_posterior) the smoothed emission variance's two parts: vbase - qinf
 void stationary(const Engine* e, double* K, double* S, double* vbase, double* qinf);      // the plan kept the head's filtered covariances (64 MB at most)
+// logpdf and its gradient with respect to the blocks of the planned model `m` (the one handed to plan) of the series y (device, T steps, no per-step
+// emission offsets): forward, backward and the sums on `stream`, the head and the host half of the gradient on the host.  Synchronises `stream`.
+// *declined: Psi does not forget within 2^20 steps (nothing was computed).  0, or a hipError_t.
+int adjoint(Engine* e, hipStream_t stream, const ModelHost& m, long long T, const double* y, double* lml_out, const tgp_adjoint::Out& out, bool* declined,
+            std::string* err);
+// the host half alone (tgp_wide_adjoint_host.hpp, the covariances re-iterated from the record's model): 0, 1 (the record does not fit), -1 (no AVX2 / FMA)
+int adjoint_finish_host(int d, const double* rec, const double* yh, long long nyh, long long head_steps, const tgp_adjoint::Out& out);
 // rand(model) with the draws supplied (lgssm.jl:65-91): x0_host the drawn initial state (host, d), eps_t [T][d], eps_e [T], y_out [T] device pointers.
 // Enqueues ONE kernel (k_wide_rand) on `stream` -- no synchronisation behind it.  *declined: the open loop does not forget (nothing was enqueued).
 int rand(Engine* e, hipStream_t stream, const ModelHost& m, long long T, const double* x0_host, const double* eps_t, const double* eps_e, double* y_out, bool* declined,

@@ -587,7 +587,8 @@ def logpdf_adjoint(model, y):
     """logpdf and its gradient with respect to the SHARED model blocks by ONE adjoint pass on the device (tgp_logpdf_adjoint): the cost
     of a posterior-marginals call whatever the number of hyper-parameters. Returns (lml, dict A (d,d), a (d,), Q (d,d), H (d,), h (),
     R (), x0m (d,), x0P (d,d)); Q and x0P gradients are symmetrised (pair them with symmetric tangents). Forward LTI models with one
-    noise variance, scalar observations, no missing data, d <= 8 -- raises Unsupported otherwise (use logpdf_and_grad).
+    noise variance, scalar observations, no missing data, d <= 8 (the stationary-gain engine) or 8 < d <= 63 with a shared emission offset
+    where the wide-state engine's plan applies (its covariance settles; TGP_OPT_WIDE = 1) -- raises Unsupported otherwise (use logpdf_and_grad).
     The reference obtains this gradient by reverse-mode AD of the sequential loop (bench/single_output_gps.jl:149-156)."""
     _check_inputs(model, y[0] if isinstance(y, tuple) else y)
     hd = model.handle()

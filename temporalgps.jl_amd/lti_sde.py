@@ -961,7 +961,8 @@ def logpdf_and_gradient(fx, y, rel_step=None, method=None):
     Regular spacing with homoscedastic noise: any supported state dimension. Irregular spacing: d <= 4, shared or per-step
     noise; the per-step tangents of exp(F dt_k) are formed on the device (tgp_logpdf_grad_sde).
     method: None (default policy), "adjoint" (ONE reverse-time pass on the stationary-gain engine, exact block tangents on the host:
-    regular spacing, homoscedastic noise, d <= 8 -- cost independent of the number of parameters), "tangent" (the forward-mode scans)
+    regular spacing, homoscedastic noise, d <= 8, or the wide-state engine for 8 < d <= 63 where its plan applies -- cost independent of the
+    number of parameters), "tangent" (the forward-mode scans)
     or "fd" (central differences of the device logpdf).
     Default: the adjoint pass where it applies, else tangent scans up to state dimension 8; from d = 9 (e.g. ApproxPeriodicKernel, d = 14) the dual-number kernels are
     out-of-line private-memory code (d = 14, T = 2e5: 2.4 s for 4 parameters against 5.7 ms per logpdf), so central differences
