@@ -184,8 +184,8 @@ int tgp_kernel_variant(const tgp_handle* h);
 /* number of calls served by replaying a recorded hipGraph since the handle was created (TGP_OPT_GRAPH; measurement / tests) */
 int64_t tgp_graph_replays(const tgp_handle* h);
 /* Diagnostics of TGP_OPT_STEADY: how many of the series' steps the last call ran with stationary gains, out of `total` = T * p --
-   the stationary-gain engine: T - n0 (tgp_logpdf, tgp_[logpdf_and_]posterior_marginals); the general engine: the steps the forward pass of
-   the last posterior-path call ran in the mean-only form. */
+   the stationary-gain engines, their one-launch kernels and the wide-state engine: T - n0 (n0: the head of steps with gains of their own);
+   the general engine: the steps the forward pass of the last posterior-path call ran in the mean-only form. */
 int tgp_steady_steps(tgp_handle* h, int64_t* mean_only, int64_t* total);
 /* Diagnostics of TGP_OPT_SWEEP for the last tgp_logpdf / tgp_[logpdf_and_]posterior_marginals call. info [8]: served by the sweep engine (0 / 1),
    steps per chunk, forward warm-up, backward warm-up, waves, attempts (launches), status bits of the last attempt (1 forward / 2 backward warm-up

@@ -259,6 +259,11 @@ constexpr int kTopBS = 512;
 
 }  // namespace
 
+// The engine that served the last compute call of a handle (tgp_steady_steps and tgp_sweep_info report it): general = the chunked-scan engine
+// (or the dense one beyond d = 16), steady2 = the stationary-gain scan engine, modal = its one-launch form, dense = the one-launch kernels on
+// the dense powers of the closed loop, sweep = the time-varying-gain engine, wide = the wide-state engine.
+enum class Served : uint8_t { general, steady2, modal, dense, sweep, wide };
+
 struct tgp_handle {
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
@@ -307,7 +312,7 @@ struct tgp_handle {
     int variant_opt = 0;   // TGP_OPT_VARIANT: 0 auto (run-time check), 1 safe, 2 fast
     int L0 = 0;
     int64_t n0 = 0;
-    bool reduce_valid = false, smoother_valid = false;
+    bool reduce_valid = false, smoother_valid = false;   // the general engine's reduction / smoother elements of the staged observations (obs_changed, drop_reduction)
     bool fused = false;          // the current forward elements were produced with the fused level-0 reduce
     bool group_active = false;   // ... by the group-per-chunk pass 1 (32 chunks per block, its own chunking)
     bool use_group = false;      // group-per-chunk logpdf kernels validated for this model (tgp_group.hpp)
@@ -331,7 +336,6 @@ struct tgp_handle {
     bool opt_sde_closed = true;
     tgp_steady::Engine* steady2 = nullptr;
     int steady2_state = 0;       // 0 untried for the bound model, 1 served the last call, -1 does not apply
-    bool steady2_last = false;   // the last logpdf / posterior-marginals call was served by it
     // TGP_OPT_STEADY = 3 (default since round 4): the ONE-LAUNCH form of that engine (tgp_modal.hip) is tried first -- host plan + one kernel
     // over y + the host's sum of the workgroups' partial sums; a model / series it does not serve (tgp_plan::Info::why) goes on as with 2.
     int opt_modal = 1;
@@ -340,8 +344,8 @@ struct tgp_handle {
     bool has_R_over = false;     // tgp_logpdf_noise: the host plans of THIS call read R_over instead of the bound model's noise variance
     double R_over = 0.0;
     int smooth_state = 0;        // the dense-powers one-launch smoother (smooth_lti_call): 0 untried / applies, -1 does not apply
-    bool modal_last = false;
-    int64_t dense_last_n0 = -1;   // >= 0: the last call ran on the dense-power one-launch kernels behind a head of that many steps with gains of their own
+    Served served = Served::general;      // the engine of the last compute call (note_served)
+    int64_t served_n0 = 0;                // ... and the head of steps with gains of their own it ran before the stationary ones
     // TGP_OPT_SWEEP (default 1): the sweep engine (tgp_sweep.hip) serves tgp_logpdf / tgp_[logpdf_and_]posterior_marginals of Forward
     // models with scalar observations, d <= 4, shared A / a / Q / H (or closed-form SDE transitions) whose gains vary in time: a mask, a noise
     // variance or an emission offset per step, irregular spacing.  One launch; a call whose warm-ups prove too short is repeated with longer
@@ -350,7 +354,6 @@ struct tgp_handle {
     long long opt_stream_min_T = -1;      // TGP_OPT_STREAM_MIN_T
     tgp_sweep::Engine* sweep = nullptr;
     int sweep_state = 0;          // 0 untried for the bound model, 1 served the last call, -1 does not apply
-    bool sweep_last = false;
     int sweep_W = 0, sweep_Wb = 0;     // warm-ups the bound model's last served call needed (0: estimate)
     int sweep_fC = 0, sweep_fW = 0, sweep_fWb = 0;   // TGP_OPT_SWEEP_CHUNK / _WARMUP / _WARMUP_BACK (tests; 0 automatic)
     int64_t sweep_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // tgp_sweep_info
@@ -714,6 +717,48 @@ __global__ void k_zero8(double* r) {
     if (threadIdx.x < 8) r[threadIdx.x] = 0.0;
 }
 
+// The general engine's records of the staged observations -- reduce_valid (pass 1 + the upward scans: what TGP_REUSE_REDUCE and the time-sharded
+// protocol reuse) and smoother_valid (the smoother's elements: what tgp_smoother_backward reuses) -- are cleared here only: obs_changed by whatever
+// stages new observations, drop_reduction by whatever changes how the general engine would reduce them.  Only the general engine sets them.
+// smoother_only: the reduction stays valid (tgp_model_set_x0: the time-sharded protocol folds onto x0, then finishes with TGP_REUSE_REDUCE).
+void drop_reduction(tgp_handle* h, bool smoother_only = false) {
+    if (!smoother_only) h->reduce_valid = false;
+    h->smoother_valid = false;
+}
+void obs_changed(tgp_handle* h) { drop_reduction(h); }
+
+// A one-launch engine served the call: the result record (lml; status "ran" and the head's n0 in the stationary-gain engine's slots -- read only
+// after a call's own copy of the device record, so no reader sees them behind a one-launch call), the engine tgp_steady_steps / tgp_sweep_info
+// report, the caller's lml.
+void note_served(tgp_handle* h, Served by, int64_t n0, double lml, double* lml_out) {
+    for (int i = 0; i < 8; ++i) h->host_result[i] = 0.0;
+    h->host_result[0] = lml;
+    h->host_result[6] = tgp_steady::kStatusRan;
+    h->host_result[7] = (double)n0;
+    h->served = by;
+    h->served_n0 = n0;
+    if (lml_out) *lml_out = lml;
+}
+
+// The log marginal likelihood of a one-launch call: a head of n0 steps with gains of their own (its quadratic form quad_head) and T - n0 steps
+// with the stationary ones (their innovations' sum of squares ssq).
+template <class Plan>
+double head_lml(const Plan& fp, int64_t T, double quad_head, double ssq) {
+    return -0.5 * ((double)T * 1.8378770664093454835606594728112 + fp.LS + (double)(T - fp.n0) * fp.logS + quad_head + fp.iS * ssq);
+}
+
+// The h2d / kernels / d2h split of the call (tgp_last_timing) from its four hipEvents, recorded only with TGP_OPT_TIMING
+void read_timing(tgp_handle* h) {
+    if (!h->timing) return;
+    float a = 0.f, b = 0.f, c = 0.f;
+    (void)hipEventElapsedTime(&a, h->ev[0], h->ev[1]);
+    (void)hipEventElapsedTime(&b, h->ev[1], h->ev[2]);
+    (void)hipEventElapsedTime(&c, h->ev[2], h->ev[3]);
+    h->h2d_ms = a;
+    h->kernel_ms = b;
+    h->d2h_ms = c;
+}
+
 struct CallTimer {
     tgp_handle* h;
     // clear == false: a later phase of a multi-phase (time-sharded) call, the flags of the earlier phases are kept.
@@ -739,15 +784,7 @@ struct CallTimer {
     }
     static int finish_wait(tgp_handle* h, double* lml_out) {
         HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->timing) {
-            float a = 0.f, b = 0.f, c = 0.f;
-            (void)hipEventElapsedTime(&a, h->ev[0], h->ev[1]);
-            (void)hipEventElapsedTime(&b, h->ev[1], h->ev[2]);
-            (void)hipEventElapsedTime(&c, h->ev[2], h->ev[3]);
-            h->h2d_ms = a;
-            h->kernel_ms = b;
-            h->d2h_ms = c;
-        }
+        read_timing(h);
         resolve_profile(h);
         if (h->steady_result_pending) {
             h->steady_result_pending = false;
@@ -770,14 +807,16 @@ void resolve_table(tgp_handle* h) {
     if (!h->table_pending) return;
     h->table_pending = false;
     select_table(h, h->d, h->lti, h->variant_opt);
-    h->reduce_valid = false;
-    h->smoother_valid = false;
+    drop_reduction(h);
 }
+// Every call on the bound model starts here: it owns the reset of the last-engine record (a one-launch engine that serves the call records
+// itself through note_served; the set-up calls through here, tgp_model_set_x0 and tgp_segment_plan, start afresh as tgp_model_set does).
 // general == false: the caller tries the stationary-gain engine first and calls resolve_table itself before the general path
 int check_ready(tgp_handle* h, bool general = true) {
     if (!h) return TGP_EINVAL;
     if (!h->have_model) return h->fail(TGP_EINVAL, "no model set (call tgp_model_set first)");
     ++h->call_seq;
+    h->served = Served::general;
     TRY(bind_device(h));
     if (general) resolve_table(h);
     return TGP_OK;
@@ -919,6 +958,7 @@ int ensure_tiled(tgp_handle* h, bool full = false) {
 // for_mode: the pass-2 mode the caller will run next (0 logpdf ...), -1 unknown (time-sharded protocol)
 int forward_reduce(tgp_handle* h, uint32_t flags, int for_mode = -1) {
     if ((flags & TGP_REUSE_REDUCE) && h->reduce_valid) return TGP_OK;
+    drop_reduction(h);
     // Group-per-chunk logpdf kernels (tgp_group.hpp). Measured at T = 1e7 (pass 1 + pass 2, ms; lane-per-chunk inlined
     // build in brackets): d = 5 1.9 (0.70), d = 6 2.2 (1.55), d = 7 2.9 (4.3), d = 8 3.4 (12.1) -- their time hardly
     // depends on d (LDS exchanges and shuffles, not flops), so they pay from d = 7 on (TGP_OPT_GROUP = 2 forces them).
@@ -964,7 +1004,6 @@ int forward_reduce(tgp_handle* h, uint32_t flags, int for_mode = -1) {
         h->fused = false;
         h->group_active = true;
         h->reduce_valid = true;
-        h->smoother_valid = false;
         return TGP_OK;
     }
     h->group_active = false;
@@ -1024,7 +1063,6 @@ int forward_reduce(tgp_handle* h, uint32_t flags, int for_mode = -1) {
     scan_up(h, h->F, fused ? 1 : 0);
     h->fused = fused;
     h->reduce_valid = true;
-    h->smoother_valid = false;
     return TGP_OK;
 }
 
@@ -1033,6 +1071,7 @@ int set_obs(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t fla
     const bool dev = (flags & TGP_IN_DEVICE) != 0;
     const void* p = nullptr;
     if ((flags & TGP_REUSE_REDUCE) && h->reduce_valid) return TGP_OK;  // caller vouches: same y as the previous call
+    obs_changed(h);
     TRY(stage_in(h, h->by, y, (size_t)h->T * h->p * sizeof(double), dev, &p));
     h->mv.y = static_cast<const double*>(p);
     TRY(stage_in(h, h->bmiss, missing, (size_t)h->T * h->p, dev, &p));
@@ -1286,8 +1325,7 @@ int tgp_set_option(tgp_handle* h, int option, int64_t value) {
     if (option == TGP_OPT_CHUNK) {
         if (value < 0 || value > 4096) return h->fail(TGP_EINVAL, "TGP_OPT_CHUNK out of range");
         h->opt_chunk = value;
-        h->reduce_valid = false;
-        h->smoother_valid = false;
+        drop_reduction(h);
         return TGP_OK;
     }
     if (option == TGP_OPT_PROFILE) {
@@ -1300,22 +1338,19 @@ int tgp_set_option(tgp_handle* h, int option, int64_t value) {
         if (h->have_model) {
             h->table_pending = false;
             select_table(h, h->d, h->lti, (int)value);
-            h->reduce_valid = false;
-            h->smoother_valid = false;
+            drop_reduction(h);
         }
         return TGP_OK;
     }
     if (option == TGP_OPT_SPLIT_SMOOTHER) {
         if (value < 0 || value > 2) return h->fail(TGP_EINVAL, "TGP_OPT_SPLIT_SMOOTHER must be 0, 1 or 2");
         h->opt_split = (int)value;
-        h->reduce_valid = false;
-        h->smoother_valid = false;
+        drop_reduction(h);
         return TGP_OK;
     }
     if (option == TGP_OPT_SHARED_PARTS) {
         h->opt_table = value != 0 ? (int)value : 0;      // 1 default policy; 2 build the table synchronously on the first call (tests)
-        h->reduce_valid = false;
-        h->smoother_valid = false;
+        drop_reduction(h);
         return TGP_OK;
     }
     if (option == TGP_OPT_STEADY) {
@@ -1326,7 +1361,7 @@ int tgp_set_option(tgp_handle* h, int option, int64_t value) {
         h->modal_state = 0;
         h->smooth_state = 0;
         h->steady_known = false;
-        h->smoother_valid = false;
+        drop_reduction(h, /*smoother_only=*/true);
         return TGP_OK;
     }
     if (option == TGP_OPT_SWEEP) {
@@ -1353,8 +1388,7 @@ int tgp_set_option(tgp_handle* h, int option, int64_t value) {
     }
     if (option == TGP_OPT_SDE_CLOSED_FORM) {
         h->opt_sde_closed = value != 0;
-        h->reduce_valid = false;
-        h->smoother_valid = false;
+        drop_reduction(h);
         return TGP_OK;
     }
     if (option == TGP_OPT_DENSE_FUSED) {
@@ -1373,14 +1407,12 @@ int tgp_set_option(tgp_handle* h, int option, int64_t value) {
         if (value < 0 || value > 6 || (value & 3) == 3) return h->fail(TGP_EINVAL, "TGP_OPT_GROUP must be 0, 1 or 2 (+ 4)");
         h->opt_group = (int)(value & 3);
         h->opt_group_scan = (value & 4) ? 0 : 1;
-        h->reduce_valid = false;
-        h->smoother_valid = false;
+        drop_reduction(h);
         return TGP_OK;
     }
     if (option == TGP_OPT_FUSE_SCAN) {
         h->opt_fuse = value != 0;
-        h->reduce_valid = false;
-        h->smoother_valid = false;
+        drop_reduction(h);
         return TGP_OK;
     }
     return h->fail(TGP_EINVAL, "unknown option");
@@ -1399,16 +1431,13 @@ int tgp_steady_steps(tgp_handle* h, int64_t* mean_only, int64_t* total) {
     if (!h || !mean_only || !total) return TGP_EINVAL;
     *mean_only = 0;
     *total = h->T * h->p;
+    // the one-launch paths (modal form, dense powers, wide-state engine): every step beyond the head's n0 ran with the stationary gains
+    if (h->served == Served::modal || h->served == Served::dense || h->served == Served::wide) {
+        *mean_only = h->T - h->served_n0;
+        return TGP_OK;
+    }
     if (h->is_dense) return TGP_OK;
-    if (h->dense_last_n0 >= 0) {              // k_filter_one / k_adjoint_one: the same, on dense powers
-        *mean_only = h->T - h->dense_last_n0;
-        return TGP_OK;
-    }
-    if (h->modal_last && h->modal) {          // one-launch path: every step beyond the head's n0 ran with the stationary gains
-        *mean_only = h->T - tgp_modal::last_plan(h->modal).n0;
-        return TGP_OK;
-    }
-    if (h->steady2_last && h->steady2) {      // stationary-gain engine: every step beyond the head's n0 ran with the stationary gains
+    if (h->served == Served::steady2) {      // stationary-gain engine: the same, as its last call recorded it on the device
         int64_t info[4] = {0, 0, 0, 0};
         HIPCHK(hipSetDevice(h->device));
         if (tgp_steady::last_info(h->steady2, h->stream, info) != 0) return h->fail(TGP_EHIP, "tgp_steady::last_info");
@@ -1432,7 +1461,7 @@ int tgp_sweep_info(tgp_handle* h, int64_t* info, double* dist) {
     if (!h) return TGP_EINVAL;
     if (info) {
         for (int i = 0; i < 8; ++i) info[i] = h->sweep_info[i];
-        info[0] = h->sweep_last ? 1 : 0;
+        info[0] = h->served == Served::sweep ? 1 : 0;
         info[7] = h->sweep_state;
     }
     if (dist) { dist[0] = h->sweep_dist[0]; dist[1] = h->sweep_dist[1]; }
@@ -1499,6 +1528,26 @@ int tgp_stream_synchronize(void* hip_stream) {
     return hipStreamSynchronize(static_cast<hipStream_t>(hip_stream)) == hipSuccess ? TGP_OK : TGP_EHIP;
 }
 
+// The six shared blocks A | a | Q | H | hh | R of a model packed on the host, column-major (what the host plans read; hh, R: the first step's where
+// they are per step).  skip_hh: hh stays 0 (a per-step emission offset, which the wide-state kernels subtract themselves).
+static int pack_host_blocks(tgp_handle* h, std::vector<double>& out, int d, bool dev, bool skip_hh, const double* A, const double* a, const double* Q,
+                            const double* H, const double* hh, const double* R) {
+    const size_t dd = (size_t)d * d;
+    out.assign(2 * dd + 2 * (size_t)d + 2, 0.0);
+    double* q = out.data();
+    const struct { const double* src; size_t n; } parts[6] = {{A, dd}, {a, (size_t)d}, {Q, dd}, {H, (size_t)d}, {hh, 1}, {R, 1}};
+    size_t off = 0;
+    for (int k = 0; k < 6; ++k) {
+        const auto& pt = parts[k];
+        if (k != 4 || !skip_hh) {
+            if (dev) HIPCHK(hipMemcpy(q + off, pt.src, pt.n * sizeof(double), hipMemcpyDeviceToHost));
+            else std::memcpy(q + off, pt.src, pt.n * sizeof(double));
+        }
+        off += pt.n;
+    }
+    return TGP_OK;
+}
+
 int tgp_model_set(tgp_handle* h, int64_t T, int d, int p, int ordering, uint32_t flags, const double* A, const double* a,
                   const double* Q, const double* H, const double* hh, const double* R, const double* x0m, const double* x0P) {
     if (h) drop_graphs(h);
@@ -1509,19 +1558,15 @@ int tgp_model_set(tgp_handle* h, int64_t T, int d, int p, int ordering, uint32_t
     h->steady_calls = 0;
     h->mv.steady = nullptr;
     h->steady2_state = 0;
-    h->steady2_last = false;
     h->modal_state = 0;
     h->smooth_state = 0;
-    h->modal_last = false;
-    h->dense_last_n0 = -1;
+    h->served = Served::general;
     h->hostm.clear();
     h->sweep_state = 0;
-    h->sweep_last = false;
     h->sweep_W = h->sweep_Wb = 0;
     if (!h->binding_sde) { h->sde_coef_host.clear(); h->sde_A1Q1_host.clear(); }
     h->fold_valid = false;
-    h->reduce_valid = false;
-    h->smoother_valid = false;
+    drop_reduction(h);
     h->sde = false;
     if (h->tab_state == 1) (void)hipStreamSynchronize(h->side_stream);       // a table of the previous model may still be in flight
     h->tab_state = 0;
@@ -1583,19 +1628,8 @@ int tgp_model_set(tgp_handle* h, int64_t T, int d, int p, int ordering, uint32_t
             const uint32_t need_shared = TGP_SHARED_A | TGP_SHARED_a | TGP_SHARED_Q | TGP_SHARED_H | TGP_SHARED_R;
             h->wide_ht = nullptr;
             if ((flags & need_shared) == need_shared && p == 1 && ordering == 0 && tgp_wide::supports(d)) {
-                const size_t dd = (size_t)d * d;
-                const bool h_per_step = !(flags & TGP_SHARED_h);
-                h->widem.assign(2 * dd + 2 * (size_t)d + 2, 0.0);
-                double* q = h->widem.data();
-                const struct { const double* src; size_t n; } parts[6] = {{A, dd}, {a, (size_t)d}, {Q, dd}, {H, (size_t)d}, {hh, 1}, {R, 1}};
-                size_t off = 0;
-                for (int k = 0; k < 6; ++k) {
-                    const auto& pt = parts[k];
-                    if (k == 4 && h_per_step) { off += 1; continue; }      // (hh stays 0: the kernels subtract h_t)
-                    if (dev) HIPCHK(hipMemcpy(q + off, pt.src, pt.n * sizeof(double), hipMemcpyDeviceToHost));
-                    else std::memcpy(q + off, pt.src, pt.n * sizeof(double));
-                    off += pt.n;
-                }
+                const bool h_per_step = !(flags & TGP_SHARED_h);      // (hh stays 0: the kernels subtract h_t)
+                TRY(pack_host_blocks(h, h->widem, d, dev, h_per_step, A, a, Q, H, hh, R));
                 if (h_per_step) h->wide_ht = static_cast<const double*>(ph);
             }
         }
@@ -1663,19 +1697,10 @@ int tgp_model_set(tgp_handle* h, int64_t T, int d, int p, int ordering, uint32_t
     const bool one_launch_model = h->lti && !h->binding_sde && p == 1 && (flags & TGP_SHARED_R) && tgp_steady::supports(d);      // what `hostm` stands for
     h->sweepm.clear();
     if ((flags & host_bits) == host_bits && p == 1 && tgp_steady::supports(d)) {
-        const size_t dd = (size_t)d * d;
-        h->sweepm.assign(2 * dd + 2 * (size_t)d + 2, 0.0);
-        double* q = h->sweepm.data();
-        const struct { const double* src; size_t n; } parts[6] = {{A, dd}, {a, (size_t)d}, {Q, dd}, {H, (size_t)d}, {hh, 1}, {R, 1}};
-        size_t off = 0;
-        for (const auto& pt : parts) {
-            if (dev) HIPCHK(hipMemcpy(q + off, pt.src, pt.n * sizeof(double), hipMemcpyDeviceToHost));
-            else std::memcpy(q + off, pt.src, pt.n * sizeof(double));
-            off += pt.n;
-        }
+        TRY(pack_host_blocks(h, h->sweepm, d, dev, /*skip_hh=*/false, A, a, Q, H, hh, R));
         // a representative noise variance (the sweep engine's warm-up estimate): the median of a sample of the per-step values below the
         // "missing" level of missings.jl:43
-        h->sweep_Rrep = q[2 * dd + 2 * (size_t)d + 1];
+        h->sweep_Rrep = h->sweepm.back();      // (R: the last block)
         if (!(flags & TGP_SHARED_R)) {
             const size_t ns = (size_t)std::min<int64_t>(T, 4096);
             std::vector<double> smp(ns);
@@ -1701,19 +1726,8 @@ int tgp_model_set(tgp_handle* h, int64_t T, int d, int p, int ordering, uint32_t
         const uint32_t need_shared = TGP_SHARED_A | TGP_SHARED_a | TGP_SHARED_Q | TGP_SHARED_H | TGP_SHARED_R;
         h->wide_ht = nullptr;
         if ((flags & need_shared) == need_shared && p == 1 && ordering == 0 && !h->binding_sde && tgp_wide::supports(d)) {
-            const size_t dd = (size_t)d * d;
             const bool h_per_step = !(flags & TGP_SHARED_h);      // (a mean function at the inputs: see the dense branch)
-            h->widem.assign(2 * dd + 2 * (size_t)d + 2, 0.0);
-            double* q = h->widem.data();
-            const struct { const double* src; size_t n; } parts[6] = {{A, dd}, {a, (size_t)d}, {Q, dd}, {H, (size_t)d}, {hh, 1}, {R, 1}};
-            size_t off = 0;
-            for (int k = 0; k < 6; ++k) {
-                const auto& pt = parts[k];
-                if (k == 4 && h_per_step) { off += 1; continue; }
-                if (dev) HIPCHK(hipMemcpy(q + off, pt.src, pt.n * sizeof(double), hipMemcpyDeviceToHost));
-                else std::memcpy(q + off, pt.src, pt.n * sizeof(double));
-                off += pt.n;
-            }
+            TRY(pack_host_blocks(h, h->widem, d, dev, h_per_step, A, a, Q, H, hh, R));
             if (h_per_step) h->wide_ht = h->mv.h;
         }
     }
@@ -1908,7 +1922,7 @@ int tgp_model_set_x0(tgp_handle* h, const double* x0m, const double* x0P) {
     h->smooth_state = 0;
     if (h->is_dense) return dense_fail(h, tgp_dense::set_x0(h->dense, x0m, x0P, h->stream));
     h->fold_valid = false;
-    h->smoother_valid = false;
+    drop_reduction(h, /*smoother_only=*/true);      // (the reduction stays: the time-sharded protocol folds onto x0, then reuses it)
     return upload_x0(h, h->bx0, x0m, x0P);
 }
 
@@ -1917,9 +1931,6 @@ int tgp_logpdf(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t 
     StreamGuard stream_guard_(h);
     TRY(check_ready(h, /*general=*/false));
     if (!out) return h->fail(TGP_EINVAL, "out is NULL");
-    h->steady2_last = false;
-    h->modal_last = false;
-    h->dense_last_n0 = -1;
     if (reverse_by_flip(h, y, missing, flags)) {
         const double* yf = nullptr;
         uint32_t ff = flags;
@@ -1951,13 +1962,12 @@ int tgp_logpdf(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t 
         TRY(smooth_lti_call(h, y, flags, nullptr, nullptr, nullptr, out, &served));
         if (served) return TGP_OK;
     }
-    h->sweep_last = false;
     if (sweep_eligible(h, flags)) {
         bool served = false;
         TRY(sweep_call(h, y, missing, flags, nullptr, nullptr, nullptr, out, &served));
         if (served) return TGP_OK;
     }
-    if (!h->widem.empty() && missing == nullptr && h->opt_chunk == 0 && h->variant_opt == 0 && h->opt_group != 2) {      // wide LTI models (8 < d <= 63): the stationary closed loop across the chip (tgp_wide.hip)
+    if (wide_eligible(h, y, missing)) {      // wide LTI models (8 < d <= 63): the stationary closed loop across the chip (tgp_wide.hip)
         bool served = false;
         TRY(wide_call(h, y, flags, nullptr, nullptr, nullptr, out, &served));
         if (served) return TGP_OK;
@@ -1998,9 +2008,6 @@ int tgp_logpdf_noise(tgp_handle* h, const double* y, uint32_t flags, double R, d
     TRY(check_ready(h, /*general=*/false));
     if (!out || !y) return h->fail(TGP_EINVAL, "tgp_logpdf_noise: null argument");
     if (!(R > 0.0) || !std::isfinite(R)) return h->fail(TGP_EINVAL, "tgp_logpdf_noise: the noise variance must be positive");
-    h->steady2_last = false;
-    h->modal_last = false;
-    h->dense_last_n0 = -1;
     if (!steady2_eligible(h, nullptr, flags) || !h->opt_modal || h->hostm.empty())
         return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_noise: Forward LTI models with scalar observations on the one-launch paths only");
     const int modal_state = h->modal_state, smooth_state = h->smooth_state;       // (the verdicts are the BOUND model's: kept for it)
@@ -2025,9 +2032,6 @@ int tgp_logpdf_noise(tgp_handle* h, const double* y, uint32_t flags, double R, d
 int tgp_filter(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* m_out, double* P_out, double* lml_out) {
     StreamGuard stream_guard_(h);
     TRY(check_ready(h, /*general=*/false));
-    h->dense_last_n0 = -1;
-    h->modal_last = false;
-    h->steady2_last = false;
     if (reverse_by_flip(h, y, missing, flags) && m_out && P_out) {
         // the Forward twin on the flipped series into device scratch, rows flipped back into the caller's arrays
         const bool odev_r = (flags & TGP_OUT_DEVICE) != 0;
@@ -2060,7 +2064,7 @@ int tgp_filter(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t 
         TRY(filter_lti_call(h, y, flags, m_out, P_out, lml_out, &served));
         if (served) return TGP_OK;
     }
-    if (!h->widem.empty() && missing == nullptr && h->p == 1 && h->opt_chunk == 0 && h->variant_opt == 0 && h->opt_group != 2) {      // wide LTI models: tgp_wide.hip
+    if (wide_eligible(h, y, missing)) {      // wide LTI models: tgp_wide.hip
         bool served = false;
         TRY(wide_filter_call(h, y, flags, m_out, P_out, lml_out, &served));
         if (served) return TGP_OK;
@@ -2141,18 +2145,11 @@ static int posterior_lti_call(tgp_handle* h, const double* y, uint32_t flags, do
     resolve_profile(h);
     double ssq = 0.0;
     for (long long w = 0; w < nwg; ++w) ssq += part[w];
-    const double lml = -0.5 * ((double)h->T * 1.8378770664093454835606594728112 + fp.LS + (double)(h->T - fp.n0) * fp.logS + quad_head + fp.iS * ssq);
-    for (int i = 0; i < 8; ++i) h->host_result[i] = 0.0;
-    h->host_result[0] = lml;
+    note_served(h, Served::dense, fp.n0, head_lml(fp, h->T, quad_head, ssq), nullptr);
     if (xfm)
         for (int i = 0; i < d; ++i) xfm[i] = fin[i];
     if (xfP)
         for (size_t e = 0; e < dd; ++e) xfP[e] = fp.Pss[e];      // (symmetric: either storage order)
-    h->reduce_valid = false;
-    h->smoother_valid = false;
-    h->modal_last = false;
-    h->steady2_last = false;
-    h->dense_last_n0 = fp.n0;
     *served = true;
     return TGP_OK;
 }
@@ -2162,9 +2159,6 @@ int tgp_posterior(tgp_handle* h, const double* y, const uint8_t* missing, uint32
     StreamGuard stream_guard_(h);
     TRY(check_ready(h, /*general=*/false));
     if ((G || g || L) && !(G && g && L)) return h->fail(TGP_EINVAL, "G, g, L must be given together");
-    h->dense_last_n0 = -1;
-    h->modal_last = false;
-    h->steady2_last = false;
     if (G && missing == nullptr && y != nullptr) {
         bool served = false;
         TRY(posterior_lti_call(h, y, flags, G, g, L, xfm, xfP, &served));
@@ -2268,9 +2262,6 @@ int tgp_posterior_marginals(tgp_handle* h, const double* y, const uint8_t* missi
     const bool idev = (flags & TGP_IN_DEVICE) != 0, odev = (flags & TGP_OUT_DEVICE) != 0;
     const bool rshared = (flags & TGP_SHARED_R) != 0;
     const size_t nT = (size_t)h->T * h->p * sizeof(double);   // one value per (time step, observation)
-    h->steady2_last = false;
-    h->modal_last = false;
-    h->dense_last_n0 = -1;
     if (steady2_eligible(h, missing, flags)) {
         bool served = false;
         TRY(modal_call(h, y, flags, Rnew, mean_out, var_out, lml_out, &served));
@@ -2295,23 +2286,19 @@ int tgp_posterior_marginals(tgp_handle* h, const double* y, const uint8_t* missi
         TRY(copy_back(h, mean_out, dm, nT, odev));
         TRY(copy_back(h, var_out, dv, nT, odev));
         const int rc = tm.finish(lml_out);
-        if (rc != TGP_OK || steady2_served(h)) {
-            h->smoother_valid = false;
-            return rc;
-        }
+        if (rc != TGP_OK || steady2_served(h)) return rc;
     }
     if (lti_but_offset(h) && missing == nullptr && y != nullptr && !(flags & TGP_REUSE_REDUCE)) {      // a mean function on a regular grid: stationary gains
         bool served = false;
         TRY(smooth_lti_call(h, y, flags, Rnew, mean_out, var_out, lml_out, &served));
         if (served) return TGP_OK;
     }
-    h->sweep_last = false;
     if (sweep_eligible(h, flags)) {
         bool served = false;
         TRY(sweep_call(h, y, missing, flags, Rnew, mean_out, var_out, lml_out, &served));
         if (served) return TGP_OK;
     }
-    if (!h->widem.empty() && missing == nullptr && h->p == 1 && h->opt_chunk == 0 && h->variant_opt == 0 && h->opt_group != 2) {      // wide LTI models: tgp_wide.hip
+    if (wide_eligible(h, y, missing)) {      // wide LTI models: tgp_wide.hip
         bool served = false;
         TRY(wide_call(h, y, flags, Rnew, mean_out, var_out, lml_out, &served));
         if (served) return TGP_OK;
@@ -2460,8 +2447,7 @@ int tgp_smoother_backward(tgp_handle* h, const double* xs_m, const double* xs_P,
 
 static int affine_impl(tgp_handle* h, bool rnd, const double* x0dev, const double* eps_t, const double* eps_e, double* mean_dev,
                        double* var_dev) {
-    h->reduce_valid = false;
-    h->smoother_valid = false;
+    drop_reduction(h);
     h->group_active = false;
     // group layout (tgp_group_smooth.hpp): prior marginals and rand, both orderings, LTI and per-step layouts. LTI Forward marginals
     // from d = 7 (measured in round 1); everything else from d = 9, where the lane-per-chunk alternative is out-of-line
@@ -2693,13 +2679,8 @@ int tgp_rand(tgp_handle* h, const double* eps_t, const double* eps_e, const doub
     CallTimer tm(h);
     if (rand_wide) {
         if (!h->wide) h->wide = tgp_wide::create();
-        const size_t dd = (size_t)d * d;
-        const double* q = h->widem.data();
         tgp_wide::ModelHost mh;
-        mh.d = d;
-        mh.A = q; mh.a = q + dd; mh.Q = q + dd + d; mh.H = q + 2 * dd + d; mh.hh = q[2 * dd + 2 * d]; mh.R = q[2 * dd + 2 * d + 1];
-        mh.x0m = h->x0m.data();
-        mh.x0P = h->x0P.data();
+        wide_host_model(h, mh);
         const void *pet = nullptr, *pee = nullptr;
         TRY(stage_in(h, h->beps_t, eps_t, (size_t)h->T * d * sizeof(double), idev, &pet));
         TRY(stage_in(h, h->beps_e, eps_e, nT, idev, &pee));

@@ -56,8 +56,6 @@ struct ModalFlagGuard {
 };
 int modal_call(tgp_handle* h, const double* y, uint32_t flags, const double* Rnew, double* mean_out, double* var_out, double* lml_out, bool* served) {
     *served = false;
-    h->modal_last = false;
-    h->dense_last_n0 = -1;
     if (!h->opt_modal || h->modal_state < 0 || h->hostm.empty()) return TGP_OK;
     if (!h->modal) h->modal = tgp_modal::create();
     static const bool dbg = getenv("TGP_STEADY_DEBUG") != nullptr;
@@ -119,31 +117,15 @@ int modal_call(tgp_handle* h, const double* y, uint32_t flags, const double* Rne
         auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
         fprintf(stderr, "[tgp modal host] plan core %.1f us, staging + launch %.1f, tables + copies %.1f, wait %.1f\n", us(tp0, tp1), us(tp1, tp2), us(tp2, tp3), us(tp3, tp4));
     }
-    if (h->timing) {
-        float t0 = 0.f, t1 = 0.f, t2 = 0.f;
-        (void)hipEventElapsedTime(&t0, h->ev[0], h->ev[1]);
-        (void)hipEventElapsedTime(&t1, h->ev[1], h->ev[2]);
-        (void)hipEventElapsedTime(&t2, h->ev[2], h->ev[3]);
-        h->h2d_ms = t0;
-        h->kernel_ms = t1;
-        h->d2h_ms = t2;
-    }
+    read_timing(h);
     resolve_profile(h);
     if (!tables_ok) {      // declined behind the launch (a head step not positive definite, a smoother transient beyond the table): the older engines serve the call
         h->modal_state = -1;
         return TGP_OK;
     }
     const double lml = tgp_modal::finish(h->modal, h->T);
-    for (int i = 0; i < 8; ++i) h->host_result[i] = 0.0;
-    h->host_result[0] = lml;
-    h->host_result[6] = tgp_steady::kStatusRan;
-    h->host_result[7] = (double)tgp_modal::last_plan(h->modal).n0;
-    if (lml_out) *lml_out = lml;
+    note_served(h, Served::modal, tgp_modal::last_plan(h->modal).n0, lml, lml_out);
     h->modal_state = 1;
-    h->modal_last = true;
-    h->steady2_last = false;
-    h->reduce_valid = false;
-    h->smoother_valid = false;
     *served = true;
     return TGP_OK;
 }
@@ -168,7 +150,6 @@ bool sweep_eligible(const tgp_handle* h, uint32_t flags) {
 int sweep_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, double* mean_out, double* var_out,
                double* lml_out, bool* served) {
     *served = false;
-    h->sweep_last = false;
     if (!h->sweep) h->sweep = tgp_sweep::create();
     static const bool dbg = getenv("TGP_STEADY_DEBUG") != nullptr;
     const int d = h->d;
@@ -261,27 +242,12 @@ int sweep_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t 
         TRY(copy_back(h, mean_out, dm, nT, odev));
         TRY(copy_back(h, var_out, dv, nT, odev));
         if ((mean_out && !odev)) HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->timing) {
-            float t0 = 0.f, t1 = 0.f, t2 = 0.f;
-            (void)hipEventElapsedTime(&t0, h->ev[0], h->ev[1]);
-            (void)hipEventElapsedTime(&t1, h->ev[1], h->ev[2]);
-            (void)hipEventElapsedTime(&t2, h->ev[2], h->ev[3]);
-            h->h2d_ms = t0;
-            h->kernel_ms = t1;
-            h->d2h_ms = t2;
-        }
-        for (int i = 0; i < 8; ++i) h->host_result[i] = 0.0;
-        h->host_result[0] = lml;
-        if (lml_out) *lml_out = lml;
+        read_timing(h);
+        note_served(h, Served::sweep, 0, lml, lml_out);
         h->sweep_W = w;
         h->sweep_Wb = wb;
         h->sweep_state = 1;
-        h->sweep_last = true;
         h->sweep_info[0] = 1;
-        h->steady2_last = false;
-        h->modal_last = false;
-        h->reduce_valid = false;
-        h->smoother_valid = false;
         *served = true;
         return TGP_OK;
     }
@@ -292,11 +258,7 @@ int sweep_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t 
 bool steady2_served(tgp_handle* h) {
     const bool ran = h->host_result[6] == tgp_steady::kStatusRan;
     h->steady2_state = ran ? 1 : -1;
-    h->steady2_last = ran;
-    if (ran) {
-        h->reduce_valid = false;        // (the general path's pass-1 elements belong to an earlier call's observations)
-        h->smoother_valid = false;
-    }
+    if (ran) h->served = Served::steady2;
     return ran;
 }
 

@@ -40,8 +40,7 @@ int tgp_logpdf_grad(tgp_handle* h, const double* y, const uint8_t* missing, uint
     HIPCHK(hipStreamSynchronize(h->stream));   // host staging vectors go out of scope
     tm.inputs_done();
     choose_chunk(h);
-    h->reduce_valid = false;
-    h->smoother_valid = false;
+    drop_reduction(h);
     TRY(scan_prepare(h, h->Fad, kFilterAD, h->n0));
     const int64_t nblocks = (h->n0 + 255) / 256;
     HIPCHK(h->partial.ensure((size_t)nblocks * 4 * sizeof(double)));
@@ -137,8 +136,7 @@ int tgp_logpdf_grad_sde(tgp_handle* h, const double* y, const uint8_t* missing, 
     h->group_active = false;
     choose_chunk(h);
     TRY(ensure_tiled(h, /*full=*/true));        // the value tile (k_tile_sde) for this chunk size
-    h->reduce_valid = false;
-    h->smoother_valid = false;
+    drop_reduction(h);
     const int Lt = h->L0;
     const size_t nblk = (size_t)((h->n0 + 63) / 64) * 64;
     HIPCHK(h->tile_tan.ensure((nblk * (size_t)Lt * (size_t)h->mv.nc_t + 1) * sizeof(double)));

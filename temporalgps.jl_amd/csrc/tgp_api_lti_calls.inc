@@ -85,16 +85,7 @@ static int adjoint_lti_call(tgp_handle* h, const double* y, uint32_t flags, doub
     for (int c = 0; c < d; ++c)
         for (int r = 0; r <= c; ++r) x0[d + c * (c + 1) / 2 + r] = h->x0P[r + (size_t)c * d];
     if (tgp_adjoint::finish(d, rec, yh, (int64_t)nhs, o, (int64_t)nhs) != 0) return h->fail(TGP_EHIP, "tgp_logpdf_adjoint: inconsistent record");
-    const double ssq = rec[dd + 3 * d + 1];
-    const double lml = -0.5 * ((double)h->T * 1.8378770664093454835606594728112 + fp.LS + (double)(h->T - fp.n0) * fp.logS + quad_head + fp.iS * ssq);
-    for (int i = 0; i < 8; ++i) h->host_result[i] = 0.0;
-    h->host_result[0] = lml;
-    if (lml_out) *lml_out = lml;
-    h->reduce_valid = false;
-    h->smoother_valid = false;
-    h->modal_last = false;
-    h->steady2_last = false;
-    h->dense_last_n0 = fp.n0;
+    note_served(h, Served::dense, fp.n0, head_lml(fp, h->T, quad_head, rec[dd + 3 * d + 1]), lml_out);
     *served = true;
     return TGP_OK;
 }
@@ -104,29 +95,14 @@ static int adjoint_lti_call(tgp_handle* h, const double* y, uint32_t flags, doub
 // gradient (tgp_wide_adjoint_host.hpp) on the host.  *served = false: the engine does not apply (nothing the caller must undo).
 static int wide_adjoint_call(tgp_handle* h, const double* y, uint32_t flags, double* lml_out, const tgp_adjoint::Out& o, bool* served) {
     *served = false;
-    static const bool env_on = [] {
-        const char* s = std::getenv("TGP_WIDE");
-        return !(s && s[0] == '0');
-    }();
-    if (!env_on || !h->opt_wide || chunk_engine_requested(h) || h->widem.empty() || h->wide_ht != nullptr || y == nullptr || h->ordering != 0) return TGP_OK;
+    if (h->wide_ht != nullptr) return TGP_OK;
     if (!h->wide) h->wide = tgp_wide::create();
-    const int d = h->d;
-    const size_t dd = (size_t)d * d;
-    const double* q = h->widem.data();
     tgp_wide::ModelHost mh;
-    mh.d = d;
-    mh.A = q; mh.a = q + dd; mh.Q = q + dd + d; mh.H = q + 2 * dd + d; mh.hh = q[2 * dd + 2 * d]; mh.R = q[2 * dd + 2 * d + 1];
-    mh.x0m = h->x0m.data();
-    mh.x0P = h->x0P.data();
+    wide_host_model(h, mh);
     if (!tgp_wide::plan(h->wide, mh, h->T)) {
         h->wide_state = -1;
         return TGP_OK;
     }
-    // (the observations are about to change: no later TGP_REUSE_REDUCE call may read an earlier call's reduction, whatever becomes of this one)
-    h->reduce_valid = false;
-    h->smoother_valid = false;
-    h->modal_last = false;
-    h->steady2_last = false;
     CallTimer tm(h, /*clear=*/false);
     TRY(set_obs(h, y, nullptr, flags));
     tm.inputs_done();
@@ -146,10 +122,7 @@ static int wide_adjoint_call(tgp_handle* h, const double* y, uint32_t flags, dou
         fprintf(stderr, "[tgp wide adjoint] n0 %d halo %d chunks %lld x %lld steps, plan %.3f ms, host finish %.3f ms\n", in.n0, in.halo, in.chunks, in.chunk_len, in.plan_ms,
                 in.finish_ms);
     }
-    for (int i = 0; i < 8; ++i) h->host_result[i] = 0.0;
-    h->host_result[0] = lml;
-    if (lml_out) *lml_out = lml;
-    h->dense_last_n0 = tgp_wide::last_plan(h->wide).n0;
+    note_served(h, Served::wide, tgp_wide::last_plan(h->wide).n0, lml, lml_out);
     *served = true;
     return TGP_OK;
 }
@@ -158,20 +131,17 @@ int tgp_logpdf_adjoint(tgp_handle* h, const double* y, uint32_t flags, double* l
                        double* ghh, double* gR, double* gx0m, double* gx0P) {
     StreamGuard stream_guard_(h);
     TRY(check_ready(h, /*general=*/false));
-    h->dense_last_n0 = -1;
-    h->modal_last = false;
     if (y != nullptr) {
         bool served = false;
         const tgp_adjoint::Out o1{gA, ga, gQ, gH, ghh, gR, gx0m, gx0P};
         TRY(adjoint_lti_call(h, y, flags, lml_out, o1, &served));
         if (served) return TGP_OK;
     }
-    h->steady2_last = false;
     const int keep_state = h->steady2_state;
     h->steady2_state = 0;            // (an earlier "does not apply" verdict of a posterior call -- series shorter than head + tail -- does not bind this one)
     const bool ok = steady2_eligible(h, nullptr, flags);
     h->steady2_state = keep_state;
-    if (!ok && y != nullptr && tgp_wide::supports(h->d)) {
+    if (!ok && wide_eligible(h, y, nullptr)) {
         bool served = false;
         const tgp_adjoint::Out ow{gA, ga, gQ, gH, ghh, gR, gx0m, gx0P};
         TRY(wide_adjoint_call(h, y, flags, lml_out, ow, &served));
@@ -197,8 +167,6 @@ int tgp_logpdf_adjoint(tgp_handle* h, const double* y, uint32_t flags, double* l
     if (h->host_result[6] != tgp_steady::kStatusRan)
         return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint: the filter covariance of this model does not settle within the head (or the series is shorter "
                                          "than the head); use tgp_logpdf_grad");
-    h->reduce_valid = false;
-    h->smoother_valid = false;
     const tgp_adjoint::Out o{gA, ga, gQ, gH, ghh, gR, gx0m, gx0P};
     if (tgp_adjoint::finish(h->d, h->adj_host, h->adj_host + nrec, nyh, o) != 0) return h->fail(TGP_EHIP, "tgp_logpdf_adjoint: inconsistent record");
     return TGP_OK;
@@ -246,15 +214,7 @@ static int filter_lti_call(tgp_handle* h, const double* y, uint32_t flags, doubl
     resolve_profile(h);
     double ssq = 0.0;
     for (long long g = 0; g < nwg; ++g) ssq += part[g];
-    const double lml = -0.5 * ((double)h->T * 1.8378770664093454835606594728112 + fp.LS + (double)(h->T - fp.n0) * fp.logS + quad_head + fp.iS * ssq);
-    for (int i = 0; i < 8; ++i) h->host_result[i] = 0.0;
-    h->host_result[0] = lml;
-    if (lml_out) *lml_out = lml;
-    h->reduce_valid = false;
-    h->smoother_valid = false;
-    h->modal_last = false;
-    h->steady2_last = false;
-    h->dense_last_n0 = fp.n0;
+    note_served(h, Served::dense, fp.n0, head_lml(fp, h->T, quad_head, ssq), lml_out);
     *served = true;
     return TGP_OK;
 }
@@ -446,19 +406,12 @@ static int smooth_lti_call(tgp_handle* h, const double* y, uint32_t flags, const
     }
     double ssq = 0.0;
     for (long long g = 0; g < nwg; ++g) ssq += part[g];
-    const double lml = -0.5 * ((double)h->T * 1.8378770664093454835606594728112 + fp.LS + (double)(h->T - fp.n0) * fp.logS + quad_head + fp.iS * ssq);
+    const double lml = head_lml(fp, h->T, quad_head, ssq);
     if (rnd && !(lml == lml)) return TGP_OK;      // (a NaN in the series -- NaN == missing in the mirrors' convention --: the evaluated route serves the draw)
     if (getenv("TGP_STEADY_DEBUG") != nullptr)
         fprintf(stderr, "[tgp smooth] T %lld post %d overlap %d idev %d odev %d nwg %lld nhs %d halo %d n1 %d seq %lld quad_head %.6g ssq %.6g lml %.10g\n", (long long)h->T,
                 (int)post, (int)overlap, (int)idev, (int)odev, nwg, fp.nhs, sp.halo, sp.n1, seq, quad_head, ssq, lml);
-    for (int i = 0; i < 8; ++i) h->host_result[i] = 0.0;
-    h->host_result[0] = lml;
-    if (lml_out) *lml_out = lml;
-    h->reduce_valid = false;
-    h->smoother_valid = false;
-    h->modal_last = false;
-    h->steady2_last = false;
-    h->dense_last_n0 = fp.n0;
+    note_served(h, Served::dense, fp.n0, lml, lml_out);
     *served = true;
     return TGP_OK;
 }
@@ -471,9 +424,6 @@ int tgp_posterior_rand(tgp_handle* h, const double* y, const double* Rnew, const
     StreamGuard stream_guard_(h);
     TRY(check_ready(h, /*general=*/false));
     if (!y || !Rnew || !eps_t || !eps_e || !eps_0 || !y_out) return h->fail(TGP_EINVAL, "tgp_posterior_rand: null argument");
-    h->steady2_last = false;
-    h->modal_last = false;
-    h->dense_last_n0 = -1;
     bool served = false;
     const SmoothRand rnd{eps_t, eps_e, eps_0};
     if (steady2_eligible(h, nullptr, flags)) TRY(smooth_lti_call(h, y, flags, Rnew, y_out, nullptr, nullptr, &served, &rnd));

@@ -91,26 +91,41 @@ int flip_series(tgp_handle* h, const double* y, uint32_t flags, const double** y
 }
 }  // namespace
 
-// ---- wide LTI models (16 < d <= 63; tgp_wide.hip): logpdf across the chip on the stationary closed loop.  *served = false: the engine declined
-// (nothing the caller must undo) -- the dense engine's passes serve the call.
-static int wide_call(tgp_handle* h, const double* y, uint32_t flags, const double* Rnew, double* mean_out, double* var_out, double* out, bool* served) {
-    *served = false;
-    static const bool env_on = [] {
+// ---- wide LTI models (8 < d <= 63; tgp_wide.hip) ----------------------------------------------------------------------------------------
+// TGP_WIDE=0: such models on the engines they had before (A/B runs)
+bool wide_env_on() {
+    static const bool on = [] {
         const char* s = std::getenv("TGP_WIDE");
         return !(s && s[0] == '0');
     }();
-    if (!env_on || !h->opt_wide || h->wide_state < 0 || h->widem.empty() || y == nullptr || h->ordering != 0 || (flags & TGP_REUSE_REDUCE)) return TGP_OK;
-    const bool post = mean_out != nullptr;
-    if (post && h->wide_post_state < 0) return TGP_OK;
-    if (!h->wide) h->wide = tgp_wide::create();
+    return on;
+}
+// What every call site of the wide-state engine asks (each adds its own conditions): a wide LTI model bound (`widem`: every block shared, scalar
+// observations, Forward), the engine not switched off, no chunked-scan kernels requested, observations given and none missing.
+bool wide_eligible(const tgp_handle* h, const double* y, const uint8_t* missing) {
+    return wide_env_on() && h->opt_wide && !h->widem.empty() && !chunk_engine_requested(h) && y != nullptr && missing == nullptr;
+}
+// the bound model as the engine's host plan reads it (the twin of modal_host_model)
+void wide_host_model(const tgp_handle* h, tgp_wide::ModelHost& mh) {
     const int d = h->d;
     const size_t dd = (size_t)d * d;
     const double* q = h->widem.data();
-    tgp_wide::ModelHost mh;
     mh.d = d;
     mh.A = q; mh.a = q + dd; mh.Q = q + dd + d; mh.H = q + 2 * dd + d; mh.hh = q[2 * dd + 2 * d]; mh.R = q[2 * dd + 2 * d + 1];
     mh.x0m = h->x0m.data();
     mh.x0P = h->x0P.data();
+}
+
+// logpdf and posterior marginals across the chip on the stationary closed loop.  *served = false: the engine declined (nothing the caller must
+// undo) -- the dense engine's passes (d > 16) or the general engine serve the call.
+static int wide_call(tgp_handle* h, const double* y, uint32_t flags, const double* Rnew, double* mean_out, double* var_out, double* out, bool* served) {
+    *served = false;
+    if (h->opt_group == 2 || (flags & TGP_REUSE_REDUCE) || h->wide_state < 0) return TGP_OK;
+    const bool post = mean_out != nullptr;
+    if (post && h->wide_post_state < 0) return TGP_OK;
+    if (!h->wide) h->wide = tgp_wide::create();
+    tgp_wide::ModelHost mh;
+    wide_host_model(h, mh);
     const bool dbg = getenv("TGP_STEADY_DEBUG") != nullptr;
     if (!tgp_wide::plan(h->wide, mh, h->T)) {
         h->wide_state = -1;
@@ -162,11 +177,7 @@ static int wide_call(tgp_handle* h, const double* y, uint32_t flags, const doubl
         fprintf(stderr, "[tgp wide] n0 %d halo %d / %d n1 %d chunks %lld x %lld steps, plan %.3f + %.3f ms\n", in.n0, in.halo, in.halo_back, in.n1, in.chunks, in.chunk_len, in.plan_ms,
                 in.plan_post_ms);
     }
-    for (int i = 0; i < 8; ++i) h->host_result[i] = 0.0;
-    h->host_result[0] = lml;
-    h->host_result[6] = tgp_steady::kStatusRan;
-    h->host_result[7] = (double)tgp_wide::last_plan(h->wide).n0;
-    if (out) *out = lml;
+    note_served(h, Served::wide, tgp_wide::last_plan(h->wide).n0, lml, out);
     h->wide_state = 1;
     *served = true;
     return TGP_OK;
@@ -176,20 +187,11 @@ static int wide_call(tgp_handle* h, const double* y, uint32_t flags, const doubl
 // and the settled one behind it (one fill kernel).  *served = false: the engine declined.
 static int wide_filter_call(tgp_handle* h, const double* y, uint32_t flags, double* m_out, double* P_out, double* lml_out, bool* served) {
     *served = false;
-    static const bool env_on = [] {
-        const char* s = std::getenv("TGP_WIDE");
-        return !(s && s[0] == '0');
-    }();
-    if (!env_on || !h->opt_wide || h->wide_state < 0 || h->widem.empty() || y == nullptr || !m_out || !P_out || h->ordering != 0 || (flags & TGP_REUSE_REDUCE)) return TGP_OK;
+    if (h->opt_group == 2 || (flags & TGP_REUSE_REDUCE) || h->wide_state < 0 || !m_out || !P_out) return TGP_OK;
     if (!h->wide) h->wide = tgp_wide::create();
     const int d = h->d;
-    const size_t dd = (size_t)d * d;
-    const double* q = h->widem.data();
     tgp_wide::ModelHost mh;
-    mh.d = d;
-    mh.A = q; mh.a = q + dd; mh.Q = q + dd + d; mh.H = q + 2 * dd + d; mh.hh = q[2 * dd + 2 * d]; mh.R = q[2 * dd + 2 * d + 1];
-    mh.x0m = h->x0m.data();
-    mh.x0P = h->x0P.data();
+    wide_host_model(h, mh);
     if (!tgp_wide::plan(h->wide, mh, h->T)) {
         h->wide_state = -1;
         return TGP_OK;
@@ -220,10 +222,7 @@ static int wide_filter_call(tgp_handle* h, const double* y, uint32_t flags, doub
     TRY(copy_back(h, P_out, dP, nP, odev));
     if (h->profile || !odev) HIPCHK(hipStreamSynchronize(h->stream));
     resolve_profile(h);
-    for (int i = 0; i < 8; ++i) h->host_result[i] = 0.0;
-    h->host_result[0] = lml;
-    h->host_result[6] = tgp_steady::kStatusRan;
-    if (lml_out) *lml_out = lml;
+    note_served(h, Served::wide, tgp_wide::last_plan(h->wide).n0, lml, lml_out);
     h->wide_state = 1;
     *served = true;
     return TGP_OK;

@@ -54,9 +54,6 @@ int tgp_segment_logpdf_and_posterior_marginals(tgp_handle* h, int64_t T_total, i
     if (h->T != seg_hi - seg_lo || seg_lo < 0 || seg_hi > T_total || !y_seg) return h->fail(TGP_EINVAL, "tgp_segment_*: the bound model has not the segment's length");
     if ((mean_out != nullptr) != (var_out != nullptr) || (mean_out && !Rnew)) return h->fail(TGP_EINVAL, "tgp_segment_*: mean, var and Rnew go together");
     if (!h->modal) h->modal = tgp_modal::create();
-    h->modal_last = false;
-    h->dense_last_n0 = -1;
-    h->steady2_last = false;
     if (!tgp_modal::plan(h->modal, mh, T_total)) return h->fail(TGP_EUNSUPPORTED, "tgp_segment_*: the one-launch path does not apply to this model / series");
     const tgp_plan::Modal& md = tgp_modal::last_modal(h->modal);
     if ((seg_lo > 0 && !y_left) || (seg_hi < T_total && !y_right)) return h->fail(TGP_EINVAL, "tgp_segment_*: the neighbours' observations are missing");
@@ -71,6 +68,7 @@ int tgp_segment_logpdf_and_posterior_marginals(tgp_handle* h, int64_t T_total, i
     CallTimer tm(h, /*clear=*/false);
     const void* pR = nullptr;
     if (mean_out) TRY(stage_in(h, h->bRnew, Rnew, rshared ? sizeof(double) : nT, (flags & TGP_IN_DEVICE) != 0, &pR));
+    obs_changed(h);
     h->mv.y = y_seg;
     h->mv.missing = nullptr;
     tm.inputs_done();
@@ -105,11 +103,8 @@ int tgp_segment_logpdf_and_posterior_marginals(tgp_handle* h, int64_t T_total, i
     double ssq = 0.0, hq = 0.0;
     tgp_modal::finish_parts(h->modal, &ssq, &hq);
     double share = -0.5 * (hq + md.iS * ssq);
-    if (seg_lo == 0) share += -0.5 * ((double)T_total * 1.8378770664093454835606594728112 + md.LS + (double)(T_total - md.n0) * md.logS);
-    *lml_share = share;
-    h->modal_last = true;
-    h->reduce_valid = false;
-    h->smoother_valid = false;
+    if (seg_lo == 0) share += head_lml(md, T_total, 0.0, 0.0);      // (the head's and the stationary steps' constant terms: the first segment's)
+    note_served(h, Served::modal, tgp_modal::last_plan(h->modal).n0, share, lml_share);
     return TGP_OK;
 }
 

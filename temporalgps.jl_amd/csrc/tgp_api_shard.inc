@@ -176,8 +176,7 @@ int tgp_shard_steady_finish(tgp_handle* h, const double* gathered_dev, int world
     }
     TRY(tm.finish(lml_out));
     *served = h->host_result[6] == tgp_steady::kStatusRan ? 1 : 0;
-    h->reduce_valid = false;
-    h->smoother_valid = false;
+    drop_reduction(h);
     h->fold_valid = false;
     return TGP_OK;
 }

@@ -2,6 +2,8 @@
 noise variance / emission offset per step, irregular spacing -- through the C ABI against the oracle (lgssm.jl:147-238 with missings.jl:8-41,
 lti_sde.jl:135-146).  Tolerances as everywhere: logpdf 1e-10 relative, posterior marginals 1e-8 of their scale.  Every test asserts that the
 sweep engine served the call (tgp_sweep_info) -- or, where it must decline, that it did."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -237,3 +239,31 @@ def test_the_engine_can_be_switched_off_and_leaves_the_other_engines_alone(tgp):
     lp2 = ref.logpdf(model, y)
     got = tgp.logpdf(dm, y)
     assert hd.sweep_info()["served"] == 0 and abs(got - lp2) <= 1e-10 * abs(lp2)
+
+
+def test_the_served_flag_names_the_last_call_only(tgp):
+    """tgp_sweep_info reports "served" for the sweep engine's own call only: a later call on the same handle that another engine serves
+    (the one-launch modal path, the general engine) clears it."""
+    k, dt, s2 = KERNELS[2]
+    T = 5000
+    model, y, _ = U.gp_case(k, ("regular", 0.0, dt, T), s2, seed=2)
+    missing = np.random.default_rng(3).random(T) < 0.1
+    dm = _lti_device_model(tgp, model)
+    hd = dm.handle()
+    lp, _, _ = _reference(model, y, missing, 1e-18)
+    got = tgp.logpdf(dm, np.where(missing, np.nan, y))
+    assert hd.sweep_info()["served"] == 1 and abs(got - lp) <= 1e-10 * abs(lp)
+    hd.set_option(tgp._lib.OPT_PROFILE, 1)
+    hd.profile_reset()
+    lp2 = ref.logpdf(model, y)
+    got = tgp.logpdf(dm, y)
+    names = set(hd.profile())
+    hd.set_option(tgp._lib.OPT_PROFILE, 0)
+    assert not any(n.startswith("k_sweep") for n in names), names
+    assert hd.sweep_info()["served"] == 0 and abs(got - lp2) <= 1e-10 * abs(lp2)
+    # ... and so does a call of the general engine alone (tgp_smoother_forward), behind another sweep-served call
+    got = tgp.logpdf(dm, np.where(missing, np.nan, y))
+    assert hd.sweep_info()["served"] == 1 and abs(got - lp) <= 1e-10 * abs(lp)
+    lml, yc = ctypes.c_double(), np.ascontiguousarray(y, dtype=np.float64)
+    hd.check(hd.lib.tgp_smoother_forward(hd.h, yc.ctypes.data, None, 0, None, None, None, ctypes.byref(lml)))
+    assert hd.sweep_info()["served"] == 0 and abs(lml.value - lp2) <= 1e-10 * abs(lp2)

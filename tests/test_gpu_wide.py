@@ -2,6 +2,7 @@
 on the dense closed loop, one wave per chunk -- against the literal restatement of lgssm.jl:147-165 (oracle/lgssm_ref.py) at lengths its Python loops
 finish, and against the dense engine's sequential passes (TGP_OPT_WIDE = 0) beyond.  Products of kernels (lti_sde.jl:377-400) are what produces such states:
 ApproxPeriodicKernel() * Matern32Kernel() has d = 28.  Tolerance as everywhere: 1e-10 relative."""
+import ctypes
 import os
 
 import numpy as np
@@ -286,3 +287,54 @@ def test_wide_filter(tgp, d):
         assert np.max(np.abs(fm - fm_ref)) <= 1e-8 * max(1.0, np.abs(fm_ref).max()), (d, np.max(np.abs(fm - fm_ref)))
         assert np.max(np.abs(fP - fP_ref)) <= 1e-8 * max(1.0, np.abs(fP_ref).max()), (d, np.max(np.abs(fP - fP_ref)))
         assert len(names) == 1 and next(iter(names)).startswith("k_wide_lml"), names
+
+
+def wide_head(model, T):
+    """n0 of the wide-state engine's plan for this model and length (the pure host function tgp_wide_plan)"""
+    from temporalgps_jl_amd import _lib
+    lib = _lib.load()
+    d = len(model["x0m"])
+    c = lambda x: np.ascontiguousarray(np.asarray(x, dtype=np.float64))      # noqa: E731
+    blocks = [c(model["A"][0].T), c(model["a"][0]), c(model["Q"][0].T), c(model["H"][0]), c(np.atleast_1d(model["h"])[:1]),
+              c(np.atleast_1d(model["R"])[:1]), c(model["x0m"]), c(model["x0P"].T)]
+    info, K, S, vp = np.zeros(8, dtype=np.int64), np.zeros(d), np.zeros(1), np.zeros(2)
+    p = lambda x: x.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
+    assert lib.tgp_wide_plan(d, *[p(b) for b in blocks], T, 0, p(info), p(K), p(S), p(vp)) == 0 and info[0] == 0, info
+    return int(info[1])
+
+
+@pytest.mark.parametrize("middle", ["logpdf", "filter"])
+@pytest.mark.parametrize("d", [9, 16])
+def test_no_stale_reduction_or_diagnostic_behind_a_wide_call(tgp, d, middle):
+    """A call the wide engine serves stages new observations: a later TGP_REUSE_REDUCE call, which the wide engine declines, must not run the
+    general engine on the reduction of an earlier call's observations, and tgp_steady_steps reports the wide call (T - n0), not what an earlier
+    general posterior call left.  (9 <= d <= 16: the general engine bound is the chunked scan, whose reduction is the one at stake.)"""
+    T = 3000
+    model = oc.build_lgssm(KERNELS[d], ("regular", 0.0, 0.05, T), 0.02)
+    y1, y2 = draw(model, 1), draw(model, 2)
+    dm = device_model(tgp, model, wide=0)
+    hd = dm.handle()
+    lib = hd.lib
+    p = lambda x: x.ctypes.data      # noqa: E731
+    lml = ctypes.c_double()
+    mean, var, Rn = np.zeros(T), np.zeros(T), np.array([1e-18])
+    hd.check(lib.tgp_logpdf_and_posterior_marginals(hd.h, p(y1), None, p(Rn), tgp._lib.SHARED_R, ctypes.byref(lml), p(mean), p(var)))   # general engine, y1
+    hd.set_option(tgp._lib.OPT_WIDE, 1)
+    if middle == "logpdf":
+        run = lambda: hd.check(lib.tgp_logpdf(hd.h, p(y2), None, 0, ctypes.byref(lml)))      # noqa: E731
+    else:
+        fm, fP = np.zeros((T, d)), np.zeros((T, d, d))
+        run = lambda: hd.check(lib.tgp_filter(hd.h, p(y2), None, 0, p(fm), p(fP), ctypes.byref(lml)))      # noqa: E731
+    _, names = kernels_of(tgp, dm, run)
+    assert any(n.startswith("k_wide") for n in names), names
+    lp_ref = ref.logpdf(model, y2)
+    assert abs(lml.value - lp_ref) <= 1e-10 * abs(lp_ref), (lml.value, lp_ref)
+    fast, total = ctypes.c_int64(), ctypes.c_int64()
+    hd.check(lib.tgp_steady_steps(hd.h, ctypes.byref(fast), ctypes.byref(total)))
+    hd.check(lib.tgp_logpdf_and_posterior_marginals(hd.h, p(y2), None, p(Rn), tgp._lib.SHARED_R | tgp._lib.REUSE_REDUCE, ctypes.byref(lml),
+                                                    p(mean), p(var)))
+    assert abs(lml.value - lp_ref) <= 1e-10 * abs(lp_ref), (lml.value, lp_ref, ref.logpdf(model, y1))
+    m_ref, _ = tgp.posterior_marginals(device_model(tgp, model, wide=0), y2, Rn)       # a fresh handle
+    assert np.max(np.abs(mean - m_ref)) <= 1e-8 * max(1.0, np.abs(m_ref).max()), np.max(np.abs(mean - m_ref))
+    n0 = wide_head(model, T)
+    assert 0 < n0 < T and (fast.value, total.value) == (T - n0, T), (fast.value, total.value, n0)
