@@ -31,6 +31,32 @@ __device__ __forceinline__ double readlane_d(double x, int l) {      // l wave-u
     const int lo = __builtin_amdgcn_readlane(__double2loint(x), l), hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
     return __hiloint2double(hi, lo);
 }
+// the LDS kernels' inner product: a0 + (the lane's row phi) . (the state in the LDS line zb), on four accumulator chains
+template <int DP>
+__device__ __forceinline__ double lds_dot(const double (&phi)[DP], const double* zb, double a0) {
+    double a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll
+    for (int j = 0; j < DP; j += 8) {
+        const v2d q0 = *reinterpret_cast<const v2d*>(&zb[j]), q1 = *reinterpret_cast<const v2d*>(&zb[j + 2]);
+        const v2d q2 = *reinterpret_cast<const v2d*>(&zb[j + 4]), q3 = *reinterpret_cast<const v2d*>(&zb[j + 6]);
+        a0 = fma(phi[j], q0.x, a0);
+        a1 = fma(phi[j + 1], q0.y, a1);
+        a2 = fma(phi[j + 2], q1.x, a2);
+        a3 = fma(phi[j + 3], q1.y, a3);
+        a0 = fma(phi[j + 4], q2.x, a0);
+        a1 = fma(phi[j + 5], q2.y, a1);
+        a2 = fma(phi[j + 6], q3.x, a2);
+        a3 = fma(phi[j + 7], q3.y, a3);
+    }
+    return (a0 + a1) + (a2 + a3);
+}
+// the smoothed emission variance of step t behind the head (see k_wide_bwd): a constant but for the last n1 steps, plus the replaced noise
+__device__ __forceinline__ void store_var(double* __restrict__ var, long long t, long long T, const double* __restrict__ qtab, long long n1, double vbase, double qinf,
+                                          const double* __restrict__ Rnew, int rnew_per_step) {
+    const long long jt = T - 1 - t;
+    const double q = jt < n1 ? qtab[jt] : qinf;
+    var[t] = vbase - q + (rnew_per_step ? Rnew[t] : Rnew[0]);
+}
 
 // tab: [DP + 2][64] -- column j of the lanes' rows (lane i < d: row i of Phi; lane d: -g; zero beyond), then the lanes' input gains (K_i; 1 for the
 // observer) and constants (c_i; -g0 for the observer).  One wave per chunk [s0, s1) of the steps behind the head; its warm-up starts `halo` steps
@@ -65,21 +91,7 @@ __global__ __launch_bounds__(64) void k_wide_lml(const double* __restrict__ tab,
         double outr = 0.0;
         for (int l = 0; l < nb; ++l) {
             const double u = readlane_d(yv, l) - hh;
-            double a0 = fma(kin, u, cin), a1 = 0.0, a2 = 0.0, a3 = 0.0;
-#pragma unroll
-            for (int j = 0; j < DP; j += 8) {
-                const v2d q0 = *reinterpret_cast<const v2d*>(&zb[j]), q1 = *reinterpret_cast<const v2d*>(&zb[j + 2]);
-                const v2d q2 = *reinterpret_cast<const v2d*>(&zb[j + 4]), q3 = *reinterpret_cast<const v2d*>(&zb[j + 6]);
-                a0 = fma(phi[j], q0.x, a0);
-                a1 = fma(phi[j + 1], q0.y, a1);
-                a2 = fma(phi[j + 2], q1.x, a2);
-                a3 = fma(phi[j + 3], q1.y, a3);
-                a0 = fma(phi[j + 4], q2.x, a0);
-                a1 = fma(phi[j + 5], q2.y, a1);
-                a2 = fma(phi[j + 6], q3.x, a2);
-                a3 = fma(phi[j + 7], q3.y, a3);
-            }
-            const double acc = (a0 + a1) + (a2 + a3);
+            const double acc = lds_dot<DP>(phi, zb, fma(kin, u, cin));
             lds_sync();      // (every lane has read the old state)
             zb[lane] = acc;
             lds_sync();
@@ -129,22 +141,7 @@ __global__ __launch_bounds__(64) void k_wide_bwd(const double* __restrict__ tab,
         const bool own = tb - 63 < s1;      // (some step of the block is the chunk's own)
         double outm = 0.0;
         for (int l = 0; l < nb; ++l) {
-            const double rr = readlane_d(rv, l);
-            double a0 = kin * rr, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-#pragma unroll
-            for (int j = 0; j < DP; j += 8) {
-                const v2d q0 = *reinterpret_cast<const v2d*>(&zb[j]), q1 = *reinterpret_cast<const v2d*>(&zb[j + 2]);
-                const v2d q2 = *reinterpret_cast<const v2d*>(&zb[j + 4]), q3 = *reinterpret_cast<const v2d*>(&zb[j + 6]);
-                a0 = fma(phi[j], q0.x, a0);
-                a1 = fma(phi[j + 1], q0.y, a1);
-                a2 = fma(phi[j + 2], q1.x, a2);
-                a3 = fma(phi[j + 3], q1.y, a3);
-                a0 = fma(phi[j + 4], q2.x, a0);
-                a1 = fma(phi[j + 5], q2.y, a1);
-                a2 = fma(phi[j + 6], q3.x, a2);
-                a3 = fma(phi[j + 7], q3.y, a3);
-            }
-            const double acc = (a0 + a1) + (a2 + a3);
+            const double acc = lds_dot<DP>(phi, zb, kin * readlane_d(rv, l));
             lds_sync();
             zb[lane] = acc;
             lds_sync();
@@ -158,79 +155,153 @@ __global__ __launch_bounds__(64) void k_wide_bwd(const double* __restrict__ tab,
         const long long t = tb - lane;
         if (!ADJ && own && lane < nb && t < s1) {
             mean[t] = y[t] + outm;
-            const long long jt = T - 1 - t;
-            const double q = jt < n1 ? qtab[jt] : qinf;
-            var[t] = vbase - q + (rnew_per_step ? Rnew[t] : Rnew[0]);
+            store_var(var, t, T, qtab, n1, vbase, qinf, Rnew, rnew_per_step);
         }
     }
     if (chunk == 0 && lane < d) lam_out[lane] = zb[lane];      // lam at the head's end: the head's backward pass runs on the host
 }
 
-// ---- d <= 31: FOUR chunks per wave, no LDS.  A row of sixteen lanes holds one chunk's state in two registers (lane p: components p and p + 16) and the
-// two matching rows of the matrix; component j reaches the row's lanes as the DPP operand of the multiply-add itself (v_fmac_f64_dpp row_newbcast:j), and
-// so does the step's observation out of the row's block of sixteen.  66 multiply-adds per step and wave for four chunks (the LDS form: 32 and 16 broadcast
-// reads for one).  The table is the LDS kernels' (DP = 32).
+// ---- d <= 47: FOUR chunks per wave, no LDS.  A row of sixteen lanes holds one chunk's state in NB registers (lane p: components p, p + 16, ...; NB = 1
+// for d <= 15, 2 for d <= 31, 3 for d <= 47) and the NB matching rows of the matrix, 16 NB columns each; component j reaches the row's lanes as the DPP
+// operand of the multiply-add itself (v_fmac_f64_dpp row_newbcast:j), and so does the step's observation out of the row's block of sixteen.  NB = 2: 66
+// multiply-adds per step and wave for four chunks (the LDS form: 32 and 16 broadcast reads for one); NB = 3: 146 against 64 and 32, 144 doubles of rows,
+// a fifth of them in accumulation registers (v_accvgpr reads ahead of their multiply-adds).  The table is the LDS kernels' (DP = 32; NB = 3: DP = 64).
 // (measured: 8-9 cycles per v_fmac_f64_dpp at one wave per SIMD, four accumulator chains or two alike -- 0.187 ms at d = 28, T = 1e6; two 32-bit
 //  DPP moves and two plain multiply-adds per component instead run at the full issue rate and come to 0.208 ms; the LDS form 0.36 ms)
 template <int J>
 __device__ __forceinline__ void fmac_bc(double& acc, double src, double mul) {      // acc += (lane J of the row's src) * mul
     asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(mul), "n"(J));
 }
+// (a DPP operand must not be read within two cycles of the VALU write of its register, nor within five of a write to EXEC: the recogniser that
+//  spaces such pairs does not look into inline assembly.  Every register a step's multiply-adds read through DPP passes here first)
+__device__ __forceinline__ void dpp_settle(double& a, double& b) { asm volatile("s_nop 4" : "+v"(a), "+v"(b) : : "memory"); }
+__device__ __forceinline__ void dpp_settle(double& a, double& b, double& c) { asm volatile("s_nop 4" : "+v"(a), "+v"(b), "+v"(c) : : "memory"); }
+__device__ __forceinline__ void dpp_settle(double& a, double& b, double& c, double& e) { asm volatile("s_nop 4" : "+v"(a), "+v"(b), "+v"(c), "+v"(e) : : "memory"); }
+__device__ __forceinline__ void dpp_settle(double& a, double& b, double& c, double& e, double& f) {
+    asm volatile("s_nop 4" : "+v"(a), "+v"(b), "+v"(c), "+v"(e), "+v"(f) : : "memory");
+}
+template <int NB, int... Os, class... X>
+__device__ __forceinline__ void dpp_settle(double (&z)[NB], std::integer_sequence<int, Os...>, X&... x) {
+    dpp_settle(z[Os]..., x...);
+}
 struct Acc4 {
     double v[4];
     __device__ __forceinline__ double sum() const { return (v[0] + v[1]) + (v[2] + v[3]); }
 };
-template <int OFF, int... Js>
-__device__ __forceinline__ void dot16(Acc4& a, double z, const double (&phi)[32], std::integer_sequence<int, Js...>) {
+template <int OFF, int W, int... Js>
+__device__ __forceinline__ void dot16(Acc4& a, double z, const double (&phi)[W], std::integer_sequence<int, Js...>) {
     (fmac_bc<Js>(a.v[Js % 4], z, phi[OFF + Js]), ...);
 }
-template <int OFF, int... Js>      // both outputs of the lane against the same sixteen components, their chains interleaved (eight independent accumulators)
-__device__ __forceinline__ void dot16ab(Acc4& a, Acc4& b, double z, const double (&pA)[32], const double (&pB)[32], std::integer_sequence<int, Js...>) {
+template <int OFF, int W, int... Js>      // two outputs of the lane against the same sixteen components, their chains interleaved (eight independent accumulators)
+__device__ __forceinline__ void dot16ab(Acc4& a, Acc4& b, double z, const double (&pA)[W], const double (&pB)[W], std::integer_sequence<int, Js...>) {
     ((fmac_bc<Js>(a.v[Js % 4], z, pA[OFF + Js]), fmac_bc<Js>(b.v[Js % 4], z, pB[OFF + Js])), ...);
 }
 typedef std::make_integer_sequence<int, 16> Seq16;
+// n[o] = (output o's accumulators a[o], which hold the step's inputs) + P[o] . z for the lane's NB outputs -- the two outputs of NB = 2 interleaved, the
+// three of NB = 3 one after the other
+template <int NB>
+__device__ __forceinline__ void rows_dot(double (&n)[NB], Acc4 (&a)[NB], const double (&z)[NB], const double (&P)[NB][16 * NB]) {
+    if constexpr (NB == 2) {
+        dot16ab<0>(a[0], a[1], z[0], P[0], P[1], Seq16{});
+        dot16ab<16>(a[0], a[1], z[1], P[0], P[1], Seq16{});
+    } else {
+#pragma unroll
+        for (int o = 0; o < NB; ++o) {
+            dot16<0>(a[o], z[0], P[o], Seq16{});
+            if constexpr (NB == 3) {
+                dot16<16>(a[o], z[1], P[o], Seq16{});
+                dot16<32>(a[o], z[2], P[o], Seq16{});
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 0; o < NB; ++o) n[o] = a[o].sum();
+}
+template <int NB>
+__device__ __forceinline__ double pick(const double (&n)[NB], int o) {      // n[o], o wave-uniform
+    const double n0 = n[0], n1 = n[NB >= 2 ? 1 : 0], n2 = n[NB - 1];      // (locals: the choice is made by selects)
+    return o == 0 ? n0 : (o == 1 ? n1 : n2);
+}
 
 struct RowGeom {      // per lane, the same within a row
-    long long s0, s1, w;      // own steps [s0, s1); w: where the recursion starts (forward: w <= s0, upwards; backward: w >= s1, downwards from w - 1)
-    bool valid;
+    long long chunk, s0, s1, w;      // own steps [s0, s1); w: where the recursion starts (forward: w <= s0, upwards; backward: w >= s1, downwards from w - 1)
+    bool valid, from_head;           // from_head (forward): the recursion starts at the head's end from the head's own end state, not `halo` steps early from zero
 };
+template <bool FWD>
+__device__ __forceinline__ RowGeom row_geom(long long T, long long t_head, long long chunk_len, long long halo, long long chunks) {
+    RowGeom g;
+    g.chunk = (long long)blockIdx.x * 4 + (threadIdx.x >> 4);
+    g.valid = g.chunk < chunks;
+    g.s0 = t_head + g.chunk * chunk_len;
+    g.s1 = g.s0 + chunk_len;
+    if (g.s1 > T) g.s1 = T;
+    g.from_head = FWD && g.s0 - halo <= t_head;
+    if (FWD) {
+        g.w = g.from_head ? t_head : g.s0 - halo;
+    } else {
+        g.w = g.s1 + halo;
+        if (g.w > T) g.w = T;
+    }
+    if (!g.valid) g.s0 = g.s1 = g.w = T;
+    return g;
+}
+__device__ __forceinline__ long long longest_row(long long len) {      // the largest of the four rows' number of steps (wave-uniform)
+    long long nmax = 0;
+#pragma unroll
+    for (int r4 = 0; r4 < 4; ++r4) {
+        const int lo = __builtin_amdgcn_readlane((int)(len & 0xffffffffll), 16 * r4), hi = __builtin_amdgcn_readlane((int)(len >> 32), 16 * r4);
+        const long long v = ((long long)hi << 32) | (unsigned)lo;
+        nmax = v > nmax ? v : nmax;
+    }
+    return nmax;
+}
+template <int NB>
+constexpr int kTabDP = NB <= 2 ? 32 : 64;      // the rows of the matrix in the table of a model with NB components per lane (the LDS kernels' DP)
+// the lane's NB rows of the table's matrix and their input gains (the table's row behind the matrix)
+template <int NB>
+__device__ __forceinline__ void load_rows(const double* __restrict__ tab, int p, double (&P)[NB][16 * NB], double (&kin)[NB]) {
+    constexpr int DP = kTabDP<NB>;
+#pragma unroll
+    for (int o = 0; o < NB; ++o) {
+#pragma unroll
+        for (int j = 0; j < 16 * NB; ++j) P[o][j] = tab[(size_t)j * 64 + 16 * o + p];
+        kin[o] = tab[(size_t)DP * 64 + 16 * o + p];
+    }
+}
 
 template <int L, bool KEEP, int NB>
-__device__ __forceinline__ void fwd_step4(double& yv, double& zlo, double& zhi, const double (&pA)[32], const double (&pB)[32], double kA, double kB, double cA, double cB,
-                                          long long t, const RowGeom& g, bool obsB, bool is_obs, double& ssq, double* __restrict__ rout, double* __restrict__ mout, int d, int p) {
-    // (a DPP operand must not be read within two cycles of the VALU write of its register, nor within five of a write to EXEC: the recogniser that
-    //  spaces such pairs does not look into inline assembly)
-    asm volatile("s_nop 4" : "+v"(zlo), "+v"(zhi), "+v"(yv) : : "memory");
-    Acc4 a{{cA, 0.0, 0.0, 0.0}}, b{{cB, 0.0, 0.0, 0.0}};
-    fmac_bc<L>(a.v[3], yv, kA);
-    if constexpr (NB == 2) {
-        fmac_bc<L>(b.v[3], yv, kB);
-        dot16ab<0>(a, b, zlo, pA, pB, Seq16{});
-        dot16ab<16>(a, b, zhi, pA, pB, Seq16{});
-    } else {      // (d <= 15: one component per lane, sixteen columns)
-        dot16<0>(a, zlo, pA, Seq16{});
+__device__ __forceinline__ void fwd_step4(double& yv, double (&z)[NB], const double (&P)[NB][16 * NB], const double (&kin)[NB], const double (&cin)[NB], long long t,
+                                          const RowGeom& g, int obs_o, bool is_obs, double& ssq, double* __restrict__ rout, double* __restrict__ mout, int d, int p) {
+    dpp_settle(z, std::make_integer_sequence<int, NB>{}, yv);
+    Acc4 a[NB];
+#pragma unroll
+    for (int o = 0; o < NB; ++o) {
+        a[o] = Acc4{{cin[o], 0.0, 0.0, 0.0}};
+        fmac_bc<L>(a[o].v[3], yv, kin[o]);
     }
-    const double nA = a.sum(), nB = NB == 2 ? b.sum() : 0.0;
+    double n[NB];
+    rows_dot<NB>(n, a, z, P);
     const bool live = t < g.s1;
-    zlo = live ? nA : zlo;
-    zhi = live ? nB : zhi;
+#pragma unroll
+    for (int o = 0; o < NB; ++o) z[o] = live ? n[o] : z[o];
     const bool own = live && t >= g.s0;
-    double rr = obsB ? nB : nA;
+    double rr = pick<NB>(n, obs_o);
     rr = own ? rr : 0.0;
     ssq = fma(rr, rr, ssq);
     if (KEEP) {
         if (is_obs && own) rout[t] = rr;
     }
     if (mout != nullptr) {      // (_filter: the filtered mean of the chunk's own steps -- wave-uniform test)
-        if (own && p < d) mout[t * d + p] = nA;
-        if (NB == 2 && own && 16 + p < d) mout[t * d + 16 + p] = nB;
+#pragma unroll
+        for (int o = 0; o < NB; ++o)
+            if (own && 16 * o + p < d) mout[t * d + 16 * o + p] = n[o];
     }
 }
 template <bool KEEP, int NB, int... Ls>
-__device__ __forceinline__ void fwd_block4(double& yv, double& zlo, double& zhi, const double (&pA)[32], const double (&pB)[32], double kA, double kB, double cA, double cB,
-                                           long long t0, const RowGeom& g, bool obsB, bool is_obs, double& ssq, double* __restrict__ rout, double* __restrict__ mout, int d, int p,
+__device__ __forceinline__ void fwd_block4(double& yv, double (&z)[NB], const double (&P)[NB][16 * NB], const double (&kin)[NB], const double (&cin)[NB], long long t0,
+                                           const RowGeom& g, int obs_o, bool is_obs, double& ssq, double* __restrict__ rout, double* __restrict__ mout, int d, int p,
                                            std::integer_sequence<int, Ls...>) {
-    (fwd_step4<Ls, KEEP, NB>(yv, zlo, zhi, pA, pB, kA, kB, cA, cB, t0 + Ls, g, obsB, is_obs, ssq, rout, mout, d, p), ...);
+    (fwd_step4<Ls, KEEP, NB>(yv, z, P, kin, cin, t0 + Ls, g, obs_o, is_obs, ssq, rout, mout, d, p), ...);
 }
 
 template <bool KEEP, int NB>
@@ -238,78 +309,59 @@ __global__ __launch_bounds__(64) void k_wide_lml4(const double* __restrict__ tab
                                                    long long halo, long long chunks, int d, ZArg z0, double* __restrict__ part, double* __restrict__ rout,
                                                    const double* __restrict__ ht, double* __restrict__ mout) {
     auto obs = [&](long long t) { return y[t] - (ht != nullptr ? ht[t] : 0.0); };      // (see k_wide_lml)
-    const int lane = threadIdx.x, p = lane & 15, row = lane >> 4;
-    const long long chunk = (long long)blockIdx.x * 4 + row;
-    RowGeom g;
-    g.valid = chunk < chunks;
-    g.s0 = t_head + chunk * chunk_len;
-    g.s1 = g.s0 + chunk_len;
-    if (g.s1 > T) g.s1 = T;
-    const bool from_head = g.s0 - halo <= t_head;
-    g.w = from_head ? t_head : g.s0 - halo;
-    if (!g.valid) g.s0 = g.s1 = g.w = T;
-    double pA[32], pB[32];
+    const int p = threadIdx.x & 15;
+    const RowGeom g = row_geom<true>(T, t_head, chunk_len, halo, chunks);
+    double P[NB][16 * NB], kin[NB], cin[NB], z[NB];
+    load_rows<NB>(tab, p, P, kin);
 #pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        pA[j] = j < 16 * NB ? tab[(size_t)j * 64 + p] : 0.0;
-        pB[j] = NB == 2 ? tab[(size_t)j * 64 + 16 + p] : 0.0;
+    for (int o = 0; o < NB; ++o) {
+        cin[o] = tab[(size_t)(kTabDP<NB> + 1) * 64 + 16 * o + p] - kin[o] * hh;      // (u = y - hh folded into the constant)
+        z[o] = (g.valid && g.from_head) ? z0.z[16 * o + p] : 0.0;
     }
-    const double kA = tab[(size_t)32 * 64 + p], kB = tab[(size_t)32 * 64 + 16 + p];
-    const double cA = tab[(size_t)33 * 64 + p] - kA * hh, cB = tab[(size_t)33 * 64 + 16 + p] - kB * hh;      // (u = y - hh folded into the constant)
-    double zlo = (g.valid && from_head) ? z0.z[p] : 0.0, zhi = (g.valid && from_head) ? z0.z[16 + p] : 0.0;
-    const bool obsB = d >= 16, is_obs = p == (d & 15);
-    // the longest row's number of steps (wave-uniform)
-    const long long len = g.s1 - g.w;
-    long long nmax = 0;
-#pragma unroll
-    for (int r4 = 0; r4 < 4; ++r4) {
-        const int lo = __builtin_amdgcn_readlane((int)(len & 0xffffffffll), 16 * r4), hi = __builtin_amdgcn_readlane((int)(len >> 32), 16 * r4);
-        const long long v = ((long long)hi << 32) | (unsigned)lo;
-        nmax = v > nmax ? v : nmax;
-    }
+    const int obs_o = d >> 4;      // the observer (component d) is output obs_o of lane d & 15
+    const bool is_obs = p == (d & 15);
+    const long long nmax = longest_row(g.s1 - g.w);
     double ssq = 0.0;
     double yn = (g.w + p < g.s1) ? obs(g.w + p) : 0.0;
     for (long long kb = 0; kb < nmax; kb += 16) {
         double yv = yn;
         yn = (g.w + kb + 16 + p < g.s1) ? obs(g.w + kb + 16 + p) : 0.0;      // (the next block: on its way while this one runs)
-        fwd_block4<KEEP, NB>(yv, zlo, zhi, pA, pB, kA, kB, cA, cB, g.w + kb, g, obsB, is_obs, ssq, rout, mout, d, p, Seq16{});
+        fwd_block4<KEEP, NB>(yv, z, P, kin, cin, g.w + kb, g, obs_o, is_obs, ssq, rout, mout, d, p, Seq16{});
     }
-    if (is_obs && g.valid) part[chunk] = ssq;
+    if (is_obs && g.valid) part[g.chunk] = ssq;
 }
 
 template <int L, int NB, bool ADJ>
-__device__ __forceinline__ void bwd_step4(double& rv, double& yv, double& zlo, double& zhi, const double (&pA)[32], const double (&pB)[32], double kA, double kB, double yA, double yB,
-                                          long long t, const RowGeom& g, bool obsB, bool is_obs, double* __restrict__ mean, double* __restrict__ lamT, int d, int p) {
-    asm volatile("s_nop 4" : "+v"(zlo), "+v"(zhi), "+v"(rv), "+v"(yv) : : "memory");
-    Acc4 a{{0.0, 0.0, 0.0, 0.0}}, b{{0.0, 0.0, 0.0, 0.0}};
-    fmac_bc<L>(a.v[3], rv, kA);
-    fmac_bc<L>(a.v[2], yv, yA);      // (1 at the observer: its sum is the step's mean; its slot of the state multiplies a zero column)
-    if constexpr (NB == 2) {
-        fmac_bc<L>(b.v[3], rv, kB);
-        fmac_bc<L>(b.v[2], yv, yB);
-        dot16ab<0>(a, b, zlo, pA, pB, Seq16{});
-        dot16ab<16>(a, b, zhi, pA, pB, Seq16{});
-    } else {
-        dot16<0>(a, zlo, pA, Seq16{});
+__device__ __forceinline__ void bwd_step4(double& rv, double& yv, double (&z)[NB], const double (&P)[NB][16 * NB], const double (&kin)[NB], const double (&yin)[NB], long long t,
+                                          const RowGeom& g, int obs_o, bool is_obs, double* __restrict__ mean, double* __restrict__ lamT, int d, int p) {
+    dpp_settle(z, std::make_integer_sequence<int, NB>{}, rv, yv);
+    Acc4 a[NB];
+#pragma unroll
+    for (int o = 0; o < NB; ++o) {
+        a[o] = Acc4{{0.0, 0.0, 0.0, 0.0}};
+        fmac_bc<L>(a[o].v[3], rv, kin[o]);
+        fmac_bc<L>(a[o].v[2], yv, yin[o]);      // (1 at the observer: its sum is the step's mean; its slot of the state multiplies a zero column)
     }
-    const double nA = a.sum(), nB = NB == 2 ? b.sum() : 0.0;
+    double n[NB];
+    rows_dot<NB>(n, a, z, P);
     const bool live = t >= g.s0;
-    zlo = live ? nA : zlo;
-    zhi = live ? nB : zhi;
+#pragma unroll
+    for (int o = 0; o < NB; ++o) z[o] = live ? n[o] : z[o];
     if constexpr (ADJ) {      // (lam_t of the row's own steps: see k_wide_bwd)
         if (live && t < g.s1) {
-            if (p < d) lamT[t * d + p] = nA;
-            if (NB == 2 && 16 + p < d) lamT[t * d + 16 + p] = nB;
+#pragma unroll
+            for (int o = 0; o < NB; ++o)
+                if (16 * o + p < d) lamT[t * d + 16 * o + p] = n[o];
         }
     } else {
-        if (is_obs && live && t < g.s1) mean[t] = obsB ? nB : nA;
+        if (is_obs && live && t < g.s1) mean[t] = pick<NB>(n, obs_o);
     }
 }
 template <int NB, bool ADJ, int... Ls>
-__device__ __forceinline__ void bwd_block4(double& rv, double& yv, double& zlo, double& zhi, const double (&pA)[32], const double (&pB)[32], double kA, double kB, double yA, double yB,
-                                           long long t0, const RowGeom& g, bool obsB, bool is_obs, double* __restrict__ mean, double* __restrict__ lamT, int d, int p,
+__device__ __forceinline__ void bwd_block4(double& rv, double& yv, double (&z)[NB], const double (&P)[NB][16 * NB], const double (&kin)[NB], const double (&yin)[NB], long long t0,
+                                           const RowGeom& g, int obs_o, bool is_obs, double* __restrict__ mean, double* __restrict__ lamT, int d, int p,
                                            std::integer_sequence<int, Ls...>) {
-    (bwd_step4<Ls, NB, ADJ>(rv, yv, zlo, zhi, pA, pB, kA, kB, yA, yB, t0 - Ls, g, obsB, is_obs, mean, lamT, d, p), ...);
+    (bwd_step4<Ls, NB, ADJ>(rv, yv, z, P, kin, yin, t0 - Ls, g, obs_o, is_obs, mean, lamT, d, p), ...);
 }
 
 template <int NB, bool ADJ = false>
@@ -317,34 +369,18 @@ __global__ __launch_bounds__(64) void k_wide_bwd4(const double* __restrict__ tab
                                                    int rnew_per_step, const double* __restrict__ qtab, long long n1, double vbase, double qinf, long long T, long long t_head,
                                                    long long chunk_len, long long halo, long long chunks, int d, double* __restrict__ mean, double* __restrict__ var,
                                                    double* __restrict__ lam_out, double* __restrict__ lamT) {
-    const int lane = threadIdx.x, p = lane & 15, row = lane >> 4;
-    const long long chunk = (long long)blockIdx.x * 4 + row;
-    RowGeom g;
-    g.valid = chunk < chunks;
-    g.s0 = t_head + chunk * chunk_len;
-    g.s1 = g.s0 + chunk_len;
-    if (g.s1 > T) g.s1 = T;
-    g.w = g.s1 + halo;
-    if (g.w > T) g.w = T;
-    if (!g.valid) g.s0 = g.s1 = g.w = T;
-    double pA[32], pB[32];
+    const int p = threadIdx.x & 15;
+    const RowGeom g = row_geom<false>(T, t_head, chunk_len, halo, chunks);
+    const int obs_o = d >> 4;
+    const bool is_obs = p == (d & 15);
+    double P[NB][16 * NB], kin[NB], yin[NB], z[NB];
+    load_rows<NB>(tab, p, P, kin);
 #pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        pA[j] = j < 16 * NB ? tab[(size_t)j * 64 + p] : 0.0;
-        pB[j] = NB == 2 ? tab[(size_t)j * 64 + 16 + p] : 0.0;
+    for (int o = 0; o < NB; ++o) {
+        yin[o] = (is_obs && o == obs_o) ? 1.0 : 0.0;
+        z[o] = 0.0;
     }
-    const double kA = tab[(size_t)32 * 64 + p], kB = tab[(size_t)32 * 64 + 16 + p];
-    const bool obsB = d >= 16, is_obs = p == (d & 15);
-    const double yA = (is_obs && !obsB) ? 1.0 : 0.0, yB = (is_obs && obsB) ? 1.0 : 0.0;
-    double zlo = 0.0, zhi = 0.0;
-    const long long len = g.w - g.s0;
-    long long nmax = 0;
-#pragma unroll
-    for (int r4 = 0; r4 < 4; ++r4) {
-        const int lo = __builtin_amdgcn_readlane((int)(len & 0xffffffffll), 16 * r4), hi = __builtin_amdgcn_readlane((int)(len >> 32), 16 * r4);
-        const long long v = ((long long)hi << 32) | (unsigned)lo;
-        nmax = v > nmax ? v : nmax;
-    }
+    const long long nmax = longest_row(g.w - g.s0);
     const long long top = g.w - 1;      // the row's first step
     double rn = (top - p >= g.s0) ? r[top - p] : 0.0;
     for (long long kb = 0; kb < nmax; kb += 16) {      // the block holds the steps top - kb, top - kb - 1, ..., one per lane of the row
@@ -353,16 +389,13 @@ __global__ __launch_bounds__(64) void k_wide_bwd4(const double* __restrict__ tab
         rn = (tl - 16 >= g.s0) ? r[tl - 16] : 0.0;
         const bool mine = tl >= g.s0 && tl < g.s1;
         double yv = (!ADJ && mine) ? y[tl] : 0.0;
-        bwd_block4<NB, ADJ>(rv, yv, zlo, zhi, pA, pB, kA, kB, yA, yB, top - kb, g, obsB, is_obs, mean, lamT, d, p, Seq16{});
-        if (!ADJ && mine) {
-            const long long jt = T - 1 - tl;
-            const double q = jt < n1 ? qtab[jt] : qinf;
-            var[tl] = vbase - q + (rnew_per_step ? Rnew[tl] : Rnew[0]);
-        }
+        bwd_block4<NB, ADJ>(rv, yv, z, P, kin, yin, top - kb, g, obs_o, is_obs, mean, lamT, d, p, Seq16{});
+        if (!ADJ && mine) store_var(var, tl, T, qtab, n1, vbase, qinf, Rnew, rnew_per_step);
     }
-    if (g.valid && chunk == 0) {      // lam at the head's end: the head's backward pass runs on the host
-        if (p < d) lam_out[p] = zlo;
-        if (16 + p < d) lam_out[16 + p] = zhi;
+    if (g.valid && g.chunk == 0) {      // lam at the head's end: the head's backward pass runs on the host
+#pragma unroll
+        for (int o = 0; o < NB; ++o)
+            if (16 * o + p < d) lam_out[16 * o + p] = z[o];
     }
 }
 
@@ -437,182 +470,6 @@ __global__ __launch_bounds__(64) void k_wide_rand(const double* __restrict__ tab
                 }
             }
         }
-    }
-}
-
-// ---- 32 <= d <= 47: the same four chunks per wave with THREE components per lane (p, p + 16, p + 32) and three rows of the matrix of 48 columns each --
-// 144 doubles of rows, a fifth of them in accumulation registers (v_accvgpr reads ahead of their multiply-adds); 146 multiply-adds per step and wave
-// against the LDS form's 64 and 32 broadcast reads for ONE chunk.  The table is the LDS kernels' (DP = 64).
-template <int OFF, int W, int... Js>
-__device__ __forceinline__ void dot16w(double (&a)[4], double z, const double (&phi)[W], std::integer_sequence<int, Js...>) {
-    (fmac_bc<Js>(a[Js % 4], z, phi[OFF + Js]), ...);
-}
-template <int L, bool KEEP>
-__device__ __forceinline__ void fwd_step43(double& yv, double (&z)[3], const double (&P)[3][48], const double (&kin)[3], const double (&cin)[3], long long t, const RowGeom& g,
-                                           int obs_o, bool is_obs, double& ssq, double* __restrict__ rout, double* __restrict__ mout, int d, int p) {
-    asm volatile("s_nop 4" : "+v"(z[0]), "+v"(z[1]), "+v"(z[2]), "+v"(yv) : : "memory");      // (DPP hazards: see fwd_step4)
-    double n[3];
-#pragma unroll
-    for (int o = 0; o < 3; ++o) {
-        double a[4] = {cin[o], 0.0, 0.0, 0.0};
-        fmac_bc<L>(a[3], yv, kin[o]);
-        dot16w<0, 48>(a, z[0], P[o], Seq16{});
-        dot16w<16, 48>(a, z[1], P[o], Seq16{});
-        dot16w<32, 48>(a, z[2], P[o], Seq16{});
-        n[o] = (a[0] + a[1]) + (a[2] + a[3]);
-    }
-    const bool live = t < g.s1;
-#pragma unroll
-    for (int o = 0; o < 3; ++o) z[o] = live ? n[o] : z[o];
-    const bool own = live && t >= g.s0;
-    double rr = obs_o == 0 ? n[0] : (obs_o == 1 ? n[1] : n[2]);
-    rr = own ? rr : 0.0;
-    ssq = fma(rr, rr, ssq);
-    if (KEEP) {
-        if (is_obs && own) rout[t] = rr;
-    }
-    if (mout != nullptr) {
-#pragma unroll
-        for (int o = 0; o < 3; ++o)
-            if (own && 16 * o + p < d) mout[t * d + 16 * o + p] = n[o];
-    }
-}
-template <bool KEEP, int... Ls>
-__device__ __forceinline__ void fwd_block43(double& yv, double (&z)[3], const double (&P)[3][48], const double (&kin)[3], const double (&cin)[3], long long t0, const RowGeom& g,
-                                            int obs_o, bool is_obs, double& ssq, double* __restrict__ rout, double* __restrict__ mout, int d, int p, std::integer_sequence<int, Ls...>) {
-    (fwd_step43<Ls, KEEP>(yv, z, P, kin, cin, t0 + Ls, g, obs_o, is_obs, ssq, rout, mout, d, p), ...);
-}
-template <bool KEEP>
-__global__ __launch_bounds__(64) void k_wide_lml43(const double* __restrict__ tab, const double* __restrict__ y, double hh, long long T, long long t_head, long long chunk_len,
-                                                    long long halo, long long chunks, int d, ZArg z0, double* __restrict__ part, double* __restrict__ rout,
-                                                    const double* __restrict__ ht, double* __restrict__ mout) {
-    auto obs = [&](long long t) { return y[t] - (ht != nullptr ? ht[t] : 0.0); };
-    const int lane = threadIdx.x, p = lane & 15, row = lane >> 4;
-    const long long chunk = (long long)blockIdx.x * 4 + row;
-    RowGeom g;
-    g.valid = chunk < chunks;
-    g.s0 = t_head + chunk * chunk_len;
-    g.s1 = g.s0 + chunk_len;
-    if (g.s1 > T) g.s1 = T;
-    const bool from_head = g.s0 - halo <= t_head;
-    g.w = from_head ? t_head : g.s0 - halo;
-    if (!g.valid) g.s0 = g.s1 = g.w = T;
-    double P[3][48], kin[3], cin[3], z[3];
-#pragma unroll
-    for (int o = 0; o < 3; ++o) {
-#pragma unroll
-        for (int j = 0; j < 48; ++j) P[o][j] = tab[(size_t)j * 64 + 16 * o + p];
-        kin[o] = tab[(size_t)64 * 64 + 16 * o + p];
-        cin[o] = tab[(size_t)65 * 64 + 16 * o + p] - kin[o] * hh;
-        z[o] = (g.valid && from_head) ? z0.z[16 * o + p] : 0.0;
-    }
-    const int obs_o = d >> 4;
-    const bool is_obs = p == (d & 15);
-    const long long len = g.s1 - g.w;
-    long long nmax = 0;
-#pragma unroll
-    for (int r4 = 0; r4 < 4; ++r4) {
-        const int lo = __builtin_amdgcn_readlane((int)(len & 0xffffffffll), 16 * r4), hi = __builtin_amdgcn_readlane((int)(len >> 32), 16 * r4);
-        const long long v = ((long long)hi << 32) | (unsigned)lo;
-        nmax = v > nmax ? v : nmax;
-    }
-    double ssq = 0.0;
-    double yn = (g.w + p < g.s1) ? obs(g.w + p) : 0.0;
-    for (long long kb = 0; kb < nmax; kb += 16) {
-        double yv = yn;
-        yn = (g.w + kb + 16 + p < g.s1) ? obs(g.w + kb + 16 + p) : 0.0;
-        fwd_block43<KEEP>(yv, z, P, kin, cin, g.w + kb, g, obs_o, is_obs, ssq, rout, mout, d, p, Seq16{});
-    }
-    if (is_obs && g.valid) part[chunk] = ssq;
-}
-
-template <int L, bool ADJ>
-__device__ __forceinline__ void bwd_step43(double& rv, double& yv, double (&z)[3], const double (&P)[3][48], const double (&kin)[3], const double (&yin)[3], long long t,
-                                           const RowGeom& g, int obs_o, bool is_obs, double* __restrict__ mean, double* __restrict__ lamT, int d, int p) {
-    asm volatile("s_nop 4" : "+v"(z[0]), "+v"(z[1]), "+v"(z[2]), "+v"(rv), "+v"(yv) : : "memory");
-    double n[3];
-#pragma unroll
-    for (int o = 0; o < 3; ++o) {
-        double a[4] = {0.0, 0.0, 0.0, 0.0};
-        fmac_bc<L>(a[3], rv, kin[o]);
-        fmac_bc<L>(a[2], yv, yin[o]);      // (1 at the observer)
-        dot16w<0, 48>(a, z[0], P[o], Seq16{});
-        dot16w<16, 48>(a, z[1], P[o], Seq16{});
-        dot16w<32, 48>(a, z[2], P[o], Seq16{});
-        n[o] = (a[0] + a[1]) + (a[2] + a[3]);
-    }
-    const bool live = t >= g.s0;
-#pragma unroll
-    for (int o = 0; o < 3; ++o) z[o] = live ? n[o] : z[o];
-    if constexpr (ADJ) {      // (lam_t of the row's own steps: see k_wide_bwd)
-        if (live && t < g.s1) {
-#pragma unroll
-            for (int o = 0; o < 3; ++o)
-                if (16 * o + p < d) lamT[t * d + 16 * o + p] = n[o];
-        }
-    } else {
-        if (is_obs && live && t < g.s1) mean[t] = obs_o == 0 ? n[0] : (obs_o == 1 ? n[1] : n[2]);
-    }
-}
-template <bool ADJ, int... Ls>
-__device__ __forceinline__ void bwd_block43(double& rv, double& yv, double (&z)[3], const double (&P)[3][48], const double (&kin)[3], const double (&yin)[3], long long t0,
-                                            const RowGeom& g, int obs_o, bool is_obs, double* __restrict__ mean, double* __restrict__ lamT, int d, int p,
-                                            std::integer_sequence<int, Ls...>) {
-    (bwd_step43<Ls, ADJ>(rv, yv, z, P, kin, yin, t0 - Ls, g, obs_o, is_obs, mean, lamT, d, p), ...);
-}
-template <bool ADJ = false>
-__global__ __launch_bounds__(64) void k_wide_bwd43(const double* __restrict__ tab, const double* __restrict__ y, const double* __restrict__ r, const double* __restrict__ Rnew,
-                                                    int rnew_per_step, const double* __restrict__ qtab, long long n1, double vbase, double qinf, long long T, long long t_head,
-                                                    long long chunk_len, long long halo, long long chunks, int d, double* __restrict__ mean, double* __restrict__ var,
-                                                    double* __restrict__ lam_out, double* __restrict__ lamT) {
-    const int lane = threadIdx.x, p = lane & 15, row = lane >> 4;
-    const long long chunk = (long long)blockIdx.x * 4 + row;
-    RowGeom g;
-    g.valid = chunk < chunks;
-    g.s0 = t_head + chunk * chunk_len;
-    g.s1 = g.s0 + chunk_len;
-    if (g.s1 > T) g.s1 = T;
-    g.w = g.s1 + halo;
-    if (g.w > T) g.w = T;
-    if (!g.valid) g.s0 = g.s1 = g.w = T;
-    const int obs_o = d >> 4;
-    const bool is_obs = p == (d & 15);
-    double P[3][48], kin[3], yin[3], z[3];
-#pragma unroll
-    for (int o = 0; o < 3; ++o) {
-#pragma unroll
-        for (int j = 0; j < 48; ++j) P[o][j] = tab[(size_t)j * 64 + 16 * o + p];
-        kin[o] = tab[(size_t)64 * 64 + 16 * o + p];
-        yin[o] = (is_obs && o == obs_o) ? 1.0 : 0.0;
-        z[o] = 0.0;
-    }
-    const long long len = g.w - g.s0;
-    long long nmax = 0;
-#pragma unroll
-    for (int r4 = 0; r4 < 4; ++r4) {
-        const int lo = __builtin_amdgcn_readlane((int)(len & 0xffffffffll), 16 * r4), hi = __builtin_amdgcn_readlane((int)(len >> 32), 16 * r4);
-        const long long v = ((long long)hi << 32) | (unsigned)lo;
-        nmax = v > nmax ? v : nmax;
-    }
-    const long long top = g.w - 1;
-    double rn = (top - p >= g.s0) ? r[top - p] : 0.0;
-    for (long long kb = 0; kb < nmax; kb += 16) {
-        double rv = rn;
-        const long long tl = top - kb - p;
-        rn = (tl - 16 >= g.s0) ? r[tl - 16] : 0.0;
-        const bool mine = tl >= g.s0 && tl < g.s1;
-        double yv = (!ADJ && mine) ? y[tl] : 0.0;
-        bwd_block43<ADJ>(rv, yv, z, P, kin, yin, top - kb, g, obs_o, is_obs, mean, lamT, d, p, Seq16{});
-        if (!ADJ && mine) {
-            const long long jt = T - 1 - tl;
-            const double q = jt < n1 ? qtab[jt] : qinf;
-            var[tl] = vbase - q + (rnew_per_step ? Rnew[tl] : Rnew[0]);
-        }
-    }
-    if (g.valid && chunk == 0) {
-#pragma unroll
-        for (int o = 0; o < 3; ++o)
-            if (16 * o + p < d) lam_out[16 * o + p] = z[o];
     }
 }
 
@@ -707,6 +564,23 @@ double norm_inf(int d, const double* X) {
     return n;
 }
 
+// The kernel family that serves a planned model, chosen once by plan(): one chunk per wave round an LDS line (k_wide_lml<DP>, k_wide_bwd<DP>), or four chunks
+// per wave with NB components per lane (k_wide_lml4<., NB>, k_wide_bwd4<NB>).  The name is what kernel_name() reports (profile labels, tests, bench.py).
+enum Form { kLds32, kLds64, kDpp1, kDpp2, kDpp3 };
+const char* form_name(Form f) {
+    switch (f) {
+        case kDpp1: return "k_wide_lml4<16>";
+        case kDpp2: return "k_wide_lml4";
+        case kDpp3: return "k_wide_lml4<48>";
+        case kLds32: return "k_wide_lml<32>";
+        default: return "k_wide_lml<64>";
+    }
+}
+// Engine::pinned, in doubles: the head's y, Rnew, means, variances and emission offsets, lam at the head's end, the chunks' sums (TGP_WIDE_CHUNKS: 65536 at most)
+namespace pin {
+constexpr size_t yh = 0, Rh = yh + kHeadMax, mh = Rh + kHeadMax, vh = mh + kHeadMax, hth = vh + kHeadMax, lam = hth + kHeadMax, part = lam + 64, size = part + 65536;
+}
+
 }  // namespace
 
 struct Engine {
@@ -732,9 +606,9 @@ struct Engine {
     bool dev_current = false, dev_post_current = false;
     double* rbuf = nullptr;                // device: the innovations of the steps behind the head [T]
     size_t rbuf_cap = 0;
-    double* pinned = nullptr;              // [kHeadMax] head y | [kHeadMax] head Rnew | [kHeadMax] head means | [kHeadMax] head vars | [64] lam | [kMaxChunks] sums
+    double* pinned = nullptr;              // (laid out by pin::)
     std::vector<double> head_r, head_m;
-    const char* kname = "k_wide_lml<32>";
+    Form form = kLds32;
     std::vector<double> Pf_head;          // the head's filtered covariances [n0][d d] (row-major = column-major: symmetric), for _filter; empty: too large
     double* rand_dev = nullptr;           // device: k_wide_rand's table
     size_t rand_cap = 0;
@@ -743,9 +617,8 @@ struct Engine {
     int adj_halo = -1;                     // -1: Psi does not forget within 2^20 steps
     std::vector<double> taba_host;         // [DP + 1][64]: rows of Psi, gains h / S (no observer)
     double *adj_dev = nullptr, *adj_pin = nullptr;      // device: forward table | backward table | G; pinned: G | the head's end state
-    size_t adj_cap = 0;
     double *mbuf = nullptr, *lbuf = nullptr, *gpart = nullptr;      // device: m [T][d], lam [T][d], partial sums of G
-    size_t mbuf_cap = 0, gpart_cap = 0;
+    size_t mbuf_cap = 0, lbuf_cap = 0, gpart_cap = 0;
 };
 
 namespace {
@@ -770,7 +643,7 @@ void destroy(Engine* e) {
     delete e;
 }
 const Info& last_plan(const Engine* e) { return e->info; }
-const char* kernel_name(const Engine* e) { return e->kname; }
+const char* kernel_name(const Engine* e) { return form_name(e->form); }
 void stationary(const Engine* e, double* K, double* S, double* vbase, double* qinf) {
     const int d = e->d, n0 = e->info.n0;
     if (K && n0 > 0)
@@ -850,7 +723,8 @@ bool plan(Engine* e, const ModelHost& m, long long T) {
     const size_t dd = (size_t)d * d;
     e->d = d;
     e->dp = d <= 31 ? 32 : 64;
-    e->kname = e->dp == 32 ? (dpp_enabled() ? (d <= 15 ? "k_wide_lml4<16>" : "k_wide_lml4") : "k_wide_lml<32>") : (d <= 47 && dpp_enabled() ? "k_wide_lml4<48>" : "k_wide_lml<64>");
+    const bool dpp = d <= 47 && dpp_enabled();
+    e->form = dpp ? (d <= 15 ? kDpp1 : d <= 31 ? kDpp2 : kDpp3) : (e->dp == 32 ? kLds32 : kLds64);
     e->A.assign(dd, 0.0);
     std::vector<double> Q(dd), P(dd), AP(dd), Pp(dd), Pf(dd), v(d);
     for (int i = 0; i < d; ++i)
@@ -958,7 +832,6 @@ bool plan(Engine* e, const ModelHost& m, long long T) {
     e->info.halo = (int)halo;
     const long long Tb = T - n0;      // steps behind the head
     if (Tb < 64) return done(kTooShort);
-    // chunks: as many waves as the chip holds several times over, none shorter than 64 steps
     // chunks: one wave's worth of them per SIMD (4096) at least -- none shorter than 64 steps --, and more (up to 16384: the stalls of a wave's dependent
     // DPP multiply-adds are another wave's issue slots) once a chunk is still four halos long: 12 % at T = 1e7 (scripts/r06_mid_d_time.py)
     static const long long forced_chunks = [] {      // TGP_WIDE_CHUNKS=<n>: development
@@ -991,29 +864,42 @@ bool plan(Engine* e, const ModelHost& m, long long T) {
 }
 
 namespace {
+// AK = A K and Psi = (I - h K') A' = A' - h (A K)' of the step with gain Kv: the backward recursion's matrix
+void back_step(const Engine* e, const double* Kv, std::vector<double>& AK, std::vector<double>& Psi) {
+    const int d = e->d;
+    const double *A = e->A.data(), *h = e->hvec.data();
+    for (int j = 0; j < d; ++j) {
+        double s = 0.0;
+        for (int k = 0; k < d; ++k) s += A[(size_t)j * d + k] * Kv[k];
+        AK[j] = s;
+    }
+    for (int i = 0; i < d; ++i)
+        for (int j = 0; j < d; ++j) Psi[(size_t)i * d + j] = A[(size_t)j * d + i] - h[i] * AK[j];
+}
+// the backward kernels' table (see k_wide_bwd): the rows of Psi, the gains h / S; gw != nullptr: the observer's row gw and gain -R / S as well
+void back_table(const Engine* e, const std::vector<double>& Psi, const double* gw, std::vector<double>& tab) {
+    const int d = e->d, DP = e->dp;
+    const double S = e->Sss;
+    tab.assign((size_t)(DP + 1) * 64, 0.0);
+    for (int i = 0; i < d; ++i) {
+        for (int j = 0; j < d; ++j) tab[(size_t)j * 64 + i] = Psi[(size_t)i * d + j];
+        tab[(size_t)DP * 64 + i] = e->hvec[i] / S;
+    }
+    if (gw == nullptr) return;
+    for (int j = 0; j < d; ++j) tab[(size_t)j * 64 + d] = gw[j];      // the observer: mean_t - y_t = gw . lam_(t+1) - (R / S) r_t
+    tab[(size_t)DP * 64 + d] = -e->R / S;
+}
+
 // The posterior half of the plan, data-free as the rest: Psi = (I - h K') A' and gw = R A K of the stationary step, halo_back, the partial sums
 // q_j = sum_(k < j) (gw' Psi^k h)^2 / S of the variance's quadratic form at the series' end (n1 of them until they no longer change), Lam_inf = the
 // fixed point of Lam = h h' / S + Psi Lam Psi' by doubling, and from it the head's variances backwards through the head's own steps.
 int plan_post(Engine* e, long long T) {
-    const int d = e->d, DP = e->dp, n0 = e->info.n0;
+    const int d = e->d, n0 = e->info.n0;
     const size_t dd = (size_t)d * d;
-    const double *A = e->A.data(), *h = e->hvec.data();
+    const double* h = e->hvec.data();
     const double R = e->R, S = e->Sss;
-    const double* K = e->Kt.data() + (size_t)(n0 - 1) * d;
-    auto AK_of = [&](const double* Kv, std::vector<double>& out) {
-        for (int j = 0; j < d; ++j) {
-            double s = 0.0;
-            for (int k = 0; k < d; ++k) s += A[(size_t)j * d + k] * Kv[k];
-            out[j] = s;
-        }
-    };
-    auto psi_of = [&](const std::vector<double>& AK, std::vector<double>& Psi) {      // Psi[i][j] = A[j][i] - h_i (A K)_j
-        for (int i = 0; i < d; ++i)
-            for (int j = 0; j < d; ++j) Psi[(size_t)i * d + j] = A[(size_t)j * d + i] - h[i] * AK[j];
-    };
     std::vector<double> AK(d), Psi(dd), gw(d);
-    AK_of(K, AK);
-    psi_of(AK, Psi);
+    back_step(e, e->Kt.data() + (size_t)(n0 - 1) * d, AK, Psi);
     for (int j = 0; j < d; ++j) gw[j] = R * AK[j];
     const long long hb = halo_of(d, Psi);
     if (hb < 0) return kSlowMixing;
@@ -1074,9 +960,8 @@ int plan_post(Engine* e, long long T) {
     {
         std::vector<double> AKt(d), gwt(d), Pt(dd);
         for (int t = n0 - 1; t >= 0; --t) {
-            const double* Kv = e->Kt.data() + (size_t)t * d;
             const double St = e->St[t];
-            AK_of(Kv, AKt);
+            back_step(e, e->Kt.data() + (size_t)t * d, AKt, Pt);
             for (int j = 0; j < d; ++j) gwt[j] = R * AKt[j];
             double qf = 0.0;
             for (int i = 0; i < d; ++i) {
@@ -1086,7 +971,6 @@ int plan_post(Engine* e, long long T) {
             }
             e->headvar[t] = (St - R) * R / St - qf;
             if (t == 0) break;
-            psi_of(AKt, Pt);
             matmul(d, Pt.data(), Lam.data(), T1.data());
             for (int i = 0; i < d; ++i)
                 for (int j = 0; j <= i; ++j) {
@@ -1097,14 +981,7 @@ int plan_post(Engine* e, long long T) {
             Lam.swap(T2);
         }
     }
-    // ---- the backward kernel's table
-    e->tabb_host.assign((size_t)(DP + 1) * 64, 0.0);
-    for (int i = 0; i < d; ++i) {
-        for (int j = 0; j < d; ++j) e->tabb_host[(size_t)j * 64 + i] = Psi[(size_t)i * d + j];
-        e->tabb_host[(size_t)DP * 64 + i] = h[i] / S;
-    }
-    for (int j = 0; j < d; ++j) e->tabb_host[(size_t)j * 64 + d] = gw[j];      // the observer: mean_t - y_t = gw . lam_(t+1) - (R / S) r_t
-    e->tabb_host[(size_t)DP * 64 + d] = -R / S;
+    back_table(e, Psi, gw.data(), e->tabb_host);
     return kOk;
 }
 }  // namespace
@@ -1124,6 +1001,101 @@ bool plan_posterior(Engine* e, long long T) {
     return e->post_why == kOk;
 }
 
+namespace {
+// a device buffer of at least `need` bytes: the old one is freed before the larger one is asked for; on failure p == nullptr, cap == 0
+hipError_t grow(double*& p, size_t& cap, size_t need) {
+    if (need <= cap) return hipSuccess;
+    if (p) (void)tgp_alloc::dev_free(p);
+    p = nullptr;
+    cap = 0;
+    const hipError_t rc = tgp_alloc::dev_malloc(reinterpret_cast<void**>(&p), need);
+    if (rc == hipSuccess) cap = need;
+    else p = nullptr;
+    return rc;
+}
+hipError_t pinned_ready(Engine* e) {
+    return e->pinned ? hipSuccess : tgp_alloc::host_malloc(reinterpret_cast<void**>(&e->pinned), pin::size * sizeof(double), hipHostMallocDefault);
+}
+// The head forward: lgssm.jl:147-165 with the plan's gains, on the head's observations yh (hth: their emission offsets per step, or nullptr: the
+// model's hh).  Returns the head's share of the quadratic form; z0: its end state; r_out, m_out (where asked): its innovations [n0], filtered means [n0][d].
+double head_forward(const Engine* e, const double* yh, const double* hth, ZArg& z0, std::vector<double>* r_out, std::vector<double>* m_out) {
+    const int d = e->d, n0 = e->info.n0;
+    const double *A = e->A.data(), *h = e->hvec.data();
+    double quad = 0.0;
+    if (r_out) r_out->resize(n0);
+    if (m_out) m_out->clear();
+    std::vector<double> mcur(e->x0m), mp(d);
+    for (int t = 0; t < n0; ++t) {
+        double pred = hth ? hth[t] : e->hh;
+        for (int i = 0; i < d; ++i) {
+            double s = e->avec[i];
+            const double* ai = A + (size_t)i * d;
+            for (int k = 0; k < d; ++k) s += ai[k] * mcur[k];
+            mp[i] = s;
+            pred += h[i] * s;
+        }
+        const double r = yh[t] - pred;
+        if (r_out) (*r_out)[t] = r;
+        quad += r * r / e->St[t];
+        const double* K = e->Kt.data() + (size_t)t * d;
+        for (int i = 0; i < d; ++i) mcur[i] = mp[i] + K[i] * r;
+        if (m_out) m_out->insert(m_out->end(), mcur.begin(), mcur.end());
+    }
+    for (int i = 0; i < 64; ++i) z0.z[i] = i < d ? mcur[i] : 0.0;
+    return quad;
+}
+// logpdf from the head's quadratic form and the chunks' sums of r_t^2 (in chunk order)
+double closing_lml(const Engine* e, long long T, double quad, const double* part) {
+    double ssq = 0.0;
+    for (long long k = 0; k < e->info.chunks; ++k) ssq += part[k];
+    const double kLog2Pi = 1.8378770664093454835606594728112;
+    return -0.5 * ((double)T * kLog2Pi + e->sum_logS_head + (double)(T - e->info.n0) * std::log(e->Sss) + quad + ssq / e->Sss);
+}
+// The forward kernel of the engine's form over the steps behind the head.  keep: the innovations go to rout (a posterior or adjoint call).
+void launch_forward(const Engine* e, hipStream_t stream, bool keep, const double* tab, const double* y, long long T, const ZArg& z0, double* part, double* rout,
+                    const double* ht, double* mout) {
+    const int d = e->d;
+    const long long n0 = e->info.n0, len = e->info.chunk_len, halo = e->info.halo, chunks = e->info.chunks;
+    auto dpp = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((chunks + 3) / 4)), dim3(64), 0, stream, tab, y, e->hh, T, n0, len, halo, chunks, d, z0, part, rout, ht, mout);
+    };
+    auto lds = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3((unsigned)chunks), dim3(64), 0, stream, tab, y, e->hh, T, n0, len, halo, d, z0, part, rout, ht, mout, d); };
+    switch (e->form) {
+        case kDpp1: keep ? dpp(k_wide_lml4<true, 1>) : dpp(k_wide_lml4<false, 1>); break;
+        case kDpp2: keep ? dpp(k_wide_lml4<true, 2>) : dpp(k_wide_lml4<false, 2>); break;
+        case kDpp3: keep ? dpp(k_wide_lml4<true, 3>) : dpp(k_wide_lml4<false, 3>); break;
+        case kLds32: lds(k_wide_lml<32>); break;
+        case kLds64: lds(k_wide_lml<64>); break;
+    }
+}
+// The backward kernel of the engine's form on the innovations r.  adj: lam_t to lamT (the adjoint pass: no posterior, c is not read); else the posterior
+// marginals of c with the posterior plan's tables.  lam_out: lam at the head's end.
+void launch_backward(const Engine* e, hipStream_t stream, bool adj, const double* tab, const double* qtab, long long T, const double* y, const double* r, const Call& c,
+                     double* lam_out, double* lamT) {
+    const int d = e->d;
+    const long long n0 = e->info.n0, len = e->info.chunk_len, chunks = e->info.chunks;
+    const long long halo = adj ? e->adj_halo : e->info.halo_back, n1 = adj ? 0 : e->info.n1;
+    const double vbase = adj ? 0.0 : e->vbase, qinf = adj ? 0.0 : e->qinf;
+    const double* Rnew = adj ? nullptr : c.Rnew;
+    const int per_step = adj ? 0 : c.rnew_per_step;
+    double *mean = adj ? nullptr : c.mean, *var = adj ? nullptr : c.var;
+    auto dpp = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((chunks + 3) / 4)), dim3(64), 0, stream, tab, y, r, Rnew, per_step, qtab, n1, vbase, qinf, T, n0, len, halo, chunks, d, mean, var,
+                           lam_out, lamT);
+    };
+    auto lds = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)chunks), dim3(64), 0, stream, tab, y, r, Rnew, per_step, qtab, n1, vbase, qinf, T, n0, len, halo, d, d, mean, var, lam_out, lamT);
+    };
+    switch (e->form) {
+        case kDpp1: adj ? dpp(k_wide_bwd4<1, true>) : dpp(k_wide_bwd4<1, false>); break;
+        case kDpp2: adj ? dpp(k_wide_bwd4<2, true>) : dpp(k_wide_bwd4<2, false>); break;
+        case kDpp3: adj ? dpp(k_wide_bwd4<3, true>) : dpp(k_wide_bwd4<3, false>); break;
+        case kLds32: adj ? lds(k_wide_bwd<32, true>) : lds(k_wide_bwd<32, false>); break;
+        case kLds64: adj ? lds(k_wide_bwd<64, true>) : lds(k_wide_bwd<64, false>); break;
+    }
+}
+}  // namespace
+
 int run(Engine* e, hipStream_t stream, const Call& c, double* lml_out, std::string* err) {
     auto fail = [&](hipError_t rc, const char* what) {
         if (err) *err = std::string("tgp_wide: ") + what + ": " + hipGetErrorString(rc);
@@ -1133,23 +1105,14 @@ int run(Engine* e, hipStream_t stream, const Call& c, double* lml_out, std::stri
     if (!e->have || e->info.why != kOk || (post && (!e->post_ready || e->post_why != kOk || !c.var || !c.Rnew))) return fail(hipErrorInvalidValue, "no plan");
     const int d = e->d, DP = e->dp, n0 = e->info.n0;
     const long long T = c.T;
-    hipError_t rc;
-    if (!e->pinned) {
-        rc = tgp_alloc::host_malloc(reinterpret_cast<void**>(&e->pinned), (size_t)(5 * kHeadMax + 64 + 65536) * sizeof(double), hipHostMallocDefault);
-        if (rc != hipSuccess) return fail(rc, "pinned buffer");
-    }
+    hipError_t rc = pinned_ready(e);
+    if (rc != hipSuccess) return fail(rc, "pinned buffer");
     // device tables: forward | backward | qtab
     const size_t nf = e->tab_host.size(), nb = post ? e->tabb_host.size() : 0, nq = post ? e->qtab.size() : 0;
-    const size_t need = (nf + (size_t)(DP + 1) * 64 + (size_t)kTailMax + 2) * sizeof(double);
-    if (need > e->dev_cap) {
-        if (e->dev) (void)tgp_alloc::dev_free(e->dev);
-        e->dev = nullptr;
-        e->dev_cap = 0;
-        rc = tgp_alloc::dev_malloc(reinterpret_cast<void**>(&e->dev), need);
-        if (rc != hipSuccess) return fail(rc, "tables");
-        e->dev_cap = need;
-        e->dev_current = false;
-    }
+    const size_t cap_before = e->dev_cap;
+    rc = grow(e->dev, e->dev_cap, (nf + (size_t)(DP + 1) * 64 + (size_t)kTailMax + 2) * sizeof(double));
+    if (e->dev_cap != cap_before) e->dev_current = false;      // (a new buffer, or none)
+    if (rc != hipSuccess) return fail(rc, "tables");
     double *tab_f = e->dev, *tab_b = e->dev + nf, *qtab_d = tab_b + (size_t)(DP + 1) * 64;
     if (!e->dev_current || (post && !e->dev_post_current)) {
         rc = hipMemcpyAsync(tab_f, e->tab_host.data(), nf * sizeof(double), hipMemcpyHostToDevice, stream);
@@ -1159,48 +1122,20 @@ int run(Engine* e, hipStream_t stream, const Call& c, double* lml_out, std::stri
         e->dev_current = true;
         e->dev_post_current = post;
     }
-    if (post && (size_t)T * sizeof(double) > e->rbuf_cap) {
-        if (e->rbuf) (void)tgp_alloc::dev_free(e->rbuf);
-        e->rbuf = nullptr;
-        e->rbuf_cap = 0;
-        rc = tgp_alloc::dev_malloc(reinterpret_cast<void**>(&e->rbuf), (size_t)T * sizeof(double));
+    if (post) {
+        rc = grow(e->rbuf, e->rbuf_cap, (size_t)T * sizeof(double));
         if (rc != hipSuccess) return fail(rc, "innovation buffer");
-        e->rbuf_cap = (size_t)T * sizeof(double);
     }
-    double *yh = e->pinned, *Rh = yh + kHeadMax, *mh = Rh + kHeadMax, *vh = mh + kHeadMax, *hth = vh + kHeadMax, *lam = hth + kHeadMax, *part = lam + 64;
+    double *yh = e->pinned + pin::yh, *Rh = e->pinned + pin::Rh, *mh = e->pinned + pin::mh, *vh = e->pinned + pin::vh, *hth = e->pinned + pin::hth;
+    double *lam = e->pinned + pin::lam, *part = e->pinned + pin::part;
     rc = hipMemcpyAsync(yh, c.y, (size_t)n0 * sizeof(double), hipMemcpyDeviceToHost, stream);
     if (rc == hipSuccess && post) rc = hipMemcpyAsync(Rh, c.Rnew, (size_t)(c.rnew_per_step ? n0 : 1) * sizeof(double), hipMemcpyDeviceToHost, stream);
     if (rc == hipSuccess && c.h_t) rc = hipMemcpyAsync(hth, c.h_t, (size_t)n0 * sizeof(double), hipMemcpyDeviceToHost, stream);
     if (rc != hipSuccess) return fail(rc, "head observations");
     rc = hipStreamSynchronize(stream);
     if (rc != hipSuccess) return fail(rc, "head observations");
-    // ---- the head forward: lgssm.jl:147-165 with the plan's gains
     ZArg z0;
-    for (int i = 0; i < 64; ++i) z0.z[i] = 0.0;
-    double quad = 0.0;
-    const double *A = e->A.data(), *h = e->hvec.data();
-    e->head_r.resize(n0);
-    e->head_m.clear();
-    {
-        std::vector<double> mcur(e->x0m), mp(d);
-        for (int t = 0; t < n0; ++t) {
-            double pred = c.h_t ? hth[t] : e->hh;
-            for (int i = 0; i < d; ++i) {
-                double s = e->avec[i];
-                const double* ai = A + (size_t)i * d;
-                for (int k = 0; k < d; ++k) s += ai[k] * mcur[k];
-                mp[i] = s;
-                pred += h[i] * s;
-            }
-            const double r = yh[t] - pred;
-            e->head_r[t] = r;
-            quad += r * r / e->St[t];
-            const double* K = e->Kt.data() + (size_t)t * d;
-            for (int i = 0; i < d; ++i) mcur[i] = mp[i] + K[i] * r;
-            if (c.fm) e->head_m.insert(e->head_m.end(), mcur.begin(), mcur.end());
-        }
-        for (int i = 0; i < d; ++i) z0.z[i] = mcur[i];
-    }
+    const double quad = head_forward(e, yh, c.h_t ? hth : nullptr, z0, &e->head_r, c.fm ? &e->head_m : nullptr);
     if (c.fm) {      // _filter: the head's means and covariances, the settled covariance behind them
         if (!c.fP || e->Pf_head.size() != (size_t)n0 * d * d) return fail(hipErrorInvalidValue, "filter outputs");
         rc = hipMemcpyAsync(c.fm, e->head_m.data(), (size_t)n0 * d * sizeof(double), hipMemcpyHostToDevice, stream);
@@ -1210,49 +1145,11 @@ int run(Engine* e, hipStream_t stream, const Call& c, double* lml_out, std::stri
         const unsigned blocks = (unsigned)std::min<long long>((nfill + 255) / 256, 16384);
         if (nfill > 0) hipLaunchKernelGGL(k_wide_fill_cov, dim3(blocks), dim3(256), 0, stream, c.fP, (long long)n0, T, d * d);
     }
-    const long long chunks = e->info.chunks;
-    double* rout = post ? e->rbuf : nullptr;
-    const bool four = DP == 32 && dpp_enabled();
-    const unsigned grid4 = (unsigned)((chunks + 3) / 4);
-    const bool three = DP == 64 && d <= 47 && dpp_enabled();      // three components per lane
-    const bool one = d <= 15;      // one component per lane
-#define TGP_WIDE_LML4(KEEP, NB) \
-    hipLaunchKernelGGL((k_wide_lml4<KEEP, NB>), dim3(grid4), dim3(64), 0, stream, tab_f, c.y, e->hh, T, (long long)n0, e->info.chunk_len, (long long)e->info.halo, chunks, d, z0, part, rout, c.h_t, c.fm)
-    if (three && post)
-        hipLaunchKernelGGL(k_wide_lml43<true>, dim3(grid4), dim3(64), 0, stream, tab_f, c.y, e->hh, T, (long long)n0, e->info.chunk_len, (long long)e->info.halo, chunks, d, z0, part, rout,
-                           c.h_t, c.fm);
-    else if (three)
-        hipLaunchKernelGGL(k_wide_lml43<false>, dim3(grid4), dim3(64), 0, stream, tab_f, c.y, e->hh, T, (long long)n0, e->info.chunk_len, (long long)e->info.halo, chunks, d, z0, part, rout,
-                           c.h_t, c.fm);
-    else if (four && post && one) TGP_WIDE_LML4(true, 1);
-    else if (four && post) TGP_WIDE_LML4(true, 2);
-    else if (four && one) TGP_WIDE_LML4(false, 1);
-    else if (four) TGP_WIDE_LML4(false, 2);
-#undef TGP_WIDE_LML4
-    else if (DP == 32)
-        hipLaunchKernelGGL(k_wide_lml<32>, dim3((unsigned)chunks), dim3(64), 0, stream, tab_f, c.y, e->hh, T, (long long)n0, e->info.chunk_len, (long long)e->info.halo, d, z0, part,
-                           rout, c.h_t, c.fm, d);
-    else
-        hipLaunchKernelGGL(k_wide_lml<64>, dim3((unsigned)chunks), dim3(64), 0, stream, tab_f, c.y, e->hh, T, (long long)n0, e->info.chunk_len, (long long)e->info.halo, d, z0, part,
-                           rout, c.h_t, c.fm, d);
+    launch_forward(e, stream, post, tab_f, c.y, T, z0, part, post ? e->rbuf : nullptr, c.h_t, c.fm);
     rc = hipGetLastError();
     if (rc != hipSuccess) return fail(rc, "launch");
     if (post) {
-        if (three)
-            hipLaunchKernelGGL(k_wide_bwd43<false>, dim3(grid4), dim3(64), 0, stream, tab_b, c.y, e->rbuf, c.Rnew, c.rnew_per_step, qtab_d, (long long)e->info.n1, e->vbase, e->qinf, T,
-                               (long long)n0, e->info.chunk_len, (long long)e->info.halo_back, chunks, d, c.mean, c.var, lam, nullptr);
-        else if (four && one)
-            hipLaunchKernelGGL(k_wide_bwd4<1>, dim3(grid4), dim3(64), 0, stream, tab_b, c.y, e->rbuf, c.Rnew, c.rnew_per_step, qtab_d, (long long)e->info.n1, e->vbase, e->qinf, T,
-                               (long long)n0, e->info.chunk_len, (long long)e->info.halo_back, chunks, d, c.mean, c.var, lam, nullptr);
-        else if (four)
-            hipLaunchKernelGGL(k_wide_bwd4<2>, dim3(grid4), dim3(64), 0, stream, tab_b, c.y, e->rbuf, c.Rnew, c.rnew_per_step, qtab_d, (long long)e->info.n1, e->vbase, e->qinf, T,
-                               (long long)n0, e->info.chunk_len, (long long)e->info.halo_back, chunks, d, c.mean, c.var, lam, nullptr);
-        else if (DP == 32)
-            hipLaunchKernelGGL(k_wide_bwd<32>, dim3((unsigned)chunks), dim3(64), 0, stream, tab_b, c.y, e->rbuf, c.Rnew, c.rnew_per_step, qtab_d, (long long)e->info.n1, e->vbase,
-                               e->qinf, T, (long long)n0, e->info.chunk_len, (long long)e->info.halo_back, d, d, c.mean, c.var, lam, nullptr);
-        else
-            hipLaunchKernelGGL(k_wide_bwd<64>, dim3((unsigned)chunks), dim3(64), 0, stream, tab_b, c.y, e->rbuf, c.Rnew, c.rnew_per_step, qtab_d, (long long)e->info.n1, e->vbase,
-                               e->qinf, T, (long long)n0, e->info.chunk_len, (long long)e->info.halo_back, d, d, c.mean, c.var, lam, nullptr);
+        launch_backward(e, stream, false, tab_b, qtab_d, T, c.y, e->rbuf, c, lam, nullptr);
         rc = hipGetLastError();
         if (rc != hipSuccess) return fail(rc, "launch");
     }
@@ -1260,6 +1157,7 @@ int run(Engine* e, hipStream_t stream, const Call& c, double* lml_out, std::stri
     if (rc != hipSuccess) return fail(rc, "kernel");
     if (post) {
         // ---- the head backward: lam_t = h r_t / S_t + Psi_t lam_(t+1), Psi_t lam = A' lam - h (A K_t) . lam; mean_t = y_t - (R / S_t) r_t + R (A K_t) . lam_(t+1)
+        const double *A = e->A.data(), *h = e->hvec.data();
         std::vector<double> lcur(lam, lam + d), AKt(d), ln(d);
         for (int t = n0 - 1; t >= 0; --t) {
             const double* Kv = e->Kt.data() + (size_t)t * d;
@@ -1285,10 +1183,7 @@ int run(Engine* e, hipStream_t stream, const Call& c, double* lml_out, std::stri
         if (rc == hipSuccess) rc = hipStreamSynchronize(stream);
         if (rc != hipSuccess) return fail(rc, "head outputs");
     }
-    double ssq = 0.0;
-    for (long long k = 0; k < chunks; ++k) ssq += part[k];
-    const double kLog2Pi = 1.8378770664093454835606594728112;
-    *lml_out = -0.5 * ((double)T * kLog2Pi + e->sum_logS_head + (double)(T - n0) * std::log(e->Sss) + quad + ssq / e->Sss);
+    *lml_out = closing_lml(e, T, quad, part);
     return 0;
 }
 
@@ -1300,32 +1195,20 @@ int adjoint(Engine* e, hipStream_t stream, const ModelHost& m, long long T, cons
         return (int)rc;
     };
     if (!e->have || e->info.why != kOk || e->d != m.d) return 0;
-    const int d = e->d, DP = e->dp, n0 = e->info.n0;
+    const int d = e->d, n0 = e->info.n0;
     const size_t dd = (size_t)d * d;
-    const double *A = e->A.data(), *h = e->hvec.data();
-    // ---- the backward table: Psi = (I - h K') A' of the stationary step, gains h / S; the halo of Psi
+    const double* A = e->A.data();
+    // ---- the backward table: Psi = (I - h K') A' of the stationary step, gains h / S (no observer); the halo of Psi
     if (!e->adj_ready) {
-        const double* K = e->Kt.data() + (size_t)(n0 - 1) * d;
         std::vector<double> AK(d), Psi(dd);
-        for (int j = 0; j < d; ++j) {
-            double s = 0.0;
-            for (int k = 0; k < d; ++k) s += A[(size_t)j * d + k] * K[k];
-            AK[j] = s;
-        }
-        for (int i = 0; i < d; ++i)
-            for (int j = 0; j < d; ++j) Psi[(size_t)i * d + j] = A[(size_t)j * d + i] - h[i] * AK[j];
+        back_step(e, e->Kt.data() + (size_t)(n0 - 1) * d, AK, Psi);
         const long long hb = halo_of(d, Psi);
         e->adj_halo = hb < 0 ? -1 : (int)hb;
-        e->taba_host.assign((size_t)(DP + 1) * 64, 0.0);
-        for (int i = 0; i < d; ++i) {
-            for (int j = 0; j < d; ++j) e->taba_host[(size_t)j * 64 + i] = Psi[(size_t)i * d + j];
-            e->taba_host[(size_t)DP * 64 + i] = h[i] / e->Sss;
-        }
+        back_table(e, Psi, nullptr, e->taba_host);
         e->adj_ready = true;
         if (e->adj_dev) {      // (tables of an earlier model)
             (void)tgp_alloc::dev_free(e->adj_dev);
             e->adj_dev = nullptr;
-            e->adj_cap = 0;
         }
     }
     if (e->adj_halo < 0) return 0;
@@ -1346,101 +1229,37 @@ int adjoint(Engine* e, hipStream_t stream, const ModelHost& m, long long T, cons
         rc = tgp_alloc::host_malloc(reinterpret_cast<void**>(&e->adj_pin), (size_t)(80 * 80 + 64) * sizeof(double), hipHostMallocDefault);
         if (rc != hipSuccess) return fail(rc, "pinned buffer");
     }
-    if (!e->pinned) {
-        rc = tgp_alloc::host_malloc(reinterpret_cast<void**>(&e->pinned), (size_t)(5 * kHeadMax + 64 + 65536) * sizeof(double), hipHostMallocDefault);
-        if (rc != hipSuccess) return fail(rc, "pinned buffer");
-    }
+    rc = pinned_ready(e);
+    if (rc != hipSuccess) return fail(rc, "pinned buffer");
     const size_t nTd = (size_t)T * d * sizeof(double);
-    if (nTd > e->mbuf_cap) {
-        for (double** p : {&e->mbuf, &e->lbuf}) {
-            if (*p) (void)tgp_alloc::dev_free(*p);
-            *p = nullptr;
-        }
-        e->mbuf_cap = 0;
-        rc = tgp_alloc::dev_malloc(reinterpret_cast<void**>(&e->mbuf), nTd);
-        if (rc == hipSuccess) rc = tgp_alloc::dev_malloc(reinterpret_cast<void**>(&e->lbuf), nTd);
-        if (rc != hipSuccess) return fail(rc, "per-step scratch");
-        e->mbuf_cap = nTd;
-    }
-    if ((size_t)T * sizeof(double) > e->rbuf_cap) {
-        if (e->rbuf) (void)tgp_alloc::dev_free(e->rbuf);
-        e->rbuf = nullptr;
-        e->rbuf_cap = 0;
-        rc = tgp_alloc::dev_malloc(reinterpret_cast<void**>(&e->rbuf), (size_t)T * sizeof(double));
-        if (rc != hipSuccess) return fail(rc, "innovation buffer");
-        e->rbuf_cap = (size_t)T * sizeof(double);
-    }
+    rc = grow(e->mbuf, e->mbuf_cap, nTd);
+    if (rc == hipSuccess) rc = grow(e->lbuf, e->lbuf_cap, nTd);
+    if (rc != hipSuccess) return fail(rc, "per-step scratch");
+    rc = grow(e->rbuf, e->rbuf_cap, (size_t)T * sizeof(double));
+    if (rc != hipSuccess) return fail(rc, "innovation buffer");
     // the reduction's waves: at most 2048, none with fewer than 256 steps (a multiple of four: four waves per block)
     const long long Tb = T - n0;
     long long nw = std::min<long long>(2048, std::max<long long>(1, (Tb + 255) / 256));
     nw = (nw + 3) / 4 * 4;
     long long span = (Tb + nw - 1) / nw;
     span = (span + 3) / 4 * 4;
-    const size_t gneed = (size_t)nw * ng2 * sizeof(double);
-    if (gneed > e->gpart_cap) {
-        if (e->gpart) (void)tgp_alloc::dev_free(e->gpart);
-        e->gpart = nullptr;
-        e->gpart_cap = 0;
-        rc = tgp_alloc::dev_malloc(reinterpret_cast<void**>(&e->gpart), gneed);
-        if (rc != hipSuccess) return fail(rc, "partial sums");
-        e->gpart_cap = gneed;
-    }
-    double *yh = e->pinned, *lam = yh + 5 * kHeadMax, *part = lam + 64;
+    rc = grow(e->gpart, e->gpart_cap, (size_t)nw * ng2 * sizeof(double));
+    if (rc != hipSuccess) return fail(rc, "partial sums");
+    double *yh = e->pinned + pin::yh, *lam = e->pinned + pin::lam, *part = e->pinned + pin::part;
     double *Gh = e->adj_pin, *zend = Gh + 80 * 80;
     rc = hipMemcpyAsync(yh, y, (size_t)n0 * sizeof(double), hipMemcpyDeviceToHost, stream);
     if (rc == hipSuccess) rc = hipStreamSynchronize(stream);
     if (rc != hipSuccess) return fail(rc, "head observations");
-    // ---- the head forward (as tgp_wide::run): its end state m_(n0 - 1) starts chunk 0 and is the reduction's m row n0 - 1
+    // ---- the head forward: its end state m_(n0 - 1) starts chunk 0 and is the reduction's m row n0 - 1
     ZArg z0;
-    for (int i = 0; i < 64; ++i) z0.z[i] = 0.0;
-    double quad = 0.0;
-    {
-        std::vector<double> mcur(e->x0m), mp(d);
-        for (int t = 0; t < n0; ++t) {
-            double pred = e->hh;
-            for (int i = 0; i < d; ++i) {
-                double s = e->avec[i];
-                const double* ai = A + (size_t)i * d;
-                for (int k = 0; k < d; ++k) s += ai[k] * mcur[k];
-                mp[i] = s;
-                pred += h[i] * s;
-            }
-            const double r = yh[t] - pred;
-            quad += r * r / e->St[t];
-            const double* K = e->Kt.data() + (size_t)t * d;
-            for (int i = 0; i < d; ++i) mcur[i] = mp[i] + K[i] * r;
-        }
-        for (int i = 0; i < d; ++i) z0.z[i] = zend[i] = mcur[i];
-    }
+    const double quad = head_forward(e, yh, nullptr, z0, nullptr, nullptr);
+    std::memcpy(zend, z0.z, (size_t)d * sizeof(double));
     rc = hipMemcpyAsync(e->mbuf + (size_t)(n0 - 1) * d, zend, (size_t)d * sizeof(double), hipMemcpyHostToDevice, stream);
     if (rc != hipSuccess) return fail(rc, "head's end state");
     // ---- forward (innovations and filtered means of the steps behind the head), backward (lam_t), the sums
-    const long long chunks = e->info.chunks, len = e->info.chunk_len;
-    const unsigned grid4 = (unsigned)((chunks + 3) / 4);
-    const bool four = DP == 32 && dpp_enabled(), three = DP == 64 && d <= 47 && dpp_enabled(), one = d <= 15;
-    const long long hf = e->info.halo, hb = e->adj_halo;
     double *rb = e->rbuf, *mb = e->mbuf, *lb = e->lbuf;
-    if (three) {
-        hipLaunchKernelGGL(k_wide_lml43<true>, dim3(grid4), dim3(64), 0, stream, tab_f, y, e->hh, T, (long long)n0, len, hf, chunks, d, z0, part, rb, nullptr, mb);
-        hipLaunchKernelGGL(k_wide_bwd43<true>, dim3(grid4), dim3(64), 0, stream, tab_b, y, rb, nullptr, 0, nullptr, 0ll, 0.0, 0.0, T, (long long)n0, len, hb, chunks, d, nullptr,
-                           nullptr, lam, lb);
-    } else if (four && one) {
-        hipLaunchKernelGGL((k_wide_lml4<true, 1>), dim3(grid4), dim3(64), 0, stream, tab_f, y, e->hh, T, (long long)n0, len, hf, chunks, d, z0, part, rb, nullptr, mb);
-        hipLaunchKernelGGL((k_wide_bwd4<1, true>), dim3(grid4), dim3(64), 0, stream, tab_b, y, rb, nullptr, 0, nullptr, 0ll, 0.0, 0.0, T, (long long)n0, len, hb, chunks, d, nullptr,
-                           nullptr, lam, lb);
-    } else if (four) {
-        hipLaunchKernelGGL((k_wide_lml4<true, 2>), dim3(grid4), dim3(64), 0, stream, tab_f, y, e->hh, T, (long long)n0, len, hf, chunks, d, z0, part, rb, nullptr, mb);
-        hipLaunchKernelGGL((k_wide_bwd4<2, true>), dim3(grid4), dim3(64), 0, stream, tab_b, y, rb, nullptr, 0, nullptr, 0ll, 0.0, 0.0, T, (long long)n0, len, hb, chunks, d, nullptr,
-                           nullptr, lam, lb);
-    } else if (DP == 32) {
-        hipLaunchKernelGGL(k_wide_lml<32>, dim3((unsigned)chunks), dim3(64), 0, stream, tab_f, y, e->hh, T, (long long)n0, len, hf, d, z0, part, rb, nullptr, mb, d);
-        hipLaunchKernelGGL((k_wide_bwd<32, true>), dim3((unsigned)chunks), dim3(64), 0, stream, tab_b, y, rb, nullptr, 0, nullptr, 0ll, 0.0, 0.0, T, (long long)n0, len, hb, d, d,
-                           nullptr, nullptr, lam, lb);
-    } else {
-        hipLaunchKernelGGL(k_wide_lml<64>, dim3((unsigned)chunks), dim3(64), 0, stream, tab_f, y, e->hh, T, (long long)n0, len, hf, d, z0, part, rb, nullptr, mb, d);
-        hipLaunchKernelGGL((k_wide_bwd<64, true>), dim3((unsigned)chunks), dim3(64), 0, stream, tab_b, y, rb, nullptr, 0, nullptr, 0ll, 0.0, 0.0, T, (long long)n0, len, hb, d, d,
-                           nullptr, nullptr, lam, lb);
-    }
+    launch_forward(e, stream, true, tab_f, y, T, z0, part, rb, nullptr, mb);
+    launch_backward(e, stream, true, tab_b, nullptr, T, y, rb, Call{}, lam, lb);
     const unsigned gblocks = (unsigned)(nw / 4);
     switch (NT) {
         case 1: hipLaunchKernelGGL(k_wide_gram<1>, dim3(gblocks), dim3(256), 0, stream, lb, mb, rb, (long long)n0, T, span, d, e->gpart); break;
@@ -1505,10 +1324,7 @@ int adjoint(Engine* e, hipStream_t stream, const ModelHost& m, long long T, cons
     hd.n = n0;
     if (tgp_wide_adjoint::finish(d, rec.data(), yh, n0, n0, out, &hd) != 0) return fail(hipErrorInvalidValue, "inconsistent record");
     e->info.finish_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_fin).count();
-    double ssq = 0.0;
-    for (long long k = 0; k < chunks; ++k) ssq += part[k];
-    const double kLog2Pi = 1.8378770664093454835606594728112;
-    *lml_out = -0.5 * ((double)T * kLog2Pi + e->sum_logS_head + (double)(T - n0) * std::log(e->Sss) + quad + ssq / e->Sss);
+    *lml_out = closing_lml(e, T, quad, part);
     *declined = false;
     return 0;
 }
@@ -1573,14 +1389,8 @@ int rand(Engine* e, hipStream_t stream, const ModelHost& m, long long T, const d
     tab[(size_t)(2 * DP) * 64 + d] = ha;
     hipError_t rc;
     const size_t need = tab.size() * sizeof(double);
-    if (need > e->rand_cap) {
-        if (e->rand_dev) (void)tgp_alloc::dev_free(e->rand_dev);
-        e->rand_dev = nullptr;
-        e->rand_cap = 0;
-        rc = tgp_alloc::dev_malloc(reinterpret_cast<void**>(&e->rand_dev), need);
-        if (rc != hipSuccess) return fail(rc, "rand table");
-        e->rand_cap = need;
-    }
+    rc = grow(e->rand_dev, e->rand_cap, need);
+    if (rc != hipSuccess) return fail(rc, "rand table");
     rc = hipMemcpyAsync(e->rand_dev, tab.data(), need, hipMemcpyHostToDevice, stream);
     if (rc == hipSuccess) rc = hipStreamSynchronize(stream);      // (tab is a temporary)
     if (rc != hipSuccess) return fail(rc, "rand table upload");

@@ -10,7 +10,9 @@
 //   kernel      the steps behind the head are cut into chunks, one WAVE each: lane i owns component i of the filtered mean and row i of Phi in
 //               registers, the state goes round through a 512-byte LDS line (one ds_write, d/2 broadcast ds_read_b128 per step), lane d -- the
 //               observer -- carries the row -g and so computes the innovation r_t by the same multiply-adds.  A chunk starts `halo` steps early
-//               from a zero state (the closed loop forgets it to 2^-60) and sums r_t^2 over its own steps only.
+//               from a zero state (the closed loop forgets it to 2^-60) and sums r_t^2 over its own steps only.  That is the LDS family
+//               (k_wide_lml<DP>, k_wide_bwd<DP>: 48 <= d, or every d with TGP_WIDE_DPP=0); d <= 47 runs FOUR chunks per wave without LDS, NB = 1, 2 or 3
+//               components per lane (k_wide_lml4<KEEP, NB>, k_wide_bwd4<NB, ADJ>).  plan() chooses the family once; kernel_name() reports it.
 //   posterior   marginals(replace_observation_noise_cov(posterior(model, y), Rnew)) (lgssm.jl:99-115, 193-238) in Bryson-Frazier form: the forward
 //               kernel keeps its innovations (8 B per step), a second kernel of the same shape runs lam_t = h r_t / S + Psi lam_(t+1) backwards
 //               (Psi = (I - h K') A'), its observer row gw = R A K gives mean_t = y_t - (R / S) r_t + gw . lam_(t+1); the variance is a constant
