@@ -286,6 +286,13 @@ int tgp_steady_plan(int d, const double* A, const double* a, const double* Q, co
  * var_parts [2] (want_posterior): the stationary smoothed emission variance is var_parts[0] - var_parts[1] (+ the new noise). */
 int tgp_wide_plan(int d, const double* A, const double* a, const double* Q, const double* H, const double* hh, const double* R, const double* x0m,
                   const double* x0P, int64_t T, int want_posterior, int64_t* info, double* Kss, double* Sss, double* var_parts);
+/* ... and the draw half of that plan (what tgp_posterior_rand runs on for 8 < d <= 63), likewise a pure host function: the reverse-time transition of
+ * lgssm.jl:231-238 at the settled filter covariance.  info [6]: why (of the plan above; 0 = applies), n0, why_draw (0 = applies; -1: not reached;
+ * 1: a factorisation met a pivot that is not positive, 3: G does not forget within 2^20 steps, 4: fewer than 64 steps behind the head, 7: the head's
+ * covariances were too large to keep), halo_draw (the tested number of steps after which the norm of G^k is below 2^-60), chunks, chunk length.
+ * G, L, U [d][d] row-major (each may be NULL; written when why_draw = 0): x_(t-1) | x_t ~ N(G x_t + g_t, L) behind the head, U = chol(L + 1e-9 I).U. */
+int tgp_wide_plan_draw(int d, const double* A, const double* a, const double* Q, const double* H, const double* hh, const double* R, const double* x0m,
+                       const double* x0P, int64_t T, int64_t* info, double* G, double* L, double* U);
 /* ---- time segments of ONE series on the one-launch path (TGP_OPT_STEADY = 3): what a rank of a multi-GPU run calls (tgp_multi_* and the
  * one-process-per-GPU driver use them).  Both mean recursions of the stationary region forget a state within `halo` steps, so a segment needs
  * nothing of its neighbours but their `halo` observations next to the boundary: ONE all-gather of 2 halo observations per rank before the
@@ -363,10 +370,14 @@ int tgp_marginals(tgp_handle* h, uint32_t flags, double* mean_out, double* var_o
  *      (posterior_lti_sde.jl:48-58 -> lgssm.jl:65-91 on the reverse-time model of lgssm.jl:193-221) WITHOUT
  *      evaluating that model (T x (2 d^2 + d) doubles): Forward LTI models with scalar observations, one noise
  *      variance, no missing data and d <= 6 run the filter and the reverse-time draw in ONE kernel over
- *      y and the draws. eps_t [T][d], eps_e [T] where TGP_IN_DEVICE says (as y and Rnew),
+ *      y and the draws; such models of 8 < d <= 63 (TGP_OPT_WIDE = 1, the default) run the wide-state
+ *      engine's forward kernel keeping its innovations, then k_wide_post_rand -- the reverse-time draw behind the head on
+ *      the settled transition, in the deviation from the filtered mean -- and the head's steps on the host (DESIGN 4.4;
+ *      device scratch: T doubles).  eps_t [T][d], eps_e [T] where TGP_IN_DEVICE says (as y and Rnew),
  *      eps_0 [d] host; eps_t[t] / eps_e[t] drive the transition / emission of step t and eps_0 the draw of the
  *      final filtering state, exactly as tgp_rand on the evaluated posterior uses them. Rnew: one value
- *      (TGP_SHARED_R) or T. y_out [T]. TGP_EUNSUPPORTED: not a model of this path -- evaluate the posterior
+ *      (TGP_SHARED_R) or T. y_out [T]. TGP_EUNSUPPORTED: not a model of this path (d = 7, 8; a wide model whose
+ *      covariance does not settle or whose reverse-time transition does not forget) -- evaluate the posterior
  *      (tgp_posterior), bind it as a Reverse model and call tgp_rand (what the Python mirror does). */
 int tgp_posterior_rand(tgp_handle* h, const double* y, const double* Rnew, const double* eps_t, const double* eps_e,
                        const double* eps_0, uint32_t flags, double* y_out);

@@ -368,6 +368,7 @@ struct tgp_handle {
     tgp_wide::Engine* wide = nullptr;
     int wide_state = 0;          // 0 untried for the bound model, 1 served the last call, -1 does not apply
     int wide_post_state = 0;     // ... its posterior half
+    int wide_draw_state = 0;     // ... its draw half (tgp_posterior_rand)
     const double* wide_ht = nullptr;      // device: the emission offset per step of such a model (a mean function at the inputs), else null
     int opt_wide = 1;            // TGP_WIDE=0: such models on the dense engine's one-CU passes as before (A/B runs)
     std::vector<double> sweepm;  // the same for every model with shared A, a, Q, H and scalar observations (hh, R: the first step's where they are per step)
@@ -1373,6 +1374,7 @@ int tgp_set_option(tgp_handle* h, int option, int64_t value) {
         h->opt_wide = value != 0;
         h->wide_state = 0;
         h->wide_post_state = 0;
+        h->wide_draw_state = 0;
         return TGP_OK;
     }
     if (option == TGP_OPT_STREAM_MIN_T) {
@@ -1623,6 +1625,7 @@ int tgp_model_set(tgp_handle* h, int64_t T, int d, int p, int ordering, uint32_t
         h->widem.clear();
         h->wide_state = 0;
         h->wide_post_state = 0;
+        h->wide_draw_state = 0;
         {
             // (every block shared; the emission offset may be per step -- a mean function at the inputs: the gains do not see it)
             const uint32_t need_shared = TGP_SHARED_A | TGP_SHARED_a | TGP_SHARED_Q | TGP_SHARED_H | TGP_SHARED_R;
@@ -1722,6 +1725,7 @@ int tgp_model_set(tgp_handle* h, int64_t T, int d, int p, int ordering, uint32_t
     h->widem.clear();
     h->wide_state = 0;
     h->wide_post_state = 0;
+    h->wide_draw_state = 0;
     {
         const uint32_t need_shared = TGP_SHARED_A | TGP_SHARED_a | TGP_SHARED_Q | TGP_SHARED_H | TGP_SHARED_R;
         h->wide_ht = nullptr;

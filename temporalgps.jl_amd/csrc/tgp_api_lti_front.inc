@@ -228,6 +228,70 @@ static int wide_filter_call(tgp_handle* h, const double* y, uint32_t flags, doub
     return TGP_OK;
 }
 
+// rand of posterior(model, y) with replaced observation noise of a wide LTI model WITHOUT evaluating that model (tgp_wide::posterior_rand): the forward
+// kernel keeping its innovations, k_wide_post_rand on the settled reverse-time transition, the head on the host.  *served = false: the engine or its
+// draw plan declined (nothing the caller must undo) -- the caller takes the evaluated route.
+static int wide_post_rand_call(tgp_handle* h, const double* y, uint32_t flags, const double* Rnew, const double* eps_t, const double* eps_e, const double* eps_0,
+                               double* y_out, bool* served) {
+    *served = false;
+    if (h->opt_group == 2 || (flags & TGP_REUSE_REDUCE) || h->wide_state < 0 || h->wide_draw_state < 0) return TGP_OK;
+    if (!h->wide) h->wide = tgp_wide::create();
+    tgp_wide::ModelHost mh;
+    wide_host_model(h, mh);
+    const bool dbg = getenv("TGP_STEADY_DEBUG") != nullptr;
+    if (!tgp_wide::plan(h->wide, mh, h->T)) {
+        h->wide_state = -1;
+        return TGP_OK;
+    }
+    if (!tgp_wide::plan_draw(h->wide, h->T)) {
+        h->wide_draw_state = -1;
+        if (dbg) {
+            const tgp_wide::Info& in = tgp_wide::last_plan(h->wide);
+            fprintf(stderr, "[tgp wide] posterior draw does not apply: why %d, halo_draw %d\n", in.why_draw, in.halo_draw);
+        }
+        return TGP_OK;
+    }
+    const bool idev = (flags & TGP_IN_DEVICE) != 0, odev = (flags & TGP_OUT_DEVICE) != 0, rshared = (flags & TGP_SHARED_R) != 0;
+    const size_t nT = (size_t)h->T * sizeof(double);
+    CallTimer tm(h, /*clear=*/false);
+    const void *pR = nullptr, *pet = nullptr, *pee = nullptr;
+    TRY(stage_in(h, h->bRnew, Rnew, rshared ? sizeof(double) : nT, idev, &pR));
+    TRY(stage_in(h, h->beps_t, eps_t, (size_t)h->T * h->d * sizeof(double), idev, &pet));
+    TRY(stage_in(h, h->beps_e, eps_e, nT, idev, &pee));
+    TRY(set_obs(h, y, nullptr, flags));
+    tm.inputs_done();
+    double* dy = nullptr;
+    TRY(stage_out(h, h->bo1, y_out, nT, odev, &dy));
+    tgp_wide::Call c;
+    c.T = h->T;
+    c.y = h->mv.y;
+    c.Rnew = static_cast<const double*>(pR);
+    c.rnew_per_step = rshared ? 0 : 1;
+    c.h_t = h->wide_ht;
+    std::string err;
+    double lml = 0.0;
+    {
+        const std::string nm_k = std::string("k_wide_post_rand: ") + tgp_wide::kernel_name(h->wide) + " + k_wide_post_rand";
+        LaunchScope ls(h, nm_k.c_str());
+        if (tgp_wide::posterior_rand(h->wide, h->stream, c, static_cast<const double*>(pet), static_cast<const double*>(pee), eps_0, dy, &lml, &err) != 0)
+            return h->fail(TGP_EHIP, err);
+    }
+    tm.kernels_done();
+    TRY(copy_back(h, y_out, dy, nT, odev));
+    if (h->profile || !odev) HIPCHK(hipStreamSynchronize(h->stream));      // (the bracket's closing event; host outputs)
+    resolve_profile(h);
+    if (dbg) {
+        const tgp_wide::Info& in = tgp_wide::last_plan(h->wide);
+        fprintf(stderr, "[tgp wide] posterior draw: n0 %d halo %d halo_draw %d chunks %lld x %lld steps, plan %.3f + %.3f ms\n", in.n0, in.halo, in.halo_draw, in.draw_chunks,
+                in.draw_chunk_len, in.plan_ms, in.plan_draw_ms);
+    }
+    if (!(lml == lml)) return TGP_OK;      // (a NaN in the series -- NaN == missing in the mirrors' convention --: the evaluated route serves the draw)
+    note_served(h, Served::wide, tgp_wide::last_plan(h->wide).n0, lml, nullptr);
+    h->wide_state = 1;
+    *served = true;
+    return TGP_OK;
+}
+
 // logpdf of a Forward LTI model on the one-launch kernels
 static int logpdf_lti_one_launch(tgp_handle* h, const double* y, uint32_t flags, double* out, bool* served) {
     *served = false;

@@ -177,6 +177,23 @@ int tgp_wide_plan(int d, const double* A, const double* a, const double* Q, cons
     return TGP_OK;
 }
 
+// ... and its draw half (tgp_wide::plan_draw: the reverse-time transition of lgssm.jl:231-238 at the settled filter covariance), likewise without a handle or a GPU.
+int tgp_wide_plan_draw(int d, const double* A, const double* a, const double* Q, const double* H, const double* hh, const double* R, const double* x0m, const double* x0P,
+                       int64_t T, int64_t* info, double* G, double* L, double* U) {
+    if (!tgp_wide::supports(d) || !A || !a || !Q || !H || !hh || !R || !x0m || !x0P || !info) return TGP_EINVAL;
+    tgp_wide::Engine* e = tgp_wide::create();
+    tgp_wide::ModelHost m;
+    m.d = d;
+    m.A = A; m.a = a; m.Q = Q; m.H = H; m.hh = *hh; m.R = *R; m.x0m = x0m; m.x0P = x0P;
+    const bool ok = tgp_wide::plan(e, m, T);
+    const bool okd = ok && tgp_wide::plan_draw(e, T);
+    const tgp_wide::Info& in = tgp_wide::last_plan(e);
+    info[0] = in.why; info[1] = in.n0; info[2] = ok ? in.why_draw : -1; info[3] = in.halo_draw; info[4] = in.draw_chunks; info[5] = in.draw_chunk_len;
+    if (okd) tgp_wide::draw_stationary(e, G, L, U);
+    tgp_wide::destroy(e);
+    return TGP_OK;
+}
+
 int tgp_adjoint_record_size(int d) { return (d >= 1 && d <= tgp_steady::kMaxD) ? tgp_adjoint::record_size(d) : 0; }
 
 int tgp_adjoint_finish(int d, const double* rec, const double* y_head, int64_t n_head, double* gA, double* ga, double* gQ, double* gH,

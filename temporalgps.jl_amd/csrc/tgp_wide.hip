@@ -473,6 +473,91 @@ __global__ __launch_bounds__(64) void k_wide_rand(const double* __restrict__ tab
     }
 }
 
+// ---- rand of posterior(model, y) with the draws supplied (lgssm.jl:65-91 on the Reverse model of :193-238), behind the head, in the deviation from the
+// filtered mean dl_t = x_t - m_t: dl_(t-1) = G dl_t + (G K) r_t + U' eps_t, y*_t = y_t - (R / S) r_t + h . dl_t + sqrt(Rnew_t) e_t -- r the forward kernel's
+// innovations, G and U = chol(L + 1e-9 I).U of invert_dynamics at the settled covariance.  k_wide_rand's shape run backward in time: a lane per component,
+// the state round an LDS line, a second line for the step's draws (four steps ahead on their way), the innovations a block of 64 ahead in a register.  G
+// forgets a state as the closed loop does, so a chunk starts `halo` steps behind its end from dl = 0 ON THE SAME STREAMS; the chunk that reaches the
+// series' end starts from the drawn dl_(T-1).  tab: [2 DP + 1][64] -- columns of the lanes' rows of G (observer, lane d: h, so that its sum is h . dl_t
+// of the state the step READS), of U' (observer: zero), then the gains (G K)_i on r_t (observer: zero).  Emissions leave in coalesced blocks of 64.
+template <int DP>
+__global__ __launch_bounds__(64) void k_wide_post_rand(const double* __restrict__ tab, const double* __restrict__ y, const double* __restrict__ r,
+                                                        const double* __restrict__ eps_t, const double* __restrict__ eps_e, const double* __restrict__ Rnew,
+                                                        int rnew_per_step, double rs, long long T, long long t_head, long long chunk_len, long long halo, int obs_lane,
+                                                        int d, ZArg xT, double* __restrict__ y_out, double* __restrict__ x_out) {
+    __shared__ __attribute__((aligned(16))) double zb[64];
+    __shared__ __attribute__((aligned(16))) double eb[4][64];
+    const int lane = threadIdx.x;
+    const long long chunk = blockIdx.x;
+    const long long s0 = t_head + chunk * chunk_len;
+    long long s1 = s0 + chunk_len;
+    if (s1 > T) s1 = T;
+    const bool from_end = s1 + halo >= T;
+    const long long w1 = from_end ? T : s1 + halo;
+    double pg[DP], pu[DP];
+#pragma unroll
+    for (int j = 0; j < DP; ++j) {
+        pg[j] = tab[(size_t)j * 64 + lane];
+        pu[j] = tab[(size_t)(DP + j) * 64 + lane];
+    }
+    const double kin = tab[(size_t)(2 * DP) * 64 + lane];
+    zb[lane] = from_end ? xT.z[lane] : 0.0;
+    lds_sync();
+    auto draw = [&](long long t) { return (lane < d && t >= s0) ? eps_t[t * d + lane] : 0.0; };
+    double e0 = draw(w1 - 1), e1 = draw(w1 - 2), e2 = draw(w1 - 3), e3 = draw(w1 - 4);
+    double rn = (w1 - 1 - lane >= s0) ? r[w1 - 1 - lane] : 0.0;
+    for (long long tb = w1 - 1; tb >= s0; tb -= 64) {      // the block holds the steps tb, tb - 1, ..., one per lane
+        const double rv = rn;
+        rn = (tb - 64 - lane >= s0) ? r[tb - 64 - lane] : 0.0;
+        const int nb = (int)((tb - s0 + 1 < 64) ? (tb - s0 + 1) : 64);
+        const bool own = tb - 63 < s1;      // (some step of the block is the chunk's own)
+        double outy = 0.0;
+        for (int l4 = 0; l4 < nb; l4 += 4) {
+            eb[0][lane] = e0;
+            eb[1][lane] = e1;
+            eb[2][lane] = e2;
+            eb[3][lane] = e3;
+            const long long tn = tb - l4 - 4;
+            e0 = draw(tn);
+            e1 = draw(tn - 1);
+            e2 = draw(tn - 2);
+            e3 = draw(tn - 3);
+            lds_sync();
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int l = l4 + k;
+                if (l < nb) {      // (wave-uniform)
+                    double a0 = kin * readlane_d(rv, l), a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll
+                    for (int j = 0; j < DP; j += 4) {
+                        const v2d q0 = *reinterpret_cast<const v2d*>(&zb[j]), q1 = *reinterpret_cast<const v2d*>(&zb[j + 2]);
+                        const v2d r0 = *reinterpret_cast<const v2d*>(&eb[k][j]), r1 = *reinterpret_cast<const v2d*>(&eb[k][j + 2]);
+                        a0 = fma(pg[j], q0.x, a0);
+                        a1 = fma(pg[j + 1], q0.y, a1);
+                        a2 = fma(pg[j + 2], q1.x, a2);
+                        a3 = fma(pg[j + 3], q1.y, a3);
+                        a0 = fma(pu[j], r0.x, a0);
+                        a1 = fma(pu[j + 1], r0.y, a1);
+                        a2 = fma(pu[j + 2], r1.x, a2);
+                        a3 = fma(pu[j + 3], r1.y, a3);
+                    }
+                    const double acc = (a0 + a1) + (a2 + a3);
+                    lds_sync();      // (every lane has read the old state)
+                    zb[lane] = acc;
+                    lds_sync();
+                    if (own) {
+                        const double hx = readlane_d(acc, obs_lane);
+                        outy = lane == l ? hx : outy;
+                    }
+                }
+            }
+        }
+        const long long t = tb - lane;
+        if (own && lane < nb && t < s1) y_out[t] = (y[t] - rs * rv) + outy + sqrt(rnew_per_step ? Rnew[t] : Rnew[0]) * eps_e[t];
+    }
+    if (chunk == 0 && lane < d) x_out[lane] = zb[lane];      // dl at the head's end: the head's steps run on the host
+}
+
 // _filter's covariances behind the head: the settled one (block n0 - 1, which the head's copy has just put there) into every later block
 __global__ __launch_bounds__(256) void k_wide_fill_cov(double* __restrict__ P, long long n0, long long T, int dd) {
     const double* __restrict__ src = P + (n0 - 1) * dd;
@@ -619,6 +704,15 @@ struct Engine {
     double *adj_dev = nullptr, *adj_pin = nullptr;      // device: forward table | backward table | G; pinned: G | the head's end state
     double *mbuf = nullptr, *lbuf = nullptr, *gpart = nullptr;      // device: m [T][d], lam [T][d], partial sums of G
     size_t mbuf_cap = 0, lbuf_cap = 0, gpart_cap = 0;
+    // the draw half of the plan (built by the first posterior draw of a model)
+    bool draw_ready = false;
+    int draw_why = kOk;
+    std::vector<double> tabd_host;         // k_wide_post_rand's table
+    std::vector<double> Gd, Ld, Ud;        // [n0 + 1][d d] row-major: G_t, L_t, chol(L_t + 1e-9 I).U of the head's steps, entry n0 the settled step's
+    std::vector<double> Uend;              // chol(P_(T-1) + 1e-12 I).U
+    double *draw_dev = nullptr, *draw_pin = nullptr;      // device: forward table | draw table; pinned: the head's draws [n0][d], e [n0], outputs [n0], dl [64]
+    size_t draw_pin_cap = 0;
+    bool draw_dev_current = false;
 };
 
 namespace {
@@ -637,9 +731,10 @@ void destroy(Engine* e) {
     if (e->rbuf) (void)tgp_alloc::dev_free(e->rbuf);
     if (e->rand_dev) (void)tgp_alloc::dev_free(e->rand_dev);
     if (e->pinned) (void)tgp_alloc::host_free(e->pinned);
-    for (double* p : {e->adj_dev, e->mbuf, e->lbuf, e->gpart})
+    for (double* p : {e->adj_dev, e->mbuf, e->lbuf, e->gpart, e->draw_dev})
         if (p) (void)tgp_alloc::dev_free(p);
     if (e->adj_pin) (void)tgp_alloc::host_free(e->adj_pin);
+    if (e->draw_pin) (void)tgp_alloc::host_free(e->draw_pin);
     delete e;
 }
 const Info& last_plan(const Engine* e) { return e->info; }
@@ -718,6 +813,7 @@ bool plan(Engine* e, const ModelHost& m, long long T) {
     e->dev_current = false;
     e->post_ready = false;
     e->adj_ready = false;
+    e->draw_ready = false;
     e->info = Info{};
     const int d = m.d;
     const size_t dd = (size_t)d * d;
@@ -1183,6 +1279,270 @@ int run(Engine* e, hipStream_t stream, const Call& c, double* lml_out, std::stri
         if (rc == hipSuccess) rc = hipStreamSynchronize(stream);
         if (rc != hipSuccess) return fail(rc, "head outputs");
     }
+    *lml_out = closing_lml(e, T, quad, part);
+    return 0;
+}
+
+namespace {
+// (G, L) = invert_dynamics (lgssm.jl:231-238) of the step whose predecessor's filtered covariance is Pprev, and U = chol(L + 1e-9 I).U (lgc.jl:84-87), all
+// row-major.  The solve is against the predicted covariance + 1e-10 I, of condition up to 1e10 at d = 28: O(d^3) once per plan, so in extended precision
+// (x87 long double: 64-bit significand) and rounded at the end.  false: one of the two factorisations met a pivot that is not positive.
+typedef long double xreal;
+bool invert_dynamics_host(int d, const double* A, const double* Q, const double* Pprev, double* G, double* L, double* U) {
+    const size_t dd = (size_t)d * d;
+    std::vector<xreal> AP(dd), Pp(dd), C(dd, 0.0L), X(dd), UG(dd), Lx(dd), Ux(dd, 0.0L);
+    auto at = [d](int i, int j) { return (size_t)i * d + j; };
+    for (int i = 0; i < d; ++i)
+        for (int j = 0; j < d; ++j) {
+            xreal s = 0.0L;
+            for (int k = 0; k < d; ++k) s += (xreal)A[at(i, k)] * (xreal)Pprev[at(k, j)];
+            AP[at(i, j)] = s;
+        }
+    for (int i = 0; i < d; ++i)
+        for (int j = 0; j <= i; ++j) {
+            xreal s = (xreal)Q[at(i, j)] + (i == j ? (xreal)1e-10 : 0.0L);
+            for (int k = 0; k < d; ++k) s += AP[at(i, k)] * (xreal)A[at(j, k)];
+            Pp[at(i, j)] = Pp[at(j, i)] = s;
+        }
+    for (int j = 0; j < d; ++j) {      // Pp = C C', C lower
+        xreal s = Pp[at(j, j)];
+        for (int k = 0; k < j; ++k) s -= C[at(j, k)] * C[at(j, k)];
+        if (!(s > 0.0L)) return false;
+        const xreal cj = sqrtl(s);
+        C[at(j, j)] = cj;
+        for (int i = j + 1; i < d; ++i) {
+            xreal v = Pp[at(i, j)];
+            for (int k = 0; k < j; ++k) v -= C[at(i, k)] * C[at(j, k)];
+            C[at(i, j)] = v / cj;
+        }
+    }
+    for (int c = 0; c < d; ++c) {      // X = Pp \ (A Pprev), column by column: G = X'
+        for (int i = 0; i < d; ++i) {
+            xreal v = AP[at(i, c)];
+            for (int k = 0; k < i; ++k) v -= C[at(i, k)] * UG[at(k, c)];
+            UG[at(i, c)] = v / C[at(i, i)];      // (C \ A Pprev = C' X: the factor of the term L loses)
+        }
+        for (int i = d - 1; i >= 0; --i) {
+            xreal v = UG[at(i, c)];
+            for (int k = i + 1; k < d; ++k) v -= C[at(k, i)] * X[at(k, c)];
+            X[at(i, c)] = v / C[at(i, i)];
+        }
+    }
+    for (int i = 0; i < d; ++i)
+        for (int j = 0; j < d; ++j) G[at(i, j)] = (double)X[at(j, i)];
+    for (int i = 0; i < d; ++i)
+        for (int j = 0; j <= i; ++j) {
+            xreal s = 0.5L * ((xreal)Pprev[at(i, j)] + (xreal)Pprev[at(j, i)]);
+            for (int k = 0; k < d; ++k) s -= UG[at(k, i)] * UG[at(k, j)];
+            Lx[at(i, j)] = Lx[at(j, i)] = s;
+            L[at(i, j)] = L[at(j, i)] = (double)s;
+        }
+    for (int j = 0; j < d; ++j)      // U' U = L + 1e-9 I, U upper
+        for (int i = 0; i <= j; ++i) {
+            xreal s = Lx[at(i, j)] + (i == j ? (xreal)1e-9 : 0.0L);
+            for (int k = 0; k < i; ++k) s -= Ux[at(k, i)] * Ux[at(k, j)];
+            if (i == j) {
+                if (!(s > 0.0L)) return false;
+                Ux[at(j, j)] = sqrtl(s);
+            } else {
+                Ux[at(i, j)] = s / Ux[at(i, i)];
+            }
+        }
+    for (size_t i = 0; i < dd; ++i) U[i] = (double)Ux[i];
+    return true;
+}
+
+// The draw half of the plan, data-free as the rest: (G_t, L_t, U_t) of the head's steps from its kept filtered covariances (step 0: the prior's), of the
+// settled step behind them, halo_draw of the settled G, the factor of the last filtered covariance, the kernel's table and its chunks.
+int plan_draw_build(Engine* e, long long T) {
+    const int d = e->d, n0 = e->info.n0, DP = e->dp;
+    const size_t dd = (size_t)d * d;
+    if (e->Pf_head.size() != (size_t)n0 * dd) return kNoHeadCov;
+    std::vector<double> Q(dd), P0(dd);
+    {
+        const double* k = e->key.data();      // (the model as handed to plan: A, a, Q, H, hh, R, x0m, x0P -- column-major blocks)
+        const double *Qc = k + dd + d, *Pc = k + 2 * dd + 3 * d + 2;
+        for (int i = 0; i < d; ++i)
+            for (int j = 0; j < d; ++j) {
+                Q[(size_t)i * d + j] = 0.5 * (Qc[i + (size_t)j * d] + Qc[j + (size_t)i * d]);
+                P0[(size_t)i * d + j] = 0.5 * (Pc[i + (size_t)j * d] + Pc[j + (size_t)i * d]);
+            }
+    }
+    e->Gd.assign((size_t)(n0 + 1) * dd, 0.0);
+    e->Ld.assign((size_t)(n0 + 1) * dd, 0.0);
+    e->Ud.assign((size_t)(n0 + 1) * dd, 0.0);
+    for (int t = 0; t <= n0; ++t) {
+        const double* Pprev = t == 0 ? P0.data() : e->Pf_head.data() + (size_t)(t - 1) * dd;
+        if (!invert_dynamics_host(d, e->A.data(), Q.data(), Pprev, e->Gd.data() + (size_t)t * dd, e->Ld.data() + (size_t)t * dd, e->Ud.data() + (size_t)t * dd)) return kNotPD;
+    }
+    const double *G = e->Gd.data() + (size_t)n0 * dd, *U = e->Ud.data() + (size_t)n0 * dd;
+    const long long halo = halo_of(d, std::vector<double>(G, G + dd));
+    if (halo < 0) return kSlowMixing;
+    e->info.halo_draw = (int)halo;
+    // chol(P_(T-1) + 1e-12 I).U (gaussian.jl:35-43): the last filtered covariance is the settled one
+    e->Uend.assign(dd, 0.0);
+    {
+        const double* Pe = e->Pf_head.data() + (size_t)(n0 - 1) * dd;
+        std::vector<xreal> Ux(dd, 0.0L);
+        for (int j = 0; j < d; ++j)
+            for (int i = 0; i <= j; ++i) {
+                xreal s = (xreal)Pe[(size_t)i * d + j] + (i == j ? (xreal)1e-12 : 0.0L);
+                for (int k = 0; k < i; ++k) s -= Ux[(size_t)k * d + i] * Ux[(size_t)k * d + j];
+                if (i == j) {
+                    if (!(s > 0.0L)) return kNotPD;
+                    Ux[(size_t)j * d + j] = sqrtl(s);
+                } else {
+                    Ux[(size_t)i * d + j] = s / Ux[(size_t)i * d + i];
+                }
+            }
+        for (size_t i = 0; i < dd; ++i) e->Uend[i] = (double)Ux[i];
+    }
+    const long long Tb = T - n0;
+    if (Tb < 64) return kTooShort;
+    // chunks as k_wide_rand's: one wave each, none shorter than half its warm-up
+    long long chunks = std::min<long long>(kMaxChunks, std::max<long long>(1, Tb / std::max<long long>(64, halo / 2)));
+    const long long len = (Tb + chunks - 1) / chunks;
+    chunks = (Tb + len - 1) / len;
+    e->info.draw_chunks = chunks;
+    e->info.draw_chunk_len = len;
+    const double* K = e->Kt.data() + (size_t)(n0 - 1) * d;
+    e->tabd_host.assign((size_t)(2 * DP + 1) * 64, 0.0);
+    for (int i = 0; i < d; ++i) {
+        double gk = 0.0;
+        for (int j = 0; j < d; ++j) {
+            e->tabd_host[(size_t)j * 64 + i] = G[(size_t)i * d + j];
+            e->tabd_host[(size_t)(DP + j) * 64 + i] = U[(size_t)j * d + i];      // U'[i][j]
+            gk += G[(size_t)i * d + j] * K[j];
+        }
+        e->tabd_host[(size_t)(2 * DP) * 64 + i] = gk;
+    }
+    for (int j = 0; j < d; ++j) e->tabd_host[(size_t)j * 64 + d] = e->hvec[j];      // the observer: h . dl_t
+    return kOk;
+}
+}  // namespace
+
+bool plan_draw(Engine* e, long long T) {
+    if (!e->have || e->info.why != kOk) return false;
+    const int halo_kept = e->info.halo_draw;
+    const long long chunks_kept = e->info.draw_chunks, len_kept = e->info.draw_chunk_len;
+    if (!e->draw_ready) {
+        const auto t_begin = std::chrono::steady_clock::now();
+        e->draw_why = plan_draw_build(e, T);
+        e->draw_ready = true;
+        e->draw_dev_current = false;
+        e->info.plan_draw_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    } else {
+        e->info.plan_draw_ms = 0.0;
+        e->info.halo_draw = halo_kept;
+        e->info.draw_chunks = chunks_kept;
+        e->info.draw_chunk_len = len_kept;
+    }
+    e->info.why_draw = e->draw_why;
+    return e->draw_why == kOk;
+}
+void draw_stationary(const Engine* e, double* G, double* L, double* U) {
+    const size_t dd = (size_t)e->d * e->d, off = (size_t)e->info.n0 * dd;
+    if (!e->draw_ready || e->draw_why != kOk) return;
+    if (G) std::memcpy(G, e->Gd.data() + off, dd * sizeof(double));
+    if (L) std::memcpy(L, e->Ld.data() + off, dd * sizeof(double));
+    if (U) std::memcpy(U, e->Ud.data() + off, dd * sizeof(double));
+}
+
+int posterior_rand(Engine* e, hipStream_t stream, const Call& c, const double* eps_t, const double* eps_e, const double* eps0_host, double* y_out, double* lml_out,
+                   std::string* err) {
+    auto fail = [&](hipError_t rc, const char* what) {
+        if (err) *err = std::string("tgp_wide posterior draw: ") + what + ": " + hipGetErrorString(rc);
+        return (int)rc;
+    };
+    if (!e->have || e->info.why != kOk || !e->draw_ready || e->draw_why != kOk || !c.y || !c.Rnew || !eps_t || !eps_e || !eps0_host || !y_out)
+        return fail(hipErrorInvalidValue, "no plan");
+    const int d = e->d, DP = e->dp, n0 = e->info.n0;
+    const size_t dd = (size_t)d * d;
+    const long long T = c.T;
+    hipError_t rc = pinned_ready(e);
+    if (rc != hipSuccess) return fail(rc, "pinned buffer");
+    const size_t nf = e->tab_host.size(), nd = e->tabd_host.size();
+    if (!e->draw_dev) {
+        rc = tgp_alloc::dev_malloc(reinterpret_cast<void**>(&e->draw_dev), (size_t)((64 + 2) + (2 * 64 + 1)) * 64 * sizeof(double));      // (both tables at DP = 64)
+        if (rc != hipSuccess) return fail(rc, "tables");
+        e->draw_dev_current = false;
+    }
+    double *tab_f = e->draw_dev, *tab_d = tab_f + nf;
+    if (!e->draw_dev_current) {
+        rc = hipMemcpyAsync(tab_f, e->tab_host.data(), nf * sizeof(double), hipMemcpyHostToDevice, stream);
+        if (rc == hipSuccess) rc = hipMemcpyAsync(tab_d, e->tabd_host.data(), nd * sizeof(double), hipMemcpyHostToDevice, stream);
+        if (rc != hipSuccess) return fail(rc, "table upload");
+        e->draw_dev_current = true;
+    }
+    rc = grow(e->rbuf, e->rbuf_cap, (size_t)T * sizeof(double));
+    if (rc != hipSuccess) return fail(rc, "innovation buffer");
+    const size_t npin = (size_t)n0 * (d + 2) + 64;
+    if (npin > e->draw_pin_cap) {
+        if (e->draw_pin) (void)tgp_alloc::host_free(e->draw_pin);
+        e->draw_pin = nullptr;
+        e->draw_pin_cap = 0;
+        rc = tgp_alloc::host_malloc(reinterpret_cast<void**>(&e->draw_pin), npin * sizeof(double), hipHostMallocDefault);
+        if (rc != hipSuccess) return fail(rc, "pinned buffer");
+        e->draw_pin_cap = npin;
+    }
+    double *yh = e->pinned + pin::yh, *Rh = e->pinned + pin::Rh, *hth = e->pinned + pin::hth, *part = e->pinned + pin::part;
+    double *eth = e->draw_pin, *eeh = eth + (size_t)n0 * d, *outh = eeh + n0, *dlh = outh + n0;
+    rc = hipMemcpyAsync(yh, c.y, (size_t)n0 * sizeof(double), hipMemcpyDeviceToHost, stream);
+    if (rc == hipSuccess) rc = hipMemcpyAsync(Rh, c.Rnew, (size_t)(c.rnew_per_step ? n0 : 1) * sizeof(double), hipMemcpyDeviceToHost, stream);
+    if (rc == hipSuccess && c.h_t) rc = hipMemcpyAsync(hth, c.h_t, (size_t)n0 * sizeof(double), hipMemcpyDeviceToHost, stream);
+    if (rc == hipSuccess) rc = hipMemcpyAsync(eth, eps_t, (size_t)n0 * d * sizeof(double), hipMemcpyDeviceToHost, stream);
+    if (rc == hipSuccess) rc = hipMemcpyAsync(eeh, eps_e, (size_t)n0 * sizeof(double), hipMemcpyDeviceToHost, stream);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(stream);
+    if (rc != hipSuccess) return fail(rc, "head inputs");
+    ZArg z0, xT;
+    const double quad = head_forward(e, yh, c.h_t ? hth : nullptr, z0, &e->head_r, nullptr);
+    for (int i = 0; i < 64; ++i) {      // dl_(T-1) = chol(P_(T-1) + 1e-12 I).U' eps_0
+        double s = 0.0;
+        if (i < d)
+            for (int k = 0; k <= i; ++k) s += e->Uend[(size_t)k * d + i] * eps0_host[k];
+        xT.z[i] = s;
+    }
+    launch_forward(e, stream, true, tab_f, c.y, T, z0, part, e->rbuf, c.h_t, nullptr);
+    rc = hipGetLastError();
+    if (rc != hipSuccess) return fail(rc, "launch");
+    const long long len = e->info.draw_chunk_len, halo = e->info.halo_draw;
+    const unsigned chunks = (unsigned)e->info.draw_chunks;
+    const double rs = e->R / e->Sss;
+    if (DP == 32)
+        hipLaunchKernelGGL(k_wide_post_rand<32>, dim3(chunks), dim3(64), 0, stream, tab_d, c.y, e->rbuf, eps_t, eps_e, c.Rnew, c.rnew_per_step, rs, T, (long long)n0, len, halo, d, d,
+                           xT, y_out, dlh);
+    else
+        hipLaunchKernelGGL(k_wide_post_rand<64>, dim3(chunks), dim3(64), 0, stream, tab_d, c.y, e->rbuf, eps_t, eps_e, c.Rnew, c.rnew_per_step, rs, T, (long long)n0, len, halo, d, d,
+                           xT, y_out, dlh);
+    rc = hipGetLastError();
+    if (rc != hipSuccess) return fail(rc, "launch");
+    rc = hipStreamSynchronize(stream);
+    if (rc != hipSuccess) return fail(rc, "kernel");
+    // ---- the head on the host: y*_t = y_t - (R / S_t) r_t + h . dl_t + sqrt(Rnew_t) e_t; dl_(t-1) = G_t (dl_t + K_t r_t) + U_t' eps_t
+    {
+        const double* h = e->hvec.data();
+        std::vector<double> dl(dlh, dlh + d), v(d), dn(d);
+        for (int t = n0 - 1; t >= 0; --t) {
+            const double r = e->head_r[t], St = e->St[t];
+            const double *Kt = e->Kt.data() + (size_t)t * d, *Gt = e->Gd.data() + (size_t)t * dd, *Ut = e->Ud.data() + (size_t)t * dd, *et = eth + (size_t)t * d;
+            double hx = 0.0;
+            for (int i = 0; i < d; ++i) {
+                hx += h[i] * dl[i];
+                v[i] = dl[i] + Kt[i] * r;
+            }
+            outh[t] = (yh[t] - (e->R / St) * r) + hx + std::sqrt(Rh[c.rnew_per_step ? t : 0]) * eeh[t];
+            for (int i = 0; i < d; ++i) {
+                double s = 0.0;
+                for (int k = 0; k < d; ++k) s += Gt[(size_t)i * d + k] * v[k];
+                for (int k = 0; k <= i; ++k) s += Ut[(size_t)k * d + i] * et[k];
+                dn[i] = s;
+            }
+            dl.swap(dn);
+        }
+    }
+    rc = hipMemcpyAsync(y_out, outh, (size_t)n0 * sizeof(double), hipMemcpyHostToDevice, stream);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(stream);
+    if (rc != hipSuccess) return fail(rc, "head outputs");
     *lml_out = closing_lml(e, T, quad, part);
     return 0;
 }

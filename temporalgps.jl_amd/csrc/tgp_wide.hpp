@@ -23,6 +23,12 @@
 //               into the record (mu_t = A m_(t-1) + a) and runs tgp_wide_adjoint_host.hpp's finish on the plan's kept head.  Device scratch, kept
 //               by the engine between calls: m and lam whole, 2 T d doubles (T = 1e7, d = 28: 4.5 GB), the innovations (T doubles) and the waves'
 //               partial sums of G (2048 (16 ceil((d + 2) / 16))^2 doubles at most: 8 MB at d = 28).
+//   draw        rand of posterior(model, y) with the noise replaced and the draws supplied (lgssm.jl:65-91 on the Reverse model of :193-238) without
+//               evaluating that model.  In dl_t = x_t - m_t (m_t the filtered mean) the reverse-time recursion needs no mean at all:
+//               dl_(t-1) = G_t (dl_t + K_t r_t) + U_t' eps_t, y*_t = y_t - (R / S_t) r_t + h . dl_t + sqrt(Rnew_t) e_t, with (G_t, L_t) of
+//               invert_dynamics and U_t = chol(L_t + 1e-9 I).U -- constants behind the head.  The forward kernel keeps its innovations, k_wide_post_rand
+//               (the shape of k_wide_rand, run backward: G forgets a state within halo_draw steps) draws the steps behind the head, the head's n0 steps
+//               run on the host with the per-step G_t, U_t of the draw plan.  Device scratch: the innovations (T doubles).
 // Before this engine such models ran on ONE compute unit (tgp_dense_fused.hpp: a persistent kernel, sequential in time).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -47,12 +53,14 @@ struct ModelHost {      // shared blocks, column-major as handed to tgp_model_se
     const double *x0m = nullptr, *x0P = nullptr;
 };
 
-enum Why { kOk = 0, kNotPD = 1, kNotSettled = 2, kSlowMixing = 3, kTooShort = 4, kAlloc = 5, kTailLong = 6 };
+enum Why { kOk = 0, kNotPD = 1, kNotSettled = 2, kSlowMixing = 3, kTooShort = 4, kAlloc = 5, kTailLong = 6, kNoHeadCov = 7 };
 struct Info {
     int why = kOk, n0 = -1, nhs = 0, halo = 0;
     int why_post = kOk, n1 = -1, halo_back = 0;
+    int why_draw = kOk, halo_draw = 0;
+    long long draw_chunks = 0, draw_chunk_len = 0;
     long long chunks = 0, chunk_len = 0;
-    double plan_ms = 0.0, plan_post_ms = 0.0;      // 0 when the plan of the previous call was kept
+    double plan_ms = 0.0, plan_post_ms = 0.0, plan_draw_ms = 0.0;      // 0 when the plan of the previous call was kept
     double finish_ms = 0.0;                        // the host half of the last adjoint call
 };
 
@@ -73,7 +81,12 @@ inline bool supports(int d) { return d > 8 && d <= kMaxD; }      // (d <= 8: the
 bool plan(Engine* e, const ModelHost& m, long long T);
 // ... and its posterior half (the backward recursion's matrix, the variances of the series' two ends), built once per planned model.  false: Info::why_post.
 bool plan_posterior(Engine* e, long long T);
+// ... and its draw half (the reverse-time transition of lgssm.jl:231-238 at the settled covariance and through the head, their noise factors, halo_draw, the
+// factor of the last filtered covariance), built once per planned model from the head's kept covariances.  false: Info::why_draw.
+bool plan_draw(Engine* e, long long T);
 const Info& last_plan(const Engine* e);
+// the draw plan's settled G and L (row-major d x d each) and U = chol(L + 1e-9 I).U
+void draw_stationary(const Engine* e, double* G, double* L, double* U);
 // logpdf (and, with Call::mean, the posterior marginals: lgssm.jl:99-115 on posterior(model, y) with the noise replaced by Rnew) of the planned model:
 // the head on the host, ONE kernel behind it (two for the posterior: forward keeping the innovations, backward in Bryson-Frazier form).
 // Synchronises `stream`.  0, or a hipError_t.
@@ -93,5 +106,11 @@ int adjoint_finish_host(int d, const double* rec, const double* yh, long long ny
 // Enqueues ONE kernel (k_wide_rand) on `stream` -- no synchronisation behind it.  *declined: the open loop does not forget (nothing was enqueued).
 int rand(Engine* e, hipStream_t stream, const ModelHost& m, long long T, const double* x0_host, const double* eps_t, const double* eps_e, double* y_out, bool* declined,
          std::string* err);
+
+// rand(replace_observation_noise_cov(posterior(model, y), Rnew)) of the planned model (plan and plan_draw both true) with the draws supplied: Call::y,
+// Rnew, h_t as for run; eps_t [T][d], eps_e [T], y_out [T] device pointers, eps0_host [d].  The forward kernel (innovations kept), k_wide_post_rand, the
+// head on the host.  Synchronises `stream`.  *lml_out: logpdf(model, y), the forward pass's by-product.  0, or a hipError_t.
+int posterior_rand(Engine* e, hipStream_t stream, const Call& c, const double* eps_t, const double* eps_e, const double* eps0_host, double* y_out, double* lml_out,
+                   std::string* err);
 
 }  // namespace tgp_wide
