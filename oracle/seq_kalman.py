@@ -1,6 +1,8 @@
 """ORACLE (test infrastructure only). ctypes wrapper around oracle/liboracle_seq.so
 (C restatement, see seq_kalman.c). Models use the dict convention of oracle/lgssm_ref.py,
-kind == 'scalar', ordering == 'F', d <= 8."""
+kind == 'scalar', ordering == 'F'. d <= 8 runs the functions of compile-time dimension, 8 < d <= 64 the same recursions
+with a run-time dimension (the library dispatches; the entry points here are the same). The run-time posterior_marginals
+keeps the reverse dynamics of one block of steps at a time, so series of several million steps fit in memory."""
 import ctypes
 import os
 import subprocess
@@ -89,7 +91,8 @@ def posterior_marginals(model, y, R_new):
     T = model["T"]
     y = np.ascontiguousarray(y, dtype=np.float64)
     Rn = np.ascontiguousarray(np.atleast_1d(R_new), dtype=np.float64)
-    G, g, L = np.empty((T, d, d)), np.empty((T, d)), np.empty((T, d, d))
+    # (the run-time path above d = 8 holds its reverse dynamics itself, one block at a time)
+    G, g, L = (np.empty((T, d, d)), np.empty((T, d)), np.empty((T, d, d))) if d <= 8 else (None, None, None)
     mean, var = np.empty(T), np.empty(T)
     rc = lib().oracle_seq_posterior_marginals(
         d, _i64(T), *args, _p(y), _p(x0m), _p(x0P), _p(Rn), _i64(1 if Rn.shape[0] > 1 else 0),

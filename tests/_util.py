@@ -38,6 +38,89 @@ def pack(model):
                 x0P=np.ascontiguousarray(model["x0P"].T, dtype=np.float64).reshape(-1))
 
 
+# Models whose state dimension sits on the wide-state engine's kernel-family boundaries (csrc/tgp_wide.hip: components per lane and table width
+# change at d = 15/16, 31/32, 47/48; the observer is output d >> 4 of lane d & 15, the wave's last lane at d = 63), and d = 54 in the middle of the LDS
+# form.  At spacing 0.1 and noise 0.1 every one settles (n0 = 96 ... 120, n1 = 163 ... 184) and its closed loop forgets within 512 steps.
+_m52, _m32, _m12 = ("matern52",), ("matern32",), ("matern12",)
+
+
+def _ap(n):
+    return ("approx_periodic", n, 1.0)
+
+
+BOUNDARY_KERNELS = {
+    17: ("sum", ("product", _ap(4), _m32), _m12),
+    31: ("sum", ("product", _ap(7), _m32), ("stretched", 0.6, _m52)),
+    32: ("sum", ("product", _ap(7), _m32), ("stretched", 0.6, _m52), _m12),
+    33: ("sum", ("product", _ap(5), _m52), ("stretched", 0.6, _m52)),
+    47: ("sum", ("product", _ap(11), _m32), ("stretched", 0.6, _m52)),
+    48: ("sum", ("product", _ap(11), _m32), ("stretched", 0.6, _m52), _m12),
+    49: ("sum", ("product", _ap(11), _m32), ("stretched", 0.6, _m52), ("stretched", 1.7, _m32)),
+    54: ("product", _ap(9), _m52),
+    63: ("sum", ("product", _ap(10), _m52), ("stretched", 0.6, _m52)),
+}
+
+
+# --------------------------------------------------------------------------- the wide-state engine's GPU tier (tests/test_gpu_wide*.py)
+WIDE_INFO = ("why", "n0", "halo", "why_post", "n1", "halo_back", "chunks", "chunk_len")
+
+
+def wide_form_label(d, dpp=None):
+    """the profile label of the form the wide-state engine's plan chooses at state dimension d (csrc/tgp_wide.hip form_name; TGP_WIDE_DPP=0 in the
+    environment: the LDS kernels for every d)"""
+    dpp = os.environ.get("TGP_WIDE_DPP") != "0" if dpp is None else dpp
+    if dpp and d <= 47:
+        return "k_wide_lml4<16>" if d <= 15 else "k_wide_lml4" if d <= 31 else "k_wide_lml4<48>"
+    return "k_wide_lml<32>" if d <= 31 else "k_wide_lml<64>"
+
+
+def device_model(tgp, model, wide=1):
+    tr = tgp.GaussMarkovModel(tgp.Forward, model["A"], model["a"], model["Q"], tgp.Gaussian(model["x0m"], model["x0P"]))
+    dm = tgp.LGSSM(tr, tgp.ScalarOutputLGC(model["H"], np.atleast_1d(model["h"]), np.atleast_1d(model["R"])), T=model["T"])
+    dm.handle_options[tgp._lib.OPT_WIDE] = wide
+    return dm
+
+
+def kernels_of(tgp, dm, fn):
+    hd = dm.handle()
+    hd.set_option(tgp._lib.OPT_PROFILE, 1)
+    hd.profile_reset()
+    out = fn()
+    names = set(hd.profile())
+    hd.set_option(tgp._lib.OPT_PROFILE, 0)
+    return out, names
+
+
+def wide_plan(model, T, post=0):
+    """info of the wide-state engine's plan for this model and length (the pure host function tgp_wide_plan), as a dictionary; post = 1: the posterior's plan too
+    (why_post, n1, halo_back)"""
+    from temporalgps_jl_amd import _lib
+    lib = _lib.load()
+    d = len(model["x0m"])
+    c = lambda x: np.ascontiguousarray(np.asarray(x, dtype=np.float64))      # noqa: E731
+    blocks = [c(model["A"][0].T), c(model["a"][0]), c(model["Q"][0].T), c(model["H"][0]), c(np.atleast_1d(model["h"])[:1]),
+              c(np.atleast_1d(model["R"])[:1]), c(model["x0m"]), c(model["x0P"].T)]
+    info, K, S, vp = np.zeros(8, dtype=np.int64), np.zeros(d), np.zeros(1), np.zeros(2)
+    p = lambda x: x.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
+    assert lib.tgp_wide_plan(d, *[p(b) for b in blocks], T, post, p(info), p(K), p(S), p(vp)) == 0, info
+    return dict(zip(WIDE_INFO, (int(v) for v in info)))
+
+
+def dense_gp_posterior(model, y, Rn):
+    """The posterior marginals from the model's OWN covariance function, k(s - t) = h' A^|s - t| P_inf h (x0 stationary, no offsets), by a dense Cholesky: no
+    state-space recursion involved (tests/test_gpu_wide.py)"""
+    from scipy.linalg import cho_factor, cho_solve, toeplitz
+    T = model["T"]
+    A, H, P, R = model["A"][0], model["H"][0], model["x0P"], float(model["R"][0])
+    c, v = np.empty(T), P @ H
+    for k in range(T):
+        c[k] = H @ v
+        v = A @ v
+    K = toeplitz(c)
+    cf = cho_factor(K + R * np.eye(T), lower=True)
+    return K @ cho_solve(cf, y), np.diag(K) - np.einsum("ij,ji->i", K, cho_solve(cf, K)) + Rn
+
+
 def is_lti(pk):
     return pk["sA"] == 0 and pk["sa"] == 0 and pk["sQ"] == 0 and pk["sH"] == 0 and pk["sh"] == 0
 

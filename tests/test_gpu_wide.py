@@ -10,10 +10,11 @@ import pytest
 
 from oracle import components as oc
 from oracle import lgssm_ref as ref
+from tests._util import wide_form_label
 
 pytestmark = pytest.mark.gpu
 
-# (TGP_WIDE_DPP=0 in the environment: the LDS kernels for every d -- the A/B run of DESIGN 4.4)
+# (TGP_WIDE_DPP=0 in the environment: the LDS kernels for every d -- the A/B run of DESIGN 4.4, made by hand with this file; wide_form_label follows it)
 NARROW = "k_wide_lml<32>" if os.environ.get("TGP_WIDE_DPP") == "0" else "k_wide_lml4"
 KERNELS = {
     9: ("product", ("matern52",), ("stretched", 0.7, ("matern52",))),
@@ -66,7 +67,7 @@ def test_wide_logpdf_against_the_restatement(tgp, d):
         dm = device_model(tgp, model)
         lp, names = kernels_of(tgp, dm, lambda: tgp.logpdf(dm, y))
         assert abs(lp - lp_ref) <= 1e-10 * abs(lp_ref), (d, T, lp, lp_ref)
-        assert names == {(NARROW + "<16>" if d <= 15 and NARROW == "k_wide_lml4" else NARROW) if d <= 31 else ("k_wide_lml4<48>" if d <= 47 and NARROW == "k_wide_lml4" else "k_wide_lml<64>")}, names
+        assert names == {wide_form_label(d)}, names
         # a second call of the same model keeps the plan; another series, the same answer as the dense engine's sequential pass
         y2 = draw(model, d + T + 1)
         lp2 = tgp.logpdf(dm, y2)
@@ -121,7 +122,9 @@ def dense_gp_posterior(model, y, Rn):
     return K @ cho_solve(cf, y), np.diag(K) - np.einsum("ij,ji->i", K, cho_solve(cf, K)) + Rn
 
 
-@pytest.mark.parametrize("d", (9, 15, 16, 28, 42))      # one / two components per lane with the observer in either half, the LDS kernels
+# one / two components per lane with the observer in either half, three components per lane (d = 42 is k_wide_lml4<., 3>; the LDS kernels, d >= 48, and the form
+# boundaries: tests/test_gpu_wide_edges.py)
+@pytest.mark.parametrize("d", (9, 15, 16, 28, 42))
 def test_wide_posterior_marginals(tgp, d):
     """marginals(replace_observation_noise_cov(posterior(model, y), Rnew)) (lgssm.jl:99-115, 193-238): forward kernel keeping its innovations, backward
     kernel in Bryson-Frazier form, the head and the last n1 steps' variances from the host's tables.  Two references: the dense GP on the model's own

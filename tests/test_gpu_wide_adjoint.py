@@ -9,6 +9,7 @@ import pytest
 
 from oracle import components as oc
 from oracle import lgssm_ref as ref
+from tests._util import BOUNDARY_KERNELS, wide_form_label
 
 pytestmark = pytest.mark.gpu
 
@@ -18,7 +19,15 @@ KERNELS = {
     28: ("product", ("approx_periodic", 7, 1.3), ("matern32",)),
     42: ("product", ("approx_periodic", 7, 1.3), ("matern52",)),
     60: ("product", ("approx_periodic", 10, 1.3), ("matern52",)),
+    # the two upper form boundaries and the observer in the wave's last lane (tests/test_gpu_wide_edges.py)
+    **{d: BOUNDARY_KERNELS[d] for d in (31, 32, 47, 48, 63)},
 }
+
+
+def adjoint_label(d):
+    """the profile label of the adjoint call: the form the plan chose names the backward family too (k_wide_bwd4<NB, true> behind k_wide_lml4<true, NB>,
+    k_wide_bwd<DP, true> behind k_wide_lml<DP>)"""
+    return "k_wide_adjoint: " + wide_form_label(d) + " + k_wide_bwd + k_wide_gram"
 
 
 @pytest.fixture(scope="module")
@@ -60,6 +69,7 @@ def test_block_gradients_against_directional_differences_of_the_oracle(tgp, d):
     dm = device_model(tgp, model)
     (lp, g), names = profiled(tgp, dm, lambda: tgp.lgssm.logpdf_adjoint(dm, y))
     assert names and all(n.startswith("k_wide_adjoint") for n in names), names
+    assert names == {adjoint_label(d)}, (d, names)
     lp_ref = ref.logpdf(model, y)
     assert abs(lp - lp_ref) <= 1e-10 * abs(lp_ref), (lp, lp_ref)
     eps = 1e-6
