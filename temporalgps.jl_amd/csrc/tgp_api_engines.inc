@@ -110,8 +110,10 @@ int modal_call(tgp_handle* h, const double* y, uint32_t flags, const double* Rne
     TRY(copy_back(h, mean_out, dm, nT, odev));
     TRY(copy_back(h, var_out, dv, nT, odev));
     if (h->timing) (void)hipEventRecord(h->ev[3], h->stream);
-    // (a logpdf-only call on the streaming kernel with the end-of-kernel flag: nothing but the triples in pinned memory to wait for)
-    if (h->timing || h->profile || !tgp_modal::await_done(h->modal)) HIPCHK(hipStreamSynchronize(h->stream));
+    // (a call on a streaming kernel ends on the workgroups' records in pinned memory: a logpdf-only call has nothing else to wait for, a posterior call's
+    //  outputs are in device memory in front of its records -- unless they go back to the host behind the kernel, or the call is timed or profiled)
+    const bool by_records = !h->timing && !h->profile && ((mean_out == nullptr && var_out == nullptr) || odev) && tgp_modal::await_done(h->modal);
+    if (!by_records) HIPCHK(hipStreamSynchronize(h->stream));
     if (dbg) {
         const auto tp4 = std::chrono::steady_clock::now();
         auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };

@@ -669,7 +669,9 @@ double finish(const tgp_plan::Modal& md, const Geometry& g, const double* part, 
 }
 
 bool records_there(const Geometry& g, int d, const double* part, long long seq, size_t* next) {
-    const size_t n = (size_t)g.nwg * (1 + 2 * d);
+    return records_there((size_t)g.nwg * (1 + 2 * d), part, seq, next);
+}
+bool records_there(size_t n, const double* part, long long seq, size_t* next) {
     const unsigned long long key = record_key(seq);
     const volatile unsigned long long* q = reinterpret_cast<const volatile unsigned long long*>(part);
     size_t k = *next;

@@ -45,6 +45,8 @@ __host__ __device__ inline unsigned long long record_key(long long seq) { return
 // Have all records of call `seq` arrived?  *next: the first pair not yet seen (0 at the first call; the scan resumes there).  With every record there
 // the kernel has read all of y and written all it writes: the host may go on without synchronising the stream (which stays ordered).
 bool records_there(const Geometry& g, int d, const double* part, long long seq, size_t* next);
+// ... the same over the first n pairs of any record table of call `seq` (the streaming posterior kernel's: one pair per workgroup, tgp_post.hpp)
+bool records_there(size_t n, const double* part, long long seq, size_t* next);
 
 // Wt = sum_{t < n} w_t' w_t (d x d, row-major), n = Geometry::first_tile -- data-free, O(d^2 log n) on the host
 void quad_table(const tgp_plan::Modal& md, long long n, double* Wt);

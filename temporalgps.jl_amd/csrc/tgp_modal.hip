@@ -1087,6 +1087,9 @@ struct Engine {
     tgp_lml::Geometry lg{};
     double lWt[tgp_plan::kMaxD * tgp_plan::kMaxD];
     bool lml_records = false;          // the host may take the launched kernel's end from its records in pinned memory (tgp_lml.hpp records_there)
+    // the streaming posterior kernel (tgp_post.hip): the last launch was k_post_stream (its sums are (value, check) records in `part`); the host
+    // may take that launch's end from the records (every output byte written through and acknowledged in front of them: tgp_post.hpp records_end)
+    bool post_stream = false, post_records = false;
     void* pxch = nullptr;              // device memory: the exchange records of the streaming posterior kernel's runs (tgp_post.hpp)
     long long stream_min_T = -1;       // TGP_OPT_STREAM_MIN_T
     // the core of the last plan, kept while the model and the length stand (the reference's own sequence -- logpdf(model, y), then posterior(model, y) --
@@ -1154,6 +1157,16 @@ static bool use_post_stream(const Engine* e, const Call& c) {
     return al(c.y) && al(c.mean) && al(c.var) && (!c.rnew_per_step || al(c.Rnew));
 }
 
+// TGP_POST_RECORDS=0: the end of a k_post_stream launch by hipStreamSynchronize as before (A/B runs; the twin of TGP_LML_RECORDS).  The development
+// stamps of TGP_POST_DBG are plain stores nobody waits for: they keep the synchronising end as well.
+static bool post_records_enabled() {
+    static const bool on = [] {
+        const char* s = std::getenv("TGP_POST_RECORDS");
+        return !(s && s[0] == '0') && std::getenv("TGP_POST_DBG") == nullptr;
+    }();
+    return on;
+}
+
 template <int D>
 int launch(Engine* e, hipStream_t st, const Call& c, const char** kname) {
     if (use_post_stream(e, c)) {
@@ -1187,8 +1200,11 @@ int launch(Engine* e, hipStream_t st, const Call& c, const char** kname) {
         e->nwg_local = g.nwg;
         e->owns_head = true;
         e->hh_pending = true;
+        e->post_stream = true;
+        e->post_records = post_records_enabled() && tgp_post::records_end(pc);
         return tgp_post::enqueue(st, e->md, g, pc, kname);
     }
+    e->post_stream = false;
     KArgs<D> ka;
     static_assert(sizeof(KArgs<D>) <= 4096, "the kernel-argument segment");
     std::memset(&ka, 0, sizeof ka);
@@ -1467,6 +1483,7 @@ void memo_store(Engine* e, const tgp_plan::ModelHost& m, long long T) {
 bool plan(Engine* e, const tgp_plan::ModelHost& m, long long T, bool logpdf_only) {
     e->began = false;
     e->lml = false;
+    e->post_stream = false;
     if (!host_cpu_ok()) {
         e->info = tgp_plan::Info{};
         e->info.why = tgp_plan::kEigFail;
@@ -1553,7 +1570,8 @@ bool plan(Engine* e, const tgp_plan::ModelHost& m, long long T, bool logpdf_only
     choose_geometry(e->md.d, halo, &e->nw, &e->sub);
     const long long C = (long long)e->nw * 64 * e->sub - 2LL * halo;
     e->nwg = (T - e->md.nhs + C - 1) / C;
-    const size_t need = std::max<size_t>((size_t)e->nwg + 64, 8192);      // (room for the streaming kernels' triples and development stamps)
+    // (k_steady_one: a sum per workgroup and its development stamps; k_post_stream: its record table and stamps)
+    const size_t need = std::max<size_t>({(size_t)e->nwg + 64, tgp_post::part_doubles(), (size_t)8192});
     if (need > e->part_cap) {
         if (e->part) (void)tgp_alloc::host_free(e->part);
         e->part = nullptr;
@@ -1562,6 +1580,9 @@ bool plan(Engine* e, const tgp_plan::ModelHost& m, long long T, bool logpdf_only
             e->info.why = tgp_plan::kEigFail;
             return false;
         }
+        // (cleared as the logpdf path clears its own: the allocator hands out parked pinned blocks as they were left, and another engine's records
+        //  -- its call numbers start at 1 as this one's do -- must not pass for this engine's in await_done)
+        std::memset(e->part, 0, need * sizeof(double));
         e->part_cap = need;
     }
     e->began = true;
@@ -1661,15 +1682,20 @@ bool complete(Engine* e, long long T) {
 // every record is there the kernel has read all of y and written all it writes, and the host goes on without hipStreamSynchronize (the kernel's own
 // end -- the release at the end of the dispatch, the queue's barrier packet, the completion signal -- is ~4 us the caller need not wait for; the
 // stream stays ordered: whatever is enqueued next runs behind the kernel).  false: the stream drained or failed without them -- synchronise.
+// k_post_stream takes the same end: its workgroups store mean and var write-through and issue their record -- one pair each -- behind the last
+// acknowledged output store of their waves, so with every record there the outputs are in memory for any stream of the device.  Launches that keep
+// plain stores -- a noise variance per step -- and every k_steady_one launch, segments included, synchronise as before.
 bool await_done(Engine* e) {
-    if (!e || !e->began || !e->lml || !e->lml_records) return false;
+    if (!e || !e->began) return false;
+    if (e->lml ? !e->lml_records : !(e->post_stream && e->post_records)) return false;
+    const size_t n = e->lml ? (size_t)e->lg.nwg * (1 + 2 * e->md.d) : (size_t)e->nwg_local;
     size_t next = 0;
     for (unsigned spin = 1;; ++spin) {
-        if (tgp_lml::records_there(e->lg, e->md.d, e->part, e->seq, &next)) return true;
+        if (tgp_lml::records_there(n, e->part, e->seq, &next)) return true;
         if ((spin & 4095u) == 0) {
             const hipError_t q = hipStreamQuery(e->stream);
             (void)hipGetLastError();
-            if (q != hipErrorNotReady) return tgp_lml::records_there(e->lg, e->md.d, e->part, e->seq, &next);
+            if (q != hipErrorNotReady) return tgp_lml::records_there(n, e->part, e->seq, &next);
         }
         __builtin_ia32_pause();
     }
@@ -1705,6 +1731,7 @@ int enqueue(Engine* e, hipStream_t stream, const Call& c, const char** kname, st
         b.head_in = hh_in(e);
         b.flags = hh_flag(e);
         e->lml_records = lml_records_enabled();
+        e->post_stream = false;
         e->post = false;
         e->stream = stream;
         e->owns_head = true;
@@ -1737,7 +1764,8 @@ void finish_parts(const Engine* e, double* ssq, double* head_quad) {
         return;
     }
     double s = 0.0;
-    for (long long g = 0; g < e->nwg_local; ++g) s += e->part[g];
+    const int stride = e->post_stream ? 2 : 1;      // (k_post_stream: (value, check) pairs)
+    for (long long g = 0; g < e->nwg_local; ++g) s += e->part[stride * g];
     *ssq = s;
     *head_quad = e->owns_head ? (e->hosthead ? e->host_quad : e->part[e->nwg_local]) : 0.0;
 }
@@ -1747,7 +1775,7 @@ double finish(const Engine* e, long long T) {
     const Modal& md = e->md;
     if (std::getenv("TGP_POST_DBG") != nullptr && (std::atoi(std::getenv("TGP_POST_DBG")) & 16) && e->post && e->nwg_local <= 256) {
         // development: the runs' start / end stamps of k_post_stream (100 MHz ticks)
-        const double* q = e->part + 512;
+        const double* q = e->part + tgp_post::kStampOff;
         const long long R = e->nwg_local * 8;
         double s0 = 1e300, s1 = -1e300, e0 = 1e300, e1 = -1e300, esum = 0.0;
         long long elast = -1, n = 0;

@@ -2,6 +2,8 @@
 // through the kernel-argument segment).
 #include "tgp_post.hpp"
 
+#include "tgp_lml.hpp"      // record_key: the workgroups' records are marked as k_lml_stream's are
+
 #include <cstdlib>
 #include <cstring>
 
@@ -62,6 +64,22 @@ __device__ __forceinline__ double wave_sum(double x) {
 }
 // the 16-byte slot of piece j of lane L in a wave's LDS slice (tgp_lml.hip slot_of, eight pieces per lane)
 __device__ __forceinline__ int slot_of(int L, int j) { return L * PPL + (j ^ ((L >> 1) & (PPL - 1))); }
+
+// The outputs are stored WRITE-THROUGH (sc0 sc1): the per-XCD L2s are not coherent with each other and nothing but the dispatch's end writes them back,
+// so a call that ends on its records (tgp_post.hpp) must have every byte of mean / var in memory before the record.  Sixteen bytes per lane and
+// instruction -- a 16-byte sc1 store costs what a plain one does, an 8-byte one 2.7x per byte (kept for the few element-by-element tiles).
+// (inline assembly without a memory clobber: the compiler neither counts these stores nor orders the slice's LDS reads one by one in front of them --
+//  with a clobber every ds_read waits for the store before it.  What the vmcnt(16) accounting of `landed` rests on: volatile asm statements
+//  keep their program order among themselves -- these stores, the loads into LDS and the waits are all volatile -- and the kernel has no
+//  compiler-visible access to mean or var that could pass them: every store to the outputs goes through here or through store_out.)
+template <int OFF>
+__device__ __forceinline__ void store16_wt(v2d* dst, v2d w) {
+    asm volatile("global_store_dwordx4 %0, %1, off offset:%2 sc0 sc1" ::"v"(dst), "v"(w), "n"(OFF));
+}
+__device__ __forceinline__ void store_out(double* dst, double v, bool through) {      // `through` wave-uniform
+    if (through) asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" ::"v"(dst), "v"(v) : "memory");
+    else *dst = v;
+}
 
 // a bounded wait for a flag in pinned host memory (tgp_modal.hip wait_tables): two seconds of the 100 MHz clock, then on with a poisoned sum
 constexpr long long kWaitTicks = 200000000ll;
@@ -347,6 +365,16 @@ __global__ __launch_bounds__(kNW * 64, 2) void k_post_stream(const PArgs<D> by_v
         // (y, mean, var and a per-step Rnew are on 16-byte boundaries: tgp_modal.hip sends everything else to k_steady_one.)
         // (`ln`: the lane number behind an optimisation barrier of the current pass -- the slice addresses are recomputed per pass, a handful of integer
         //  instructions, instead of living in forty registers across the whole loop)
+        // (a tile's eight whole lines of a lane: line k sits 1 KB behind line k - 1 -- two base addresses, the rest in the instructions' offsets)
+        auto store_lines = [&](v2d* q, const v2d (&w)[PPL]) {
+            static_assert(PPL == 8, "eight lines per lane");
+            v2d* q4 = q + 4 * 64;
+            store16_wt<0>(q, w[0]); store16_wt<1024>(q, w[1]); store16_wt<2048>(q, w[2]); store16_wt<3072>(q, w[3]);
+            store16_wt<0>(q4, w[4]); store16_wt<1024>(q4, w[5]); store16_wt<2048>(q4, w[6]); store16_wt<3072>(q4, w[7]);
+        };
+        // (the element-by-element tiles and the head: written through as well unless the call brings a noise variance per step -- such a call keeps plain
+        //  stores everywhere and ends on the stream's synchronisation: tgp_post.hpp records_end)
+        const bool through = !ka.rnew_per_step;
         auto flush = [&](v2d* sY, long long tile_t0, const double (&mm)[N], int ln) -> int {
             int issued = -1;      // 16: exactly the sixteen plain stores; -1: something else (the caller then waits for everything)
             lds_sync();
@@ -362,21 +390,22 @@ __global__ __launch_bounds__(kNW * 64, 2) void k_post_stream(const PArgs<D> by_v
             const bool plain = tile_t0 + TILE <= T && T - tile_t0 > (long long)tgp_plan::kTailMax + TILE && !ka.rnew_per_step;
             if (plain) {
                 if (!(ka.dbg & 1)) {
-                    v2d* __restrict__ q = reinterpret_cast<v2d*>(ka.mean + tile_t0);
+                    v2d w[PPL];
 #pragma unroll
                     for (int k = 0; k < PPL; ++k) {
                         const unsigned e = (unsigned)(k * 64 + ln);
-                        q[e] = sY[slot_of((int)(e >> 3), (int)(e & 7))];
+                        w[k] = sY[slot_of((int)(e >> 3), (int)(e & 7))];
                     }
+                    store_lines(reinterpret_cast<v2d*>(ka.mean + tile_t0) + ln, w);
                 }
                 lds_sync();
                 if (!(ka.dbg & 2)) {
-                    v2d w;
-                    w.x = ka.vb + rn0;
-                    w.y = w.x;
-                    v2d* __restrict__ q = reinterpret_cast<v2d*>(ka.var + tile_t0);
+                    v2d w[PPL];
+                    w[0].x = ka.vb + rn0;
+                    w[0].y = w[0].x;
 #pragma unroll
-                    for (int k = 0; k < PPL; ++k) q[k * 64 + ln] = w;
+                    for (int k = 1; k < PPL; ++k) w[k] = w[0];
+                    store_lines(reinterpret_cast<v2d*>(ka.var + tile_t0) + ln, w);
                 }
                 if (!(ka.dbg & 3)) issued = 16;
                 return issued;
@@ -404,12 +433,12 @@ __global__ __launch_bounds__(kNW * 64, 2) void k_post_stream(const PArgs<D> by_v
                     const v2d w = sY[slot_of((int)(e >> 3), (int)(e & 7))];
                     const long long t = tile_t0 + 2 * (long long)e;
                     if (t < T) {
-                        ka.mean[t] = w.x;
-                        ka.var[t] = tv0[k] + (ka.rnew_per_step ? ka.RnewT[t] : rn0);
+                        store_out(ka.mean + t, w.x, through);
+                        store_out(ka.var + t, tv0[k] + (ka.rnew_per_step ? ka.RnewT[t] : rn0), through);
                     }
                     if (t + 1 < T) {
-                        ka.mean[t + 1] = w.y;
-                        ka.var[t + 1] = tv1[k] + (ka.rnew_per_step ? ka.RnewT[t + 1] : rn0);
+                        store_out(ka.mean + t + 1, w.y, through);
+                        store_out(ka.var + t + 1, tv1[k] + (ka.rnew_per_step ? ka.RnewT[t + 1] : rn0), through);
                     }
                 }
                 lds_sync();
@@ -597,27 +626,35 @@ __global__ __launch_bounds__(kNW * 64, 2) void k_post_stream(const PArgs<D> by_v
         if (ka.head_out != nullptr && run == ka.R / 2) {
             if (!wait_flag(ka.hflag + 3, ka.seq)) poison = __builtin_nan("");
             for (int t = lane; t < ka.nhs; t += 64) {
-                ka.mean[t] = ka.head_out[t];
-                ka.var[t] = ka.head_out[ka.nhs + t];
+                store_out(ka.mean + t, ka.head_out[t], through);
+                store_out(ka.var + t, ka.head_out[ka.nhs + t], through);
             }
         }
         acc = wave_sum(acc) + poison;
         if ((ka.dbg & 16) && lane == 0) {      // (development: every run's start and end on the 100 MHz clock, behind the workgroups' sums)
-            ka.part[512 + 2 * run] = (double)dbg_t0;
-            ka.part[512 + 2 * run + 1] = (double)wall_clock64();
+            ka.part[kStampOff + 2 * run] = (double)dbg_t0;
+            ka.part[kStampOff + 2 * run + 1] = (double)wall_clock64();
         }
     }
     if (head_flag_due) {      // (a head wave without a run of its own: a short series)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         raise_head_flag();
     }
+    // The workgroup's record: ONE 16-byte write-through store of (sum, the sum's bits ^ the call's key), the pair k_lml_stream writes -- issued once
+    // every wave of the workgroup has all its output stores acknowledged, so that a host that sees the record of every workgroup has mean and var in memory
+    // and needs no stream synchronisation (tgp_modal.hip await_done)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (lane == 0) sAcc[wave] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
         double t = 0.0;
 #pragma unroll
         for (int w = 0; w < kNW; ++w) t += sAcc[w];
-        ka.part[blockIdx.x] = t;
+        v2d rec;
+        rec.x = t;
+        rec.y = __longlong_as_double(__double_as_longlong(t) ^ (long long)tgp_lml::record_key(ka.seq));
+        v2d* dst = reinterpret_cast<v2d*>(ka.part) + blockIdx.x;
+        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(dst), "v"(rec) : "memory");
     }
 #undef ka
 }

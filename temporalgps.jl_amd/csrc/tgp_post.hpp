@@ -9,7 +9,8 @@
 //     it (tiles are longer than the halo: whatever lies further right has decayed by 2^-64); a run's last tile takes it from a `ghost` pass over the
 //     first halo steps of the next run, a run's first tile its entry state from a state-only pass over the halo steps in front of it.
 // Same host protocol as k_steady_one with the head on the host (tgp_modal.hip `complete`): head_in / z0p / zeta_out / head_out and their flags, the
-// tail variances out of the pinned tables behind their stage flag, sum r^2 per workgroup into `part`.
+// tail variances out of the pinned tables behind their stage flag, sum r^2 per workgroup into `part` -- as a (value, check) record behind the workgroup's
+// last acknowledged output store: mean and var are stored write-through, and the host may end the call on the records.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,7 +39,7 @@ struct Call {
     const double* htab = nullptr;       // packed tables: [0] n1, tail variances at tvb_off (behind stage flag 2)
     int tvb_off = 0;
     const long long* flag = nullptr;    // the stages' flags
-    double* part = nullptr;             // [nwg] sum r^2 per workgroup
+    double* part = nullptr;             // [nwg] (sum r^2, check) pairs, one per workgroup (check = the sum's bits ^ tgp_lml::record_key(seq))
     double* head_in = nullptr;
     const double* z0p = nullptr;
     double* zeta_out = nullptr;
@@ -47,6 +48,12 @@ struct Call {
     long long seq = 0;
     void* xch = nullptr;                // device memory, xch_bytes(): the runs' exchange records (zeroed once; sequence numbers only grow)
 };
+// the development stamps of TGP_POST_DBG=16 (two per run) sit behind the largest record table
+constexpr size_t kStampOff = 2 * (size_t)kMaxWG;
+constexpr size_t part_doubles() { return kStampOff + 2 * (size_t)kMaxWG * kNW; }
+// May the host take the launch's end from the records?  Only if every output byte is written through and acknowledged in front of them: a noise variance
+// per step keeps plain stores (its tiles go out element by element), and such a call ends on the stream's synchronisation as before.
+inline bool records_end(const Call& c) { return !c.rnew_per_step; }
 inline size_t xch_bytes() { return (size_t)kMaxWG * kNW * kMaxD * 16; }
 int enqueue(hipStream_t stream, const tgp_plan::Modal& md, const Geometry& g, const Call& c, const char** kname);
 
