@@ -155,6 +155,17 @@ typedef struct tgp_handle tgp_handle;
                                    crossovers (logpdf 5e6, posterior marginals 3e6 steps at d = 3); 0: always (the tests); a length: from there on */
 #define TGP_OPT_WIDE 19 /* 1 (default): logpdf (and tgp_logpdf_adjoint) of a Forward LTI model with 16 < d <= 63 and scalar observations on the stationary closed loop across the
                            chip (tgp_wide.hip: k_wide_lml); 0: the dense engine's sequential passes (the A/B of the tests) */
+#define TGP_OPT_DENSE_CHUNKED 20 /* dense path, 16 < d <= 64, p <= 16, Forward models (any mask, any per-step block): 1 (default) the persistent passes of
+                                    TGP_OPT_DENSE_FUSED run across the chip for tgp_logpdf / tgp_filter / tgp_[logpdf_and_]posterior_marginals
+                                    (tgp_dense_chunked.hpp): a workgroup per chunk of consecutive steps; a chunk starts a warm-up early from x0
+                                    (the filter forgets), the Bryson-Frazier backward chunk a warm-up late from zero adjoints; every hand-over is checked
+                                    against the neighbour's own run (forwards 1e-12, backwards 1e-11 of the state's size), a pass whose check fails is
+                                    repeated with the warm-up doubled, a model that mixes too slowly or a series too short for 8 chunks of 4 warm-ups runs
+                                    the sequential passes. Posterior marginals of a model the chunks serve run in Bryson-Frazier form by default
+                                    (TGP_OPT_DENSE_FUSED = 2 describes its agreement with the RTS chain). 0: the sequential passes, exactly as before. */
+#define TGP_OPT_DENSE_CHUNK_STEPS 21 /* tests: steps per chunk (0 automatic); a forced geometry is never repaired */
+#define TGP_OPT_DENSE_WARMUP 22      /* tests: forward warm-up steps (0 automatic) */
+#define TGP_OPT_DENSE_WARMUP_BACK 23 /* tests: backward warm-up steps (0 automatic) */
 #define TGP_OPT_TIMING 6 /* 1: record the hipEvents behind tgp_last_timing (off by default: ~30 us of host time per call) */
 #define TGP_OPT_FUSE_SCAN 4 /* 1 (default): the level-0 scan reduce / apply of the forward scan run inside the chunk kernels;
                                0: stand-alone k_scan_reduce / k_scan_apply launches (bit-identical results, for A/B timing) */
@@ -192,6 +203,11 @@ int tgp_steady_steps(tgp_handle* h, int64_t* mean_only, int64_t* total);
    too short, 4 not positive definite, 8 non-finite), state for the bound model (0 untried, 1 serves, -1 declined).  dist [2]: the largest
    relative distance between a warm-up's end state and the run that reproduces it, forwards / backwards (the checks' 1e-12). Either may be NULL. */
 int tgp_sweep_info(tgp_handle* h, int64_t* info, double* dist);
+/* Diagnostics of TGP_OPT_DENSE_CHUNKED for the last tgp_logpdf / tgp_filter / tgp_[logpdf_and_]posterior_marginals call on the dense engine. info [8]:
+   served across the chip (0 / 1), steps per chunk, forward warm-up, backward warm-up, chunks, attempts (launch rounds, forward + backward), status bits
+   of the last attempt (1 forward / 2 backward warm-up too short, 4 not positive definite, 8 non-finite), state for the bound model (0 untried,
+   1 serves, -1 declined).  dist [2]: the worst forward / backward hand-over distance (the checks' 1e-12 / 1e-11). Either may be NULL. */
+int tgp_dense_chunk_info(tgp_handle* h, int64_t* info, double* dist);
 
 /* ---- model: replaces the LGSSM / GaussMarkovModel containers -----------------------------------
  * lgssm.jl:9-12, gauss_markov_model.jl:20-32 (As, as, Qs, x0) + emissions (A = H', a = h, Q = R).

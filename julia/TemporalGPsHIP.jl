@@ -21,6 +21,9 @@ const libtgp = get(ENV, "TGP_HIP_LIB", "libtgp_hip.so")
 # flags (include/tgp_hip.h)
 const SHARED_A, SHARED_a, SHARED_Q, SHARED_H, SHARED_h, SHARED_R = (UInt32(1) << i for i in 0:5)
 
+# options of the dense engine's passes across the chip (include/tgp_hip.h)
+const OPT_DENSE_CHUNKED, OPT_DENSE_CHUNK_STEPS, OPT_DENSE_WARMUP, OPT_DENSE_WARMUP_BACK = Cint(20), Cint(21), Cint(22), Cint(23)
+
 struct HIPStorage{T<:Real} <: StorageType{T}
     device::Int
 end
@@ -48,6 +51,9 @@ function check(h::Handle, rc::Cint)
     rc == 2 && throw(PosDefException(0))          # mirrors cholesky / sqrt failures on the CPU path
     throw(error("libtgp_hip error $rc: $msg"))
 end
+
+# (info [8], dist [2]) of tgp_dense_chunk_info for the handle's last call
+dense_chunk_info(h::Handle) = (info = zeros(Int64, 8); dist = zeros(2); check(h, ccall((:tgp_dense_chunk_info, libtgp), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}), h.ptr, info, dist)); (info, dist))
 
 """Device-backed LGSSM: the flat column-major blocks live in `bufs` (host) and are uploaded once."""
 struct DeviceLGSSM{Tord} <: AbstractLGSSM

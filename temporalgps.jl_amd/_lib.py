@@ -24,6 +24,7 @@ OPT_CHUNK, OPT_PROFILE, OPT_VARIANT, OPT_FUSE_SCAN, OPT_GROUP, OPT_TIMING, OPT_S
 OPT_SWEEP, OPT_SWEEP_CHUNK, OPT_SWEEP_WARMUP, OPT_SWEEP_WARMUP_BACK = 14, 15, 16, 17
 OPT_STREAM_MIN_T = 18
 OPT_WIDE = 19
+OPT_DENSE_CHUNKED, OPT_DENSE_CHUNK_STEPS, OPT_DENSE_WARMUP, OPT_DENSE_WARMUP_BACK = 20, 21, 22, 23
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -45,6 +46,7 @@ _SIGS = {
     "tgp_graph_replays": (_i64, [_vp]),
     "tgp_steady_steps": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "tgp_sweep_info": (ctypes.c_int, [_vp, _vp, _vp]),
+    "tgp_dense_chunk_info": (ctypes.c_int, [_vp, _vp, _vp]),
     "tgp_model_set": (ctypes.c_int, [_vp, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _u32] + [_vp] * 8),
     "tgp_model_set_sde": (ctypes.c_int, [_vp, _i64, ctypes.c_int, ctypes.c_int, _u32] + [_vp] * 10),
     "tgp_model_set_x0": (ctypes.c_int, [_vp, _vp, _vp]),
@@ -225,6 +227,16 @@ class Handle:
         info, dist = np.zeros(8, dtype=np.int64), np.zeros(2)
         self.check(self.lib.tgp_sweep_info(self.h, info.ctypes.data, dist.ctypes.data))
         keys = ("served", "C", "W", "Wb", "waves", "attempts", "status", "state")
+        out = {k: int(v) for k, v in zip(keys, info)}
+        out["dist_f"], out["dist_b"] = float(dist[0]), float(dist[1])
+        return out
+
+    def dense_chunk_info(self):
+        """diagnostics of the dense engine's passes across the chip (TGP_OPT_DENSE_CHUNKED) for the last logpdf / filter / posterior-marginals call"""
+        import numpy as np
+        info, dist = np.zeros(8, dtype=np.int64), np.zeros(2)
+        self.check(self.lib.tgp_dense_chunk_info(self.h, info.ctypes.data, dist.ctypes.data))
+        keys = ("served", "C", "W", "Wb", "chunks", "attempts", "status", "state")
         out = {k: int(v) for k, v in zip(keys, info)}
         out["dist_f"], out["dist_b"] = float(dist[0]), float(dist[1])
         return out

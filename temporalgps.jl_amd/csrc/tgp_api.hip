@@ -261,8 +261,9 @@ constexpr int kTopBS = 512;
 
 // The engine that served the last compute call of a handle (tgp_steady_steps and tgp_sweep_info report it): general = the chunked-scan engine
 // (or the dense one beyond d = 16), steady2 = the stationary-gain scan engine, modal = its one-launch form, dense = the one-launch kernels on
-// the dense powers of the closed loop, sweep = the time-varying-gain engine, wide = the wide-state engine.
-enum class Served : uint8_t { general, steady2, modal, dense, sweep, wide };
+// the dense powers of the closed loop, sweep = the time-varying-gain engine, wide = the wide-state engine, dense_chunked = the dense engine's
+// persistent passes across the chip (tgp_dense_chunk_info).
+enum class Served : uint8_t { general, steady2, modal, dense, sweep, wide, dense_chunked };
 
 struct tgp_handle {
     int device = 0;
@@ -273,6 +274,8 @@ struct tgp_handle {
     bool is_dense = false;
     int dense_structure = 1;     // TGP_OPT_DENSE_STRUCTURE
     int dense_fused = 1;         // TGP_OPT_DENSE_FUSED
+    int dense_chunked = 1;       // TGP_OPT_DENSE_CHUNKED
+    int64_t dense_fC = 0, dense_fW = 0, dense_fWb = 0;      // TGP_OPT_DENSE_CHUNK_STEPS / _WARMUP / _WARMUP_BACK (tests; 0 automatic)
     // model
     bool have_model = false, lti = false;
     int64_t T = 0;
@@ -828,6 +831,14 @@ int scan_only(tgp_handle* h, const char* what) {
     return TGP_OK;
 }
 int dense_fail(tgp_handle* h, int rc) { return rc == TGP_OK ? TGP_OK : h->fail(rc, tgp_dense::last_error(h->dense)); }
+// the end of a dense-engine call whose passes may have run across the chip (tgp_dense_chunked.hpp): such a call records itself as every engine does
+int dense_finish(tgp_handle* h, CallTimer& tm, double* lml_out) {
+    TRY(tm.finish(lml_out));
+    int64_t info[8];
+    tgp_dense::chunk_info(h->dense, info, nullptr);
+    if (info[0] == 1) note_served(h, Served::dense_chunked, 0, h->host_result[0], nullptr);
+    return TGP_OK;
+}
 
 // ---- hipGraph replay (TGP_OPT_GRAPH) --------------------------------------------------------------------------------------
 // A logpdf / posterior-marginals call on a short series is a chain of ~10-15 dependent launches of a few microseconds each:
@@ -1393,6 +1404,17 @@ int tgp_set_option(tgp_handle* h, int option, int64_t value) {
         drop_reduction(h);
         return TGP_OK;
     }
+    if (option == TGP_OPT_DENSE_CHUNKED) {
+        h->dense_chunked = value != 0;
+        if (h->dense) tgp_dense::set_chunked(h->dense, h->dense_chunked);
+        return TGP_OK;
+    }
+    if (option == TGP_OPT_DENSE_CHUNK_STEPS || option == TGP_OPT_DENSE_WARMUP || option == TGP_OPT_DENSE_WARMUP_BACK) {
+        if (value < 0 || value > (1 << 24)) return h->fail(TGP_EINVAL, "dense chunk geometry out of range");
+        (option == TGP_OPT_DENSE_CHUNK_STEPS ? h->dense_fC : option == TGP_OPT_DENSE_WARMUP ? h->dense_fW : h->dense_fWb) = value;
+        if (h->dense) tgp_dense::set_chunk_geometry(h->dense, h->dense_fC, h->dense_fW, h->dense_fWb);
+        return TGP_OK;
+    }
     if (option == TGP_OPT_DENSE_FUSED) {
         h->dense_fused = value < 0 ? 0 : (value > 2 ? 2 : (int)value);       // 0 / 1 / 2; takes effect at the next tgp_model_set
         return TGP_OK;
@@ -1467,6 +1489,17 @@ int tgp_sweep_info(tgp_handle* h, int64_t* info, double* dist) {
         info[7] = h->sweep_state;
     }
     if (dist) { dist[0] = h->sweep_dist[0]; dist[1] = h->sweep_dist[1]; }
+    return TGP_OK;
+}
+
+int tgp_dense_chunk_info(tgp_handle* h, int64_t* info, double* dist) {
+    if (!h) return TGP_EINVAL;
+    if (info)
+        for (int i = 0; i < 8; ++i) info[i] = 0;
+    if (dist) dist[0] = dist[1] = 0.0;
+    if (!h->is_dense || !h->dense) return TGP_OK;
+    tgp_dense::chunk_info(h->dense, info, dist);
+    if (info) info[0] = h->served == Served::dense_chunked ? 1 : 0;
     return TGP_OK;
 }
 
@@ -1614,6 +1647,8 @@ int tgp_model_set(tgp_handle* h, int64_t T, int d, int p, int ordering, uint32_t
         tgp_dense::set_profile(h->dense, h->profile);
         tgp_dense::set_structure(h->dense, h->dense_structure);
         tgp_dense::set_fused(h->dense, h->dense_fused);
+        tgp_dense::set_chunked(h->dense, h->dense_chunked);
+        tgp_dense::set_chunk_geometry(h->dense, h->dense_fC, h->dense_fW, h->dense_fWb);
         TRY(dense_fail(h, tgp_dense::model_set(h->dense, md, h->stream)));
         HIPCHK(hipStreamSynchronize(h->stream));
         for (DevBuf* b : {&h->bA, &h->bQ, &h->bH}) b->release();   // the packed copy is what the kernels read
@@ -1995,7 +2030,7 @@ int tgp_logpdf(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t 
         tgp_dense::set_profile(h->dense, h->profile);
         TRY(dense_fail(h, tgp_dense::filter(h->dense, h->mv.y, h->mv.missing, nullptr, nullptr, h->result.d(), h->stream)));
         tm.kernels_done();
-        return tm.finish(out);
+        return dense_finish(h, tm, out);
     }
     TRY(forward_reduce(h, flags, 0));
     FilterOut fo{};
@@ -2088,7 +2123,7 @@ int tgp_filter(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t 
         tm.kernels_done();
         TRY(copy_back(h, m_out, dm, nm, odev));
         TRY(copy_back(h, P_out, dP, nP, odev));
-        return tm.finish(lml_out);
+        return dense_finish(h, tm, lml_out);
     }
     TRY(forward_reduce(h, flags, 1));
     FilterOut fo{};
@@ -2335,7 +2370,7 @@ int tgp_posterior_marginals(tgp_handle* h, const double* y, const uint8_t* missi
         tm.kernels_done();
         TRY(copy_back(h, mean_out, dm2, nT, odev));
         TRY(copy_back(h, var_out, dv2, nT, odev));
-        return tm.finish(lml_out);
+        return dense_finish(h, tm, lml_out);
     }
     TRY(smoother_forward_impl(h, flags, nullptr, /*allow_group=*/true));
     double *dm = nullptr, *dv = nullptr;

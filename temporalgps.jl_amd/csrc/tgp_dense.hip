@@ -311,6 +311,7 @@ __device__ inline double rdlane(double v, int l) {
 }
 
 #include "tgp_dense_fused.hpp"
+#include "tgp_dense_chunked.hpp"
 
 // One workgroup of 16 waves factorises S = L L' (right-looking, 16-wide panels). Waves 1..15 keep the lower 16 x 16 tiles in
 // registers for the whole factorisation, TRANSPOSED in the MFMA accumulator layout (lane l, register r holds
@@ -903,6 +904,16 @@ struct Engine {
     Buf bPstore, bmstore, bLd, bDinvd, bW0, bW1, bW2, bW3, bslots_blk, bslots_tail, bzero, bPbound, bmbound;
     int fused_opt = 1;           // mid-sized states (Dp <= 64, p <= 16): the persistent single-kernel passes of tgp_dense_fused.hpp
     Buf bfin;                    // state handed from one launch of a persistent pass to the next
+    // the persistent passes across the chip (tgp_dense_chunked.hpp): options, what the bound model needed, the last call's record
+    int chunk_opt = 1;                                 // TGP_OPT_DENSE_CHUNKED
+    int64_t chunk_fC = 0, chunk_fW = 0, chunk_fWb = 0;     // TGP_OPT_DENSE_CHUNK_STEPS / _WARMUP / _WARMUP_BACK (tests; 0 automatic)
+    int chunk_state = 0;                               // bound model: 0 untried, 1 serves, -1 declined
+    int64_t chunk_W = 0, chunk_Wb = 0;                 // warm-ups the bound model's last served call needed (0: estimate first)
+    int64_t chunk_guess = 0;                           // the estimate (0: not made yet)
+    int64_t chunk_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double chunk_dist[2] = {0.0, 0.0};
+    int chunk_cus = 0, chunk_occ_f = 0, chunk_occ_b = 0;
+    Buf bcwarm, bcfin, bcslots, bcstat;
     int64_t segment_opt = 0;     // smoother segment length (0 = automatic); tests force small segments
     // ELL form of a shared A / H with few entries per row (0 == dense)
     int structure_opt = 1;
@@ -938,7 +949,7 @@ void destroy(Engine* e) {
     if (!e) return;
     for (Buf* b : {&e->bA, &e->bQ, &e->bH, &e->ba, &e->bh, &e->bR, &e->bx0, &e->bm, &e->bmp, &e->bP, &e->bPp, &e->bT1, &e->bV, &e->bS,
                    &e->bL, &e->bDinv, &e->bB, &e->bscal, &e->bslots, &e->bAcol, &e->bAval, &e->bHcol, &e->bHval, &e->bPstore, &e->bmstore, &e->bLd, &e->bDinvd, &e->bW0, &e->bW1, &e->bW2, &e->bW3,
-                   &e->bslots_blk, &e->bslots_tail, &e->bzero, &e->bPbound, &e->bmbound, &e->bfin})
+                   &e->bslots_blk, &e->bslots_tail, &e->bzero, &e->bPbound, &e->bmbound, &e->bfin, &e->bcwarm, &e->bcfin, &e->bcslots, &e->bcstat})
         b->release();
     for (auto& pe : e->pending) {
         (void)hipEventDestroy(pe.a);
@@ -953,6 +964,29 @@ void set_structure(Engine* e, int on) { e->structure_opt = on; }
 void set_segment(Engine* e, int64_t steps) { e->segment_opt = steps; }
 void set_fused(Engine* e, int on) { e->fused_opt = on; }
 int fused(const Engine* e) { return e->fused_opt && e->Dp <= 64 && e->p <= 16; }
+static void chunk_forget(Engine* e) {      // a new model or new options: the bound model is untried again
+    e->chunk_state = 0;
+    e->chunk_W = e->chunk_Wb = e->chunk_guess = 0;
+    for (int64_t& v : e->chunk_info) v = 0;
+    e->chunk_dist[0] = e->chunk_dist[1] = 0.0;
+}
+void set_chunked(Engine* e, int on) {
+    e->chunk_opt = on;
+    chunk_forget(e);
+}
+void set_chunk_geometry(Engine* e, int64_t steps, int64_t warmup, int64_t warmup_back) {
+    e->chunk_fC = steps;
+    e->chunk_fW = warmup;
+    e->chunk_fWb = warmup_back;
+    chunk_forget(e);
+}
+void chunk_info(const Engine* e, int64_t* info, double* dist) {
+    if (info) {
+        for (int i = 0; i < 8; ++i) info[i] = e->chunk_info[i];
+        info[7] = e->chunk_state;
+    }
+    if (dist) { dist[0] = e->chunk_dist[0]; dist[1] = e->chunk_dist[1]; }
+}
 int structure(const Engine* e) { return (e->nnzA ? 1 : 0) | (e->nnzH ? 2 : 0) | ((e->fused_opt && e->Dp <= 64 && e->p <= 16) ? 4 : 0); }
 static void resolve_pending(Engine* e);
 int profile_count(Engine* e) {
@@ -1043,12 +1077,18 @@ int set_attrs(Engine* e) {
     DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_fused_filter<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedCfg<32>::LDS_BYTES));
     DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_fused_filter<48>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedCfg<48>::LDS_BYTES));
     DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_fused_filter<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedCfg<64>::LDS_BYTES));
+    DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_chunk_filter<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedCfg<32>::LDS_BYTES));
+    DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_chunk_filter<48>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedCfg<48>::LDS_BYTES));
+    DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_chunk_filter<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedCfg<64>::LDS_BYTES));
     DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_fused_rand<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedRandCfg<32>::LDS_BYTES));
     DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_fused_rand<48>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedRandCfg<48>::LDS_BYTES));
     DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_fused_rand<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedRandCfg<64>::LDS_BYTES));
     DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_fused_smooth<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedSmoothCfg<32>::LDS_BYTES));
     DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_fused_smooth<48>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedSmoothCfg<48>::LDS_BYTES));
     DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_fused_smooth<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedSmoothCfg<64>::LDS_BYTES));
+    DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_chunk_smooth<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedSmoothCfg<32>::LDS_BYTES));
+    DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_chunk_smooth<48>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedSmoothCfg<48>::LDS_BYTES));
+    DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_chunk_smooth<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedSmoothCfg<64>::LDS_BYTES));
     e->attrs_set = true;
     return TGP_OK;
 }
@@ -1067,6 +1107,7 @@ int model_set(Engine* e, const ModelDesc& m, hipStream_t st) {
     e->d = m.d;
     e->p = m.p;
     e->ordering = m.ordering;
+    chunk_forget(e);
     const int Dp = rup16(m.d), Pq = rup16(m.p);
     e->Dp = Dp;
     e->Pq = Pq;
@@ -1335,7 +1376,7 @@ FusedArgs fused_args(const Engine* e, const double* y, const uint8_t* mask, doub
 }
 
 // the filter pass as persistent launches of dk_fused_filter (the state travels through e->bfin between launches)
-int fused_filter(Engine* e, const double* y, const uint8_t* mask, double* m_out, double* P_out, double* result8, hipStream_t st, double* aux_out = nullptr) {
+int fused_filter_seq(Engine* e, const double* y, const uint8_t* mask, double* m_out, double* P_out, double* result8, hipStream_t st, double* aux_out) {
     const size_t nst = ((size_t)e->Dp * e->Dp + e->Dp) * 8;
     DCHK(e->bfin.ensure(nst));
     FusedArgs g = fused_args(e, y, mask, result8);
@@ -1353,32 +1394,302 @@ int fused_filter(Engine* e, const double* y, const uint8_t* mask, double* m_out,
     DCHK(hipGetLastError());
     return TGP_OK;
 }
+
+FusedSmoothArgs fused_smooth_args(const Engine* e, const double* Rnew, int64_t sRn, double* mean_out, double* var_out) {
+    FusedSmoothArgs g;
+    g.T = e->T; g.d = e->d; g.p = e->p; g.Pq = e->Pq;
+    g.A = e->bA.d(); g.H = e->bH.d(); g.h = e->bh.d();
+    g.sA = e->sA; g.sH = e->sH; g.sh = e->sh;
+    g.m_f = e->bmstore.d(); g.P_f = e->bPstore.d(); g.aux = e->bPbound.d();
+    g.Rnew = Rnew; g.sRn = sRn;
+    g.mean_out = mean_out; g.var_out = var_out;
+    return g;
+}
+
+// ------------------------------------------------------------------------------------------------ the passes across the chip
+// (tgp_dense_chunked.hpp) Tolerances of the hand-over checks as in the sweep engine: forwards 1e-12 of the state's size
+// (holds the log-likelihood to 1e-10 relative), backwards 1e-11 (holds the marginals to 1e-8).
+constexpr double kChunkTolF = 1e-12, kChunkTolB = 1e-11;
+constexpr int64_t kChunkMinW = 32, kChunkGuessPerStep = 64;
+constexpr int64_t kChunkMaxChunks = 1 << 16;
+
+struct ChunkPlan {
+    int64_t C = 0, W = 0, Wb = 0, n = 0;
+    bool forced = false;
+};
+
+// First guess of the warm-up: the closed loop Phi = prod_j (I - K_j h_j) A of the fully observed stationary filter at the model's first noise
+// variances, squared until its infinity norm is below 1e-13, plus an eighth. A launch parameter, never a result: the checks decide.
+int chunk_estimate(Engine* e) {
+    e->chunk_guess = kChunkGuessPerStep;
+    if (e->sA != 0 || e->sQ != 0 || e->sH != 0) return TGP_OK;
+    const int d = e->d, p = e->p, Dp = e->Dp, Pq = e->Pq;
+    std::vector<double> Ap((size_t)Dp * Dp), Qp((size_t)Dp * Dp), Hp((size_t)Pq * Dp), Rp((size_t)Pq);
+    DCHK(hipMemcpy(Ap.data(), e->bA.p, Ap.size() * 8, hipMemcpyDeviceToHost));
+    DCHK(hipMemcpy(Qp.data(), e->bQ.p, Qp.size() * 8, hipMemcpyDeviceToHost));
+    DCHK(hipMemcpy(Hp.data(), e->bH.p, Hp.size() * 8, hipMemcpyDeviceToHost));
+    DCHK(hipMemcpy(Rp.data(), e->bR.p, Rp.size() * 8, hipMemcpyDeviceToHost));
+    const size_t dd = (size_t)d * d;
+    std::vector<double> A(dd), P(dd), T1(dd), Phi(dd), M(dd), v((size_t)d);      // row-major
+    for (int i = 0; i < d; ++i)
+        for (int j = 0; j < d; ++j) {
+            A[(size_t)i * d + j] = Ap[i + (size_t)j * Dp];
+            P[(size_t)i * d + j] = Qp[i + (size_t)j * Dp];
+        }
+    auto mul = [&](const std::vector<double>& X, const std::vector<double>& Y, bool Yt, std::vector<double>& Z) {
+        for (int i = 0; i < d; ++i)
+            for (int j = 0; j < d; ++j) {
+                double acc = 0.0;
+                for (int k = 0; k < d; ++k) acc += X[(size_t)i * d + k] * (Yt ? Y[(size_t)j * d + k] : Y[(size_t)k * d + j]);
+                Z[(size_t)i * d + j] = acc;
+            }
+    };
+    bool settled = false;
+    for (int it = 0; it < 600 && !settled; ++it) {
+        mul(A, P, false, T1);
+        mul(T1, A, true, M);                      // M = A P A'
+        for (int i = 0; i < d; ++i)
+            for (int j = 0; j < d; ++j) M[(size_t)i * d + j] += Qp[i + (size_t)j * Dp];
+        Phi = A;
+        for (int j = 0; j < p; ++j) {             // scalar update j: v = P h', s = h v + R, P -= v v' / s, Phi <- (I - v h / s) Phi
+            double sv = Rp[j];
+            for (int i = 0; i < d; ++i) {
+                double acc = 0.0;
+                for (int k = 0; k < d; ++k) acc += M[(size_t)i * d + k] * Hp[j + (size_t)k * Pq];
+                v[i] = acc;
+            }
+            for (int k = 0; k < d; ++k) sv += Hp[j + (size_t)k * Pq] * v[k];
+            if (!(sv > 0.0)) return TGP_OK;
+            for (int i = 0; i < d; ++i)
+                for (int k = 0; k < d; ++k) M[(size_t)i * d + k] -= v[i] * v[k] / sv;
+            for (int c = 0; c < d; ++c) {
+                double hphi = 0.0;
+                for (int k = 0; k < d; ++k) hphi += Hp[j + (size_t)k * Pq] * Phi[(size_t)k * d + c];
+                for (int i = 0; i < d; ++i) Phi[(size_t)i * d + c] -= v[i] * hphi / sv;
+            }
+        }
+        double diff = 0.0, size = 0.0;
+        for (size_t q = 0; q < dd; ++q) {
+            diff = std::max(diff, std::fabs(M[q] - P[q]));
+            size = std::max(size, std::fabs(M[q]));
+        }
+        P = M;
+        settled = diff <= 1e-9 * size;
+    }
+    int64_t k = 1;
+    auto norm = [&](const std::vector<double>& X) {
+        double n = 0.0;
+        for (int i = 0; i < d; ++i) {
+            double r = 0.0;
+            for (int j = 0; j < d; ++j) r += std::fabs(X[(size_t)i * d + j]);
+            n = std::max(n, r);
+        }
+        return n;
+    };
+    while (!(norm(Phi) <= 1e-13) && k < (1 << 22)) {
+        mul(Phi, Phi, false, T1);
+        Phi = T1;
+        k *= 2;
+        if (!std::isfinite(norm(Phi))) return TGP_OK;
+    }
+    e->chunk_guess = std::max(kChunkMinW, k + k / 8);
+    return TGP_OK;
+}
+
+// the geometry of this call; applies == false: the sequential passes serve it
+int chunk_geometry(Engine* e, bool with_backward, ChunkPlan& pl, bool& applies) {
+    applies = false;
+    for (int i = 0; i < 7; ++i) e->chunk_info[i] = 0;
+    e->chunk_dist[0] = e->chunk_dist[1] = 0.0;
+    if (!e->chunk_opt || e->ordering != 0 || e->chunk_state < 0) return TGP_OK;
+    if (e->chunk_cus == 0) {
+        int cus = 0, of = 0, ob = 0;
+        DCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device));
+        if (e->Dp == 32) {
+            DCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&of, dk_chunk_filter<32>, 256, FusedCfg<32>::LDS_BYTES));
+            DCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&ob, dk_chunk_smooth<32>, 256, FusedSmoothCfg<32>::LDS_BYTES));
+        } else if (e->Dp == 48) {
+            DCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&of, dk_chunk_filter<48>, 256, FusedCfg<48>::LDS_BYTES));
+            DCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&ob, dk_chunk_smooth<48>, 256, FusedSmoothCfg<48>::LDS_BYTES));
+        } else {
+            DCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&of, dk_chunk_filter<64>, 256, FusedCfg<64>::LDS_BYTES));
+            DCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&ob, dk_chunk_smooth<64>, 256, FusedSmoothCfg<64>::LDS_BYTES));
+        }
+        e->chunk_cus = std::max(cus, 1);
+        e->chunk_occ_f = std::max(of, 1);
+        e->chunk_occ_b = std::max(ob, 1);
+    }
+    if (e->chunk_guess == 0)
+        if (int rc = chunk_estimate(e)) return rc;
+    pl.forced = e->chunk_fC != 0 || e->chunk_fW != 0 || e->chunk_fWb != 0;
+    pl.W = e->chunk_fW ? e->chunk_fW : (e->chunk_W ? e->chunk_W : e->chunk_guess);
+    pl.Wb = e->chunk_fWb ? e->chunk_fWb : (e->chunk_Wb ? e->chunk_Wb : e->chunk_guess);
+    if (e->chunk_fC) {
+        pl.C = e->chunk_fC;
+    } else {      // chunks of >= 4 W; as many as are resident at once (one round: the least warm-up per step), at least 8. W here is the first
+                  // guess (or the forced one): a warm-up the bound model's repair doubled keeps the chunks it was repaired in (C >= 2 W)
+        const int64_t Wf = e->chunk_fW ? e->chunk_fW : e->chunk_guess, Wk = e->chunk_fWb ? e->chunk_fWb : e->chunk_guess;
+        const int64_t Wm = with_backward ? std::max(Wf, Wk) : Wf;
+        const int64_t nmax = e->T / (4 * Wm);
+        if (nmax < 8) return TGP_OK;
+        const int64_t resident = (int64_t)e->chunk_cus * (with_backward ? std::min(e->chunk_occ_f, e->chunk_occ_b) : e->chunk_occ_f);
+        const int64_t n = std::min(nmax, resident);
+        pl.C = (e->T + n - 1) / n;
+    }
+    pl.n = (e->T + pl.C - 1) / pl.C;
+    if (pl.n < 2 || pl.n > kChunkMaxChunks) return TGP_OK;
+    const size_t nst = ((size_t)e->Dp * e->Dp + e->Dp) * 8;
+    DCHK(e->bcwarm.ensure((size_t)pl.n * nst));
+    DCHK(e->bcfin.ensure((size_t)pl.n * nst));
+    DCHK(e->bcslots.ensure((size_t)pl.n * 4 * 8));
+    DCHK(e->bcstat.ensure(4 * 8));
+    applies = true;
+    return TGP_OK;
+}
+
+void chunk_record(Engine* e, const ChunkPlan& pl, int served, int attempts, int status) {
+    e->chunk_info[0] = served; e->chunk_info[1] = pl.C; e->chunk_info[2] = pl.W; e->chunk_info[3] = pl.Wb; e->chunk_info[4] = pl.n;
+    e->chunk_info[5] = attempts; e->chunk_info[6] = status;
+}
+
+// one forward pass over the chunks + its close kernel; status: the close kernel's bits
+int chunk_forward_once(Engine* e, const ChunkPlan& pl, const double* y, const uint8_t* mask, double* m_out, double* P_out, double* aux_out,
+                       double* result8, hipStream_t st, int& status, double& dist) {
+    FusedArgs g = fused_args(e, y, mask, result8);
+    g.m_out = m_out; g.P_out = P_out; g.aux_out = aux_out;
+    g.x0 = e->bx0.d();
+    ChunkGeom q;
+    q.C = pl.C; q.W = pl.W; q.warm = e->bcwarm.d(); q.fin = e->bcfin.d(); q.slots = e->bcslots.d();
+    const int nst = e->Dp * e->Dp + e->Dp;
+    {
+        Scope sc(e, st, "dk_chunk_filter", e->profile != 0);
+        if (e->Dp == 32) hipLaunchKernelGGL(dk_chunk_filter<32>, dim3((unsigned)pl.n), dim3(256), FusedCfg<32>::LDS_BYTES, st, g, q);
+        else if (e->Dp == 48) hipLaunchKernelGGL(dk_chunk_filter<48>, dim3((unsigned)pl.n), dim3(256), FusedCfg<48>::LDS_BYTES, st, g, q);
+        else hipLaunchKernelGGL(dk_chunk_filter<64>, dim3((unsigned)pl.n), dim3(256), FusedCfg<64>::LDS_BYTES, st, g, q);
+    }
+    {   // hand-over c (1 <= c < n): chunk c's warm-up state against chunk c - 1's end state
+        Scope sc(e, st, "dk_chunk_close", e->profile != 0);
+        hipLaunchKernelGGL(dk_chunk_close, dim3(1), dim3(kCloseThreads), 0, st, e->bcwarm.d() + nst, e->bcfin.d(), nst, (int)pl.n - 1, e->bcslots.d(), (int)pl.n,
+                           kChunkTolF, result8, e->bcstat.d());
+    }
+    double out[2] = {0.0, 0.0};
+    DCHK(hipMemcpyAsync(out, e->bcstat.p, sizeof out, hipMemcpyDeviceToHost, st));
+    DCHK(hipStreamSynchronize(st));
+    resolve(e);
+    DCHK(hipGetLastError());
+    dist = out[0];
+    status = (int)out[1];
+    return TGP_OK;
+}
+
+int chunk_backward_once(Engine* e, const ChunkPlan& pl, const double* Rnew, int64_t sRn, double* mean_out, double* var_out, hipStream_t st, int& status,
+                        double& dist) {
+    FusedSmoothArgs g = fused_smooth_args(e, Rnew, sRn, mean_out, var_out);
+    ChunkGeom q;
+    q.C = pl.C; q.W = pl.Wb; q.warm = e->bcwarm.d(); q.fin = e->bcfin.d();
+    const int Dp = e->Dp, nst = Dp * Dp + Dp;
+    {
+        Scope sc(e, st, "dk_chunk_smooth", e->profile != 0);
+        if (Dp == 32) hipLaunchKernelGGL(dk_chunk_smooth<32>, dim3((unsigned)pl.n), dim3(256), FusedSmoothCfg<32>::LDS_BYTES, st, g, q);
+        else if (Dp == 48) hipLaunchKernelGGL(dk_chunk_smooth<48>, dim3((unsigned)pl.n), dim3(256), FusedSmoothCfg<48>::LDS_BYTES, st, g, q);
+        else hipLaunchKernelGGL(dk_chunk_smooth<64>, dim3((unsigned)pl.n), dim3(256), FusedSmoothCfg<64>::LDS_BYTES, st, g, q);
+    }
+    {   // hand-over c (0 <= c < n - 1): chunk c's warm-up pair against the pair chunk c + 1 carried out of its own steps
+        Scope sc(e, st, "dk_chunk_close", e->profile != 0);
+        hipLaunchKernelGGL(dk_chunk_close, dim3(1), dim3(kCloseThreads), 0, st, e->bcwarm.d(), e->bcfin.d() + nst, nst, (int)pl.n - 1, (const double*)nullptr, 0,
+                           kChunkTolB, (double*)nullptr, e->bcstat.d());
+    }
+    double out[2] = {0.0, 0.0};
+    DCHK(hipMemcpyAsync(out, e->bcstat.p, sizeof out, hipMemcpyDeviceToHost, st));
+    DCHK(hipStreamSynchronize(st));
+    resolve(e);
+    DCHK(hipGetLastError());
+    dist = out[0];
+    status = (int)out[1];
+    return TGP_OK;
+}
+
+// The filter pass of a mid-sized model: across the chip where that applies and its checks pass (*plan_out then holds the geometry), else --
+// seq_fallback -- the sequential launches; without seq_fallback a call the chunks do not serve returns TGP_EUNSUPPORTED with nothing written
+// to result8.
+int fused_filter(Engine* e, const double* y, const uint8_t* mask, double* m_out, double* P_out, double* result8, hipStream_t st, double* aux_out = nullptr,
+                 bool with_backward = false, bool seq_fallback = true, ChunkPlan* plan_out = nullptr) {
+    ChunkPlan pl;
+    bool applies = false;
+    if (int rc = chunk_geometry(e, with_backward, pl, applies)) return rc;
+    if (plan_out) *plan_out = ChunkPlan{};
+    if (applies) {
+        for (int attempt = 1;; ++attempt) {
+            int status = 0;
+            double dist = 0.0;
+            if (int rc = chunk_forward_once(e, pl, y, mask, m_out, P_out, aux_out, result8, st, status, dist)) return rc;
+            e->chunk_dist[0] = dist;
+            const bool ok = !(status & (1 | 8));
+            chunk_record(e, pl, ok ? 1 : 0, attempt, status);
+            if (ok) {
+                e->chunk_state = 1;
+                if (!pl.forced) e->chunk_W = pl.W;
+                if (plan_out) *plan_out = pl;
+                return TGP_OK;
+            }
+            if (pl.forced || (status & 8) || pl.C < 4 * pl.W) {      // (the doubled warm-up must leave C >= 2 W)
+                e->chunk_state = -1;
+                break;
+            }
+            pl.W *= 2;
+        }
+    }
+    if (!seq_fallback) return TGP_EUNSUPPORTED;
+    return fused_filter_seq(e, y, mask, m_out, P_out, result8, st, aux_out);
+}
 // posterior marginals of a mid-sized Forward model: the persistent filter keeps (m_t, P_t) and the per-update records, the
-// persistent Bryson-Frazier pass walks back (tgp_dense_fused.hpp). Returns TGP_EUNSUPPORTED (quietly, no message) when the
-// stored states do not fit: the caller then runs the segmented chain.
+// persistent Bryson-Frazier pass walks back (tgp_dense_fused.hpp) -- both across the chip where the chunks serve the model. Returns
+// TGP_EUNSUPPORTED (quietly, no message) when the stored states do not fit, or when the chunks do not serve the call and the sequential
+// Bryson-Frazier pass is not opted in: the caller then runs the segmented chain.
 int fused_posterior_marginals(Engine* e, const double* y, const uint8_t* mask, const double* Rnew, int64_t sRn, double* mean_out, double* var_out,
                               double* result8, hipStream_t st) {
     const int d = e->d, p = e->p, Dp = e->Dp;
     const size_t nP = (size_t)e->T * d * d * 8, nm = (size_t)e->T * d * 8, nx = (size_t)e->T * p * (d + 2) * 8;
     size_t free_b = 0, total_b = 0;
+    if (e->fused_opt < 2) {       // (served only across the chip: decided before the stores are sized)
+        ChunkPlan probe;
+        bool applies = false;
+        if (int rc = chunk_geometry(e, true, probe, applies)) return rc;
+        if (!applies) return TGP_EUNSUPPORTED;
+    }
     DCHK(hipMemGetInfo(&free_b, &total_b));
     if ((double)(nP + nm + nx) > 0.8 * ((double)free_b + (double)e->bPstore.cap + (double)e->bmstore.cap + (double)e->bPbound.cap)) return TGP_EUNSUPPORTED;
     DCHK(e->bPstore.ensure(nP));
     DCHK(e->bmstore.ensure(nm));
     DCHK(e->bPbound.ensure(nx));            // (the boundary buffer of the segmented smoother doubles as the record store)
     DCHK(e->bfin.ensure(((size_t)Dp * Dp + Dp) * 8));
-    const int rcf = fused_filter(e, y, mask, e->bmstore.d(), e->bPstore.d(), result8, st, e->bPbound.d());
+    ChunkPlan pl;
+    const int rcf = fused_filter(e, y, mask, e->bmstore.d(), e->bPstore.d(), result8, st, e->bPbound.d(), true, e->fused_opt >= 2, &pl);
     if (rcf != TGP_OK) return rcf;
+    if (pl.n > 0) {       // the forward pass ran across the chip: so does the backward pass, with its own check and repair
+        const int attempts_f = (int)e->chunk_info[5];
+        for (int attempt = 1;; ++attempt) {
+            int status = 0;
+            double dist = 0.0;
+            if (int rc = chunk_backward_once(e, pl, Rnew, sRn, mean_out, var_out, st, status, dist)) return rc;
+            e->chunk_dist[1] = dist;
+            const bool ok = !(status & (1 | 8));
+            chunk_record(e, pl, ok ? 1 : 0, attempts_f + attempt, ((status & 1) ? 2 : 0) | (status & 8));
+            if (ok) {
+                if (!pl.forced) e->chunk_Wb = pl.Wb;
+                return TGP_OK;
+            }
+            if (pl.forced || (status & 8) || pl.C < 4 * pl.Wb) {
+                e->chunk_state = -1;
+                break;
+            }
+            pl.Wb *= 2;
+        }
+    }
     Buf adj;
     DCHK(adj.ensure(((size_t)Dp * Dp + Dp) * 8));
-    FusedSmoothArgs g;
-    g.T = e->T; g.d = d; g.p = p; g.Pq = e->Pq;
-    g.A = e->bA.d(); g.H = e->bH.d(); g.h = e->bh.d();
-    g.sA = e->sA; g.sH = e->sH; g.sh = e->sh;
-    g.m_f = e->bmstore.d(); g.P_f = e->bPstore.d(); g.aux = e->bPbound.d();
-    g.Rnew = Rnew; g.sRn = sRn;
+    FusedSmoothArgs g = fused_smooth_args(e, Rnew, sRn, mean_out, var_out);
     g.adj = adj.d();
-    g.mean_out = mean_out; g.var_out = var_out;
     for (int64_t s1 = e->T; s1 > 0; s1 -= kFusedStepsPerLaunch) {
         g.step1 = s1;
         g.step0 = std::max<int64_t>(0, s1 - kFusedStepsPerLaunch);
@@ -1720,10 +2031,14 @@ int posterior_marginals(Engine* e, const double* y, const uint8_t* mask, const d
     if (!e->have_model) return e->fail(TGP_EINVAL, "no model");
     if (e->ordering != 0) return e->fail(TGP_EUNSUPPORTED, "dense path: posterior of a Reverse-ordered model is not implemented");
     DCHK(hipSetDevice(e->device));
+    e->chunk_info[0] = 0;
     // The persistent backward pass is a modified Bryson-Frazier recursion: it has no counterpart of the reference's 1e-10 jitter on the
     // predicted covariance in invert_dynamics (lgssm.jl:235) and forms variances by a difference, so it agrees with the reference's RTS
     // chain to ~1e-6 relative only. It is therefore opt-in (TGP_OPT_DENSE_FUSED = 2); the default is the jitter-faithful chain below.
-    if (fused(e) && e->fused_opt >= 2 && e->segment_opt == 0) {
+    // Across the chip (tgp_dense_chunked.hpp) the same recursion serves the default too, where its chunks apply: the chain's per-step launches
+    // are what a long series cannot afford.
+    const bool chunks_may_serve = e->chunk_opt && e->chunk_state >= 0;
+    if (fused(e) && (e->fused_opt >= 2 || chunks_may_serve) && e->segment_opt == 0) {
         const int rcq = fused_posterior_marginals(e, y, mask, Rnew, sRn ? 1 : 0, mean_out, var_out, result8, st);
         if (rcq != TGP_EUNSUPPORTED) return rcq;
     }

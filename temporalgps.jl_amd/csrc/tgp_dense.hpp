@@ -44,6 +44,12 @@ void set_structure(Engine* e, int on);
 void set_segment(Engine* e, int64_t steps);
 // mid-sized states (d <= 64, p <= 16): 1 (default) the persistent single-kernel passes, 0 the per-step kernel chain
 void set_fused(Engine* e, int on);
+// mid-sized states, Forward models: 1 (default) the persistent passes run across the chip -- a workgroup per chunk of steps behind a checked
+// warm-up (tgp_dense_chunked.hpp); 0 one workgroup, sequential in time. Geometry (tests): steps per chunk, forward / backward warm-up; 0 automatic
+void set_chunked(Engine* e, int on);
+void set_chunk_geometry(Engine* e, int64_t steps, int64_t warmup, int64_t warmup_back);
+// the last filter / posterior-marginals call: info [8] and dist [2] of tgp_dense_chunk_info (tgp_hip.h); either may be null
+void chunk_info(const Engine* e, int64_t* info, double* dist);
 int structure(const Engine* e);   // bit 0: A sparse, bit 1: H sparse, bit 2: persistent single-kernel passes (current model)
 int profile_count(Engine* e);
 KernelTime profile_get(const Engine* e, int idx);

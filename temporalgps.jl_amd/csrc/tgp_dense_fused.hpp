@@ -62,8 +62,16 @@ struct FusedCfg {
 // accumulator layout (lane (lr, lq), register r <-> row 16 x + lq + 4 r, column 16 b + lr): v = h P is formed from them (each
 // lane: 4 rows of one column; the 4 NT row slices are summed by wave 0), the rank-1 downdate is 4 FMAs per tile and lane, and only
 // then a tile goes to LDS, where the next step's A P reads it as the B operand.
-template <int DP>
-__global__ __launch_bounds__(256) void dk_fused_filter(const FusedArgs g) {
+// The walk is shared by the sequential kernel (CH = false: dk_fused_filter, one workgroup, steps [step0, step1)) and by the time-parallel
+// one (CH = true: dk_chunk_filter, tgp_dense_chunked.hpp -- the workgroup owns the steps [run.own0, step1) and walks [step0, run.own0) in
+// front of them as a warm-up that writes nothing).
+struct FusedChunkRun {
+    int64_t own0 = 0;                  // first step of the chunk's own (forward: step index; backward: own1, one past its last step)
+    double* warm = nullptr;            // the state at the crossing from the warm-up into the own steps (layout of x0 / adj)
+    double* slot = nullptr;            // forward: (lml, missing count, first bad step + 1) of the own steps
+};
+template <int DP, bool CH>
+__device__ __forceinline__ void fused_filter_walk(const FusedArgs& g, const FusedChunkRun& run) {
     using C = FusedCfg<DP>;
     constexpr int NT = C::NT, KS = C::KS, LD = C::LD, NSL = C::NSL, HPT = C::HPT;
     constexpr int NGW = 4 / NT > 0 ? 4 / NT : 1;       // waves per block index (NT = 2: two waves share a block row, one x each)
@@ -172,6 +180,13 @@ __global__ __launch_bounds__(256) void dk_fused_filter(const FusedArgs g) {
 
     for (int64_t step = g.step0; step < g.step1; ++step) {
         const int64_t t = tstep(step);
+        const bool own = !CH || step >= run.own0;      // (a warm-up step writes nothing: the neighbour owns those addresses)
+        if constexpr (CH) {
+            if (step == run.own0 && step > g.step0) {  // the warm-up's end state (sP, sm are complete behind the last barrier of update)
+                for (int e = tid; e < DP * DP; e += 256) run.warm[e] = sP[(e % DP) * LD + e / DP];
+                if (tid < DP) run.warm[DP * DP + tid] = sm[tid];
+            }
+        }
         // this step's prefetched inputs; then the loads of the next step
         const double y_c = y_n;
         const int miss_c = miss_n;
@@ -257,7 +272,7 @@ __global__ __launch_bounds__(256) void dk_fused_filter(const FusedArgs g) {
                         sv[lane] = v;
                         sm[lane] = mi + v * sinv * nu;
                     }
-                    if (g.aux_out && !continue_marg) {
+                    if (g.aux_out && !continue_marg && own) {
                         double* ax = g.aux_out + (t * g.p + j) * (int64_t)(g.d + 2);
                         if (lane < g.d) ax[lane] = v;
                         if (lane == 0) {
@@ -265,8 +280,8 @@ __global__ __launch_bounds__(256) void dk_fused_filter(const FusedArgs g) {
                             ax[g.d + 1] = nu;
                         }
                     }
-                    if (lane == 0 && !continue_marg) {
-                        ss[0] = sinv;
+                    if (lane == 0 && !continue_marg) ss[0] = sinv;
+                    if (lane == 0 && !continue_marg && own) {
                         lml += -0.5 * (kLog2Pi + nu * nu * sinv) + (miss ? 0.5 * (kLog2Pi + log(kLargeVar)) : 0.0);
                         sprod *= s;
                         if (sprod > 1e100 || sprod < 1e-100) {
@@ -295,6 +310,7 @@ __global__ __launch_bounds__(256) void dk_fused_filter(const FusedArgs g) {
             lds_barrier();
         };
         auto emit = [&]() __attribute__((always_inline)) {       // filtering distribution of step t (sP, sm are current)
+            if (!own) return;
             if (g.m_out && tid < g.d) g.m_out[t * g.d + tid] = sm[tid];
             if (g.P_out) {
                 double* Po = g.P_out + t * (int64_t)g.d * g.d;
@@ -330,10 +346,20 @@ __global__ __launch_bounds__(256) void dk_fused_filter(const FusedArgs g) {
         if (tid < DP) g.xfin[DP * DP + tid] = sm[tid];
     }
     if (tid == 0) {
-        g.result8[0] += lml - 0.5 * log(sprod);
-        g.result8[1] += nmiss;
-        if (bad != 0.0 && g.result8[2] == 0.0) g.result8[2] = bad;
+        if constexpr (CH) {      // (many workgroups: a slot each, summed in chunk order by dk_chunk_close)
+            run.slot[0] = lml - 0.5 * log(sprod);
+            run.slot[1] = nmiss;
+            run.slot[2] = bad;
+        } else {
+            g.result8[0] += lml - 0.5 * log(sprod);
+            g.result8[1] += nmiss;
+            if (bad != 0.0 && g.result8[2] == 0.0) g.result8[2] = bad;
+        }
     }
+}
+template <int DP>
+__global__ __launch_bounds__(256) void dk_fused_filter(const FusedArgs g) {
+    fused_filter_walk<DP, false>(g, FusedChunkRun{});
 }
 
 // ------------------------------------------------------------------------------------------------ rand (shared A, a, Q)
@@ -455,8 +481,10 @@ struct FusedSmoothCfg {
     static constexpr size_t LDS_BYTES = (size_t)TOTAL * sizeof(double);
 };
 
-template <int DP>
-__global__ __launch_bounds__(256) void dk_fused_smooth(const FusedSmoothArgs g) {
+// CH = true (dk_chunk_smooth): the workgroup owns the steps [step0, run.own0) and walks [run.own0, step1) behind them first, from
+// (lambda, Lambda) = 0, as a warm-up that reads the forward pass's records only and writes nothing.
+template <int DP, bool CH>
+__device__ __forceinline__ void fused_smooth_walk(const FusedSmoothArgs& g, const FusedChunkRun& run) {
     using C = FusedSmoothCfg<DP>;
     constexpr int NT = C::NT, KS = C::KS, LD = C::LD, NG = C::NG;
     extern __shared__ double lds[];
@@ -514,6 +542,7 @@ __global__ __launch_bounds__(256) void dk_fused_smooth(const FusedSmoothArgs g) 
             ax_n[u] = e < naux ? g.aux[t * (int64_t)naux + e] : 0.0;
         }
         if (tid < g.p) rn_n = g.Rnew[g.sRn ? t * g.p + tid : tid];
+        if (CH && t >= run.own0) return;      // (a warm-up step moves the adjoints only: no filtering state)
         const double* P = g.P_f + t * (int64_t)d * d;
 #pragma unroll
         for (int u = 0; u < PPT; ++u) {
@@ -544,6 +573,13 @@ __global__ __launch_bounds__(256) void dk_fused_smooth(const FusedSmoothArgs g) 
     };
 
     for (int64_t t = g.step1 - 1; t >= g.step0; --t) {
+        const bool own = !CH || t < run.own0;
+        if constexpr (CH) {
+            if (t == run.own0 - 1 && g.step1 > run.own0) {      // the warm-up's end state (sL, sl are complete behind the loop's last barrier)
+                for (int e = tid; e < DP * DP; e += 256) run.warm[e] = sL[(e / DP) * LD + e % DP];
+                if (tid < DP) run.warm[DP * DP + tid] = sl[tid];
+            }
+        }
         // ---- filtering state of step t -> LDS; prefetch step t - 1
 #pragma unroll
         for (int u = 0; u < PPT; ++u) {
@@ -561,7 +597,7 @@ __global__ __launch_bounds__(256) void dk_fused_smooth(const FusedSmoothArgs g) 
         if (!H_shared) load_H(t);
         lds_barrier();
         // ---- emission marginals of step t under the smoothed state
-        for (int j = 0; j < g.p; ++j) {
+        for (int j = 0; j < g.p && own; ++j) {
             matvec(sPf, sH + j * DP, sw);          // w = P_f h_j'
             matvec(sL, sw, sz);                     // z = Lambda w
             if (w == 0) {
@@ -660,4 +696,8 @@ __global__ __launch_bounds__(256) void dk_fused_smooth(const FusedSmoothArgs g) 
         for (int e = tid; e < DP * DP; e += 256) g.adj[e] = sL[(e / DP) * LD + e % DP];
         if (tid < DP) g.adj[DP * DP + tid] = sl[tid];
     }
+}
+template <int DP>
+__global__ __launch_bounds__(256) void dk_fused_smooth(const FusedSmoothArgs g) {
+    fused_smooth_walk<DP, false>(g, FusedChunkRun{});
 }
