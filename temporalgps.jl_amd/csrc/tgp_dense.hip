@@ -1109,6 +1109,7 @@ int model_set(Engine* e, const ModelDesc& m, hipStream_t st) {
     e->ordering = m.ordering;
     chunk_forget(e);
     const int Dp = rup16(m.d), Pq = rup16(m.p);
+    if (Dp != e->Dp) e->chunk_cus = 0;      // (the occupancy chunk_geometry looks up is that of the kernels instantiated for the model's DP)
     e->Dp = Dp;
     e->Pq = Pq;
     e->ldB = Dp + 16;
@@ -2031,7 +2032,8 @@ int posterior_marginals(Engine* e, const double* y, const uint8_t* mask, const d
     if (!e->have_model) return e->fail(TGP_EINVAL, "no model");
     if (e->ordering != 0) return e->fail(TGP_EUNSUPPORTED, "dense path: posterior of a Reverse-ordered model is not implemented");
     DCHK(hipSetDevice(e->device));
-    e->chunk_info[0] = 0;
+    for (int i = 0; i < 7; ++i) e->chunk_info[i] = 0;      // (a declined model under the default option 10 goes to the chain below without asking
+    e->chunk_dist[0] = e->chunk_dist[1] = 0.0;             //  chunk_geometry: the record is this call's, not the declining call's)
     // The persistent backward pass is a modified Bryson-Frazier recursion: it has no counterpart of the reference's 1e-10 jitter on the
     // predicted covariance in invert_dynamics (lgssm.jl:235) and forms variances by a difference, so it agrees with the reference's RTS
     // chain to ~1e-6 relative only. It is therefore opt-in (TGP_OPT_DENSE_FUSED = 2); the default is the jitter-faithful chain below.

@@ -403,3 +403,148 @@ def sweepsim_run(model, y, missing=None, Rnew=None, post=True, sde=None, C=0, W=
         int(rn.shape[0] > 1), int(post), C, W, Wb, w_hint, wb_hint, num_cu, _p(mean), _p(var), _p(out))
     return dict(rc=rc, lml=out[0], status=int(out[1]), dist_f=out[2], dist_b=out[3], C=int(out[4]), W=int(out[5]), Wb=int(out[6]),
                 nwaves=int(out[7]), mean=mean, var=var)
+
+
+# --------------------------------------------------------------------------- the dense engine's passes across the chip (tests/test_gpu_dense_chunked*.py)
+DENSE_TOL_F, DENSE_TOL_B = 1e-12, 1e-11          # the hand-over checks' tolerances (csrc/tgp_dense.hip kChunkTolF / kChunkTolB)
+
+
+def scalar_dev(tgp, model, geometry=None, fused=2):
+    L = tgp._lib
+    dm = tgp.LGSSM(tgp.GaussMarkovModel(tgp.Forward, model["A"], model["a"], model["Q"], tgp.Gaussian(model["x0m"], model["x0P"])),
+                   tgp.ScalarOutputLGC(model["H"], np.atleast_1d(model["h"]), np.atleast_1d(model["R"])), T=model["T"])
+    dm.handle_options[L.OPT_WIDE] = 0                # (the dense engine is what is under test)
+    dm.handle_options[L.OPT_DENSE_FUSED] = fused     # 2: the sequential passes of option 20 = 0 are the persistent Bryson-Frazier pass too
+    if geometry:
+        dm.handle_options.update({L.OPT_DENSE_CHUNK_STEPS: geometry[0], L.OPT_DENSE_WARMUP: geometry[1], L.OPT_DENSE_WARMUP_BACK: geometry[2]})
+    return dm
+
+
+def served_once(dm, backward):
+    info = dm.handle().dense_chunk_info()
+    assert info["served"] == 1 and info["chunks"] > 1 and info["attempts"] == (2 if backward else 1) and info["status"] == 0 and info["state"] == 1, info
+    assert info["dist_f"] <= DENSE_TOL_F and (not backward or info["dist_b"] <= DENSE_TOL_B), info
+    return info
+
+
+def sequential(tgp, dm, fn):
+    """the same handle with option 20 = 0: the parent's path"""
+    hd = dm.handle()
+    hd.set_option(tgp._lib.OPT_DENSE_CHUNKED, 0)
+    out = fn()
+    assert hd.dense_chunk_info()["served"] == 0
+    hd.set_option(tgp._lib.OPT_DENSE_CHUNKED, 1)
+    return out
+
+
+def against_sequential(chunked, seq):
+    (lp, mean, var), (lp0, mean0, var0) = chunked, seq
+    assert abs(lp - lp0) <= 1e-10 * abs(lp0), (lp, lp0)
+    np.testing.assert_allclose(mean, mean0, rtol=0, atol=1e-8 * max(1.0, np.abs(mean0).max()))
+    np.testing.assert_allclose(var, var0, rtol=1e-8, atol=0)
+
+
+def _spd(rng, n, scale=1.0):
+    X = rng.standard_normal((n, n)) / np.sqrt(n)
+    return scale * (X @ X.T + 0.5 * np.eye(n))
+
+
+def random_model(rng, T, d, p, ordering="F", per_step=False, rho=None):      # (tests/test_gpu_dense.py)
+    """rho = None: the contraction |A_t| ~ U(0.4, 0.9) is drawn per block; a number: |A_t| = rho x orthogonal, nothing drawn for it"""
+    nA = T if per_step else 1
+    A = np.stack([np.linalg.qr(rng.standard_normal((d, d)))[0] * (rng.uniform(0.4, 0.9) if rho is None else rho) for _ in range(nA)])
+    a = rng.standard_normal((nA, d)) * 0.1
+    Q = np.stack([_spd(rng, d, 0.3) for _ in range(nA)])
+    H = rng.standard_normal((nA, p, d)) / np.sqrt(d)
+    h = rng.standard_normal((nA, p)) * 0.1
+    Rd = rng.uniform(0.05, 0.3, size=(T, p))
+    R = np.stack([np.diag(r) for r in Rd])
+    model = dict(ordering=ordering, kind="small", T=T, A=A, a=a, Q=Q, H=H, h=h, R=R, x0m=rng.standard_normal(d), x0P=_spd(rng, d))
+    return model, Rd
+
+
+def vector_dev(tgp, model, Rd, opts):
+    order = tgp.Forward if model["ordering"] == "F" else tgp.Reverse
+    dm = tgp.LGSSM(tgp.GaussMarkovModel(order, model["A"], model["a"], model["Q"], tgp.Gaussian(model["x0m"], model["x0P"])),
+                   tgp.SmallOutputLGC(model["H"], model["h"], Rd), T=model["T"])
+    dm.handle_options.update(opts)
+    return dm
+
+
+def with_missing(model, y, mk):
+    m2 = dict(model)
+    R2, y2 = model["R"].copy(), y.copy()
+    for t, i in zip(*np.nonzero(mk)):
+        R2[t][i, i] = 1e15
+        y2[t, i] = 0.0
+    m2["R"] = R2
+    return m2, y2, mk.sum() * 0.5 * np.log(2 * np.pi * 1e15)
+
+
+def forced(tgp, C, W, Wb, fused=2):
+    L = tgp._lib
+    return {L.OPT_DENSE_FUSED: fused, L.OPT_DENSE_CHUNK_STEPS: C, L.OPT_DENSE_WARMUP: W, L.OPT_DENSE_WARMUP_BACK: Wb}
+
+
+def dense_chunk_distances(model, y, mk, C, W, Wb):
+    """The hand-over distances (dist_f, dist_b) of the dense engine's chunked passes at the geometry (C, W, Wb), in NumPy: scripts/dense_chunk_proto.py's
+    forward() / backward() with the p observations of a step applied as p scalar updates (diagonal noise; a missing entry as y := 0, R := 1e15), so that
+    vector-observation models have what run() gives the scalar ones.  mk: (T, p) mask (or None).  Only the adjoint pair is walked backwards: the
+    marginals are ref.bryson_frazier_marginals' business."""
+    T, d = model["T"], len(model["x0m"])
+    n = -(-T // C)
+    dist = lambda x, r: float(np.max(np.abs(x - r)) / max(np.max(np.abs(r)), 1e-300))      # noqa: E731
+    blocks = []
+    for t in range(T):
+        A, a, Q = ref.transition(model, t)
+        H, h, R = ref.emission(model, t)
+        H, h = np.atleast_2d(H), np.atleast_1d(h)
+        Rd = np.array(np.atleast_1d(R) if np.ndim(R) < 2 else np.diagonal(R), dtype=np.float64)
+        yt = np.array(np.atleast_1d(y[t]), dtype=np.float64)
+        if mk is not None:
+            mt = np.broadcast_to(np.atleast_1d(mk[t]), Rd.shape)
+            Rd[mt], yt[mt] = 1e15, 0.0
+        blocks.append((A, np.ravel(a), Q, H, h, Rd, yt))
+
+    def step(t, m, P):
+        A, a, Q, H, h, Rd, yt = blocks[t]
+        m, P, upd = A @ m + a, A @ P @ A.T + Q, []
+        for j in range(len(h)):
+            v = P @ H[j]
+            s = H[j] @ v + Rd[j]
+            nu = yt[j] - H[j] @ m - h[j]
+            m, P = m + v * nu / s, P - np.outer(v, v) / s
+            upd.append((v, s, nu))
+        return m, P, upd
+    rec, warm, fin = [None] * T, [None] * n, [None] * n
+    for c in range(n):
+        s0, s1 = c * C, min(T, (c + 1) * C)
+        m, P = model["x0m"].copy(), model["x0P"].copy()
+        for t in range(max(0, s0 - W), s1):
+            if t == s0 and t > max(0, s0 - W):
+                warm[c] = np.concatenate([P.ravel(), m])
+            m, P, upd = step(t, m, P)
+            if t >= s0:
+                rec[t] = upd
+        fin[c] = np.concatenate([P.ravel(), m])
+    dist_f = max([dist(warm[c], fin[c - 1]) for c in range(1, n) if warm[c] is not None] or [0.0])
+    warm, out = [None] * n, [None] * n
+    for c in range(n):
+        s0, s1 = c * C, min(T, (c + 1) * C)
+        top = min(T, s1 + Wb)
+        lam, Lam = np.zeros(d), np.zeros((d, d))
+        for t in range(top - 1, s0 - 1, -1):
+            A, H = blocks[t][0], blocks[t][3]
+            if t == s1 - 1 and top > s1:
+                warm[c] = np.concatenate([Lam.ravel(), lam])
+            for j in range(len(rec[t]) - 1, -1, -1):
+                v, s, nu = rec[t][j]
+                Cm = np.eye(d) - np.outer(v / s, H[j])
+                Lam = Cm.T @ Lam @ Cm + np.outer(H[j], H[j]) / s
+                lam = Cm.T @ lam - H[j] * nu / s
+            if t == 0:
+                break
+            Lam, lam = A.T @ Lam @ A, A.T @ lam
+        out[c] = np.concatenate([Lam.ravel(), lam])
+    dist_b = max([dist(warm[c], out[c + 1]) for c in range(n - 1) if warm[c] is not None] or [0.0])
+    return dist_f, dist_b

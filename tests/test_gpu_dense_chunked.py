@@ -14,9 +14,12 @@ import pytest
 
 from oracle import lgssm_ref as ref
 
+from tests._util import DENSE_TOL_B as TOL_B
+from tests._util import DENSE_TOL_F as TOL_F
+from tests._util import against_sequential, forced, random_model, scalar_dev, sequential, served_once, vector_dev, with_missing
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOL_F, TOL_B = 1e-12, 1e-11
 
 
 @pytest.fixture(scope="module")
@@ -32,41 +35,6 @@ def proto():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
-
-
-def scalar_dev(tgp, model, geometry=None, fused=2):
-    L = tgp._lib
-    dm = tgp.LGSSM(tgp.GaussMarkovModel(tgp.Forward, model["A"], model["a"], model["Q"], tgp.Gaussian(model["x0m"], model["x0P"])),
-                   tgp.ScalarOutputLGC(model["H"], np.atleast_1d(model["h"]), np.atleast_1d(model["R"])), T=model["T"])
-    dm.handle_options[L.OPT_WIDE] = 0                # (the dense engine is what is under test)
-    dm.handle_options[L.OPT_DENSE_FUSED] = fused     # 2: the sequential passes of option 20 = 0 are the persistent Bryson-Frazier pass too
-    if geometry:
-        dm.handle_options.update({L.OPT_DENSE_CHUNK_STEPS: geometry[0], L.OPT_DENSE_WARMUP: geometry[1], L.OPT_DENSE_WARMUP_BACK: geometry[2]})
-    return dm
-
-
-def served_once(dm, backward):
-    info = dm.handle().dense_chunk_info()
-    assert info["served"] == 1 and info["chunks"] > 1 and info["attempts"] == (2 if backward else 1) and info["status"] == 0 and info["state"] == 1, info
-    assert info["dist_f"] <= TOL_F and (not backward or info["dist_b"] <= TOL_B), info
-    return info
-
-
-def sequential(tgp, dm, fn):
-    """the same handle with option 20 = 0: the parent's path"""
-    hd = dm.handle()
-    hd.set_option(tgp._lib.OPT_DENSE_CHUNKED, 0)
-    out = fn()
-    assert hd.dense_chunk_info()["served"] == 0
-    hd.set_option(tgp._lib.OPT_DENSE_CHUNKED, 1)
-    return out
-
-
-def against_sequential(chunked, seq):
-    (lp, mean, var), (lp0, mean0, var0) = chunked, seq
-    assert abs(lp - lp0) <= 1e-10 * abs(lp0), (lp, lp0)
-    np.testing.assert_allclose(mean, mean0, rtol=0, atol=1e-8 * max(1.0, np.abs(mean0).max()))
-    np.testing.assert_allclose(var, var0, rtol=1e-8, atol=0)
 
 
 # ------------------------------------------------------------------------------------------------ product kernels, DP = 32, 48, 64
@@ -165,47 +133,6 @@ def test_two_identical_calls_are_bit_identical(tgp, edge):
 
 
 # ------------------------------------------------------------------------------------------------ random dense models: vector observations, per-step blocks
-def _spd(rng, n, scale=1.0):
-    X = rng.standard_normal((n, n)) / np.sqrt(n)
-    return scale * (X @ X.T + 0.5 * np.eye(n))
-
-
-def random_model(rng, T, d, p, ordering="F", per_step=False):      # (tests/test_gpu_dense.py)
-    nA = T if per_step else 1
-    A = np.stack([np.linalg.qr(rng.standard_normal((d, d)))[0] * rng.uniform(0.4, 0.9) for _ in range(nA)])
-    a = rng.standard_normal((nA, d)) * 0.1
-    Q = np.stack([_spd(rng, d, 0.3) for _ in range(nA)])
-    H = rng.standard_normal((nA, p, d)) / np.sqrt(d)
-    h = rng.standard_normal((nA, p)) * 0.1
-    Rd = rng.uniform(0.05, 0.3, size=(T, p))
-    R = np.stack([np.diag(r) for r in Rd])
-    model = dict(ordering=ordering, kind="small", T=T, A=A, a=a, Q=Q, H=H, h=h, R=R, x0m=rng.standard_normal(d), x0P=_spd(rng, d))
-    return model, Rd
-
-
-def vector_dev(tgp, model, Rd, opts):
-    order = tgp.Forward if model["ordering"] == "F" else tgp.Reverse
-    dm = tgp.LGSSM(tgp.GaussMarkovModel(order, model["A"], model["a"], model["Q"], tgp.Gaussian(model["x0m"], model["x0P"])),
-                   tgp.SmallOutputLGC(model["H"], model["h"], Rd), T=model["T"])
-    dm.handle_options.update(opts)
-    return dm
-
-
-def with_missing(model, y, mk):
-    m2 = dict(model)
-    R2, y2 = model["R"].copy(), y.copy()
-    for t, i in zip(*np.nonzero(mk)):
-        R2[t][i, i] = 1e15
-        y2[t, i] = 0.0
-    m2["R"] = R2
-    return m2, y2, mk.sum() * 0.5 * np.log(2 * np.pi * 1e15)
-
-
-def forced(tgp, C, W, Wb, fused=2):
-    L = tgp._lib
-    return {L.OPT_DENSE_FUSED: fused, L.OPT_DENSE_CHUNK_STEPS: C, L.OPT_DENSE_WARMUP: W, L.OPT_DENSE_WARMUP_BACK: Wb}
-
-
 @pytest.mark.parametrize("d,p", [(20, 2), (40, 16)])
 def test_vector_observations_with_every_block_per_step(tgp, d, p):
     """per-step A, Q (sA != 0), H, h, R and an element-wise mask; p scalar updates per step, forwards and backwards"""
