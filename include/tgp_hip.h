@@ -203,8 +203,9 @@ int tgp_steady_steps(tgp_handle* h, int64_t* mean_only, int64_t* total);
    too short, 4 not positive definite, 8 non-finite), state for the bound model (0 untried, 1 serves, -1 declined).  dist [2]: the largest
    relative distance between a warm-up's end state and the run that reproduces it, forwards / backwards (the checks' 1e-12). Either may be NULL. */
 int tgp_sweep_info(tgp_handle* h, int64_t* info, double* dist);
-/* Diagnostics of TGP_OPT_DENSE_CHUNKED for the last tgp_logpdf / tgp_filter / tgp_[logpdf_and_]posterior_marginals call on the dense engine. info [8]:
-   served across the chip (0 / 1), steps per chunk, forward warm-up, backward warm-up, chunks, attempts (launch rounds, forward + backward), status bits
+/* Diagnostics of TGP_OPT_DENSE_CHUNKED for the last tgp_logpdf / tgp_filter / tgp_[logpdf_and_]posterior_marginals / tgp_posterior_rand_missing call on
+   the dense engine. info [8]: served across the chip (0 / 1), steps per chunk, forward warm-up, backward warm-up (tgp_posterior_rand_missing: the draw
+   pass's), chunks, attempts (launch rounds, forward + backward), status bits
    of the last attempt (1 forward / 2 backward warm-up too short, 4 not positive definite, 8 non-finite), state for the bound model (0 untried,
    1 serves, -1 declined).  dist [2]: the worst forward / backward hand-over distance (the checks' 1e-12 / 1e-11). Either may be NULL. */
 int tgp_dense_chunk_info(tgp_handle* h, int64_t* info, double* dist);
@@ -397,6 +398,21 @@ int tgp_marginals(tgp_handle* h, uint32_t flags, double* mean_out, double* var_o
  *      (tgp_posterior), bind it as a Reverse model and call tgp_rand (what the Python mirror does). */
 int tgp_posterior_rand(tgp_handle* h, const double* y, const double* Rnew, const double* eps_t, const double* eps_e,
                        const double* eps_0, uint32_t flags, double* y_out);
+
+/* ---- the same draw (posterior_lti_sde.jl:48-58 -> missings.jl:25-53, lgssm.jl:193-238, lgssm.jl:65-91, lgc.jl:84-87 / 241-243)
+ *      for what merge_datasets makes of rand(rng, posterior(fx, y)(x_new)): an LGSSM with missing steps, per-step transitions,
+ *      per-step noise, vector observations with diagonal noise -- Forward models of 16 < d <= 64, p <= 16 on the dense engine
+ *      (DESIGN 4.6).  The persistent filter keeps the filtering states and its per-update records (T (d^2 + d + p (d + 2))
+ *      doubles of device scratch, never the reverse-time model), the draw pass walks back on them in the deviation from the
+ *      filtered mean, both across the chip behind checked warm-ups (tgp_dense_chunk_info reports the call: the draw pass in the
+ *      backward slots), else one workgroup sequentially.  missing [T][p] as in tgp_posterior_marginals (may be NULL); eps_t [T][d],
+ *      eps_e / y_out [T][p]; Rnew [p] with TGP_SHARED_R, else [T][p]; eps_0 [d] host; the others where TGP_IN_DEVICE /
+ *      TGP_OUT_DEVICE say.  Draws are used as tgp_rand on the evaluated posterior uses them; emissions of p > 1 (or
+ *      TGP_SMALL_OUTPUT) models add the reference's 1e-9 to Rnew.  TGP_EUNSUPPORTED (nothing written to y_out): another engine's
+ *      handle, a Reverse model, TGP_OPT_DENSE_CHUNKED = 0 or TGP_OPT_DENSE_FUSED = 0, or stores that do not fit -- take
+ *      tgp_posterior_rand (d <= 16) or tgp_posterior + tgp_rand. */
+int tgp_posterior_rand_missing(tgp_handle* h, const double* y, const uint8_t* missing, const double* Rnew, const double* eps_t,
+                               const double* eps_e, const double* eps_0, uint32_t flags, double* y_out);
 
 /* ---- logpdf(replace_observation_noise_cov(posterior(model, y), R_new), y_new) (posterior_lti_sde.jl:62-78 ->
  *      lgssm.jl:147-151 on the reverse-time model of lgssm.jl:193-221) without a posterior: two observations of

@@ -218,15 +218,30 @@ function AbstractGPs.rand(rng::AbstractRNG, p::DevicePosterior)
             m.h.ptr, yv, Rn, eps_t, eps_e, eps_0, length(Rn) == 1 ? SHARED_R : UInt32(0), out)
         rc == 0 && return out
         rc == 4 || check(m.h, rc)
-        # (not a model of the one-launch path: the same draws through the evaluated model)
+        # not a model of the one-launch path: the dense engine's draw pass on the same draws where it serves the model, else the evaluated model
+        dense = _dense_draw(m) ? posterior_rand_missing(m, p.y, Σ, eps_t, eps_e, eps_0) : nothing
+        dense === nothing || return dense
         y = Vector{Float64}(undef, m.T)
         pm = materialise(p)
         check(pm.h, ccall((:tgp_rand, libtgp), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, UInt32, Ptr{Float64}),
             pm.h.ptr, eps_t, eps_e, eps_0, UInt32(0), y))
         return y
     end
+    if p.model === nothing && _dense_draw(m)
+        # what the one-launch path excludes -- missing entries, vector observations with diagonal noise -- on the dense engine's draw pass
+        # (tgp_posterior_rand_missing, DESIGN 4.6), draws in the reference's order; TGP_EUNSUPPORTED: the same draws through the evaluated model
+        eps_t = randn(rng, m.d, m.T); eps_e = randn(rng, m.p, m.T); eps_0 = randn(rng, m.d)
+        out = posterior_rand_missing(m, p.y, p.Σs_new === nothing ? _prior_noise(m) : p.Σs_new, eps_t, eps_e, eps_0)
+        out === nothing || return _per_step(out, m)
+        y = Vector{Float64}(undef, m.p * m.T)
+        pm = materialise(p)
+        check(pm.h, ccall((:tgp_rand, libtgp), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, UInt32, Ptr{Float64}),
+            pm.h.ptr, eps_t, eps_e, eps_0, UInt32(0), y))
+        return _per_step(y, m)
+    end
     return rand(rng, materialise(p))
 end
+_dense_draw(m) = m isa DeviceLGSSM{Forward} && 16 < m.d <= 64 && m.p <= 16
 # logpdf of a posterior that has not been evaluated (posterior_lti_sde.jl:62-78's last line): log p(y* | y) = log p(y, y*) - log p(y), and two
 # observations of one latent value with independent noise are one observation of it (DESIGN 3.18) -- two tgp_logpdf calls of the PRIOR, no
 # reverse-time model of T x (2 d^2 + d) doubles evaluated or filtered.  (`lgssm.py::_posterior_logpdf_pair` is this function.)
@@ -325,6 +340,20 @@ function AbstractGPs.rand(rng::AbstractRNG, m::DeviceLGSSM)
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, UInt32, Ptr{Float64}),
         m.h.ptr, eps_t, eps_e, eps_0, UInt32(0), y))
     return _per_step(y, m)
+end
+
+"""`rand` of `replace_observation_noise_cov(posterior(model, y), Σs_new)` on supplied draws without evaluating the posterior
+(tgp_posterior_rand_missing: 16 < d <= 64, p <= 16 on the dense engine). `nothing`: TGP_EUNSUPPORTED, take the evaluated route."""
+function posterior_rand_missing(m::DeviceLGSSM{Forward}, y::AbstractVector, Σs_new::AbstractVector, eps_t, eps_e, eps_0)
+    yv, mp, mask = _split_missing(y)
+    (R, shared) = m.p == 1 ? _flat(Σs_new) : _flat_diag(Σs_new)
+    out = Vector{Float64}(undef, m.p * m.T)
+    rc = GC.@preserve yv mask R ccall((:tgp_posterior_rand_missing, libtgp), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, UInt32, Ptr{Float64}),
+        m.h.ptr, yv, mp, R, eps_t, eps_e, eps_0, shared ? SHARED_R : UInt32(0), out)
+    rc == 4 && return nothing
+    check(m.h, rc)
+    return out
 end
 
 """Fused `marginals(replace_observation_noise_cov(posterior(model, y), Σs_new))` (posterior_lti_sde.jl:27-36): nothing is

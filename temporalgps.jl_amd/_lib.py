@@ -70,6 +70,7 @@ _SIGS = {
     "tgp_marginals": (ctypes.c_int, [_vp, _u32, _vp, _vp]),
     "tgp_rand": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u32, _vp]),
     "tgp_posterior_rand": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "tgp_posterior_rand_missing": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "tgp_logpdf_noise": (ctypes.c_int, [_vp, _vp, _u32, ctypes.c_double, _vp]),
     "tgp_pair_statistic": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "tgp_elem_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
@@ -232,7 +233,8 @@ class Handle:
         return out
 
     def dense_chunk_info(self):
-        """diagnostics of the dense engine's passes across the chip (TGP_OPT_DENSE_CHUNKED) for the last logpdf / filter / posterior-marginals call"""
+        """diagnostics of the dense engine's passes across the chip (TGP_OPT_DENSE_CHUNKED) for the last logpdf / filter / posterior-marginals /
+        posterior-draw call (the draw pass reports its warm-up and distance in Wb / dist_b)"""
         import numpy as np
         info, dist = np.zeros(8, dtype=np.int64), np.zeros(2)
         self.check(self.lib.tgp_dense_chunk_info(self.h, info.ctypes.data, dist.ctypes.data))

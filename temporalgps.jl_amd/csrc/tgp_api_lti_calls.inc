@@ -435,6 +435,36 @@ int tgp_posterior_rand(tgp_handle* h, const double* y, const double* Rnew, const
     return TGP_OK;
 }
 
+// The same draw where the series has missing steps, the transitions or the noise are per step, or the observations are vectors with diagonal noise --
+// what merge_datasets makes of rand(rng, posterior(fx, y)(x_new)) -- on the dense engine's persistent passes (16 < d <= 64, p <= 16; DESIGN 4.6,
+// tgp_dense_draw.hpp). TGP_EUNSUPPORTED: the caller takes the evaluated route.
+int tgp_posterior_rand_missing(tgp_handle* h, const double* y, const uint8_t* missing, const double* Rnew, const double* eps_t, const double* eps_e,
+                               const double* eps_0, uint32_t flags, double* y_out) {
+    StreamGuard stream_guard_(h);
+    TRY(check_ready(h, /*general=*/false));
+    if (!y || !Rnew || !eps_t || !eps_e || !eps_0 || !y_out) return h->fail(TGP_EINVAL, "tgp_posterior_rand_missing: null argument");
+    if (!h->is_dense || h->ordering != 0 || h->d > 64 || h->p > 16 || !h->dense_fused || !h->dense_chunked)
+        return h->fail(TGP_EUNSUPPORTED, "tgp_posterior_rand_missing: Forward models with 16 < d <= 64 and p <= 16 on the dense engine's passes across the chip "
+                                         "(take tgp_posterior_rand for d <= 16, else tgp_posterior + tgp_rand)");
+    const bool idev = (flags & TGP_IN_DEVICE) != 0, odev = (flags & TGP_OUT_DEVICE) != 0, rshared = (flags & TGP_SHARED_R) != 0;
+    const size_t nT = (size_t)h->T * h->p * sizeof(double);
+    CallTimer tm(h);
+    const void *pR = nullptr, *pet = nullptr, *pee = nullptr;
+    TRY(stage_in(h, h->bRnew, Rnew, rshared ? (size_t)h->p * sizeof(double) : nT, idev, &pR));
+    TRY(set_obs(h, y, missing, flags & ~(uint32_t)TGP_REUSE_REDUCE));
+    TRY(stage_in(h, h->beps_t, eps_t, (size_t)h->T * h->d * sizeof(double), idev, &pet));
+    TRY(stage_in(h, h->beps_e, eps_e, nT, idev, &pee));
+    tm.inputs_done();
+    double* dy = nullptr;
+    TRY(stage_out(h, h->bo1, y_out, nT, odev, &dy));
+    tgp_dense::set_profile(h->dense, h->profile);
+    TRY(dense_fail(h, tgp_dense::posterior_rand(h->dense, h->mv.y, h->mv.missing, (const double*)pR, rshared ? 0 : h->p, (const double*)pet, (const double*)pee,
+                                                eps_0, h->mv.small_out, dy, h->result.d(), h->stream)));
+    tm.kernels_done();
+    TRY(copy_back(h, y_out, dy, nT, odev));
+    return dense_finish(h, tm, nullptr);
+}
+
 // Two observations per step of ONE latent value with independent noise are one observation of it:
 //     N(y; f, R) N(y*; f, R*) = N(ybar; f, Rbar) N(y - y*; 0, R + R*),   Rbar = R R* / (R + R*),   ybar = (R* y + R y*) / (R + R*)
 // -- what turns logpdf(replace_observation_noise_cov(posterior(model, y), R*), y*) (posterior_lti_sde.jl:62-78 -> lgssm.jl:147-151 on the

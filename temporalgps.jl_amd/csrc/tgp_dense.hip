@@ -312,6 +312,7 @@ __device__ inline double rdlane(double v, int l) {
 
 #include "tgp_dense_fused.hpp"
 #include "tgp_dense_chunked.hpp"
+#include "tgp_dense_draw.hpp"
 
 // One workgroup of 16 waves factorises S = L L' (right-looking, 16-wide panels). Waves 1..15 keep the lower 16 x 16 tiles in
 // registers for the whole factorisation, TRANSPOSED in the MFMA accumulator layout (lane l, register r holds
@@ -908,12 +909,15 @@ struct Engine {
     int chunk_opt = 1;                                 // TGP_OPT_DENSE_CHUNKED
     int64_t chunk_fC = 0, chunk_fW = 0, chunk_fWb = 0;     // TGP_OPT_DENSE_CHUNK_STEPS / _WARMUP / _WARMUP_BACK (tests; 0 automatic)
     int chunk_state = 0;                               // bound model: 0 untried, 1 serves, -1 declined
-    int64_t chunk_W = 0, chunk_Wb = 0;                 // warm-ups the bound model's last served call needed (0: estimate first)
+    int64_t chunk_W = 0, chunk_Wb = 0, chunk_Wd = 0;   // warm-ups the bound model's last served call needed (0: estimate first); Wd: the draw pass
     int64_t chunk_guess = 0;                           // the estimate (0: not made yet)
     int64_t chunk_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     double chunk_dist[2] = {0.0, 0.0};
-    int chunk_cus = 0, chunk_occ_f = 0, chunk_occ_b = 0;
+    int chunk_cus = 0, chunk_occ_f = 0, chunk_occ_b = 0, chunk_occ_d = 0;
+    int chunk_draw_state = 0;                          // the draw pass of the bound model: 0 untried, 1 serves, -1 declined (the other passes keep theirs)
+    bool chunk_draw_call = false;                      // the geometry is planned for posterior_rand: the draw kernel's occupancy beside the filter's
     Buf bcwarm, bcfin, bcslots, bcstat;
+    Buf bdraw;                   // posterior_rand: delta of the last step | delta carried between sequential launches | the sequential pass's flag
     int64_t segment_opt = 0;     // smoother segment length (0 = automatic); tests force small segments
     // ELL form of a shared A / H with few entries per row (0 == dense)
     int structure_opt = 1;
@@ -949,7 +953,7 @@ void destroy(Engine* e) {
     if (!e) return;
     for (Buf* b : {&e->bA, &e->bQ, &e->bH, &e->ba, &e->bh, &e->bR, &e->bx0, &e->bm, &e->bmp, &e->bP, &e->bPp, &e->bT1, &e->bV, &e->bS,
                    &e->bL, &e->bDinv, &e->bB, &e->bscal, &e->bslots, &e->bAcol, &e->bAval, &e->bHcol, &e->bHval, &e->bPstore, &e->bmstore, &e->bLd, &e->bDinvd, &e->bW0, &e->bW1, &e->bW2, &e->bW3,
-                   &e->bslots_blk, &e->bslots_tail, &e->bzero, &e->bPbound, &e->bmbound, &e->bfin, &e->bcwarm, &e->bcfin, &e->bcslots, &e->bcstat})
+                   &e->bslots_blk, &e->bslots_tail, &e->bzero, &e->bPbound, &e->bmbound, &e->bfin, &e->bcwarm, &e->bcfin, &e->bcslots, &e->bcstat, &e->bdraw})
         b->release();
     for (auto& pe : e->pending) {
         (void)hipEventDestroy(pe.a);
@@ -965,8 +969,8 @@ void set_segment(Engine* e, int64_t steps) { e->segment_opt = steps; }
 void set_fused(Engine* e, int on) { e->fused_opt = on; }
 int fused(const Engine* e) { return e->fused_opt && e->Dp <= 64 && e->p <= 16; }
 static void chunk_forget(Engine* e) {      // a new model or new options: the bound model is untried again
-    e->chunk_state = 0;
-    e->chunk_W = e->chunk_Wb = e->chunk_guess = 0;
+    e->chunk_state = e->chunk_draw_state = 0;
+    e->chunk_W = e->chunk_Wb = e->chunk_Wd = e->chunk_guess = 0;
     for (int64_t& v : e->chunk_info) v = 0;
     e->chunk_dist[0] = e->chunk_dist[1] = 0.0;
 }
@@ -1089,6 +1093,12 @@ int set_attrs(Engine* e) {
     DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_chunk_smooth<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedSmoothCfg<32>::LDS_BYTES));
     DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_chunk_smooth<48>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedSmoothCfg<48>::LDS_BYTES));
     DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_chunk_smooth<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedSmoothCfg<64>::LDS_BYTES));
+    DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_fused_draw<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedDrawCfg<32>::LDS_BYTES));
+    DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_fused_draw<48>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedDrawCfg<48>::LDS_BYTES));
+    DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_fused_draw<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedDrawCfg<64>::LDS_BYTES));
+    DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_chunk_draw<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedDrawCfg<32>::LDS_BYTES));
+    DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_chunk_draw<48>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedDrawCfg<48>::LDS_BYTES));
+    DCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dk_chunk_draw<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedDrawCfg<64>::LDS_BYTES));
     e->attrs_set = true;
     return TGP_OK;
 }
@@ -1504,21 +1514,25 @@ int chunk_geometry(Engine* e, bool with_backward, ChunkPlan& pl, bool& applies) 
     e->chunk_dist[0] = e->chunk_dist[1] = 0.0;
     if (!e->chunk_opt || e->ordering != 0 || e->chunk_state < 0) return TGP_OK;
     if (e->chunk_cus == 0) {
-        int cus = 0, of = 0, ob = 0;
+        int cus = 0, of = 0, ob = 0, od = 0;
         DCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device));
         if (e->Dp == 32) {
             DCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&of, dk_chunk_filter<32>, 256, FusedCfg<32>::LDS_BYTES));
             DCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&ob, dk_chunk_smooth<32>, 256, FusedSmoothCfg<32>::LDS_BYTES));
+            DCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&od, dk_chunk_draw<32>, 256, FusedDrawCfg<32>::LDS_BYTES));
         } else if (e->Dp == 48) {
             DCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&of, dk_chunk_filter<48>, 256, FusedCfg<48>::LDS_BYTES));
             DCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&ob, dk_chunk_smooth<48>, 256, FusedSmoothCfg<48>::LDS_BYTES));
+            DCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&od, dk_chunk_draw<48>, 256, FusedDrawCfg<48>::LDS_BYTES));
         } else {
             DCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&of, dk_chunk_filter<64>, 256, FusedCfg<64>::LDS_BYTES));
             DCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&ob, dk_chunk_smooth<64>, 256, FusedSmoothCfg<64>::LDS_BYTES));
+            DCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&od, dk_chunk_draw<64>, 256, FusedDrawCfg<64>::LDS_BYTES));
         }
         e->chunk_cus = std::max(cus, 1);
         e->chunk_occ_f = std::max(of, 1);
         e->chunk_occ_b = std::max(ob, 1);
+        e->chunk_occ_d = std::max(od, 1);
     }
     if (e->chunk_guess == 0)
         if (int rc = chunk_estimate(e)) return rc;
@@ -1533,7 +1547,8 @@ int chunk_geometry(Engine* e, bool with_backward, ChunkPlan& pl, bool& applies) 
         const int64_t Wm = with_backward ? std::max(Wf, Wk) : Wf;
         const int64_t nmax = e->T / (4 * Wm);
         if (nmax < 8) return TGP_OK;
-        const int64_t resident = (int64_t)e->chunk_cus * (with_backward ? std::min(e->chunk_occ_f, e->chunk_occ_b) : e->chunk_occ_f);
+        const int occ_back = e->chunk_draw_call ? e->chunk_occ_d : e->chunk_occ_b;
+        const int64_t resident = (int64_t)e->chunk_cus * (with_backward ? std::min(e->chunk_occ_f, occ_back) : e->chunk_occ_f);
         const int64_t n = std::min(nmax, resident);
         pl.C = (e->T + n - 1) / n;
     }
@@ -1705,7 +1720,148 @@ int fused_posterior_marginals(Engine* e, const double* y, const uint8_t* mask, c
     adj.release();
     return TGP_OK;
 }
+
+FusedDrawArgs fused_draw_args(const Engine* e, const double* Rnew, int64_t sRn, const double* eps_t, const double* eps_e, int small_out, double* y_out) {
+    FusedDrawArgs g;
+    g.T = e->T; g.d = e->d; g.p = e->p; g.Pq = e->Pq; g.small_out = small_out;
+    g.A = e->bA.d(); g.Q = e->bQ.d(); g.H = e->bH.d(); g.h = e->bh.d();
+    g.sA = e->sA; g.sQ = e->sQ; g.sH = e->sH; g.sh = e->sh;
+    g.m_f = e->bmstore.d(); g.P_f = e->bPstore.d(); g.aux = e->bPbound.d();
+    g.Rnew = Rnew; g.sRn = sRn;
+    g.eps_t = eps_t; g.eps_e = eps_e;
+    g.y_out = y_out;
+    return g;
+}
+
+// one draw pass over the chunks + its close kernel (hand-over c, 0 <= c < n - 1: chunk c's delta at its crossing against the delta chunk c + 1
+// carried out of its own steps); status: the close kernel's bits
+int chunk_draw_once(Engine* e, const ChunkPlan& pl, const FusedDrawArgs& g, hipStream_t st, int& status, double& dist) {
+    ChunkGeom q;
+    q.C = pl.C; q.W = pl.Wb; q.warm = e->bcwarm.d(); q.fin = e->bcfin.d();
+    const int Dp = e->Dp;
+    const double* start = e->bdraw.d();
+    {
+        Scope sc(e, st, "dk_chunk_draw", e->profile != 0);
+        if (Dp == 32) hipLaunchKernelGGL(dk_chunk_draw<32>, dim3((unsigned)pl.n), dim3(256), FusedDrawCfg<32>::LDS_BYTES, st, g, q, start);
+        else if (Dp == 48) hipLaunchKernelGGL(dk_chunk_draw<48>, dim3((unsigned)pl.n), dim3(256), FusedDrawCfg<48>::LDS_BYTES, st, g, q, start);
+        else hipLaunchKernelGGL(dk_chunk_draw<64>, dim3((unsigned)pl.n), dim3(256), FusedDrawCfg<64>::LDS_BYTES, st, g, q, start);
+    }
+    {
+        Scope sc(e, st, "dk_chunk_close", e->profile != 0);
+        hipLaunchKernelGGL(dk_chunk_close, dim3(1), dim3(kCloseThreads), 0, st, e->bcwarm.d(), e->bcfin.d() + Dp, Dp, (int)pl.n - 1, (const double*)nullptr, 0,
+                           kChunkTolB, (double*)nullptr, e->bcstat.d());
+    }
+    double out[2] = {0.0, 0.0};
+    DCHK(hipMemcpyAsync(out, e->bcstat.p, sizeof out, hipMemcpyDeviceToHost, st));
+    DCHK(hipStreamSynchronize(st));
+    resolve(e);
+    DCHK(hipGetLastError());
+    dist = out[0];
+    status = (int)out[1];
+    return TGP_OK;
+}
 }  // namespace
+
+// rand(posterior(model, y) with replaced observation noise) of a mid-sized Forward model without evaluating the posterior: the persistent filter
+// keeps (m_t, P_t) and the per-update records, the draw pass walks back on them (tgp_dense_draw.hpp) -- both across the chip where the chunks
+// serve the model, else one workgroup sequentially. TGP_EUNSUPPORTED: not such a model, the chunked passes are off (the caller's evaluated route
+// is then "exactly as before"), or the stores do not fit; nothing has been written to y_out.
+int posterior_rand(Engine* e, const double* y, const uint8_t* mask, const double* Rnew, int64_t sRn, const double* eps_t, const double* eps_e,
+                   const double* eps_0_host, int small_out, double* y_out, double* result8, hipStream_t st) {
+    if (!e->have_model) return e->fail(TGP_EINVAL, "no model");
+    DCHK(hipSetDevice(e->device));
+    for (int i = 0; i < 7; ++i) e->chunk_info[i] = 0;
+    e->chunk_dist[0] = e->chunk_dist[1] = 0.0;
+    const int d = e->d, p = e->p, Dp = e->Dp;
+    if (!fused(e) || d <= 16 || e->ordering != 0)
+        return e->fail(TGP_EUNSUPPORTED, "posterior_rand: Forward models with 16 < d <= 64 and p <= 16 on the persistent passes only");
+    if (!e->chunk_opt) return e->fail(TGP_EUNSUPPORTED, "posterior_rand: the passes across the chip are switched off");
+    const size_t nP = (size_t)e->T * d * d * 8, nm = (size_t)e->T * d * 8, nx = (size_t)e->T * p * (d + 2) * 8;
+    size_t free_b = 0, total_b = 0;
+    DCHK(hipMemGetInfo(&free_b, &total_b));
+    if ((double)(nP + nm + nx) > 0.8 * ((double)free_b + (double)e->bPstore.cap + (double)e->bmstore.cap + (double)e->bPbound.cap))
+        return e->fail(TGP_EUNSUPPORTED, "posterior_rand: the filtering states of the series do not fit the device's free memory");
+    DCHK(e->bPstore.ensure(nP));
+    DCHK(e->bmstore.ensure(nm));
+    DCHK(e->bPbound.ensure(nx));
+    DCHK(e->bfin.ensure(((size_t)Dp * Dp + Dp) * 8));
+    DCHK(e->bdraw.ensure((size_t)(2 * Dp + 8) * 8));
+    ChunkPlan pl;
+    e->chunk_draw_call = true;
+    const int rcf = fused_filter(e, y, mask, e->bmstore.d(), e->bPstore.d(), result8, st, e->bPbound.d(), true, true, &pl);
+    e->chunk_draw_call = false;
+    if (rcf != TGP_OK) return rcf;
+    // delta_{T-1} = chol(P_f[T-1] + 1e-12 I).U' eps_0 on the host (gaussian.jl:35-43; the upper triangle, as Symmetric reads it)
+    std::vector<double> Pl((size_t)d * d), start((size_t)2 * Dp + 8, 0.0);
+    DCHK(hipMemcpyAsync(Pl.data(), e->bPstore.d() + (size_t)(e->T - 1) * d * d, Pl.size() * 8, hipMemcpyDeviceToHost, st));
+    DCHK(hipStreamSynchronize(st));
+    resolve(e);
+    for (int k = 0; k < d; ++k) {       // U[k][j] at Pl[k + j d] (column-major), j >= k, in place
+        double piv = Pl[k + (size_t)k * d] + 1e-12;
+        for (int m = 0; m < k; ++m) piv -= Pl[m + (size_t)k * d] * Pl[m + (size_t)k * d];
+        if (!(piv > 0.0)) return e->fail(TGP_ENOTPD, "posterior_rand: the last filtering covariance is not positive definite");
+        const double r = std::sqrt(piv);
+        Pl[k + (size_t)k * d] = r;
+        for (int j = k + 1; j < d; ++j) {
+            double v = Pl[k + (size_t)j * d];
+            for (int m = 0; m < k; ++m) v -= Pl[m + (size_t)k * d] * Pl[m + (size_t)j * d];
+            Pl[k + (size_t)j * d] = v / r;
+        }
+    }
+    for (int i = 0; i < d; ++i) {
+        double v = 0.0;
+        for (int k = 0; k <= i; ++k) v += Pl[k + (size_t)i * d] * eps_0_host[k];
+        start[i] = v;
+    }
+    DCHK(hipMemcpyAsync(e->bdraw.p, start.data(), start.size() * 8, hipMemcpyHostToDevice, st));
+    FusedDrawArgs g = fused_draw_args(e, Rnew, sRn, eps_t, eps_e, small_out, y_out);
+    if (pl.n > 0 && e->chunk_draw_state < 0) {      // this model's draw pass declined before: the sequential walk on the stores of the chunked filter
+        pl.Wb = 0;
+        chunk_record(e, pl, 0, (int)e->chunk_info[5], 2);
+    } else if (pl.n > 0) {       // the forward pass ran across the chip: so does the draw pass, with its own check and repair
+        const int attempts_f = (int)e->chunk_info[5];
+        pl.Wb = e->chunk_fWb ? e->chunk_fWb : (e->chunk_Wd ? e->chunk_Wd : e->chunk_guess);
+        for (int attempt = 1;; ++attempt) {
+            int status = 0;
+            double dist = 0.0;
+            if (int rc = chunk_draw_once(e, pl, g, st, status, dist)) return rc;
+            e->chunk_dist[1] = dist;
+            const bool ok = !(status & (1 | 8));
+            chunk_record(e, pl, ok ? 1 : 0, attempts_f + attempt, ((status & 1) ? 2 : 0) | (status & 8));
+            if (ok) {
+                e->chunk_draw_state = 1;
+                if (!pl.forced) e->chunk_Wd = pl.Wb;
+                return TGP_OK;
+            }
+            if (pl.forced || (status & 8) || pl.C < 4 * pl.Wb) {      // (the filter and the smoother keep the state their own checks gave them)
+                e->chunk_draw_state = -1;
+                break;
+            }
+            pl.Wb *= 2;
+        }
+    }
+    double* carry = e->bdraw.d() + Dp;
+    double* stat = e->bdraw.d() + 2 * Dp;
+    g.stat = stat;
+    g.dout = carry;
+    for (int64_t s1 = e->T; s1 > 0; s1 -= kFusedStepsPerLaunch) {
+        g.step1 = s1;
+        g.step0 = std::max<int64_t>(0, s1 - kFusedStepsPerLaunch);
+        g.d0 = s1 == e->T ? e->bdraw.d() : carry;
+        Scope sc(e, st, "dk_fused_draw", e->profile != 0);
+        if (Dp == 32) hipLaunchKernelGGL(dk_fused_draw<32>, dim3(1), dim3(256), FusedDrawCfg<32>::LDS_BYTES, st, g);
+        else if (Dp == 48) hipLaunchKernelGGL(dk_fused_draw<48>, dim3(1), dim3(256), FusedDrawCfg<48>::LDS_BYTES, st, g);
+        else hipLaunchKernelGGL(dk_fused_draw<64>, dim3(1), dim3(256), FusedDrawCfg<64>::LDS_BYTES, st, g);
+    }
+    double flag = 0.0;
+    DCHK(hipMemcpyAsync(&flag, stat, 8, hipMemcpyDeviceToHost, st));
+    DCHK(hipStreamSynchronize(st));
+    resolve(e);
+    DCHK(hipGetLastError());
+    if (flag == 1.0) return e->fail(TGP_ENOTPD, "posterior_rand: a covariance of the reverse-time model is not positive definite");
+    if (flag != 0.0) return e->fail(TGP_ENOTPD, "posterior_rand: the reverse-time walk met a non-finite value (series, draws or filtering states)");
+    return TGP_OK;
+}
 
 int filter(Engine* e, const double* y, const uint8_t* mask, double* m_out, double* P_out, double* result8, hipStream_t st) {
     if (!e->have_model) return e->fail(TGP_EINVAL, "no model");

@@ -48,7 +48,7 @@ void set_fused(Engine* e, int on);
 // warm-up (tgp_dense_chunked.hpp); 0 one workgroup, sequential in time. Geometry (tests): steps per chunk, forward / backward warm-up; 0 automatic
 void set_chunked(Engine* e, int on);
 void set_chunk_geometry(Engine* e, int64_t steps, int64_t warmup, int64_t warmup_back);
-// the last filter / posterior-marginals call: info [8] and dist [2] of tgp_dense_chunk_info (tgp_hip.h); either may be null
+// the last filter / posterior-marginals / posterior_rand call: info [8] and dist [2] of tgp_dense_chunk_info (tgp_hip.h); either may be null
 void chunk_info(const Engine* e, int64_t* info, double* dist);
 int structure(const Engine* e);   // bit 0: A sparse, bit 1: H sparse, bit 2: persistent single-kernel passes (current model)
 int profile_count(Engine* e);
@@ -77,5 +77,10 @@ int posterior(Engine* e, const double* y, const uint8_t* mask, double* G_out, do
 // rand with supplied noise: x0_host the drawn initial state (d, host), eps_t (T x d), eps_e (T x p), y_out (T x p) device pointers
 int rand(Engine* e, const double* x0_host, const double* eps_t, const double* eps_e, int small_out, double* y_out, hipStream_t stream);
 int marginals(Engine* e, double* mean_out, double* var_out, double* result8, hipStream_t stream);
+// rand(replace_observation_noise_cov(posterior(model, y), Rnew)) without evaluating the posterior (tgp_dense_draw.hpp): Forward models with
+// 16 < d <= 64, p <= 16 on the persistent passes. y, mask, Rnew (sRn as in posterior_marginals), eps_t [T][d], eps_e [T][p], y_out [T][p] device
+// pointers; eps_0_host [d] host. small_out: sqrt(Rnew + 1e-9) (vector emissions, lgc.jl:84-87). TGP_EUNSUPPORTED: nothing written to y_out.
+int posterior_rand(Engine* e, const double* y, const uint8_t* mask, const double* Rnew, int64_t sRn, const double* eps_t, const double* eps_e,
+                   const double* eps_0_host, int small_out, double* y_out, double* result8, hipStream_t stream);
 
 }  // namespace tgp_dense

@@ -950,6 +950,67 @@ def _posterior_rand_one_launch(post, eps_t, eps_e, eps_0):
     return out
 
 
+def _posterior_rand_dense(post, eps_t, eps_e, eps_0):
+    """rand of a posterior that has not been evaluated, on the dense engine (tgp_posterior_rand_missing: 16 < d <= 64, p <= 16, diagonal noise -- missing
+    steps, per-step blocks and vector observations included; the persistent filter keeps its states and records, the draw pass walks back on them across
+    the chip).  A NaN of a host series is a missing entry (the mask, with a finite value in y); a device series gets its mask from
+    torch.isnan on the device.  None: not a model of that path, or one the library declines -- the caller evaluates the posterior."""
+    prior = post._prior
+    if (post._model is not None or isinstance(prior, PosteriorLGSSM) or prior.ordering is not Forward or not 16 < prior.dim <= 64 or prior.p > 16
+            or prior._whiten is not None or isinstance(post._y, tuple) or isinstance(prior.transitions, SDETransitions)):
+        return None
+    em = post._emissions()
+    if any(isinstance(e, SmallOutputLGC) and e.dense for e in (em, prior.emissions)):
+        return None
+    y, R_new = post._y, em.R
+    T, d, p = prior.T, prior.dim, prior.p
+    dev = _lib.is_device(eps_t)
+    if dev != _lib.is_device(y):
+        return None
+    if dev:
+        import torch
+        # every buffer the kernels read is float64, contiguous, of exactly the size they index, and on ONE device (as _posterior_rand_one_launch)
+        if not (_is_torch(eps_e) and _lib.is_device(eps_e)) or eps_t.numel() != T * d or y.numel() != T * p or eps_e.numel() != T * p:
+            return None
+        et = eps_t.to(torch.float64).reshape(T, d).contiguous()
+        ee = eps_e.to(torch.float64).reshape(T, p).contiguous()
+        yy = y.to(torch.float64).reshape(T, p)
+        mk = torch.isnan(yy)
+        yy = torch.where(mk, torch.zeros_like(yy), yy).contiguous()
+        mm = mk.to(torch.uint8).contiguous()
+        if _is_torch(R_new):
+            Rn = R_new.to(device=yy.device, dtype=torch.float64).reshape(-1, p).contiguous()
+        else:
+            Rn = torch.as_tensor(np.asarray(_to_numpy(R_new), dtype=np.float64).reshape(-1, p), device=yy.device)
+        if et.device != yy.device or ee.device != yy.device:
+            return None
+        _sync_torch(et)
+    else:
+        if np.size(_to_numpy(eps_t)) != T * d or np.size(_to_numpy(y)) != T * p or np.size(_to_numpy(eps_e)) != T * p:
+            return None
+        et = np.ascontiguousarray(_to_numpy(eps_t), dtype=np.float64).reshape(T, d)
+        ee = np.ascontiguousarray(_to_numpy(eps_e), dtype=np.float64).reshape(T, p)
+        yy = np.array(_to_numpy(y), dtype=np.float64).reshape(T, p)
+        mk = np.isnan(yy)
+        yy = np.ascontiguousarray(np.where(mk, 0.0, yy))
+        mm = np.ascontiguousarray(mk, dtype=np.uint8) if mk.any() else None
+        Rn = np.ascontiguousarray(np.asarray(_to_numpy(R_new), dtype=np.float64).reshape(-1, p))
+    if Rn.shape[0] not in (1, T):
+        return None
+    e0 = np.ascontiguousarray(_to_numpy(eps_0), dtype=np.float64).reshape(-1)
+    if e0.shape[0] != d:
+        return None
+    hd = prior.handle()
+    out = _out(prior, _osh(prior), dev)
+    flags = ((_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0) | (_lib.SHARED_R if Rn.shape[0] == 1 else 0)
+    try:
+        hd.check(hd.lib.tgp_posterior_rand_missing(hd.h, _lib.ptr(yy), _lib.ptr(mm), _lib.ptr(Rn), _lib.ptr(et), _lib.ptr(ee), _lib.ptr(e0), flags,
+                                                   _lib.ptr(out)))
+    except _lib.Unsupported:
+        return None
+    return out
+
+
 def rand(rng_or_eps, model):
     """lgssm.jl:65-69. `rng_or_eps` is a numpy Generator, or the explicit (eps_t (T,d), eps_e (T,), eps_0 (d,))."""
     if isinstance(model, PosteriorLGSSM) and model._model is None:
@@ -959,6 +1020,8 @@ def rand(rng_or_eps, model):
             et, ee = rng_or_eps.standard_normal((model.T, model.dim)), rng_or_eps.standard_normal((model.T,) if model.p == 1 else (model.T, model.p))
             eps = (et, ee, rng_or_eps.standard_normal(model.dim))
         y1 = _posterior_rand_one_launch(model, *eps)
+        if y1 is None:
+            y1 = _posterior_rand_dense(model, *eps)
         if y1 is not None:
             return y1
         rng_or_eps = eps
