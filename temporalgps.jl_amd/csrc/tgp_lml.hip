@@ -72,7 +72,8 @@ __device__ __forceinline__ int slot_of(int L, int j) {
     return L * PPL + (j ^ ((L / (16 / PPL)) & (PPL - 1)));
 }
 
-template <int D, int N, bool ALIGNED>
+// NT: the tiles' loads carry the non-temporal hint (kNonTemporal below, where it was measured)
+template <int D, int N, bool ALIGNED, bool NT>
 __global__ __launch_bounds__(kNW * 64, (N == 16 ? 4 : 2)) void k_lml_stream(const LArgs<D, N> by_value) {
     // (read where they lie, in the kernel-argument segment: tgp_modal.hip k_steady_one on why)
     (void)by_value;
@@ -166,14 +167,13 @@ __global__ __launch_bounds__(kNW * 64, (N == 16 ? 4 : 2)) void k_lml_stream(cons
             if (ALIGNED) {
                 const v2d* __restrict__ src = reinterpret_cast<const v2d*>(y + tile_t0);
 #pragma unroll
-                for (int k = 0; k < PPL; ++k) stage[k] = __builtin_nontemporal_load(src + k * 64 + lane);
+                for (int k = 0; k < PPL; ++k) stage[k] = NT ? __builtin_nontemporal_load(src + k * 64 + lane) : src[k * 64 + lane];
             } else {      // a pointer off the 16-byte boundary
 #pragma unroll
                 for (int k = 0; k < PPL; ++k) {
                     const double* __restrict__ src = y + tile_t0 + 2 * (k * 64 + lane);
                     v2d w;
-                    w.x = src[0];
-                    w.y = src[1];
+                    __builtin_memcpy(&w, src, 16);      // (ONE 16-byte copy from an 8-byte boundary; as two loads the d = 4 build kept a dead stack slot, below)
                     stage[k] = w;
                 }
             }
@@ -278,6 +278,10 @@ __global__ __launch_bounds__(kNW * 64, (N == 16 ? 4 : 2)) void k_lml_stream(cons
 #pragma unroll
                 for (int i = 0; i < D; ++i) z[i] += (lane == 0) ? add[i] : 0.0;
             }
+            // (d = 4, 5: the coefficients' live ranges end here.  Without it the allocator of ROCm 7.2 spills a 512-bit tuple of scalar loads, rematerialises
+            //  every use and leaves the tuple's stack slot behind: a private segment of 68 / 36 bytes that no instruction touches, and a launch with
+            //  scratch enabled -- tests/test_lml_tile_resources.py)
+            if (D == 4) asm volatile("" : "+s"(kap));
             // ---- inclusive scan over the lanes: four levels inside the rows of 16 (row_shr moves with M^(N 2^k)), then the rows' totals across
 #define TGP_LML_ROW_LEVEL(K)                                                                                         \
     do {                                                                                                             \
@@ -306,6 +310,7 @@ __global__ __launch_bounds__(kNW * 64, (N == 16 ? 4 : 2)) void k_lml_stream(cons
 #pragma unroll
                 for (int i = 0; i < D; ++i) z[i] = fma(mpr[i], g[i], fma(mpi[i], g[partner<D>(i)], z[i]));
             }
+            if (D == 5) asm volatile("" : "+s"(kap));      // (as in front of the scan, for d = 5)
             // the tile's true end state: the inclusive value of its last lane with a step in it
             const int le = full ? 63 : (int)((nv - 1) / N);
             double zend[D];
@@ -504,6 +509,14 @@ void fill(LArgs<D, N>& ka, const tgp_plan::Modal& md) {
     }
 }
 
+// LDS of a workgroup: the eight slices and the runs' (Q, active, V, E); a CU has 160 KB, and a request above half of that keeps the CU to one workgroup
+constexpr size_t kLdsCu = 160 * 1024, kLdsAlone = kLdsCu / 2 + 1024, kLdsMax = 136 * 1024;
+constexpr size_t lds_used(int d, int n) { return (size_t)kNW * 64 * (n / 2) * 16 + (size_t)kNW * (2 + 2 * d) * sizeof(double); }
+static_assert(lds_used(tgp_plan::kMaxD, 32) <= kLdsMax && kLdsAlone <= kLdsMax && 2 * lds_used(tgp_plan::kMaxD, 16) <= kLdsCu, "the CU's LDS");
+// Do the tiles' loads carry the non-temporal hint?  No: the posterior call reads the same series microseconds later, and behind plain loads it finds
+// it in the caches -- k_post_stream 49.5 -> 43.2 us at d = 3, T = 1e7, this kernel + 1 us (measured on the whole step)
+constexpr bool kNonTemporal = false;
+
 template <int D, int N>
 int launch(hipStream_t st, const tgp_plan::Modal& md, const Geometry& g, long long T, const double* y, const Buffers& b, long long seq, const double* Wt) {
     static_assert(sizeof(LArgs<D, N>) <= 8192, "the kernel-argument segment");
@@ -530,25 +543,22 @@ int launch(hipStream_t st, const tgp_plan::Modal& md, const Geometry& g, long lo
         }();
         a.dbg = dbg;
     }
-    static const size_t lds_pad = [] {      // TGP_LML_LDS_PAD=<bytes>: development (does a launch that asks for more LDS start later?)
-        const char* v = std::getenv("TGP_LML_LDS_PAD");
-        return v ? (size_t)std::atol(v) : (size_t)0;
-    }();
-    const size_t lds = (size_t)kNW * 64 * (N / 2) * 16 + (size_t)kNW * (2 + 2 * D) * sizeof(double) + lds_pad;
+    const size_t lds = g.lds;      // (the slices and the runs' hand-over, or more: what keeps a second workgroup off the CU -- choose_geometry)
+    if (lds < lds_used(D, N) || lds > kLdsMax) return (int)hipErrorInvalidValue;
     const bool aligned = (reinterpret_cast<uintptr_t>(y) & 15) == 0;
-    // (the limit on dynamic LDS is a per-device attribute of the function)
+    // (the limit on dynamic LDS is a per-device attribute of the function: set once, to the most a geometry of this kernel asks for)
     static bool attr_done_dev[64][2] = {{false, false}};
     int dev = 0;
     (void)hipGetDevice(&dev);
     bool& attr_done = attr_done_dev[dev & 63][aligned ? 1 : 0];
     if (!attr_done) {
-        const void* fn = aligned ? reinterpret_cast<const void*>(&k_lml_stream<D, N, true>) : reinterpret_cast<const void*>(&k_lml_stream<D, N, false>);
-        const hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const void* fn = aligned ? reinterpret_cast<const void*>(&k_lml_stream<D, N, true, kNonTemporal>) : reinterpret_cast<const void*>(&k_lml_stream<D, N, false, false>);
+        const hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
         if (rc != hipSuccess) return (int)rc;
         attr_done = true;
     }
-    if (aligned) hipLaunchKernelGGL((k_lml_stream<D, N, true>), dim3(g.nwg), dim3(kNW * 64), lds, st, a);
-    else hipLaunchKernelGGL((k_lml_stream<D, N, false>), dim3(g.nwg), dim3(kNW * 64), lds, st, a);
+    if (aligned) hipLaunchKernelGGL((k_lml_stream<D, N, true, kNonTemporal>), dim3(g.nwg), dim3(kNW * 64), lds, st, a);
+    else hipLaunchKernelGGL((k_lml_stream<D, N, false, false>), dim3(g.nwg), dim3(kNW * 64), lds, st, a);      // (the 8-byte loads of an odd pointer are plain ones)
     return (int)hipGetLastError();
 }
 
@@ -556,20 +566,36 @@ int launch(hipStream_t st, const tgp_plan::Modal& md, const Geometry& g, long lo
 
 Geometry choose_geometry(const tgp_plan::Modal& md, long long T) {
     Geometry g;
-    static const int forced = [] {
+    // TGP_LML_N = 16 | 32, TGP_LML_WAVES = 2 | 4: development (read once) -- the steps per lane and the waves per SIMD of every launch
+    static const int forced_n = [] {
         const char* v = std::getenv("TGP_LML_N");
         const int n = v ? std::atoi(v) : 0;
         return (n == 16 || n == 32) ? n : 0;
     }();
-    // sixteen steps per lane and four waves per SIMD where the registers allow it (d <= 2), thirty-two and two beyond
-    g.n = forced ? forced : (md.d <= 2 ? 16 : 32);      // (d = 3 at sixteen steps per lane: 28 registers spilled under the four-waves budget)
+    static const int forced_wps = [] {
+        const char* v = std::getenv("TGP_LML_WAVES");
+        const int w = v ? std::atoi(v) : 0;
+        return (w == 2 || w == 4) ? w : 0;
+    }();
+    // TWO decisions.  Steps per lane: the tile (64 n steps) is what a run exposes at its ends -- its first tile's load with nothing to compute, its
+    // last tile's arithmetic with nothing in flight -- against the per-tile work (scan, closure), paid once per tile.  Waves per SIMD: the wave slots
+    // of the chip (2048 or 4096), and with them the tiles per run.  By measurement at T = 1e7 (profiles/lml_tiles_time.txt): four waves
+    // per SIMD lose at every d (the first burst of 4096 waves lands at 8 us, that of 2048 at 3); d = 2 moved from (16, 4) to (32, 2) on the step's
+    // time; (16, 2) has the shortest kernel at d <= 3 but did not pass the step rule over (32, 2); d = 1 was traced only and stays.  At d >= 4 the
+    // sixteen-step builds spill under their 128-register bound
+    g.n = forced_n ? forced_n : (md.d <= 1 ? 16 : 32);
+    g.wps = forced_wps ? forced_wps : (md.d <= 1 ? 4 : 2);
     if (64 * g.n < md.halo) g.n = 32;      // (a tile must outlast the halo: 2048 >= kHaloMax)
+    if (g.n == 32) g.wps = 2;              // (the eight slices of 32-step lanes are 128 KB: one workgroup per CU whatever else)
+    // four waves per SIMD are two workgroups per CU, two are one: the launch must not put two workgroups on one CU and none on another (the
+    // per-SIMD dealing below counts on a workgroup's waves w and w + 4 being the SIMD's only ones), and what decides that is the LDS it asks for
+    g.lds = g.wps == 2 ? std::max(lds_used(md.d, g.n), kLdsAlone) : lds_used(md.d, g.n);
     const long long Tp = T - md.nhs, tile = 64LL * g.n;
     g.G = (Tp + tile - 1) / tile;          // tiles behind the head; the last one may be partial
     g.W = Tp / tile;                       // whole tiles: a run holds at least one (a partial last tile is its run's second or later)
-    // tiles per SIMD: the fewest (Chi + Clo) that the workgroups the chip holds at once cover -- four (n = 16) or two waves per SIMD: what LDS and registers
-    // hold -- and two at least (every wave of a workgroup a run: the head's hand-over rides on the last one) once there are tiles for that
-    const long long wgmax = g.n == 16 ? kMaxWG : kMaxWG / 2;
+    // tiles per SIMD: the fewest (Chi + Clo) that the workgroups the chip holds at once cover, and two at least (every wave of a workgroup a run: the
+    // head's hand-over rides on the last one) once there are tiles for that
+    const long long wgmax = g.wps == 4 ? kMaxWG : kMaxWG / 2;
     long long S = (g.W + 4 * wgmax - 1) / (4 * wgmax);
     if (S < 2) S = 2;
     g.Chi = (S + 1) / 2;

@@ -19,10 +19,12 @@
 namespace tgp_lml {
 
 constexpr int kNW = 8;            // waves per workgroup (one workgroup per CU: its LDS holds the eight tiles)
-constexpr int kMaxWG = 512;       // workgroups of a launch at most (n = 16: two per CU; n = 32: one per CU, 256)
+constexpr int kMaxWG = 512;       // workgroups of a launch at most (four waves per SIMD: two per CU; two: one per CU, 256)
 
 struct Geometry {
     int n = 32;                    // steps per lane (16 or 32)
+    int wps = 2;                   // waves per SIMD (2: one workgroup per CU; 4, n = 16 only: two)
+    size_t lds = 0;                // dynamic LDS of the launch in bytes: with wps = 2, more than half a CU's, so that a CU takes ONE workgroup
     long long G = 0, R = 0, C = 1; // tiles of 64 n steps behind the head (the last one may be partial), runs (one wave each) that hold a tile, C = Chi
     long long W = 0, Chi = 1, Clo = 1;      // whole tiles; tiles per run of a workgroup's waves 0-3 / 4-7 (waves w and w + 4 share a SIMD)
     int nwg = 0;
