@@ -146,10 +146,12 @@ typedef struct tgp_handle tgp_handle;
                            checkpoints.  Every hand-over is checked (the run from the handed-over state must reproduce the warm-up's end state
                            to 1e-12 of a state's size): a call whose warm-ups prove too short is repeated with longer ones, a model that mixes
                            too slowly goes to the general engine.  What the reference's predict path produces: posterior_lti_sde.jl:20-37,97-131,
-                           missings.jl:25-41, lti_sde.jl:135-146.  0: the general chunked-scan engine as before. */
+                           missings.jl:25-41, lti_sde.jl:135-146.  The same models (T >= 2048) have tgp_posterior_rand_missing served by the
+                           engine's draw kernel (k_sweep_draw).  0: the general chunked-scan engine as before, and
+                           tgp_posterior_rand_missing answers TGP_EUNSUPPORTED for these models. */
 #define TGP_OPT_SWEEP_CHUNK 15       /* tests: steps per chunk of the sweep engine (0 automatic) */
 #define TGP_OPT_SWEEP_WARMUP 16      /* tests: forward warm-up steps (0 automatic); a forced geometry is never repaired by longer warm-ups */
-#define TGP_OPT_SWEEP_WARMUP_BACK 17 /* tests: backward warm-up steps (0 automatic) */
+#define TGP_OPT_SWEEP_WARMUP_BACK 17 /* tests: backward warm-up steps (0 automatic); in tgp_posterior_rand_missing: the draw's warm-up */
 #define TGP_OPT_STREAM_MIN_T 18 /* series length from which the STREAMING kernels of the stationary-gain engine serve a call: persistent
                                    waves with ~7 us more fixed latency and 1.3 - 2.7 x the throughput of k_steady_one.  -1 (default): the measured
                                    crossovers (logpdf 5e6, posterior marginals 3e6 steps at d = 3); 0: always (the tests); a length: from there on */
@@ -198,10 +200,12 @@ int64_t tgp_graph_replays(const tgp_handle* h);
    the stationary-gain engines, their one-launch kernels and the wide-state engine: T - n0 (n0: the head of steps with gains of their own);
    the general engine: the steps the forward pass of the last posterior-path call ran in the mean-only form. */
 int tgp_steady_steps(tgp_handle* h, int64_t* mean_only, int64_t* total);
-/* Diagnostics of TGP_OPT_SWEEP for the last tgp_logpdf / tgp_[logpdf_and_]posterior_marginals call. info [8]: served by the sweep engine (0 / 1),
-   steps per chunk, forward warm-up, backward warm-up, waves, attempts (launches), status bits of the last attempt (1 forward / 2 backward warm-up
-   too short, 4 not positive definite, 8 non-finite), state for the bound model (0 untried, 1 serves, -1 declined).  dist [2]: the largest
-   relative distance between a warm-up's end state and the run that reproduces it, forwards / backwards (the checks' 1e-12). Either may be NULL. */
+/* Diagnostics of TGP_OPT_SWEEP for the last tgp_logpdf / tgp_[logpdf_and_]posterior_marginals / tgp_posterior_rand_missing call. info [8]: served by
+   the sweep engine (0 / 1), steps per chunk, forward warm-up, backward warm-up (tgp_posterior_rand_missing: the draw's), waves, attempts (launches),
+   status bits of the last attempt (1 forward / 2 backward or draw warm-up too short, 4 not positive definite, 8 non-finite), state for the bound
+   model (0 untried, 1 serves, -1 declined).  dist [2]: the largest relative distance between a warm-up's end state and the run that reproduces it,
+   forwards / backwards (the checks' 1e-12 / 1e-11; tgp_posterior_rand_missing: dist[1] compares the sample states of the draw's hand-over).
+   Either may be NULL. */
 int tgp_sweep_info(tgp_handle* h, int64_t* info, double* dist);
 /* Diagnostics of TGP_OPT_DENSE_CHUNKED for the last tgp_logpdf / tgp_filter / tgp_[logpdf_and_]posterior_marginals / tgp_posterior_rand_missing call on
    the dense engine. info [8]: served across the chip (0 / 1), steps per chunk, forward warm-up, backward warm-up (tgp_posterior_rand_missing: the draw
@@ -401,16 +405,23 @@ int tgp_posterior_rand(tgp_handle* h, const double* y, const double* Rnew, const
 
 /* ---- the same draw (posterior_lti_sde.jl:48-58 -> missings.jl:25-53, lgssm.jl:193-238, lgssm.jl:65-91, lgc.jl:84-87 / 241-243)
  *      for what merge_datasets makes of rand(rng, posterior(fx, y)(x_new)): an LGSSM with missing steps, per-step transitions,
- *      per-step noise, vector observations with diagonal noise -- Forward models of 16 < d <= 64, p <= 16 on the dense engine
- *      (DESIGN 4.6).  The persistent filter keeps the filtering states and its per-update records (T (d^2 + d + p (d + 2))
+ *      per-step noise, vector observations with diagonal noise.
+ *      Forward models with scalar observations, d <= 4 and T >= 2048 that TGP_OPT_SWEEP serves (shared A, a, Q, H or closed-form
+ *      SDE transitions; a mask, a noise variance and an emission offset per step in any combination): ONE kernel of the sweep
+ *      engine, k_sweep_draw -- the filter of a chunk per lane with checkpoints, then the walk back over the chunk from
+ *      the next chunk's sample state, both hand-overs checked (1e-12 / 1e-11), warm-ups that prove too short repaired by up to
+ *      three longer attempts (not under TGP_OPT_SWEEP_CHUNK / _WARMUP / _WARMUP_BACK, the last forcing the draw's warm-up);
+ *      tgp_sweep_info reports the call, the draw in the backward slots.  T doubles of device scratch beside the checkpoints.
+ *      Forward models of 16 < d <= 64, p <= 16 on the dense engine.  The persistent filter keeps the filtering states and its per-update records (T (d^2 + d + p (d + 2))
  *      doubles of device scratch, never the reverse-time model), the draw pass walks back on them in the deviation from the
  *      filtered mean, both across the chip behind checked warm-ups (tgp_dense_chunk_info reports the call: the draw pass in the
  *      backward slots), else one workgroup sequentially.  missing [T][p] as in tgp_posterior_marginals (may be NULL); eps_t [T][d],
  *      eps_e / y_out [T][p]; Rnew [p] with TGP_SHARED_R, else [T][p]; eps_0 [d] host; the others where TGP_IN_DEVICE /
  *      TGP_OUT_DEVICE say.  Draws are used as tgp_rand on the evaluated posterior uses them; emissions of p > 1 (or
  *      TGP_SMALL_OUTPUT) models add the reference's 1e-9 to Rnew.  TGP_EUNSUPPORTED (nothing written to y_out): another engine's
- *      handle, a Reverse model, TGP_OPT_DENSE_CHUNKED = 0 or TGP_OPT_DENSE_FUSED = 0, or stores that do not fit -- take
- *      tgp_posterior_rand (d <= 16) or tgp_posterior + tgp_rand. */
+ *      handle, a Reverse model, TGP_OPT_SWEEP = 0 (d <= 4), a sweep-engine draw whose Cholesky pivots are not positive, whose values
+ *      are not finite or whose forced warm-ups are too short, TGP_OPT_DENSE_CHUNKED = 0 or TGP_OPT_DENSE_FUSED = 0, or stores that do
+ *      not fit -- take tgp_posterior_rand (LTI, d <= 16) or tgp_posterior + tgp_rand. */
 int tgp_posterior_rand_missing(tgp_handle* h, const double* y, const uint8_t* missing, const double* Rnew, const double* eps_t,
                                const double* eps_e, const double* eps_0, uint32_t flags, double* y_out);
 

@@ -229,7 +229,7 @@ function AbstractGPs.rand(rng::AbstractRNG, p::DevicePosterior)
     end
     if p.model === nothing && _dense_draw(m)
         # what the one-launch path excludes -- missing entries, vector observations with diagonal noise -- on the dense engine's draw pass
-        # (tgp_posterior_rand_missing, DESIGN 4.6), draws in the reference's order; TGP_EUNSUPPORTED: the same draws through the evaluated model
+        # (tgp_posterior_rand_missing, DESIGN 4.6 / 4.7), draws in the reference's order; TGP_EUNSUPPORTED: the same draws through the evaluated model
         eps_t = randn(rng, m.d, m.T); eps_e = randn(rng, m.p, m.T); eps_0 = randn(rng, m.d)
         out = posterior_rand_missing(m, p.y, p.Σs_new === nothing ? _prior_noise(m) : p.Σs_new, eps_t, eps_e, eps_0)
         out === nothing || return _per_step(out, m)
@@ -343,7 +343,8 @@ function AbstractGPs.rand(rng::AbstractRNG, m::DeviceLGSSM)
 end
 
 """`rand` of `replace_observation_noise_cov(posterior(model, y), Σs_new)` on supplied draws without evaluating the posterior
-(tgp_posterior_rand_missing: 16 < d <= 64, p <= 16 on the dense engine). `nothing`: TGP_EUNSUPPORTED, take the evaluated route."""
+(tgp_posterior_rand_missing: scalar observations, d <= 4, T >= 2048 on the sweep engine's draw kernel; 16 < d <= 64, p <= 16 on the dense engine).
+`nothing`: TGP_EUNSUPPORTED, take the evaluated route."""
 function posterior_rand_missing(m::DeviceLGSSM{Forward}, y::AbstractVector, Σs_new::AbstractVector, eps_t, eps_e, eps_0)
     yv, mp, mask = _split_missing(y)
     (R, shared) = m.p == 1 ? _flat(Σs_new) : _flat_diag(Σs_new)

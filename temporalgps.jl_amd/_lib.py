@@ -223,7 +223,8 @@ class Handle:
         return dict(kernel_ms=k.value, h2d_ms=a.value, d2h_ms=b.value)
 
     def sweep_info(self):
-        """diagnostics of the sweep engine (TGP_OPT_SWEEP) for the last logpdf / posterior-marginals call"""
+        """diagnostics of the sweep engine (TGP_OPT_SWEEP) for the last logpdf / posterior-marginals / posterior-draw call (a draw: Wb and dist_b are
+        the draw warm-up's)"""
         import numpy as np
         info, dist = np.zeros(8, dtype=np.int64), np.zeros(2)
         self.check(self.lib.tgp_sweep_info(self.h, info.ctypes.data, dist.ctypes.data))

@@ -257,6 +257,120 @@ int sweep_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t 
     return TGP_OK;
 }
 
+// rand of the posterior on the engine (k_sweep_draw, DESIGN 4.7): sweep_call's staging and repair loop around the draw kernel.  The draw pass sits in
+// the backward slots of tgp_sweep_info (its warm-up Wd is remembered apart from Wb; TGP_OPT_SWEEP_WARMUP_BACK forces it here).  *served = false with
+// *why set: the engine declined, nothing was written to y_out.
+int sweep_draw_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, const double* eps_t, const double* eps_e,
+                    const double* eps_0, double* y_out, bool* served, std::string* why) {
+    *served = false;
+    if (!h->sweep) h->sweep = tgp_sweep::create();
+    static const bool dbg = getenv("TGP_STEADY_DEBUG") != nullptr;
+    const int d = h->d;
+    const size_t dd = (size_t)d * d;
+    const double* q = h->sweepm.data();
+    tgp_sweep::ModelHost mh;
+    mh.d = d;
+    mh.sde = h->sde;
+    mh.A = h->sde ? h->sde_A1Q1_host.data() : q;
+    mh.a = q + dd;
+    mh.Q = h->sde ? h->sde_A1Q1_host.data() + dd : q + dd + d;
+    mh.H = q + 2 * dd + d;
+    mh.hh = q[2 * dd + 2 * d];
+    mh.R = h->sweep_Rrep;
+    mh.x0m = h->x0m.data();
+    mh.x0P = h->x0P.data();
+    mh.coef = h->sde ? h->sde_coef_host.data() : nullptr;
+    mh.tau_typ = h->sweep_tau;
+    const bool idev = (flags & TGP_IN_DEVICE) != 0, odev = (flags & TGP_OUT_DEVICE) != 0;
+    const bool rshared = (flags & TGP_SHARED_R) != 0;
+    const size_t nT = (size_t)h->T * sizeof(double);
+    const bool forced = h->sweep_fW || h->sweep_fWb || h->sweep_fC;
+    int W = h->sweep_W, Wd = h->sweep_Wd;
+    for (int64_t& v : h->sweep_info) v = 0;
+    auto replan = [&]() {
+        std::string w;
+        tgp_sweep::force_geometry(h->sweep, h->sweep_fC, h->sweep_fW, 0, h->sweep_fWb);
+        if (tgp_sweep::plan(h->sweep, mh, h->T, W, h->sweep_Wb, h->num_cu, &w, Wd)) return true;
+        if (dbg) fprintf(stderr, "[tgp sweep] does not apply: %s\n", w.c_str());
+        h->sweep_state = -1;
+        *why = "the sweep engine's plan declines the model (" + w + ")";
+        return false;
+    };
+    if (!replan()) return TGP_OK;
+    // inputs and the output are staged ONCE, in front of the attempts.  The draw goes to the handle's own buffer and reaches y_out behind the checks:
+    // a declined call leaves a device y_out untouched as well.
+    CallTimer tm(h, /*clear=*/false);
+    const void *pR = nullptr, *pet = nullptr, *pee = nullptr;
+    TRY(stage_in(h, h->bRnew, Rnew, rshared ? sizeof(double) : nT, idev, &pR));
+    TRY(set_obs(h, y, missing, flags));
+    TRY(stage_in(h, h->beps_t, eps_t, (size_t)h->T * d * sizeof(double), idev, &pet));
+    TRY(stage_in(h, h->beps_e, eps_e, nT, idev, &pee));
+    tm.inputs_done();
+    HIPCHK(h->bo1.ensure(nT));
+    double* dy = h->bo1.d();
+    for (int attempt = 0; attempt < 4; ++attempt) {
+        if (attempt > 0 && !replan()) return TGP_OK;
+        tgp_sweep::Call c;
+        c.T = h->T;
+        c.y = h->mv.y;
+        c.mask = h->mv.missing;
+        c.R = h->mv.sR != 0 ? h->mv.R : nullptr;
+        c.hh = h->mv.sh != 0 ? h->mv.h : nullptr;
+        c.tau = h->sde ? h->btau.d() : nullptr;
+        c.Rnew = static_cast<const double*>(pR);
+        c.rnew_per_step = rshared ? 0 : 1;
+        c.eps_t = static_cast<const double*>(pet);
+        c.eps_e = static_cast<const double*>(pee);
+        for (int k = 0; k < d; ++k) c.eps_0[k] = eps_0[k];
+        c.y_out = dy;
+        {
+            std::string err;
+            const char* kname = tgp_sweep::kernel_name(d, h->sde, true, true);
+            LaunchScope ls(h, kname);
+            if (tgp_sweep::enqueue(h->sweep, h->stream, c, &kname, &err) != 0) return h->fail(TGP_EHIP, err);
+        }
+        tm.kernels_done();
+        if (h->timing) (void)hipEventRecord(h->ev[3], h->stream);
+        HIPCHK(hipStreamSynchronize(h->stream));
+        resolve_profile(h);
+        int status = 0, w = 0, wd = 0;
+        (void)tgp_sweep::finish(h->sweep, &status, &w, nullptr, &h->sweep_dist[0], &h->sweep_dist[1], &wd);
+        int C = 0;
+        int64_t nw = 0;
+        tgp_sweep::geometry(h->sweep, &C, nullptr, nullptr, &nw);
+        h->sweep_info[1] = C; h->sweep_info[2] = w; h->sweep_info[3] = wd; h->sweep_info[4] = nw; h->sweep_info[5] = attempt + 1; h->sweep_info[6] = status;
+        if (dbg) fprintf(stderr, "[tgp sweep draw] attempt %d: C %d W %d Wd %d waves %lld status %d dist %.3g / %.3g\n", attempt, C, w, wd, (long long)nw, status, h->sweep_dist[0], h->sweep_dist[1]);
+        if (status & 12) {      // not positive definite / non-finite values: the evaluated route reports it the way it always has
+            if (status & 4) h->sweep_state = -1;
+            *why = (status & 4) ? "a Cholesky pivot of the draw is not positive" : "non-finite values in the draw";
+            return TGP_OK;
+        }
+        if (status & 3) {       // a warm-up was too short: longer ones (a forced geometry is a test's: report, do not repair)
+            if (forced) {
+                *why = "a warm-up of the forced geometry is too short (tgp_sweep_info)";
+                return TGP_OK;
+            }
+            if (status & 1) W = 2 * w;
+            if (status & 2) Wd = 2 * wd;
+            continue;
+        }
+        if (odev) HIPCHK(hipMemcpyAsync(y_out, dy, nT, hipMemcpyDeviceToDevice, h->stream));
+        else HIPCHK(hipMemcpyAsync(y_out, dy, nT, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        read_timing(h);
+        note_served(h, Served::sweep, 0, 0.0, nullptr);
+        h->sweep_W = w;
+        h->sweep_Wd = wd;
+        h->sweep_state = 1;
+        h->sweep_info[0] = 1;
+        *served = true;
+        return TGP_OK;
+    }
+    h->sweep_state = -1;      // four attempts, warm-ups still too short: a model that mixes too slowly for this engine
+    *why = "the warm-ups stayed too short over four attempts";
+    return TGP_OK;
+}
+
 bool steady2_served(tgp_handle* h) {
     const bool ran = h->host_result[6] == tgp_steady::kStatusRan;
     h->steady2_state = ran ? 1 : -1;

@@ -436,16 +436,25 @@ int tgp_posterior_rand(tgp_handle* h, const double* y, const double* Rnew, const
 }
 
 // The same draw where the series has missing steps, the transitions or the noise are per step, or the observations are vectors with diagonal noise --
-// what merge_datasets makes of rand(rng, posterior(fx, y)(x_new)) -- on the dense engine's persistent passes (16 < d <= 64, p <= 16; DESIGN 4.6,
-// tgp_dense_draw.hpp). TGP_EUNSUPPORTED: the caller takes the evaluated route.
+// what merge_datasets makes of rand(rng, posterior(fx, y)(x_new)) -- on the sweep engine's draw kernel (what sweep_eligible accepts: scalar observations,
+// d <= 4, T >= 2048; DESIGN 4.7, k_sweep_draw) or on the dense engine's persistent passes (16 < d <= 64, p <= 16; DESIGN 4.6, tgp_dense_draw.hpp).
+// TGP_EUNSUPPORTED: nothing was written to y_out, the caller takes the evaluated route.
 int tgp_posterior_rand_missing(tgp_handle* h, const double* y, const uint8_t* missing, const double* Rnew, const double* eps_t, const double* eps_e,
                                const double* eps_0, uint32_t flags, double* y_out) {
     StreamGuard stream_guard_(h);
     TRY(check_ready(h, /*general=*/false));
     if (!y || !Rnew || !eps_t || !eps_e || !eps_0 || !y_out) return h->fail(TGP_EINVAL, "tgp_posterior_rand_missing: null argument");
+    if (sweep_eligible(h, flags)) {
+        bool served = false;
+        std::string why;
+        TRY(sweep_draw_call(h, y, missing, flags, Rnew, eps_t, eps_e, eps_0, y_out, &served, &why));
+        if (served) return TGP_OK;
+        return h->fail(TGP_EUNSUPPORTED, "tgp_posterior_rand_missing: the sweep engine declines the draw: " + why + " (take tgp_posterior + tgp_rand)");
+    }
     if (!h->is_dense || h->ordering != 0 || h->d > 64 || h->p > 16 || !h->dense_fused || !h->dense_chunked)
-        return h->fail(TGP_EUNSUPPORTED, "tgp_posterior_rand_missing: Forward models with 16 < d <= 64 and p <= 16 on the dense engine's passes across the chip "
-                                         "(take tgp_posterior_rand for d <= 16, else tgp_posterior + tgp_rand)");
+        return h->fail(TGP_EUNSUPPORTED, "tgp_posterior_rand_missing: Forward models with scalar observations, d <= 4 and T >= 2048 on the sweep engine, or with "
+                                         "16 < d <= 64 and p <= 16 on the dense engine's passes across the chip (else take tgp_posterior_rand, or "
+                                         "tgp_posterior + tgp_rand)");
     const bool idev = (flags & TGP_IN_DEVICE) != 0, odev = (flags & TGP_OUT_DEVICE) != 0, rshared = (flags & TGP_SHARED_R) != 0;
     const size_t nT = (size_t)h->T * h->p * sizeof(double);
     CallTimer tm(h);

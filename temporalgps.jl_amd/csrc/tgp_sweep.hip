@@ -135,6 +135,116 @@ __global__ __launch_bounds__(64, 1) void k_sweep(const KArgs<D> by_value) {
     }
 }
 
+// The posterior draw (tgp_sweep.hpp): k_sweep<POST>'s forward half -- warm-up, hand-over, checkpoints, dist_f -- with the walk over a
+// chunk's first Wd steps composed on the way (DrawAcc; ka.Wb holds Wd), then the walk over the chunk from the next lane's sample state of ITS
+// first step.  The check of the second hand-over compares sample states.
+template <int D> struct DArgs {
+    KArgs<D> ka;
+    DrawArgs da;
+};
+
+template <int D, bool SDE, int XS>
+__global__ __launch_bounds__(64, 1) void k_sweep_draw(const DArgs<D> by_value) {
+    (void)by_value;
+    const DArgs<D>& ar = *(const DArgs<D>*)__builtin_amdgcn_kernarg_segment_ptr();
+    const KArgs<D>& ka = ar.ka;
+    const DrawArgs& da = ar.da;
+    constexpr int B = Geo<D>::B, NS = SD<D>::NS, DS = SD<D>::DS;
+    __shared__ double sF[B * NS * 64];      // the block's filtering states; later in a block, its output tile (64 (B + 1) doubles)
+    const int lane = threadIdx.x;
+    const long long wave = blockIdx.x;
+    const long long T = ka.T;
+    const int C = ka.C;
+    const long long c = wave * kOwned + lane - 1;
+    const bool active = c >= 0 && c < ka.nchunks;
+    const long long t0 = active ? c * C : 0;
+    long long t1 = active ? t0 + C : 0;
+    t1 = t1 < T ? t1 : (active ? T : 0);
+    const long long t1r = (t1 + 7) & ~7ll;
+    const bool runs = active && lane >= 1;
+    const bool owned = runs && lane <= kOwned;
+    bool ok = true;
+
+    ModelR<D, SDE> mr;
+    mr.init(ka.mc);
+    State<D> gen, x0;
+    set_state<D>(gen, ka.mc.gm, ka.mc.gP);
+    set_state<D>(x0, ka.mc.x0m, ka.mc.x0P);
+    double* ck = ka.ckpt + (size_t)wave * (size_t)(C / B) * NS * 64;
+
+    State<D> x, e1;
+    LmlAcc acc;
+    const long long te = (t0 + ka.Wb < t1) ? t0 + ka.Wb : t1;
+    DrawAcc<D> dr;
+    dr.reset();
+    double b1[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) b1[k] = gen.m[k];
+    {
+        const long long tw = t1r - ka.W;
+        x = tw <= 0 ? x0 : gen;
+        // segment 0: the warm-up; 1: the chunk's first Wd steps, with the walk composed; 2: the rest of the chunk
+        const int nwin = ka.Wb / B;
+        for (int seg = 0; seg < 3; ++seg) {
+            if (seg == 1) {
+                forward_run_draw<D, SDE, XS, B>(ka, da, mr, t0, nwin, t0, runs ? t1r : t0, x, ck, lane, ok, dr, t0, te, b1);
+            } else {
+                const bool warm = seg == 0;
+                const long long ts = warm ? tw : t0 + (long long)nwin * B;
+                forward_run<D, SDE, XS, B>(ka, mr, ts, warm ? ka.W / B : C / B - nwin, warm ? (tw > 0 ? tw : 0) : t0, warm ? t1r : (runs ? t1r : t0), x, acc, false,
+                                           warm ? (double*)nullptr : ck + (size_t)nwin * NS * 64, lane, ok);
+                if (warm) {
+                    e1 = x;
+#pragma unroll
+                    for (int k = 0; k < D; ++k) x.m[k] = shfl_up1(e1.m[k]);
+#pragma unroll
+                    for (int k = 0; k < DS; ++k) x.P[k] = shfl_up1(e1.P[k]);
+                    if (t0 == 0) x = x0;
+                }
+            }
+        }
+    }
+    double dist_f = 0.0, dist_b = 0.0;
+    bool finite = true;
+    if (owned) {
+        dist_f = state_distance<D>(ka.mc, x, e1);
+        finite = state_finite<D>(x) && state_finite<D>(e1);
+    }
+
+    // ---- backwards: the chunk from the next lane's sample state of ITS first step; the emission of every step
+    double xw[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) xw[k] = shfl_dn1(b1[k]);
+    backward_run_draw<D, SDE, XS, B>(ka, da, mr, t0, C / B, owned ? t1 : t0, t1 == T, xw, ck, sF, lane, ok);
+    if (owned) {
+        dist_b = draw_distance<D>(ka.mc, xw, b1);
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < D; ++k) s += ::fabs(xw[k]) + ::fabs(b1[k]);
+        finite = finite && (s < 1e300);
+    }
+
+    unsigned bits = 0;
+    if (owned && !(dist_f <= ka.mc.tol)) bits |= 1u;
+    if (owned && !(dist_b <= ka.mc.tol_b)) bits |= 2u;
+    if (!ok) bits |= 4u;
+    if (!finite) bits |= 8u;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        bits |= (unsigned)__shfl_xor((int)bits, off, 64);
+        const double of = __shfl_xor(dist_f, off, 64), ob = __shfl_xor(dist_b, off, 64);
+        dist_f = (of > dist_f) ? of : dist_f;
+        dist_b = (ob > dist_b) ? ob : dist_b;
+    }
+    if (lane == 0) {
+        double* p = ka.part + (size_t)wave * 4;
+        p[0] = 0.0;
+        p[1] = (double)bits;
+        p[2] = dist_f;
+        p[3] = dist_b;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------------ host side
 struct Engine {
     Plan p;
@@ -152,25 +262,26 @@ void destroy(Engine* e) {
     if (e->ckpt) (void)tgp_alloc::dev_free(e->ckpt);
     delete e;
 }
-void force_geometry(Engine* e, int C, int W, int Wb) {
+void force_geometry(Engine* e, int C, int W, int Wb, int Wd) {
     e->forced.C = C;
     e->forced.W = W;
     e->forced.Wb = Wb;
+    e->forced.Wd = Wd;
 }
-void geometry(const Engine* e, int* C, int* W, int* Wb, int64_t* nwaves) {
+void geometry(const Engine* e, int* C, int* W, int* Wb, int64_t* nwaves, int* Wd) {
     if (C) *C = e->p.C;
     if (W) *W = e->p.W;
     if (Wb) *Wb = e->p.Wb;
     if (nwaves) *nwaves = e->p.nwaves;
+    if (Wd) *Wd = e->p.Wd;
 }
-bool plan(Engine* e, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, std::string* why) {
-    return make_plan(&e->p, e->forced, m, T, w_hint, wb_hint, num_cu, why);
+bool plan(Engine* e, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, std::string* why, int wd_hint) {
+    return make_plan(&e->p, e->forced, m, T, w_hint, wb_hint, num_cu, why, wd_hint);
 }
 
 namespace {
 
-template <int D, bool SDE, int XS, bool POST> void launch(Engine* e, hipStream_t stream, const Call& c) {
-    KArgs<D> ka;
+template <int D> void fill_args(const Engine* e, const Call& c, KArgs<D>& ka) {
     std::memcpy(&ka.mc, e->p.mc, sizeof ka.mc);
     ka.st.y = c.y;
     ka.st.mask = c.mask;
@@ -188,11 +299,26 @@ template <int D, bool SDE, int XS, bool POST> void launch(Engine* e, hipStream_t
     ka.var = c.var;
     ka.ckpt = static_cast<double*>(e->ckpt);
     ka.part = e->part;
+}
+template <int D, bool SDE, int XS, bool POST> void launch(Engine* e, hipStream_t stream, const Call& c) {
+    KArgs<D> ka;
+    fill_args<D>(e, c, ka);
     hipLaunchKernelGGL((k_sweep<D, SDE, XS, POST>), dim3((unsigned)e->p.nwaves), dim3(64), 0, stream, ka);
+}
+template <int D, bool SDE, int XS> void launch_draw(Engine* e, hipStream_t stream, const Call& c) {
+    DArgs<D> ar;
+    fill_args<D>(e, c, ar.ka);
+    ar.ka.Wb = e->p.Wd;      // (the kernel's second warm-up is the draw's)
+    ar.da.eps_t = c.eps_t;
+    ar.da.eps_e = c.eps_e;
+    for (int k = 0; k < 4; ++k) ar.da.eps_0[k] = c.eps_0[k];
+    ar.da.y_out = c.y_out;
+    hipLaunchKernelGGL((k_sweep_draw<D, SDE, XS>), dim3((unsigned)e->p.nwaves), dim3(64), 0, stream, ar);
 }
 
 template <int D, bool SDE, int XS> void launch_x(Engine* e, hipStream_t stream, const Call& c) {
-    if (c.mean != nullptr) launch<D, SDE, XS, true>(e, stream, c);
+    if (c.y_out != nullptr) launch_draw<D, SDE, XS>(e, stream, c);
+    else if (c.mean != nullptr) launch<D, SDE, XS, true>(e, stream, c);
     else launch<D, SDE, XS, false>(e, stream, c);
 }
 template <int D, bool SDE> void launch_s(Engine* e, hipStream_t stream, const Call& c) {
@@ -211,7 +337,8 @@ template <int D> void launch_d(Engine* e, hipStream_t stream, const Call& c) {
 
 }  // namespace
 
-const char* kernel_name(int, bool sde, bool post) {
+const char* kernel_name(int, bool sde, bool post, bool draw) {
+    if (draw) return sde ? "k_sweep_draw<sde>" : "k_sweep_draw<lti>";
     return sde ? (post ? "k_sweep<sde,posterior>" : "k_sweep<sde,logpdf>") : (post ? "k_sweep<lti,posterior>" : "k_sweep<lti,logpdf>");
 }
 
@@ -221,7 +348,8 @@ int enqueue(Engine* e, hipStream_t stream, const Call& c, const char** kname, st
         return 1;
     };
     const Plan& p = e->p;
-    const bool post = c.mean != nullptr;
+    const bool draw = c.y_out != nullptr;
+    const bool post = c.mean != nullptr || draw;      // (the draw keeps the posterior call's checkpoints)
     const size_t need_part = (size_t)p.nwaves * 4 * sizeof(double);
     if (need_part > e->part_cap) {
         if (e->part) (void)tgp_alloc::host_free(e->part);
@@ -244,7 +372,11 @@ int enqueue(Engine* e, hipStream_t stream, const Call& c, const char** kname, st
             e->ckpt_cap = need;
         }
     }
-    if (kname) *kname = kernel_name(p.d, p.sde, post);
+    if (draw && (c.eps_t == nullptr || c.eps_e == nullptr || c.Rnew == nullptr)) {
+        if (err) *err = "k_sweep_draw: a draw needs eps_t, eps_e and Rnew";
+        return 1;
+    }
+    if (kname) *kname = kernel_name(p.d, p.sde, post, draw);
     switch (p.d) {
         case 1: launch_d<1>(e, stream, c); break;
         case 2: launch_d<2>(e, stream, c); break;
@@ -256,7 +388,7 @@ int enqueue(Engine* e, hipStream_t stream, const Call& c, const char** kname, st
     return 0;
 }
 
-double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* dist_b) {
+double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* dist_b, int* wd) {
     double lml = 0.0, df = 0.0, db = 0.0;
     unsigned bits = 0;
     for (int64_t i = 0; i < e->p.nwaves; ++i) {      // fixed order: the same sum for the same geometry
@@ -269,6 +401,7 @@ double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* d
     if (status) *status = (int)bits;
     if (w) *w = e->p.W;
     if (wb) *wb = e->p.Wb;
+    if (wd) *wd = e->p.Wd;
     if (dist_f) *dist_f = df;
     if (dist_b) *dist_b = db;
     return lml;

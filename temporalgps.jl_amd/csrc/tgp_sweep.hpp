@@ -14,6 +14,10 @@
 // A wave = 64 consecutive chunks, 62 of them its own (lane 0 only warms up for lane 1, lane 63 only for lane 62); waves are independent.
 // Nothing is assumed about W: the run from the handed-over start must reproduce the warm-up's end state (and the same backwards) to
 // `tol`, else the call reports it and the host repeats it with longer warm-ups (or hands it to the general engine).
+//
+// A draw from the posterior (k_sweep_draw) is the same forward half and, backwards, the reverse-time model's sample path instead of its
+// marginals: a state of d doubles walks back over the chunk from the next lane's sample state of ITS first step, which that lane composed during its
+// forward run over its first Wd steps from zero deviation (the walk forgets as the smoother does); the hand-over is checked on the sample states.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -41,19 +45,25 @@ struct Call {
     int rnew_per_step = 0;
     double* mean = nullptr;               // device; null: logpdf only
     double* var = nullptr;
+    // a posterior draw instead (y_out set; mean / var null): k_sweep_draw
+    const double* eps_t = nullptr;        // device [T][d]: row t drives the reverse-time transition out of step t (row 0 unused)
+    const double* eps_e = nullptr;        // device [T]
+    double eps_0[4] = {0.0, 0.0, 0.0, 0.0};      // the start x_(T-1): travels in the kernel arguments
+    double* y_out = nullptr;              // device [T]
 };
 
 // Chooses the geometry (chunk length, warm-ups) for this model and series; false: the engine declines (`why` says so).
 // w_hint / wb_hint: warm-ups a previous call on the same bound model needed (0: estimate from the model).
-bool plan(Engine* e, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, std::string* why);
+// wd_hint: the draw's warm-up (0: the backward warm-up's value; a draw call that passes one may lengthen the chunk to hold it).
+bool plan(Engine* e, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, std::string* why, int wd_hint = 0);
 int enqueue(Engine* e, hipStream_t stream, const Call& c, const char** kernel_name, std::string* err);
-const char* kernel_name(int d, bool sde, bool post);
+const char* kernel_name(int d, bool sde, bool post, bool draw = false);
 // After the stream has been synchronised.  status bits: 1 forward warm-up too short, 2 backward warm-up too short, 4 not positive definite,
-// 8 non-finite values.  *w / *wb: the warm-ups the call ran with.
-double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* dist_b);
+// 8 non-finite values.  *w / *wb: the warm-ups the call ran with.  A draw: bit 2 and *dist_b are the draw warm-up's (*wd), the returned value is 0.
+double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* dist_b, int* wd = nullptr);
 // geometry of the last plan (diagnostics / tests)
-void geometry(const Engine* e, int* C, int* W, int* Wb, int64_t* nwaves);
+void geometry(const Engine* e, int* C, int* W, int* Wb, int64_t* nwaves, int* Wd = nullptr);
 // test hook: force the geometry of the next plan (0: automatic)
-void force_geometry(Engine* e, int C, int W, int Wb);
+void force_geometry(Engine* e, int C, int W, int Wb, int Wd = 0);
 
 }  // namespace tgp_sweep

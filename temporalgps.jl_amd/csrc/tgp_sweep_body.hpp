@@ -751,4 +751,325 @@ TGP_HD void backward_run(const KArgs<D>& ka, const ModelR<D, SDE>& mr, long long
     }
 }
 
+// ---- posterior draws (k_sweep_draw): rand of the reverse-time model (lgssm.jl:65-91 on :193-238) without writing it ----------------
+// Index roles as oracle/lgssm_ref.py posterior / rand: the reverse-time model's start is x_(T-1) ~ N(mf, Pf) of the last step (rand_x0: jitter
+// 1e-12); its transition of step t >= 1 takes x_t to x_(t-1) = G_t x_t + g_t + chol(L_t + 1e-9 I).U' eps_t[t] (lgc.jl:84-87), with
+// (G_t, g_t, L_t) = invert_dynamics of step t - 1's filtering state and step t's predicted one; step 0's transition is drawn and discarded.
+// The emission of step t is H x_t + h_t + sqrt(Rnew_t) eps_e[t] (scalar: lgc.jl:241-243, no jitter).
+constexpr double kJitterDraw = 1e-9, kJitterStart = 1e-12;
+
+// upper Cholesky factor of Symmetric(M) + jit I (M packed): U[k + j D], k <= j, and the reciprocal pivots
+template <int D> TGP_HD void chol_upper(const double* M, double jit, double* U, double* inv, bool& ok) {
+    TGP_UNROLL for (int j = 0; j < D; ++j) {
+        TGP_UNROLL for (int i = 0; i < j; ++i) {
+            double acc = M[pidx(i, j)];
+            TGP_UNROLL for (int k = 0; k < i; ++k) acc = ::fma(-U[k + i * D], U[k + j * D], acc);
+            U[i + j * D] = acc * inv[i];
+        }
+        double acc = M[pidx(j, j)] + jit;
+        TGP_UNROLL for (int k = 0; k < j; ++k) acc = ::fma(-U[k + j * D], U[k + j * D], acc);
+        ok = ok && (acc > 0.0);
+        double s, rs;
+        fast_sqrt_rsqrt(acc, s, rs);
+        U[j + j * D] = s;
+        inv[j] = rs;
+    }
+}
+// out = U' e
+template <int D> TGP_HD void mul_Ut(const double* U, const double* e, double* out) {
+    TGP_UNROLL for (int i = 0; i < D; ++i) {
+        double acc = 0.0;
+        TGP_UNROLL for (int k = 0; k <= i; ++k) acc = ::fma(U[k + i * D], e[k], acc);
+        out[i] = acc;
+    }
+}
+
+// x_(T-1) = mf + chol(Pf + 1e-12 I).U' eps_0
+template <int D> TGP_HD void draw_start(const State<D>& xf, const double* eps0, double* x, bool& ok) {
+    double U[D * D], inv[D], nz[D];
+    chol_upper<D>(xf.P, kJitterStart, U, inv, ok);
+    mul_Ut<D>(U, eps0, nz);
+    TGP_UNROLL for (int i = 0; i < D; ++i) x[i] = xf.m[i] + nz[i];
+}
+
+// The reverse-time element of step t - 1: xf its filtering state, (mp, Pp) step t's predicted state, AP = A Symmetric(xf.P), eps = eps_t[t].
+// Wt = G' (G[i][k] = Wt[k + i D]); nz = chol(L + 1e-9 I).U' eps, L = Pf - (U G')'(U G').
+template <int D> TGP_HD void draw_elem(const State<D>& xf, const double* Pp, const double* AP, const double* eps, double* Wt, double* nz, bool& ok) {
+    constexpr int DS = SD<D>::DS;
+    double U[D * D], inv[D];
+    chol_upper<D>(Pp, kJitter, U, inv, ok);
+    double Z[D * D];      // Z = U^-T (A Pf) = U G';  Wt = U^-1 Z
+    TGP_UNROLL for (int j = 0; j < D; ++j) {
+        TGP_UNROLL for (int i = 0; i < D; ++i) {
+            double acc = AP[i + j * D];
+            TGP_UNROLL for (int k = 0; k < i; ++k) acc = ::fma(-U[k + i * D], Z[k + j * D], acc);
+            Z[i + j * D] = acc * inv[i];
+        }
+        TGP_UNROLL for (int i = D - 1; i >= 0; --i) {
+            double acc = Z[i + j * D];
+            TGP_UNROLL for (int k = i + 1; k < D; ++k) acc = ::fma(-U[i + k * D], Wt[k + j * D], acc);
+            Wt[i + j * D] = acc * inv[i];
+        }
+    }
+    double Lt[DS];
+    TGP_UNROLL for (int j = 0; j < D; ++j)
+        TGP_UNROLL for (int i = 0; i <= j; ++i) {
+            double acc = xf.P[pidx(i, j)];
+            TGP_UNROLL for (int k = 0; k < D; ++k) acc = ::fma(-Z[k + i * D], Z[k + j * D], acc);
+            Lt[pidx(i, j)] = acc;
+        }
+    double UL[D * D], invL[D];
+    chol_upper<D>(Lt, kJitterDraw, UL, invL, ok);
+    mul_Ut<D>(UL, eps, nz);
+}
+
+// One step of the walk on the register-resident model: xf = filtering state of step t, A = transition of step t + 1, eps = eps_t[t + 1];
+// x = x_(t+1) on entry, x_t on return:  x_t = mf + G (x_(t+1) - mp) + chol(L + 1e-9 I).U' eps
+template <int D, bool SDE> TGP_HD void draw_step_r(const ModelR<D, SDE>& mr, const double* A, const State<D>& xf, double* x, const double* eps, bool& ok) {
+    constexpr int DS = SD<D>::DS;
+    double mp[D], Pp[DS], AP[D * D];
+    TGP_UNROLL for (int i = 0; i < D; ++i) mp[i] = xf.m[i];
+    TGP_UNROLL for (int i = 0; i < DS; ++i) Pp[i] = xf.P[i];
+    predict_r<D, SDE>(mr, A, mp, Pp);      // (the filter's own predict, to the bit: see forward_run_draw)
+    mul_A_sym<D>(A, xf.P, AP);
+    double Wt[D * D], nz[D], dm[D];
+    draw_elem<D>(xf, Pp, AP, eps, Wt, nz, ok);
+    TGP_UNROLL for (int i = 0; i < D; ++i) dm[i] = x[i] - mp[i];
+    TGP_UNROLL for (int i = 0; i < D; ++i) {
+        double acc = xf.m[i] + nz[i];
+        TGP_UNROLL for (int k = 0; k < D; ++k) acc = ::fma(Wt[k + i * D], dm[k], acc);
+        x[i] = acc;
+    }
+}
+
+// The walk over a window of steps [t0, te), composed FORWARDS as RevAcc composes the smoother's: x_(t0) = E x_(te-1) + g, with g carrying the
+// noise terms (no covariance: the walk is a sample path).
+template <int D> struct DrawAcc {
+    double E[D * D], g[D];
+    TGP_HD void reset() {
+        TGP_UNROLL for (int j = 0; j < D; ++j) TGP_UNROLL for (int i = 0; i < D; ++i) E[i + j * D] = i == j ? 1.0 : 0.0;
+        TGP_UNROLL for (int i = 0; i < D; ++i) g[i] = 0.0;
+    }
+    // appends step t - 1's element (arguments as draw_elem; mp: step t's predicted mean)
+    TGP_HD void append(const State<D>& xf, const double* mp, const double* Pp, const double* AP, const double* eps, bool& ok) {
+        double Wt[D * D], nz[D], gt[D], En[D * D];
+        draw_elem<D>(xf, Pp, AP, eps, Wt, nz, ok);
+        TGP_UNROLL for (int i = 0; i < D; ++i) {      // g_t = mf - G mp + noise
+            double acc = xf.m[i] + nz[i];
+            TGP_UNROLL for (int k = 0; k < D; ++k) acc = ::fma(-Wt[k + i * D], mp[k], acc);
+            gt[i] = acc;
+        }
+        TGP_UNROLL for (int i = 0; i < D; ++i) {      // g += E g_t;  E <- E G
+            double acc = g[i];
+            TGP_UNROLL for (int k = 0; k < D; ++k) acc = ::fma(E[i + k * D], gt[k], acc);
+            g[i] = acc;
+        }
+        TGP_UNROLL for (int j = 0; j < D; ++j)
+            TGP_UNROLL for (int i = 0; i < D; ++i) {
+                double acc = 0.0;
+                TGP_UNROLL for (int k = 0; k < D; ++k) acc = ::fma(E[i + k * D], Wt[j + k * D], acc);
+                En[i + j * D] = acc;
+            }
+        TGP_UNROLL for (int i = 0; i < D * D; ++i) E[i] = En[i];
+    }
+    // x_(t0) from the window's last step: its filtering mean (zero deviation), or the true x_(T-1) where the window reaches the series' end
+    TGP_HD void finish(const State<D>& xl, bool at_end, const double* eps0, double* out, bool& ok) const {
+        double xe[D], xd[D];
+        bool okd = true;
+        draw_start<D>(xl, eps0, xd, okd);
+        if (at_end) ok = ok && okd;
+        TGP_UNROLL for (int i = 0; i < D; ++i) xe[i] = at_end ? xd[i] : xl.m[i];
+        TGP_UNROLL for (int i = 0; i < D; ++i) {
+            double acc = g[i];
+            TGP_UNROLL for (int k = 0; k < D; ++k) acc = ::fma(E[i + k * D], xe[k], acc);
+            out[i] = acc;
+        }
+    }
+};
+
+// distance of two sample states, on the scale of state_distance's mean part
+template <int D> TGP_HD double draw_distance(const ModelC<D>& mc, const double* a, const double* b) {
+    double worst = 0.0;
+    TGP_UNROLL for (int i = 0; i < D; ++i) {
+        const double sc = ::sqrt(mc.gP[pidx(i, i)]) + ::fabs(a[i]) + ::fabs(b[i]);
+        const double r = ::fabs(a[i] - b[i]) / sc;
+        worst = r > worst ? r : worst;
+    }
+    return worst;
+}
+
+// The draw's streams (beside Streams): eps_t [T][D] (row t: the transition out of step t), eps_e [T], eps_0 (the start), the sample path's emissions.
+struct DrawArgs {
+    const double* eps_t = nullptr;
+    const double* eps_e = nullptr;
+    double eps_0[4] = {0.0, 0.0, 0.0, 0.0};
+    double* y_out = nullptr;
+};
+
+// The forward run over a chunk's first blocks with the walk over the steps (rev_t0, rev_te) composed on the way: forward_run<REV> with DrawAcc
+// in RevAcc's place.  The filter's steps are the plain ones (predict_r without its A P output, which takes another form for SDE models): the walk over
+// the chunk recomputes them from the checkpoints to the bit, so both sides of the draw's hand-over check see the same (G, L) -- L = Pf - (U G')'(U G')
+// is a difference of near-equal terms behind a tie (dt = 0), and its rounding under the 1e-9 jitter would otherwise sit in the check.
+// *out: x_(rev_t0) from the window's last step (DrawAcc::finish).
+template <int D, bool SDE, int XS, int B>
+TGP_HD void forward_run_draw(const KArgs<D>& ka, const DrawArgs& da, const ModelR<D, SDE>& mr, long long ts, int nblk, long long lo, long long hi, State<D>& x,
+                             double* ckpt, int lane, bool& ok, DrawAcc<D>& dr, long long rev_t0, long long rev_te, double* out) {
+    constexpr int NS = SD<D>::NS;
+    Inputs<D, SDE, XS, B> in, nx;
+    load_inputs<D, SDE, XS, B>(ka, ts, in);
+    for (int b = 0; b < nblk; ++b) {
+        const long long tb = ts + (long long)b * B;
+        load_inputs<D, SDE, XS, B>(ka, tb + B, nx);
+        double et[D], etn[D];      // the row of eps_t of the step in hand, and the next step's (asked for a step ahead: d doubles in flight, not B d)
+        TGP_UNROLL for (int k = 0; k < D; ++k) etn[k] = da.eps_t[(size_t)clamp_t(tb, ka.T) * D + k];
+        TGP_ISSUE_BARRIER();
+        if (ckpt != nullptr) {
+            double* q = ckpt + (size_t)b * NS * 64 + lane;
+            TGP_UNROLL for (int k = 0; k < D; ++k) q[(size_t)k * 64] = x.m[k];
+            TGP_UNROLL for (int k = 0; k < SD<D>::DS; ++k) q[(size_t)(D + k) * 64] = x.P[k];
+        }
+        if (tb >= lo && tb < hi) {
+            TGP_UNROLL for (int j = 0; j < B; ++j) {
+                TGP_UNROLL for (int k = 0; k < D; ++k) et[k] = etn[k];
+                if (j + 1 < B) { TGP_UNROLL for (int k = 0; k < D; ++k) etn[k] = da.eps_t[(size_t)clamp_t(tb + j + 1, ka.T) * D + k]; }
+                double A[D * D];
+                step_A<D, SDE>(ka.mc, mr, SDE ? in.tau[j] : 0.0, SDE && tb + j == 0, A);
+                const long long t = tb + j;
+                State<D> xf = x;
+                predict_r<D, SDE>(mr, A, x.m, x.P);
+                if (t > rev_t0 && t < rev_te) {
+                    double AP[D * D];
+                    mul_A_sym<D>(A, xf.P, AP);
+                    dr.append(xf, x.m, x.P, AP, et, ok);
+                }
+                update<D>(mr.H, (XS & 2) ? in.hh[j] : mr.hh, (XS & 1) ? in.R[j] : mr.R, in.y[j], in.obs(j, t, ka.T), x.m, x.P, (LmlAcc*)nullptr, ok);
+                if (t == rev_te - 1) dr.finish(x, rev_te == ka.T, da.eps_0, out, ok);
+            }
+        }
+        in = nx;
+    }
+}
+
+// The walk of a lane over the blocks nblk - 1 .. 0 of its chunk (backward_run with a sample state in the smoothing state's place): the steps
+// below hi are drawn.  fresh: the walk starts at step hi - 1 = T - 1 with draw_start; otherwise x holds x_(hi), the next lane's first step.  On
+// return x is x_(t0).
+template <int D, bool SDE, int XS, int B>
+TGP_HD void backward_run_draw(const KArgs<D>& ka, const DrawArgs& da, const ModelR<D, SDE>& mr, long long t0, int nblk, long long hi, bool fresh, double* x,
+                              const double* ckpt, double* sF, int lane, bool& ok) {
+    constexpr int NS = SD<D>::NS, DS = SD<D>::DS;
+    const long long T = ka.T;
+    Inputs<D, SDE, XS, B> in, nx;
+    double tau_next = 0.0;      // gap in front of the step behind the block in hand
+    const long long tlast = t0 + (long long)(nblk - 1) * B;
+    if (SDE) tau_next = ka.st.tau[clamp_t(tlast + B, T)];
+    load_inputs<D, SDE, XS, B>(ka, tlast, in);
+    State<D> ck, ckN;
+    {
+        const double* q = ckpt + (size_t)(nblk - 1) * NS * 64 + lane;
+        TGP_UNROLL for (int k = 0; k < D; ++k) ck.m[k] = q[(size_t)k * 64];
+        TGP_UNROLL for (int k = 0; k < DS; ++k) ck.P[k] = q[(size_t)(D + k) * 64];
+    }
+    for (int b = nblk - 1; b >= 0; --b) {
+        const long long tb = t0 + (long long)b * B;
+        load_inputs<D, SDE, XS, B>(ka, tb - B, nx);      // the next block (block b - 1): in flight through this one
+        {
+            const double* q = ckpt + (size_t)(b > 0 ? b - 1 : 0) * NS * 64 + lane;
+            TGP_UNROLL for (int k = 0; k < D; ++k) ckN.m[k] = q[(size_t)k * 64];
+            TGP_UNROLL for (int k = 0; k < DS; ++k) ckN.P[k] = q[(size_t)(D + k) * 64];
+        }
+        // the draws of a step are asked for a step ahead (the block's last step: here, in front of the recomputation): d + 2 doubles in flight
+        double et[D], etn[D], ee, een, rn, rnn;
+        TGP_UNROLL for (int k = 0; k < D; ++k) etn[k] = da.eps_t[(size_t)clamp_t(tb + B, T) * D + k];
+        een = da.eps_e[clamp_t(tb + B - 1, T)];
+        rnn = ka.st.Rnew[ka.st.rnew_per_step ? clamp_t(tb + B - 1, T) : 0];
+        TGP_ISSUE_BARRIER();
+        // ---- the block's filtering states, forwards from its checkpoint
+        State<D> xr = ck;
+        TGP_UNROLL for (int j = 0; j < B; ++j) {
+            double A[D * D];
+            step_A<D, SDE>(ka.mc, mr, SDE ? in.tau[j] : 0.0, SDE && tb + j == 0, A);
+            predict_r<D, SDE>(mr, A, xr.m, xr.P);
+            update<D>(mr.H, (XS & 2) ? in.hh[j] : mr.hh, (XS & 1) ? in.R[j] : mr.R, in.y[j], in.obs(j, tb + j, T), xr.m, xr.P, (LmlAcc*)nullptr, ok);
+            TGP_UNROLL for (int k = 0; k < D; ++k) sF[(j * NS + k) * 64 + lane] = xr.m[k];
+            TGP_UNROLL for (int k = 0; k < DS; ++k) sF[(j * NS + D + k) * 64 + lane] = xr.P[k];
+        }
+        TGP_ISSUE_BARRIER();      // (the states are to be read back from LDS: backward_run)
+        double oy[B];
+        TGP_UNROLL for (int j = B - 1; j >= 0; --j) {
+            const long long t = tb + j;
+            oy[j] = 0.0;
+            TGP_UNROLL for (int k = 0; k < D; ++k) et[k] = etn[k];
+            ee = een;
+            rn = rnn;
+            if (j > 0) {
+                TGP_UNROLL for (int k = 0; k < D; ++k) etn[k] = da.eps_t[(size_t)clamp_t(t, T) * D + k];
+                een = da.eps_e[clamp_t(t - 1, T)];
+                rnn = ka.st.Rnew[ka.st.rnew_per_step ? clamp_t(t - 1, T) : 0];
+            }
+            if (t < hi) {
+                State<D> xf;
+                TGP_UNROLL for (int k = 0; k < D; ++k) xf.m[k] = sF[(j * NS + k) * 64 + lane];
+                TGP_UNROLL for (int k = 0; k < DS; ++k) xf.P[k] = sF[(j * NS + D + k) * 64 + lane];
+                if (fresh && t == hi - 1) {
+                    draw_start<D>(xf, da.eps_0, x, ok);
+                } else {
+                    double A[D * D];
+                    step_A<D, SDE>(ka.mc, mr, SDE ? (j == B - 1 ? tau_next : in.tau[j + 1 < B ? j + 1 : j]) : 0.0, false, A);
+                    draw_step_r<D, SDE>(mr, A, xf, x, et, ok);
+                }
+                double mu = (XS & 2) ? in.hh[j] : mr.hh;
+                TGP_UNROLL for (int k = 0; k < D; ++k) mu = ::fma(mr.H[k], x[k], mu);
+                oy[j] = ::fma(::sqrt(rn), ee, mu);
+            }
+        }
+#if defined(__HIP_DEVICE_COMPILE__)
+        {
+            // the block's outputs leave through LDS rows of B values (backward_run's tile path, one array)
+            constexpr int LD = B + 1, RPI = 64 / B;
+            const unsigned long long emits = __builtin_amdgcn_ballot_w64(hi > t0);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            TGP_UNROLL for (int j = 0; j < B; ++j) sF[lane * LD + j] = oy[j];
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            // first step of lane 0's chunk, from lane 1's (always a chunk of the series; a lane without one has t0 = 0)
+            const long long tw0 = (((long long)__builtin_amdgcn_readlane((int)(t0 >> 32), 1) << 32) | (unsigned)__builtin_amdgcn_readlane((int)t0, 1)) - ka.C;
+            const bool wide = ((unsigned long long)da.y_out & 15ull) == 0ull;      // (wave-uniform)
+            if (wide) {      // 16-byte pieces: B / 2 lanes per row, 128 / B rows per instruction
+                constexpr int PPR = B / 2, RPW = 64 / PPR;
+                const int pc = lane % PPR, rw = lane / PPR;
+                TGP_UNROLL for (int k = 0; k < PPR; ++k) {
+                    const int r = rw + RPW * k;
+                    const long long t = tw0 + (long long)r * ka.C + (tb - t0) + 2 * pc;
+                    double2 vy;
+                    vy.x = sF[r * LD + 2 * pc];
+                    vy.y = sF[r * LD + 2 * pc + 1];
+                    if (((emits >> r) & 1ull) != 0ull) {
+                        if (t + 1 < T) *reinterpret_cast<double2*>(da.y_out + t) = vy;
+                        else if (t < T) da.y_out[t] = vy.x;
+                    }
+                }
+            } else {
+                const int e = lane % B, r0 = lane / B;
+                TGP_UNROLL for (int k = 0; k < B; ++k) {
+                    const int r = r0 + RPI * k;
+                    const long long t = tw0 + (long long)r * ka.C + (tb - t0) + e;
+                    const double vy = sF[r * LD + e];
+                    if (((emits >> r) & 1ull) != 0ull && t < T) da.y_out[t] = vy;
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+#else
+        TGP_UNROLL for (int j = 0; j < B; ++j) {
+            if (tb + j < hi) da.y_out[tb + j] = oy[j];
+        }
+#endif
+        if (SDE) tau_next = in.tau[0];
+        in = nx;
+        ck = ckN;
+    }
+}
+
 }  // namespace tgp_sweep

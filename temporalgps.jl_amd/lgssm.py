@@ -950,6 +950,65 @@ def _posterior_rand_one_launch(post, eps_t, eps_e, eps_0):
     return out
 
 
+def _posterior_rand_sweep(post, eps_t, eps_e, eps_0):
+    """rand of a posterior that has not been evaluated, on the sweep engine (tgp_posterior_rand_missing: Forward, scalar observations, d <= 4, T >= 2048;
+    shared blocks or closed-form SDE transitions, a mask / noise variance / emission offset per step -- one kernel, k_sweep_draw).  A NaN of a
+    host series is a missing step (the mask, with a finite value in y); a device series gets its mask from torch.isnan on the device.  None: not a
+    model of that path, or one the library declines -- the caller goes on to the evaluated route."""
+    prior = post._prior
+    if (post._model is not None or isinstance(prior, PosteriorLGSSM) or prior.ordering is not Forward or prior.p != 1 or prior.dim > 4
+            or prior._whiten is not None or isinstance(post._y, tuple)):
+        return None
+    y = post._y
+    R_new = post._R_new if post._R_new is not None else prior.emissions.R
+    T, d = prior.T, prior.dim
+    dev = _lib.is_device(eps_t)
+    if dev != _lib.is_device(y):
+        return None
+    if dev:
+        import torch
+        # every buffer the kernel reads is float64, contiguous, of exactly the size it indexes, and on ONE device (as _posterior_rand_one_launch)
+        if not (_is_torch(eps_e) and _lib.is_device(eps_e)) or eps_t.numel() != T * d or y.numel() != T or eps_e.numel() != T:
+            return None
+        et = eps_t.to(torch.float64).reshape(T, d).contiguous()
+        ee = eps_e.to(torch.float64).reshape(T).contiguous()
+        yy = y.to(torch.float64).reshape(T)
+        mk = torch.isnan(yy)
+        yy = torch.where(mk, torch.zeros_like(yy), yy).contiguous()
+        mm = mk.to(torch.uint8).contiguous()
+        if _is_torch(R_new):
+            Rn = R_new.to(device=yy.device, dtype=torch.float64).reshape(-1).contiguous()
+        else:
+            Rn = torch.as_tensor(np.atleast_1d(np.asarray(_to_numpy(R_new), dtype=np.float64)).reshape(-1), device=yy.device)
+        if et.device != yy.device or ee.device != yy.device:
+            return None
+        _sync_torch(et)
+    else:
+        if np.size(_to_numpy(eps_t)) != T * d or np.size(_to_numpy(y)) != T or np.size(_to_numpy(eps_e)) != T:
+            return None
+        et = np.ascontiguousarray(_to_numpy(eps_t), dtype=np.float64).reshape(T, d)
+        ee = np.ascontiguousarray(_to_numpy(eps_e), dtype=np.float64).reshape(T)
+        yy = np.array(_to_numpy(y), dtype=np.float64).reshape(T)
+        mk = np.isnan(yy)
+        yy = np.ascontiguousarray(np.where(mk, 0.0, yy))
+        mm = np.ascontiguousarray(mk, dtype=np.uint8) if mk.any() else None
+        Rn = np.ascontiguousarray(np.atleast_1d(_to_numpy(R_new)), dtype=np.float64).reshape(-1)
+    if Rn.shape[0] not in (1, T):
+        return None
+    e0 = np.ascontiguousarray(_to_numpy(eps_0), dtype=np.float64).reshape(-1)
+    if e0.shape[0] != d:
+        return None
+    hd = prior.handle()
+    out = _out(prior, _osh(prior), dev)
+    flags = ((_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0) | (_lib.SHARED_R if Rn.shape[0] == 1 else 0)
+    try:
+        hd.check(hd.lib.tgp_posterior_rand_missing(hd.h, _lib.ptr(yy), _lib.ptr(mm), _lib.ptr(Rn), _lib.ptr(et), _lib.ptr(ee), _lib.ptr(e0), flags,
+                                                   _lib.ptr(out)))
+    except _lib.Unsupported:
+        return None
+    return out
+
+
 def _posterior_rand_dense(post, eps_t, eps_e, eps_0):
     """rand of a posterior that has not been evaluated, on the dense engine (tgp_posterior_rand_missing: 16 < d <= 64, p <= 16, diagonal noise -- missing
     steps, per-step blocks and vector observations included; the persistent filter keeps its states and records, the draw pass walks back on them across
@@ -1020,6 +1079,8 @@ def rand(rng_or_eps, model):
             et, ee = rng_or_eps.standard_normal((model.T, model.dim)), rng_or_eps.standard_normal((model.T,) if model.p == 1 else (model.T, model.p))
             eps = (et, ee, rng_or_eps.standard_normal(model.dim))
         y1 = _posterior_rand_one_launch(model, *eps)
+        if y1 is None:
+            y1 = _posterior_rand_sweep(model, *eps)
         if y1 is None:
             y1 = _posterior_rand_dense(model, *eps)
         if y1 is not None:
