@@ -205,7 +205,8 @@ int tgp_steady_steps(tgp_handle* h, int64_t* mean_only, int64_t* total);
    status bits of the last attempt (1 forward / 2 backward or draw warm-up too short, 4 not positive definite, 8 non-finite), state for the bound
    model (0 untried, 1 serves, -1 declined).  dist [2]: the largest relative distance between a warm-up's end state and the run that reproduces it,
    forwards / backwards (the checks' 1e-12 / 1e-11; tgp_posterior_rand_missing: dist[1] compares the sample states of the draw's hand-over).
-   Either may be NULL. */
+   A call the sweep engine was not asked for reports zeros beside the state.  State -1 holds for the bound model, whatever the series of a later
+   call, until tgp_model_set or one of the options 14-17.  Either may be NULL. */
 int tgp_sweep_info(tgp_handle* h, int64_t* info, double* dist);
 /* Diagnostics of TGP_OPT_DENSE_CHUNKED for the last tgp_logpdf / tgp_filter / tgp_[logpdf_and_]posterior_marginals / tgp_posterior_rand_missing call on
    the dense engine. info [8]: served across the chip (0 / 1), steps per chunk, forward warm-up, backward warm-up (tgp_posterior_rand_missing: the draw

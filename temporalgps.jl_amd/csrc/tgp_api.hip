@@ -822,6 +822,8 @@ int check_ready(tgp_handle* h, bool general = true) {
     if (!h->have_model) return h->fail(TGP_EINVAL, "no model set (call tgp_model_set first)");
     ++h->call_seq;
     h->served = Served::general;
+    for (int64_t& v : h->sweep_info) v = 0;      // tgp_sweep_info is the record of THIS call: one the sweep engine is not asked for made no attempt
+    h->sweep_dist[0] = h->sweep_dist[1] = 0.0;
     TRY(bind_device(h));
     if (general) resolve_table(h);
     return TGP_OK;

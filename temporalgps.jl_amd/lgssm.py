@@ -282,6 +282,8 @@ def _handle_sde(self):
     R, sR = self._blocks(em.R, 1)
     flags = _lib.SHARED_a | (_lib.SHARED_H if sH else 0) | (_lib.SHARED_h if sh else 0) | (_lib.SHARED_R if sR else 0)
     hd = _lib.Handle(self.device)
+    for opt, value in self.handle_options.items():
+        hd.set_option(opt, value)
     F = np.ascontiguousarray(tr.F.T)                                  # column-major
     a = np.zeros(d)
     times = np.ascontiguousarray(tr.times)

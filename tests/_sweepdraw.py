@@ -34,13 +34,13 @@ def sweepdrawsim_run(model, y, eps, missing=None, Rnew=None, sde=None, C=0, W=0,
     h = np.atleast_1d(np.asarray(model["h"], dtype=np.float64))
     Rstep = np.ascontiguousarray(R) if R.shape[0] > 1 else None
     hstep = np.ascontiguousarray(h) if h.shape[0] > 1 else None
-    Rrep = float(np.median(R[R < 1e14])) if np.any(R < 1e14) else 1.0
+    Rrep = U.sweep_representative(R, noise=True)
     coef, tau, tau_typ = None, None, 0.0
     if sde is not None:
         F, times_ = sde
         coef = U.sde_coef(F)
         tau = np.concatenate([[-1.0], np.diff(np.asarray(times_, dtype=np.float64))])
-        tau_typ = float(np.median(tau[1:])) if T > 1 else 1.0
+        tau_typ = U.sweep_representative(tau[1:], noise=False)
     A, Q = cm(model["A"][0]), cm(model["Q"][0])
     a = np.ascontiguousarray(model["a"][0], dtype=np.float64)
     H = np.ascontiguousarray(model["H"][0], dtype=np.float64)
@@ -63,11 +63,14 @@ def sweepdrawsim_run(model, y, eps, missing=None, Rnew=None, sde=None, C=0, W=0,
 
 def sweepdrawsim_served(model, y, eps, **kw):
     """sweepdrawsim_run inside the repair loop of the C ABI's call (tgp_api_engines.inc sweep_draw_call): up to four attempts, a warm-up that a check found
-    short doubled for the next one.  Returns the last attempt's dict with `attempts` added."""
+    short doubled for the next one.  Returns the last attempt's dict with `attempts` and `tries` added."""
     w, wd = 0, 0
+    tries = []
     for attempt in range(4):
         r = sweepdrawsim_run(model, y, eps, w_hint=w, wd_hint=wd, **kw)
         r["attempts"] = attempt + 1
+        tries.append((r["C"], r["W"], r["Wd"], r["status"], float(r["dist_f"]), float(r["dist_d"])))
+        r["tries"] = tries      # one (C, W, Wd, status, dist_f, dist_d) per attempt
         if r["rc"] != 0 or r["status"] & 12 or not r["status"] & 3:
             return r
         if r["status"] & 1:

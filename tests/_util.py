@@ -371,6 +371,18 @@ def sde_coef(F):
     return np.concatenate([lam, N.T.reshape(-1), N2.T.reshape(-1)])     # column-major blocks
 
 
+def sweep_representative(v, noise):
+    """The value tgp_model_set hands the sweep engine's plan for its warm-up estimate (csrc/tgp_api.hip sweep_Rrep / sweep_tau): the upper median of the
+    first 4096 entries -- noise variances: of those in (0, 1e14), the shared value as it is; gaps: of all of them -- and 1 where there is none."""
+    v = np.atleast_1d(np.asarray(v, dtype=np.float64))
+    if noise and v.shape[0] == 1:
+        return float(v[0])
+    v = v[:4096]
+    if noise:
+        v = v[(v > 0.0) & (v < 1e14)]
+    return float(np.sort(v)[v.shape[0] // 2]) if v.shape[0] else 1.0
+
+
 def sweepsim_run(model, y, missing=None, Rnew=None, post=True, sde=None, C=0, W=0, Wb=0, num_cu=1, w_hint=0, wb_hint=0):
     """model: oracle dict with SHARED A, a, Q, H (or, with sde = (F, times): transitions by the closed form from the gaps); R / h may be
     per step.  Returns dict(rc, lml, status, dist_f, dist_b, C, W, Wb, nwaves, mean, var)."""
@@ -380,13 +392,13 @@ def sweepsim_run(model, y, missing=None, Rnew=None, post=True, sde=None, C=0, W=
     h = np.atleast_1d(np.asarray(model["h"], dtype=np.float64))
     Rstep = np.ascontiguousarray(R) if R.shape[0] > 1 else None
     hstep = np.ascontiguousarray(h) if h.shape[0] > 1 else None
-    Rrep = float(np.median(R[R < 1e14])) if np.any(R < 1e14) else 1.0
+    Rrep = sweep_representative(R, noise=True)
     coef, tau, tau_typ = None, None, 0.0
     if sde is not None:
         F, times_ = sde
         coef = sde_coef(F)
         tau = np.concatenate([[-1.0], np.diff(np.asarray(times_, dtype=np.float64))])
-        tau_typ = float(np.median(tau[1:])) if T > 1 else 1.0
+        tau_typ = sweep_representative(tau[1:], noise=False)
     A, Q = cm(model["A"][0]), cm(model["Q"][0])
     a = np.ascontiguousarray(model["a"][0], dtype=np.float64)
     H = np.ascontiguousarray(model["H"][0], dtype=np.float64)
@@ -403,6 +415,40 @@ def sweepsim_run(model, y, missing=None, Rnew=None, post=True, sde=None, C=0, W=
         int(rn.shape[0] > 1), int(post), C, W, Wb, w_hint, wb_hint, num_cu, _p(mean), _p(var), _p(out))
     return dict(rc=rc, lml=out[0], status=int(out[1]), dist_f=out[2], dist_b=out[3], C=int(out[4]), W=int(out[5]), Wb=int(out[6]),
                 nwaves=int(out[7]), mean=mean, var=var)
+
+
+def sweepsim_served(model, y, C=0, W=0, Wb=0, w0=0, wb0=0, **kw):
+    """sweepsim_run inside the repair loop of the C ABI's call (csrc/tgp_api_engines.inc sweep_call): up to four attempts, a warm-up that a check found
+    short doubled for the next one; a forced geometry is reported, not repaired; the plan may decline a doubled warm-up ("forward warm-up longer than four
+    chunks").  Returns what tgp_sweep_info shows behind the call -- served, C, W, Wb, waves, attempts (launches), status, state (1 served, -1 the engine is
+    off for the bound model, 0 untouched) -- with the last launch's lml / mean / var, `why` ("", "forced", "values", "plan", "attempts") and `tries`: one
+    (C, W, Wb, status, dist_f, dist_b) per launch.  w0 / wb0: the warm-ups the bound model remembers from an earlier served call (0: none)."""
+    forced = bool(C or W or Wb)
+    out = dict(served=0, C=0, W=0, Wb=0, waves=0, attempts=0, status=0, state=0, why="", tries=[], lml=None, mean=None, var=None)
+    w, wb = w0, wb0
+    for attempt in range(4):
+        r = sweepsim_run(model, y, C=C, W=W, Wb=Wb, w_hint=w, wb_hint=wb, **kw)
+        if r["rc"] != 0:
+            out.update(state=-1, why="plan")
+            return out
+        out.update(C=r["C"], W=r["W"], Wb=r["Wb"], waves=r["nwaves"], attempts=attempt + 1, status=r["status"], lml=r["lml"], mean=r["mean"], var=r["var"])
+        out["tries"].append((r["C"], r["W"], r["Wb"], r["status"], float(r["dist_f"]), float(r["dist_b"])))
+        if r["status"] & 12:
+            out.update(state=-1 if r["status"] & 4 else 0, why="values")
+            return out
+        if r["status"] & 3:
+            if forced:
+                out.update(why="forced")
+                return out
+            if r["status"] & 1:
+                w = 2 * r["W"]
+            if r["status"] & 2:
+                wb = 2 * r["Wb"]
+            continue
+        out.update(served=1, state=1)
+        return out
+    out.update(state=-1, why="attempts")
+    return out
 
 
 # --------------------------------------------------------------------------- the dense engine's passes across the chip (tests/test_gpu_dense_chunked*.py)
