@@ -301,6 +301,12 @@ int tgp_logpdf_adjoint(tgp_handle* h, const double* y, uint32_t flags, double* l
 int tgp_steady_plan(int d, const double* A, const double* a, const double* Q, const double* H, const double* hh, const double* R,
                     const double* x0m, const double* x0P, int64_t T, int32_t* info_i, double* info_d, double* modal_out,
                     double* tables_out);
+/* The FILTER plan of the same path, likewise a pure host function (d <= 8): what the one-launch adjoint pass (tgp_logpdf_adjoint, d <= 6), tgp_filter
+ * and the dense-powers smoother are laid out on.  info [4]: why (as above; 3 here: series shorter than head + 2), n0 (-1: not settled), head steps
+ * (16-step multiple behind n0; 0 when n0 is unknown), halo steps (16-step multiple after which the closed loop's powers are below 2^-60; 0 when the
+ * plan stopped before it).  The adjoint kernel's spans are 4096 steps, of which a workgroup owns 4096 - 2 halo. */
+int tgp_filter_plan(int d, const double* A, const double* a, const double* Q, const double* H, const double* hh, const double* R,
+                    const double* x0m, const double* x0P, int64_t T, int32_t* info);
 
 /* The host plan of the wide-state engine (8 < d <= 63: csrc/tgp_wide.hip) as a pure host function -- no handle, no GPU: the covariance half of
  * lgssm.jl:99-165 to its fixed point.  info [8]: why (0 = applies), n0 (head steps), halo, why_post (-1: not asked), n1 (steps at the series' end whose

@@ -117,6 +117,88 @@ def run(model, y, R_new=None, missing=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# 50-digit gradient of run()'s logpdf with respect to the SHARED blocks of a Forward scalar-output model: the loop of run() on blocks
+# that stay in 50 digits (run() itself rounds its inputs to fp64, which would swallow a 1e-20 step), central differences with step
+# 1e-20 along every elementary direction of every block (symmetric pairs for Q and x0P) -- the reference value the long-double
+# sequential adjoint (oracle/seq_adjoint.py) is held against (tests/test_oracle_adjoint.py). Test infrastructure.
+BLOCKS = ("A", "a", "Q", "H", "h", "R", "x0m", "x0P")
+
+
+def blocks_mp(model):
+    """the shared blocks of a model dict as mp matrices / numbers"""
+    for k in ("A", "a", "Q", "H"):
+        assert np.asarray(model[k]).shape[0] == 1, k
+    return dict(A=_M(model["A"][0]), a=_M(model["a"][0]), Q=_M(model["Q"][0]), H=_M(model["H"][0]),
+                h=mp.mpf(float(np.atleast_1d(model["h"])[0])), R=mp.mpf(float(np.atleast_1d(model["R"])[0])),
+                x0m=_M(model["x0m"]), x0P=_M(model["x0P"]))
+
+
+def logpdf_blocks_mp(b, y):
+    """run()'s forward loop (predict, update_scalar, the sum of the log terms) on 50-digit blocks; -> mp number"""
+    # (predict and update_scalar above, statement by statement, on lists of rows with mp.fdot for the inner products: several times
+    #  faster than mp.matrix arithmetic, which matters for the few hundred evaluations of a block gradient at d = 8)
+    d = b["A"].rows
+    rows = lambda X: [[X[i, j] for j in range(X.cols)] for i in range(X.rows)]
+    A, Q = rows(b["A"]), rows(b["Q"])
+    a, H, m = ([X[i] for i in range(d)] for X in (b["a"], b["H"], b["x0m"]))
+    P = rows(b["x0P"])
+    h, R = b["h"], b["R"]
+    rd = range(d)
+    lml = mp.mpf(0)
+    log2pi = mp.log(2 * mp.pi)
+    for yt in y:
+        S = [[P[min(i, j)][max(i, j)] for j in rd] for i in rd]                   # Symmetric(P)
+        mpred = [mp.fdot(A[i], m) + a[i] for i in rd]
+        AS = [[mp.fdot(A[i], S[j]) for j in rd] for i in rd]                       # (S symmetric: its column j is its row j)
+        Pp = [[mp.fdot(AS[i], A[j]) + Q[i][j] for j in rd] for i in rd]
+        V = [mp.fdot(H, [Pp[k][j] for k in rd]) for j in rd]                       # H' Pp
+        s2 = mp.fdot(V, H) + R
+        sq = mp.sqrt(s2)
+        B = [v / sq for v in V]
+        alpha = (yt - (mp.fdot(H, mpred) + h)) / sq
+        lml += -(log2pi + 2 * mp.log(sq) + alpha ** 2) / 2
+        m = [mpred[i] + B[i] * alpha for i in rd]
+        P = [[Pp[i][j] - B[i] * B[j] for j in rd] for i in rd]
+    return lml
+
+
+def block_gradient_mp(model, y, step=mp.mpf("1e-20")):
+    """-> (logpdf, dict of block gradients) as Python floats / arrays, in the convention of temporalgps_jl_amd.lgssm.logpdf_adjoint:
+    A, Q, x0P as [i][k]; the Q and x0P entries are HALF the derivative along E_ik + E_ki off the diagonal (the symmetrised gradient)."""
+    b0 = blocks_mp(model)
+    ym = [mp.mpf(float(v)) for v in y]
+    d = b0["A"].rows
+
+    def along(key, idx, sym):
+        vals = []
+        for sgn in (1, -1):
+            b = dict(b0)
+            if key in ("h", "R"):
+                b[key] = b0[key] + sgn * step
+            else:
+                X = b0[key].copy()
+                X[idx] += sgn * step
+                if sym and idx[0] != idx[1]:
+                    X[idx[1], idx[0]] += sgn * step
+                b[key] = X
+            vals.append(logpdf_blocks_mp(b, ym))
+        return (vals[0] - vals[1]) / (2 * step)
+
+    g = dict(A=np.zeros((d, d)), a=np.zeros(d), Q=np.zeros((d, d)), H=np.zeros(d), x0m=np.zeros(d), x0P=np.zeros((d, d)))
+    for i in range(d):
+        for key in ("a", "H", "x0m"):
+            g[key][i] = float(along(key, (i, 0), False))
+        for k in range(d):
+            g["A"][i, k] = float(along("A", (i, k), False))
+            if k >= i:
+                for key in ("Q", "x0P"):
+                    v = float(along(key, (i, k), True))
+                    g[key][i, k] = g[key][k, i] = v if i == k else 0.5 * v
+    g["h"], g["R"] = float(along("h", None, False)), float(along("R", None, False))
+    return float(logpdf_blocks_mp(b0, ym)), g
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # 50-digit logpdf of a sum of scaled, stretched Matern kernels on a regular grid, INCLUDING the map hyper-parameters -> blocks
 # (lti_sde.jl:148-160: A = exp(F s dt), Q = P - A P A'; :205-235 the Matern tables; :324-346 scaling; :350-373 stretching; :404-422 sums),
 # and its gradient by central differences in the same arithmetic (step 1e-20 relative: truncation ~1e-40, rounding ~1e-30) -- the

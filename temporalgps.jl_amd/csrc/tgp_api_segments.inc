@@ -155,6 +155,20 @@ int tgp_steady_plan(int d, const double* A, const double* a, const double* Q, co
     return TGP_OK;
 }
 
+// Host-only (no GPU needed): the FILTER plan (tgp_plan::FilterPlan through tgp_modal::plan_filter) that k_adjoint_one, k_filter_one and the dense-powers
+// smoother are laid out on -- head length and halo decide where their spans, tiles and workgroups begin and end (tests place their lengths by it).
+int tgp_filter_plan(int d, const double* A, const double* a, const double* Q, const double* H, const double* hh, const double* R, const double* x0m,
+                    const double* x0P, int64_t T, int32_t* info) {
+    if (d < 1 || d > tgp_plan::kRandMaxD || !A || !a || !Q || !H || !hh || !R || !x0m || !x0P || T <= 0 || !info) return TGP_EINVAL;
+    tgp_plan::ModelHost mh;
+    mh.d = d;
+    mh.A = A; mh.a = a; mh.Q = Q; mh.H = H; mh.hh = hh; mh.R = R; mh.x0m = x0m; mh.x0P = x0P;
+    tgp_plan::FilterPlan fp;
+    tgp_modal::plan_filter(mh, T, fp);
+    info[0] = fp.why; info[1] = fp.n0; info[2] = fp.nhs; info[3] = fp.halo;
+    return TGP_OK;
+}
+
 // The host plan of the wide-state engine (tgp_wide.hip) without a handle or a GPU (the CPU tier checks it against the discrete Riccati equation).
 int tgp_wide_plan(int d, const double* A, const double* a, const double* Q, const double* H, const double* hh, const double* R, const double* x0m, const double* x0P, int64_t T,
                   int want_posterior, int64_t* info, double* Kss, double* Sss, double* var_parts) {
