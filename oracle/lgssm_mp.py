@@ -162,6 +162,45 @@ def logpdf_blocks_mp(b, y):
     return lml
 
 
+def _along_mp(b0, ym, key, idx, sym, step):
+    """central difference of logpdf_blocks_mp along one elementary direction of block `key` (sym: along E_ik + E_ki)"""
+    vals = []
+    for sgn in (1, -1):
+        b = dict(b0)
+        if key in ("h", "R"):
+            b[key] = b0[key] + sgn * step
+        else:
+            X = b0[key].copy()
+            X[idx] += sgn * step
+            if sym and idx[0] != idx[1]:
+                X[idx[1], idx[0]] += sgn * step
+            b[key] = X
+        vals.append(logpdf_blocks_mp(b, ym))
+    return (vals[0] - vals[1]) / (2 * step)
+
+
+def block_gradient_entries_mp(model, y, picks, step=mp.mpf("1e-20")):
+    """the entries `picks` = {block: [index tuples; () for h and R]} of block_gradient_mp's gradient alone (a wide model has too many entries for
+    all of them): -> {block: [floats, in the order of picks[block]]}; Q and x0P entries (i, k) in the symmetrised convention"""
+    b0 = blocks_mp(model)
+    ym = [mp.mpf(float(v)) for v in y]
+    out = {}
+    for key, idxs in picks.items():
+        vals = []
+        for idx in idxs:
+            if key in ("h", "R"):
+                vals.append(float(_along_mp(b0, ym, key, None, False, step)))
+            elif key in ("a", "H", "x0m"):
+                vals.append(float(_along_mp(b0, ym, key, (idx[0], 0), False, step)))
+            elif key == "A":
+                vals.append(float(_along_mp(b0, ym, key, idx, False, step)))
+            else:
+                v = float(_along_mp(b0, ym, key, idx, True, step))
+                vals.append(v if idx[0] == idx[1] else 0.5 * v)
+        out[key] = vals
+    return out
+
+
 def block_gradient_mp(model, y, step=mp.mpf("1e-20")):
     """-> (logpdf, dict of block gradients) as Python floats / arrays, in the convention of temporalgps_jl_amd.lgssm.logpdf_adjoint:
     A, Q, x0P as [i][k]; the Q and x0P entries are HALF the derivative along E_ik + E_ki off the diagonal (the symmetrised gradient)."""
@@ -170,19 +209,7 @@ def block_gradient_mp(model, y, step=mp.mpf("1e-20")):
     d = b0["A"].rows
 
     def along(key, idx, sym):
-        vals = []
-        for sgn in (1, -1):
-            b = dict(b0)
-            if key in ("h", "R"):
-                b[key] = b0[key] + sgn * step
-            else:
-                X = b0[key].copy()
-                X[idx] += sgn * step
-                if sym and idx[0] != idx[1]:
-                    X[idx[1], idx[0]] += sgn * step
-                b[key] = X
-            vals.append(logpdf_blocks_mp(b, ym))
-        return (vals[0] - vals[1]) / (2 * step)
+        return _along_mp(b0, ym, key, idx, sym, step)
 
     g = dict(A=np.zeros((d, d)), a=np.zeros(d), Q=np.zeros((d, d)), H=np.zeros(d), x0m=np.zeros(d), x0P=np.zeros((d, d)))
     for i in range(d):

@@ -10,7 +10,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#define ADJ_MAXD 8
+#define ADJ_MAXD 64      /* d <= 8: the modal engines' models; 8 < d <= 63: the wide-state engine's */
 #define LOG2PI_L 1.8378770664093454835606594728112353L
 #define RCAT_(a, b) a##_##b
 #define RCAT(a, b) RCAT_(a, b)

@@ -1,7 +1,8 @@
 """ORACLE (test infrastructure only; never on the product path). ctypes wrapper around the exact sequential adjoint of
 oracle/liboracle_seq.so (seq_adjoint.c): logpdf and its gradient with respect to the SHARED blocks of a Forward scalar-output
 model, by reverse mode through the full recursion of seq_kalman.filter_ (time-varying covariance, no stationarity assumption).
-Models use the dict convention of oracle/lgssm_ref.py (kind == 'scalar', ordering == 'F', every block shared: leading axis 1), d <= 8.
+Models use the dict convention of oracle/lgssm_ref.py (kind == 'scalar', ordering == 'F', every block shared: leading axis 1), d <= 64
+(the kept steps take T (d^2 + d) long doubles: 0.8 GB at d = 9, T = 530 000; 0.1 GB at d = 63, T = 1500).
 Returns the convention of temporalgps_jl_amd.lgssm.logpdf_adjoint: (lml, dict A (d,d), a (d,), Q (d,d), H (d,), h, R, x0m (d,),
 x0P (d,d)); A, Q, x0P as [i][k]; the Q and x0P gradients symmetrised (pair them with symmetric tangents)."""
 import ctypes

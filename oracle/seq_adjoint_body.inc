@@ -3,7 +3,9 @@
  *
  * The reverse-mode derivative of the FULL sequential recursion of seq_kalman_body.inc (seq_filter: predict, scalar update,
  * the per-step log term; time-varying covariance, no stationarity assumption) with respect to the shared blocks A, a, Q, H, h, R
- * and x0m, x0P. Run-time state dimension d <= 8; column-major d x d blocks as in seq_kalman_body.inc.
+ * and x0m, x0P. Run-time state dimension d <= ADJ_MAXD (64: the wide-state engine's models too); column-major d x d blocks as in
+ * seq_kalman_body.inc. The d x d work arrays live on the heap beside the kept steps (eleven of them: 0.7 MB in long double at d = 64, and the
+ * oracle may be called off the main thread); only d-vectors are on the stack.
  *
  * Forward, step t (m, P: the filtered state of step t - 1; x0m, x0P before the first), as seq_kalman_body.inc / lgssm_ref.py:
  *     S  = Symmetric(P)  (upper triangle mirrored)      mp = A m + a         Pp = A S A' + Q
@@ -29,14 +31,16 @@ static int RNAME(seq_adjoint)(int d, int64_t T, const double *A_, const double *
                               double *gH, double *gh, double *gR, double *gx0m, double *gx0P) {
     if (d < 1 || d > ADJ_MAXD || T < 1) return 1;
     const int dd = d * d;
-    REAL A[ADJ_MAXD * ADJ_MAXD], a[ADJ_MAXD], Q[ADJ_MAXD * ADJ_MAXD], H[ADJ_MAXD], m[ADJ_MAXD], P[ADJ_MAXD * ADJ_MAXD];
+    REAL a[ADJ_MAXD], H[ADJ_MAXD], m[ADJ_MAXD], V[ADJ_MAXD];
     const REAL h = (REAL)h_, R = (REAL)R_;
-    for (int i = 0; i < dd; ++i) { A[i] = (REAL)A_[i]; Q[i] = (REAL)Q_[i]; P[i] = (REAL)x0P_[i]; }
-    for (int i = 0; i < d; ++i) { a[i] = (REAL)a_[i]; H[i] = (REAL)H_[i]; m[i] = (REAL)x0m_[i]; }
-    REAL *mps = (REAL *)malloc((size_t)T * (size_t)(dd + d) * sizeof(REAL));
+    /* one block: mp and Pp of every step, then the eleven d x d work arrays */
+    REAL *mps = (REAL *)malloc(((size_t)T * (size_t)(dd + d) + (size_t)11 * dd) * sizeof(REAL));
     if (!mps) return 3;
     REAL *Pps = mps + (size_t)T * d;
-    REAL S[ADJ_MAXD * ADJ_MAXD], AS[ADJ_MAXD * ADJ_MAXD], V[ADJ_MAXD];
+    REAL *A = Pps + (size_t)T * dd, *Q = A + dd, *P = Q + dd, *S = P + dd, *AS = S + dd;
+    REAL *Ab = AS + dd, *Qb = Ab + dd, *Pb = Qb + dd, *Ppb = Pb + dd, *X = Ppb + dd, *Sb = X + dd;
+    for (int i = 0; i < dd; ++i) { A[i] = (REAL)A_[i]; Q[i] = (REAL)Q_[i]; P[i] = (REAL)x0P_[i]; }
+    for (int i = 0; i < d; ++i) { a[i] = (REAL)a_[i]; H[i] = (REAL)H_[i]; m[i] = (REAL)x0m_[i]; }
     REAL acc = 0;
     /* ---- forward */
     for (int64_t t = 0; t < T; ++t) {
@@ -75,7 +79,7 @@ static int RNAME(seq_adjoint)(int d, int64_t T, const double *A_, const double *
         acc += -((REAL)LOG2PI_L + RLOG(s) + e * e / s) / 2;
     }
     /* ---- backward */
-    REAL Ab[ADJ_MAXD * ADJ_MAXD], ab[ADJ_MAXD], Qb[ADJ_MAXD * ADJ_MAXD], Hb[ADJ_MAXD], hb = 0, Rb = 0, mb[ADJ_MAXD], Pb[ADJ_MAXD * ADJ_MAXD];
+    REAL ab[ADJ_MAXD], Hb[ADJ_MAXD], hb = 0, Rb = 0, mb[ADJ_MAXD];
     for (int i = 0; i < dd; ++i) { Ab[i] = 0; Qb[i] = 0; Pb[i] = 0; }
     for (int i = 0; i < d; ++i) { ab[i] = 0; Hb[i] = 0; mb[i] = 0; }
     for (int64_t t = T - 1; t >= 0; --t) {
@@ -108,7 +112,7 @@ static int RNAME(seq_adjoint)(int d, int64_t T, const double *A_, const double *
         }
         for (int j = 0; j < d; ++j)
             for (int i = 0; i < d; ++i) S[i + j * d] = (i <= j) ? P[i + j * d] : P[j + i * d];
-        REAL mbV = 0, VPV = 0, Vb[ADJ_MAXD], mpb[ADJ_MAXD], Ppb[ADJ_MAXD * ADJ_MAXD];
+        REAL mbV = 0, VPV = 0, Vb[ADJ_MAXD], mpb[ADJ_MAXD];
         for (int i = 0; i < d; ++i) mbV += mb[i] * V[i];
         for (int j = 0; j < d; ++j)
             for (int i = 0; i < d; ++i) VPV += V[i] * Pb[i + j * d] * V[j];
@@ -130,7 +134,6 @@ static int RNAME(seq_adjoint)(int d, int64_t T, const double *A_, const double *
             for (int j = 0; j < d; ++j) Ppb[k + j * d] += H[k] * Vb[j];
         }
         /* Pp = A S A' + Q */
-        REAL X[ADJ_MAXD * ADJ_MAXD], Sb[ADJ_MAXD * ADJ_MAXD];
         for (int i = 0; i < dd; ++i) Qb[i] += Ppb[i];
         for (int j = 0; j < d; ++j)              /* AS = A S (S symmetric) */
             for (int i = 0; i < d; ++i) {
@@ -165,7 +168,6 @@ static int RNAME(seq_adjoint)(int d, int64_t T, const double *A_, const double *
         for (int j = 0; j < d; ++j)
             for (int i = 0; i < d; ++i) Pb[i + j * d] = (i < j) ? Sb[i + j * d] + Sb[j + i * d] : (i == j ? Sb[i + j * d] : 0);
     }
-    free(mps);
     *lml_out = (double)acc;
     for (int j = 0; j < d; ++j)
         for (int i = 0; i < d; ++i) {
@@ -176,5 +178,6 @@ static int RNAME(seq_adjoint)(int d, int64_t T, const double *A_, const double *
     for (int i = 0; i < d; ++i) { ga[i] = (double)ab[i]; gH[i] = (double)Hb[i]; gx0m[i] = (double)mb[i]; }
     *gh = (double)hb;
     *gR = (double)Rb;
+    free(mps);      /* (behind the copies: Ab, Qb and Pb live in it) */
     return 0;
 }

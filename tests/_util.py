@@ -61,6 +61,94 @@ BOUNDARY_KERNELS = {
 }
 
 
+# Models of the wide-state adjoint's parity tiers (tests/test_wide_adjoint_host.py, tests/test_gpu_wide_adjoint_edges.py): the state dimensions at which the
+# Gram kernel's two extra columns (r_t at d, the constant at d + 1; csrc/tgp_wide.hip k_wide_gram<NT>, NT = ceil((d + 2) / 16)) are the last two of the last tile
+# (d = 14, 30, 46, 62) or split over two tiles (15, 31, 47, 63: the first d of NT = 2 ... 5 too), the d around each change of form (15/16/17, 31/32/33, 47/48/49),
+# the smallest d (9), and the d of the chunk-geometry cases (12, 28, 42, 54).
+WIDE_ADJOINT_KERNELS = {
+    9: ("product", _m52, ("stretched", 0.7, _m52)),
+    12: ("product", _m32, _ap(3)),
+    14: ("product", _ap(7), _m12),
+    15: ("sum", ("product", _ap(3), _m32), ("stretched", 0.6, _m52)),
+    16: ("sum", ("product", _ap(3), _m32), _m52, _m12),
+    28: ("product", ("approx_periodic", 7, 1.3), _m32),
+    30: ("product", _ap(5), _m52),
+    42: ("product", ("approx_periodic", 7, 1.3), _m52),
+    46: ("sum", ("product", _ap(7), _m52), ("product", _ap(2), _m12)),
+    62: ("sum", ("product", _ap(10), _m52), ("stretched", 0.6, _m32)),
+    **{d: BOUNDARY_KERNELS[d] for d in (17, 31, 32, 33, 47, 48, 49, 54, 63)},
+}
+
+
+def wide_adjoint_model(d, dt, T):
+    """the class (d, dt) of the wide-state adjoint's parity tiers: noise 0.1, non-zero a and h (the kernels' a and hh terms are otherwise multiplied by zero)"""
+    model = oc.build_lgssm(WIDE_ADJOINT_KERNELS[d], ("regular", 0.0, dt, int(T)), 0.1)
+    assert len(model["x0m"]) == d
+    model["a"] = 0.01 * np.linspace(-1.0, 1.0, d)[None]
+    model["h"] = np.array([0.4])
+    return model
+
+
+def wide_adjoint_length(d):
+    """the length of a class's default case (the long-double oracle takes up to 6 s per case at d = 63, T = 2500)"""
+    return 1500 if d >= 46 else 2500
+
+
+def wide_adjoint_draw(model, seed):
+    from oracle import seq_kalman as sk
+    T, d = model["T"], len(model["x0m"])
+    rng = np.random.default_rng(seed)
+    return sk.rand(model, rng.standard_normal((T, d)), rng.standard_normal(T), rng.standard_normal(d))
+
+
+# every class at spacing 0.2; d = 9 at 0.1 too (the class of the second Gram regime: halo 152, chunks of 129 steps are shorter than their warm-up)
+WIDE_ADJOINT_CLASSES = [(d, 0.2) for d in sorted(WIDE_ADJOINT_KERNELS)] + [(9, 0.1)]
+# the lengths of the host tier beyond wide_adjoint_length(d): those of the GPU tier's cases at which a class's restatement stands farthest from the exact gradient
+# (the two long series of d = 9, a short series at d = 12 and 63, T = 3000 at d = 42 and 54)
+WIDE_ADJOINT_HOST_EXTRA = [(9, 0.1, 46 + 2048 * 256 + 1), (9, 0.2, 27 + 4096 * 70 - 5), (12, 0.2, 44 + 80), (63, 0.2, 48 + 64), (42, 0.2, 3000), (54, 0.2, 3000)]
+GRADIENT_BLOCKS = ("A", "a", "Q", "H", "h", "R", "x0m", "x0P")
+# Measured on the CPU (x86-64): the NumPy restatement of the wide-state engine's algorithm + tgp_adjoint_finish_wide
+# (tests/test_wide_adjoint_host.py::test_the_algorithm_against_the_exact_sequential_adjoint_entry_by_entry) against the long-double sequential adjoint, the worst entry
+# of each block over the largest entry of that block of the reference -- the LARGEST figure over every (length, series) at which the host tier and
+# tests/test_gpu_wide_adjoint_edges.py run the class (draws of seed 17 by wide_adjoint_draw; d = 28 also seeds 18 and 19 scaled by 1.5 and 0.6).  The host tier asserts ten times these; the GPU tier's
+# per-block bars are ten times these, floored at 1e-10 (wide_adjoint_block_bar).  "global": the worst entry over the largest entry of the whole gradient.
+WIDE_ADJOINT_MEASURED = {
+    (9, 0.1): dict(A=5.9e-10, a=2.0e-12, Q=8.5e-10, H=3.9e-09, h=2.1e-12, R=1.4e-10, x0m=6.5e-16, x0P=4.3e-10),      # global 8.7e-10
+    (9, 0.2): dict(A=9.4e-11, a=3.2e-13, Q=8.1e-11, H=1.2e-10, h=1.7e-13, R=3.5e-11, x0m=4.7e-16, x0P=2.3e-10),      # global 1.2e-10
+    (12, 0.2): dict(A=7.2e-12, a=1.5e-14, Q=9.3e-12, H=5.9e-12, h=8.8e-14, R=1.0e-11, x0m=9.3e-16, x0P=7.8e-11),      # global 6.2e-12
+    (14, 0.2): dict(A=2.4e-12, a=1.2e-14, Q=8.2e-11, H=2.1e-12, h=7.8e-15, R=9.5e-12, x0m=4.3e-16, x0P=7.6e-09),      # global 8.2e-11
+    (15, 0.2): dict(A=4.4e-13, a=7.9e-15, Q=6.6e-14, H=4.3e-13, h=5.7e-14, R=6.4e-13, x0m=1.6e-15, x0P=1.6e-13),      # global 1.3e-13
+    (16, 0.2): dict(A=1.5e-12, a=8.5e-14, Q=1.6e-12, H=1.7e-13, h=6.5e-14, R=5.8e-14, x0m=9.6e-17, x0P=7.6e-12),      # global 1.5e-12
+    (17, 0.2): dict(A=1.6e-13, a=8.8e-15, Q=3.7e-14, H=7.1e-14, h=3.3e-15, R=3.7e-13, x0m=5.5e-16, x0P=1.6e-12),      # global 3.7e-14
+    (28, 0.2): dict(A=4.6e-12, a=3.8e-14, Q=3.1e-12, H=2.8e-12, h=7.0e-14, R=1.3e-12, x0m=1.6e-15, x0P=1.7e-09),      # global 3.1e-12
+    (30, 0.2): dict(A=1.8e-12, a=1.6e-13, Q=3.4e-13, H=3.1e-12, h=1.1e-13, R=5.5e-13, x0m=2.8e-16, x0P=2.0e-12),      # global 3.4e-13
+    (31, 0.2): dict(A=1.5e-13, a=5.3e-15, Q=1.5e-14, H=2.4e-13, h=1.5e-14, R=7.8e-15, x0m=3.2e-16, x0P=3.6e-13),      # global 1.5e-14
+    (32, 0.2): dict(A=1.1e-12, a=4.1e-15, Q=2.9e-14, H=1.2e-14, h=2.4e-15, R=3.6e-14, x0m=8.0e-16, x0P=1.7e-12),      # global 1.5e-13
+    (33, 0.2): dict(A=7.8e-12, a=7.7e-14, Q=1.8e-12, H=8.7e-12, h=5.1e-14, R=3.0e-12, x0m=4.0e-16, x0P=9.4e-12),      # global 4.0e-12
+    (42, 0.2): dict(A=8.2e-12, a=1.9e-13, Q=3.2e-12, H=3.1e-11, h=2.1e-13, R=9.5e-12, x0m=7.8e-16, x0P=1.6e-11),      # global 4.4e-12
+    (46, 0.2): dict(A=4.4e-12, a=2.9e-14, Q=6.5e-12, H=5.9e-13, h=3.5e-14, R=6.6e-12, x0m=6.7e-16, x0P=7.5e-11),      # global 6.5e-12
+    (47, 0.2): dict(A=2.2e-13, a=1.9e-15, Q=1.2e-13, H=1.2e-13, h=1.1e-15, R=2.4e-13, x0m=1.8e-15, x0P=1.0e-13),      # global 1.2e-13
+    (48, 0.2): dict(A=2.0e-12, a=1.4e-15, Q=1.4e-13, H=5.3e-14, h=4.2e-15, R=5.9e-14, x0m=6.4e-16, x0P=1.8e-12),      # global 6.9e-13
+    (49, 0.2): dict(A=1.2e-12, a=1.3e-15, Q=1.0e-13, H=5.3e-14, h=1.7e-14, R=1.1e-13, x0m=1.6e-15, x0P=2.4e-13),      # global 4.5e-13
+    (54, 0.2): dict(A=5.1e-12, a=6.5e-14, Q=4.5e-13, H=1.1e-11, h=7.5e-14, R=4.8e-12, x0m=1.4e-15, x0P=4.0e-13),      # global 7.5e-13
+    (62, 0.2): dict(A=2.8e-12, a=5.4e-14, Q=3.5e-13, H=2.4e-12, h=6.2e-14, R=2.5e-12, x0m=4.0e-16, x0P=6.6e-13),      # global 9.7e-13
+    (63, 0.2): dict(A=1.5e-11, a=4.2e-13, Q=1.8e-12, H=1.2e-11, h=4.2e-13, R=6.2e-12, x0m=1.5e-15, x0P=2.9e-12),      # global 4.3e-12
+}
+
+
+def wide_adjoint_block_bar(d, dt, block):
+    """the GPU tier's bar of a block, relative to the block's own largest entry: ten times the CPU restatement's figure (the device's head length and halo differ a
+    little from NumPy's), floored at 1e-10"""
+    return max(10.0 * WIDE_ADJOINT_MEASURED[(d, dt)][block], 1e-10)
+
+
+def gradient_deviations(g, g_ref):
+    """-> ({block: worst entry / the largest entry of the whole reference gradient}, {block: worst entry / the largest entry of the reference's own block})"""
+    scale = max(np.abs(np.asarray(g_ref[k])).max() for k in GRADIENT_BLOCKS)
+    err = {k: float(np.abs(np.asarray(g[k]) - np.asarray(g_ref[k])).max()) for k in GRADIENT_BLOCKS}
+    return {k: err[k] / scale for k in GRADIENT_BLOCKS}, {k: err[k] / float(np.abs(np.asarray(g_ref[k])).max()) for k in GRADIENT_BLOCKS}
+
+
 # --------------------------------------------------------------------------- the wide-state engine's GPU tier (tests/test_gpu_wide*.py)
 WIDE_INFO = ("why", "n0", "halo", "why_post", "n1", "halo_back", "chunks", "chunk_len")
 

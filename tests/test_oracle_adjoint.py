@@ -83,6 +83,66 @@ def test_adjoint_against_50_digit_central_differences_of_every_block_entry(case,
     assert dev_d <= 1e-11, (case, dev_d)               # (the double build is the same derivation: it too sits far below the GPU tier's bar here)
 
 
+def _picks(d, rng, n=24):
+    """a seeded sample of at least n entries per block (the whole block where it has fewer); upper-triangle pairs for Q and x0P"""
+    some = lambda pairs: [pairs[i] for i in sorted(rng.choice(len(pairs), size=min(n, len(pairs)), replace=False))]      # noqa: E731
+    full = [(i, k) for i in range(d) for k in range(d)]
+    upper = [(i, k) for i in range(d) for k in range(i, d)]
+    vec = [(i,) for i in range(d)]
+    return dict(A=some(full), a=some(vec), Q=some(upper), H=some(vec), h=[()], R=[()], x0m=some(vec), x0P=some(upper))
+
+
+@pytest.mark.parametrize("d,T,every_entry", [(9, 25, True), (17, 20, False)])
+def test_wide_adjoint_against_50_digit_central_differences(d, T, every_entry):
+    """the wide-state engine's models (tests/_util.py WIDE_ADJOINT_KERNELS, spacing 0.2, a and h non-zero) through the same derivation at d > 8: every entry at d = 9;
+    at d = 17 (1296 evaluations of 0.14 s for all 648 entries) a seeded sample of 24 entries per block, every entry of a, H, x0m, h and R.  Measured here:
+        d = 9  T = 25   long double 1.2e-19   double build 5.1e-16   (every entry)
+        d = 17 T = 20   long double 1.8e-19   double build 3.7e-16   (the sample)
+    -- below the module's MEASURED_VS_MPMATH, so within BAR_VS_MPMATH as the d <= 8 cases are."""
+    model = U.wide_adjoint_model(d, 0.2, T)
+    y = _draw(model, 5)
+    lp, g = sa.logpdf_adjoint(model, y)
+    lp_d, g_d = sa.logpdf_adjoint(model, y, use_double=True)
+    if every_entry:
+        lp_mp, g_mp = M.block_gradient_mp(model, y)
+        assert abs(lp - lp_mp) <= 1e-15 * abs(lp_mp)
+        dev, dev_d = _max_dev(g, g_mp), _max_dev(g_d, g_mp)
+    else:
+        picks = _picks(d, np.random.default_rng(1700 + d))
+        assert all(len(picks[k]) >= min(24, np.size(g[k])) for k in ("A", "a", "Q", "H", "x0m", "x0P"))
+        want = M.block_gradient_entries_mp(model, y, picks)
+        scale = max(np.abs(np.asarray(g[k])).max() for k in BLOCKS)      # (of the long-double gradient: the sample need not hold the largest entry)
+        at = lambda gg, k, idx: float(np.asarray(gg[k])[idx]) if idx else float(gg[k])      # noqa: E731
+        dev = max(abs(at(g, k, idx) - w) for k in BLOCKS for idx, w in zip(picks[k], want[k])) / scale
+        dev_d = max(abs(at(g_d, k, idx) - w) for k in BLOCKS for idx, w in zip(picks[k], want[k])) / scale
+    print(f"wide d={d} T={T}: long double {dev:.2e}, double build {dev_d:.2e} of the largest entry (bar {BAR_VS_MPMATH:.1e})")
+    for k in ("Q", "x0P"):
+        assert np.array_equal(g[k], g[k].T)
+    assert dev <= BAR_VS_MPMATH, (d, dev)
+    assert dev_d <= 1e-11, (d, dev_d)
+
+
+@pytest.mark.parametrize("d", [14, 30, 46, 63])
+def test_wide_adjoint_long_double_against_double_build(d):
+    """T = 2500 at spacing 0.1 (the slower of the two spacings: the longer memory), the Gram kernel's tile-edge dimensions.  Measured here: 3.8e-15 (d = 14),
+    3.7e-15 (30), 6.3e-15 (46), 3.9e-15 (63) of the largest entry, against a bar of 1e-9."""
+    model = U.wide_adjoint_model(d, 0.1, 2500)
+    y = _draw(model, 6)
+    lp, g = sa.logpdf_adjoint(model, y)
+    lp_ref = sk.logpdf(model, y)
+    assert abs(lp - lp_ref) <= 1e-12 * abs(lp_ref)
+    lp_d, g_d = sa.logpdf_adjoint(model, y, use_double=True)
+    dev = _max_dev(g_d, g)
+    print(f"wide d={d} T=2500: long double against double build {dev:.2e} of the largest entry (bar 1e-9)")
+    assert dev <= 1e-9, (d, dev)
+
+
+def test_the_oracle_refuses_a_state_wider_than_its_cap():
+    model = U.random_lgssm(np.random.default_rng(1), False, 65, 10)
+    with pytest.raises(AssertionError):
+        sa.logpdf_adjoint(model, np.zeros(10))
+
+
 def long_cases():
     """the models of the long checks: a slow and a fast one at d = 3 and d = 6, at the GPU tests' lengths"""
     T = 12_000

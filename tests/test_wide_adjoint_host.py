@@ -1,11 +1,14 @@
 """CPU tier: the host half of the wide models' adjoint gradient (tgp_adjoint_finish_wide, csrc/tgp_wide_adjoint_host.hpp) on a record that NumPy
 builds the way the wide-state engine does -- the head is the n0 + 1 steps up to the settled gain, the sums run over the steps behind it -- against
-central differences of the ORACLE's sequential logpdf along random directions in every model block, for products of kernels with 9 <= d <= 60."""
+central differences of the ORACLE's sequential logpdf along random directions in every model block, for products of kernels with 9 <= d <= 60; and, entry
+by entry, against the oracle's exact sequential adjoint in long double for every class of the GPU tier's edge tests (9 <= d <= 63)."""
 import numpy as np
 import pytest
 
 from oracle import components as oc
 from oracle import lgssm_ref as ref
+from oracle import seq_adjoint as sa
+from tests import _util as U
 
 KERNELS = {
     9: ("product", ("matern52",), ("stretched", 0.7, ("matern52",))),
@@ -129,6 +132,39 @@ def test_wide_host_half_against_directional_differences_of_the_oracle(d):
         terms = [np.sum(np.asarray(g[k]) * np.asarray(D[k])) for k in BLOCKS]
         ad, gross = float(sum(terms)), float(sum(abs(t) for t in terms))
         assert abs(ad - fd) <= 2e-6 * max(1.0, abs(fd), gross), (ad, fd, gross)
+
+
+# --------------------------------------------------------------------------- the algorithm against the exact gradient, entry by entry
+def restated_gradient(lib, model, y):
+    """wide_record (NumPy) + tgp_adjoint_finish_wide: the gradient the wide-state engine's algorithm gives with no kernel involved -> (logpdf, gradient)"""
+    rec, nh, lp = wide_record(model, y)
+    return lp, finish_wide(lib, len(model["x0m"]), rec, np.ascontiguousarray(y[:nh]), nh)
+
+
+@pytest.mark.parametrize("d,dt,T", [(d, dt, U.wide_adjoint_length(d)) for d, dt in U.WIDE_ADJOINT_CLASSES] + U.WIDE_ADJOINT_HOST_EXTRA)
+def test_the_algorithm_against_the_exact_sequential_adjoint_entry_by_entry(d, dt, T):
+    """What the stationary head and the truncated covariance recursion cost, apart from any kernel: every entry of every block against the oracle's exact
+    sequential adjoint in long double (oracle/seq_adjoint.py), for every class of tests/test_gpu_wide_adjoint_edges.py.  Asserted: the plan accepts the class;
+    the worst entry stands within 1e-9 of the largest entry of the whole gradient (the GPU tier's 1e-8 keeps a decade); every block stands within ten times the
+    figure measured for it (tests/_util.py WIDE_ADJOINT_MEASURED: the worst entry of a block over the block's own largest entry, the largest over the class's
+    lengths).  Lengths: wide_adjoint_length(d) for every class, and the GPU tier's lengths at which a class stands farthest (WIDE_ADJOINT_HOST_EXTRA) -- d = 9 at
+    spacing 0.1 and T = 524 335 is the nearest to the limit: 8.7e-10 (H: 3.9e-9 of its own block).  Not a class: d = 14 at spacing 0.1 (3.9e-9, x0P 1.5e-7 of its
+    own block) and d = 9 at spacing 0.1 and T = 528 425 (1.09e-9): the algorithm's own cost there is outside the 1e-9 that keeps a decade under the GPU tier's 1e-8."""
+    import temporalgps_jl_amd as tgp
+    lib = tgp._lib.load()
+    model = U.wide_adjoint_model(d, dt, T)
+    pl = U.wide_plan(model, T)
+    assert pl["why"] == 0 and pl["n0"] + 64 <= T, pl
+    y = U.wide_adjoint_draw(model, 17)
+    lp, g = restated_gradient(lib, model, y)
+    lp_ref, g_ref = sa.logpdf_adjoint(model, y)
+    assert abs(lp - lp_ref) <= 1e-10 * abs(lp_ref), (lp, lp_ref)
+    glob, own = U.gradient_deviations(g, g_ref)
+    print(f"d {d} dt {dt} T {T} plan {pl}: global {max(glob.values()):.1e} | own " + " ".join(f"{k} {v:.1e}" for k, v in own.items()))
+    assert max(glob.values()) <= 1e-9, (d, dt, glob)
+    measured = U.WIDE_ADJOINT_MEASURED[(d, dt)]
+    for k in BLOCKS:      # (a figure at rounding level is floored at T 2^-53: sums of T fp64 terms in another order differ by that much)
+        assert own[k] <= 10.0 * max(measured[k], T * 2.0 ** -53), (d, dt, k, own[k], measured[k])
 
 
 def test_wide_host_half_refuses_records_that_do_not_fit():

@@ -66,3 +66,35 @@ def test_chunked_adjoint_sums_equal_the_sequential_ones(proto, d, chunks):
         w = np.asarray(w)
         err = np.max(np.abs(np.asarray(got[k]) - w))
         assert err <= 1e-12 * max(1.0, np.abs(w).max()), (k, err, np.abs(w).max())
+
+
+@pytest.mark.parametrize("d", sorted(KERNELS))
+@pytest.mark.parametrize("geometry", ("two_chunks_per_halo", "four_chunks_per_halo", "last_chunk_of_a_few_steps"))
+def test_chunks_shorter_than_the_backward_warm_up(proto, d, geometry):
+    """chunks shorter than halo_b: a chunk's backward warm-up from zero crosses two (four) or more of the chunks ahead of it, as it does on the device when the plan
+    makes thousands of chunks; and a count whose last chunk is 1 ... 15 steps (the series' end is then inside nearly every warm-up of the last halo_b steps)"""
+    T = 1600
+    model = oc.build_lgssm(KERNELS[d], ("regular", 0.0, 0.2, T), 0.1)
+    model["h"] = np.array([0.3])
+    model["a"] = 0.01 * np.linspace(-1.0, 1.0, d)[None]
+    rng = np.random.default_rng(100 + d)
+    y = ref.rand(model, rng.standard_normal((T, d)), rng.standard_normal(T), rng.standard_normal(d))
+    pl = proto.plan(model, T)
+    assert pl is not None and pl["n0"] + 64 <= T and pl["halo_b"] is not None and pl["halo_b"] >= 16
+    Tb, hb = T - pl["n0"], pl["halo_b"]
+    if geometry == "last_chunk_of_a_few_steps":
+        chunks = next(c for c in range(2, Tb) if 1 <= Tb - (-(-Tb // -(-Tb // c)) - 1) * -(-Tb // c) <= 15)
+    else:
+        chunks = -(-Tb // (hb // (2 if geometry == "two_chunks_per_halo" else 4)))
+    ln = -(-Tb // chunks)
+    n, last = -(-Tb // ln), Tb - (-(-Tb // ln) - 1) * ln
+    print(f"d {d} {geometry}: halo_b {hb}, {n} chunks of {ln} steps, the last of {last}")
+    if geometry == "last_chunk_of_a_few_steps":
+        assert 1 <= last <= 15 and n >= 2
+    else:
+        assert ln * (2 if geometry == "two_chunks_per_halo" else 4) <= hb and n >= 8
+    got, want = proto.sums(pl, y, chunks=chunks), sequential_sums(pl, y)
+    for k, w in want.items():
+        w = np.asarray(w)
+        err = np.max(np.abs(np.asarray(got[k]) - w))
+        assert err <= 1e-12 * max(1.0, np.abs(w).max()), (k, err, np.abs(w).max())
