@@ -307,6 +307,19 @@ int tgp_steady_plan(int d, const double* A, const double* a, const double* Q, co
  * plan stopped before it).  The adjoint kernel's spans are 4096 steps, of which a workgroup owns 4096 - 2 halo. */
 int tgp_filter_plan(int d, const double* A, const double* a, const double* Q, const double* H, const double* hh, const double* R,
                     const double* x0m, const double* x0P, int64_t T, int32_t* info);
+/* The plan of the dense-powers smoother on top of it (d <= 8; a pure host function): what a logpdf (want_posterior = 0) or a posterior-marginals /
+ * posterior-draw call (want_posterior != 0) of the one-launch smoother is laid out on.  info [8]: why (as above; 5 also when a workgroup would own
+ * fewer than 1024 steps, 3: series shorter than head + tail + 16), n0, head steps, the filter's halo, the smoother's halo (the longer of the filter's
+ * and the settled reverse-time transition's; the filter's without the posterior), n1 (steps at the series' end whose smoothed variance is in its
+ * transient; 0 without the posterior, -1 unknown), span (steps a workgroup owns: 4096 - halo, 4096 - 2 halo with the posterior; 0 when the halo is
+ * unknown), workgroups = ceil((T - head steps) / span) (0 when the plan declines). */
+int tgp_smooth_plan(int d, const double* A, const double* a, const double* Q, const double* H, const double* hh, const double* R,
+                    const double* x0m, const double* x0P, int64_t T, int want_posterior, int32_t* info);
+/* The plan of the prior's one-launch draw (tgp_rand of a Forward LTI model, d <= 8; a pure host function of the model -- T only counts the workgroups).
+ * info [4]: why (0 applies, 2 noise not positive definite, 5 the open loop's powers are not below 2^-60 after 1536 steps), halo steps, span
+ * (4096 - halo: the steps a workgroup owns; there is no head), workgroups = ceil(T / span). */
+int tgp_rand_plan(int d, const double* A, const double* a, const double* Q, const double* H, const double* hh, const double* R,
+                  const double* x0m, const double* x0P, int64_t T, int32_t* info);
 
 /* The host plan of the wide-state engine (8 < d <= 63: csrc/tgp_wide.hip) as a pure host function -- no handle, no GPU: the covariance half of
  * lgssm.jl:99-165 to its fixed point.  info [8]: why (0 = applies), n0 (head steps), halo, why_post (-1: not asked), n1 (steps at the series' end whose

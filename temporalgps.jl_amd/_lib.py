@@ -57,6 +57,8 @@ _SIGS = {
     "tgp_adjoint_record_size": (ctypes.c_int, [ctypes.c_int]),
     "tgp_steady_plan": (ctypes.c_int, [ctypes.c_int] + [_vp] * 8 + [_i64, _vp, _vp, _vp, _vp]),
     "tgp_filter_plan": (ctypes.c_int, [ctypes.c_int] + [_vp] * 8 + [_i64, _vp]),
+    "tgp_smooth_plan": (ctypes.c_int, [ctypes.c_int] + [_vp] * 8 + [_i64, ctypes.c_int, _vp]),
+    "tgp_rand_plan": (ctypes.c_int, [ctypes.c_int] + [_vp] * 8 + [_i64, _vp]),
     "tgp_wide_plan": (ctypes.c_int, [ctypes.c_int] + [_vp] * 8 + [_i64, ctypes.c_int, _vp, _vp, _vp, _vp]),
     "tgp_wide_plan_draw": (ctypes.c_int, [ctypes.c_int] + [_vp] * 8 + [_i64, _vp, _vp, _vp, _vp]),
     "tgp_segment_plan": (ctypes.c_int, [_vp, _i64, ctypes.c_int, _vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),

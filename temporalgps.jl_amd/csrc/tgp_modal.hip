@@ -2173,6 +2173,12 @@ int rand_lti(hipStream_t stream, const tgp_plan::RandPlan& plan, const double* x
     return (int)hipErrorInvalidValue;
 }
 
+long long rand_span(const tgp_plan::RandPlan& rp) { return 8LL * 64 * kWJ - rp.halo; }      // (launch_rand's ka.C)
+long long rand_workgroups(const tgp_plan::RandPlan& rp, long long T) {
+    const long long C = rand_span(rp);
+    return (T + C - 1) / C;
+}
+
 // =================================================================================================================================
 // _filter of an LTI model behind its head (lgssm.jl:171-187): mu' = Phi mu + a + (A K) u, r = u - h' mu, m_t = mu_t + K r_t, P_t = P_ss.
 // k_rand_one's structure on the dense powers of the closed loop Phi = A - (A K) h': a first sweep of a lane's 8 steps from a zero state gives

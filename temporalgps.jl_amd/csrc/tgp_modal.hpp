@@ -155,5 +155,8 @@ long long smooth_workgroups(const tgp_plan::SmoothPlan& sp, long long T, bool po
 int smooth_lti(hipStream_t stream, const tgp_plan::SmoothPlan& sp, const double* mu_start, const SmoothCall& c);
 int rand_lti(hipStream_t stream, const tgp_plan::RandPlan& plan, const double* x0, const double* eps_t, const double* eps_e, long long T, double* y,
              const char** kname);
+// steps a workgroup of k_rand_one owns (its tiles minus the run-in in front), and the workgroups of a T-step draw (no head: the first one starts at step 0)
+long long rand_span(const tgp_plan::RandPlan& plan);
+long long rand_workgroups(const tgp_plan::RandPlan& plan, long long T);
 
 }  // namespace tgp_modal

@@ -414,6 +414,27 @@ def smoothsim_run(model, y, Rnew, eps=None, hh_t=None):
                 mean=mean, var=var)
 
 
+def posterior_draw(post, R_new, eps_t, eps_e, eps_0):
+    """ref.rand(ref.replace_observation_noise_cov(post, R_new), eps_t, eps_e, eps_0) of an EVALUATED posterior (ordering "R": oracle.seq_kalman.posterior's
+    or oracle.lgssm_ref.posterior's G, g, L in A, a, Q; scalar observations), restated with the factorisations batched: the Cholesky factors of
+    Symmetric(L_t + 1e-9 I) (lgc.jl:84-87) and of Symmetric(P_final + 1e-12 I) (gaussian.jl:35-43) at once, then the plain loop backwards over the steps
+    (lgssm.jl:65-91).  R_new None: the model's own noise.  tests/test_smooth_host.py holds it to the literal loop."""
+    assert post["ordering"] == "R" and post["kind"] == "scalar"
+    T, d = post["T"], len(post["x0m"])
+    G, g, L = (np.broadcast_to(np.asarray(post[k], dtype=np.float64), (T,) + np.asarray(post[k]).shape[1:]) for k in ("A", "a", "Q"))
+    sym = lambda M: np.triu(M) + np.swapaxes(np.triu(M, 1), -1, -2)      # noqa: E731  (LinearAlgebra.Symmetric: the upper triangle is the matrix)
+    low = np.linalg.cholesky(sym(L) + 1e-9 * np.eye(d))                    # (T, d, d): U_t'
+    push = g + np.einsum("tij,tj->ti", low, np.asarray(eps_t, dtype=np.float64))
+    x = post["x0m"] + np.linalg.cholesky(sym(np.asarray(post["x0P"])) + 1e-12 * np.eye(d)) @ np.asarray(eps_0, dtype=np.float64)
+    H = np.broadcast_to(np.asarray(post["H"], dtype=np.float64), (T, d))
+    hx = np.empty(T)
+    for t in range(T - 1, -1, -1):
+        hx[t] = H[t] @ x
+        x = G[t] @ x + push[t]
+    R = np.broadcast_to(np.atleast_1d(np.asarray(post["R"] if R_new is None else R_new, dtype=np.float64)), (T,))
+    return hx + np.broadcast_to(np.atleast_1d(np.asarray(post["h"], dtype=np.float64)), (T,)) + np.sqrt(R) * np.asarray(eps_e, dtype=np.float64)
+
+
 def kernel_sde(k):
     """(F, H) of a kernel expression built from Matern terms with scaled / stretched / sum (what the closed-form transitions cover)."""
     from scipy.linalg import block_diag

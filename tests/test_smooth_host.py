@@ -98,6 +98,123 @@ def test_a_halo_longer_than_a_span():
     _check(r, lp, pm, pv)
 
 
+# ---------------------------------------------------------------------------- the edge suite's geometry without a GPU (tests/_dense_powers_edges.py)
+def _edge_case(name):
+    from oracle import seq_kalman as sk
+    from tests import _dense_powers_edges as E
+    spec, dt, noise, route = E.CLASSES[name]
+    blocks = E.blocks_of(spec, dt, noise)
+    d, N = len(blocks["x0m"]), E.T_CAP
+    rng = np.random.default_rng(17)
+    y = sk.rand(dict(blocks, T=N), rng.standard_normal((N, d)), rng.standard_normal(N), rng.standard_normal(d))
+    hh = E.offsets(N) if route == "offset" else None
+    if hh is not None:
+        y = y - float(blocks["h"][0]) + hh
+    return blocks, d, y, hh, 0.01 + 0.1 * rng.random(N), (rng.standard_normal((N, d)), rng.standard_normal(N), rng.standard_normal(d))
+
+
+def _edge_names():
+    from tests import _dense_powers_edges as E
+    return [n for n in E.CLASSES if E.EXPECTED[n]["why"] == 0]
+
+
+def _restatements_head_and_tail(blocks, sp):
+    """The restatement compiles the plan header itself, without the fused multiply-adds of the library's build.  Halos (16-step multiples with a 2^-60 margin)
+    agree with tgp_smooth_plan; the two lengths that end where a recursion stops changing by 2 ulp may differ by a step or two -- the head (the 16-step
+    multiple behind n0) then by 16 steps where n0 sits next to a multiple (stretched_d6: n0 = 351), the tail n1 by a step.  The lengths of these tests are
+    placed by the restatement's own head and tail, through the same edge_lengths()."""
+    from tests import _dense_powers_edges as E
+    r = U.smoothsim_run(dict(blocks, T=E.T_CAP), np.zeros(E.T_CAP), 0.1)
+    assert r["why"] == 0 and r["halo"] == sp["halo"] and r["nhs"] - sp["nhs"] in (-16, 0, 16) and abs(r["n1"] - sp["n1"]) <= 2, (r["nhs"], r["halo"], r["n1"], sp)
+    return r["nhs"], r["n1"]
+
+
+@pytest.mark.parametrize("name", _edge_names())
+def test_posterior_marginals_at_the_edge_suites_lengths(name):
+    """the host restatement of k_smooth_one<posterior> at the lengths tests/test_gpu_dense_powers_edges.py computes for the class from tgp_smooth_plan -- the
+    `from_head` classes among them, and the lengths that put the variance tail over two workgroups (no served class has a tail longer than a span:
+    _dense_powers_edges.EXPECTED); "offset" classes with their emission offset per step.  Against
+    the oracle's C restatement (oracle/seq_kalman.py: tests/test_oracle_c.py holds it to the literal loops used above)."""
+    from oracle import seq_kalman as sk
+    from tests import _dense_powers_edges as E
+    blocks, d, y, hh, Rn, _ = _edge_case(name)
+    sp = E.smooth_plan(blocks, E.T_CAP)
+    assert sp["why"] == 0
+    nhs, C, halo, n1 = sp["nhs"], sp["span"], sp["halo"], sp["n1"]
+    nhs, n1 = _restatements_head_and_tail(blocks, sp)
+    tmin = nhs + n1 + 16
+    worst = [0.0, 0.0, 0.0]
+    for T in sorted(set(E.edge_lengths(nhs, C, halo, n1) + [tmin, tmin - 1])):
+        model = dict(blocks, T=T) if hh is None else dict(blocks, T=T, h=hh[:T].copy())
+        r = U.smoothsim_run(model, y[:T], Rn[:T], hh_t=None if hh is None else hh[:T])
+        if T < tmin:
+            assert r["why"] == E.WHY_TOO_SHORT, (T, r["why"])
+            continue
+        assert (r["why"], r["nhs"], r["halo"], r["n1"], r["nwg"]) == (0, nhs, halo, n1, -(-(T - nhs) // C)), (T, r)
+        lp, (pm, pv) = sk.logpdf(model, y[:T]), sk.posterior_marginals(model, y[:T], Rn[:T])
+        dev = (abs(r["lml"] - lp) / abs(lp), np.abs(r["mean"] - pm).max() / max(1.0, np.abs(pm).max()), np.abs(r["var"] - pv).max())
+        worst = [max(a, b) for a, b in zip(worst, dev)]
+        assert dev[0] <= 1e-10 and dev[1] <= 1e-8 and dev[2] <= 1e-8, (T, dev)
+    print(f"{name}: worst lp {worst[0]:.1e} mean {worst[1]:.1e} var {worst[2]:.1e}")
+
+
+@pytest.mark.parametrize("name", [n for n in _edge_names() if int(n.rsplit("_d", 1)[1]) <= 6])
+def test_posterior_draws_at_the_edge_suites_lengths(name):
+    """... and of k_smooth_one<rand> (the LTI form of every class with d <= 6), against the vectorised restatement of the literal draw on the oracle's evaluated posterior"""
+    from oracle import seq_kalman as sk
+    from tests import _dense_powers_edges as E
+    blocks, d, y, hh, Rn, eps = _edge_case(name)
+    if hh is not None:
+        y = y - hh + float(blocks["h"][0])      # (the draw's kernel serves the LTI form)
+    sp = E.smooth_plan(blocks, E.T_CAP)
+    C, halo = sp["span"], sp["halo"]
+    nhs, n1 = _restatements_head_and_tail(blocks, sp)
+    worst = 0.0
+    for T in (T for T in E.edge_lengths(nhs, C, halo, n1) + [nhs + n1 + 16] if T >= nhs + n1 + 16):
+        model = dict(blocks, T=T)
+        e = (eps[0][:T], eps[1][:T], eps[2])
+        r = U.smoothsim_run(model, y[:T], Rn[:T], eps=e)
+        assert r["rc"] == 0 and r["why"] == 0, (T, r)
+        want = U.posterior_draw(sk.posterior(model, y[:T]), Rn[:T], *e)
+        dev = np.abs(r["mean"] - want).max() / max(1.0, np.abs(want).max())
+        worst = max(worst, dev)
+        assert dev <= 1e-8, (T, dev)
+    print(f"{name}: worst draw {worst:.1e}")
+
+
+@pytest.mark.parametrize("i,T", [(0, 700), (4, 333)])
+def test_the_vectorised_posterior_draw_is_the_literal_loop(i, T):
+    """tests/_util.py posterior_draw (batched factorisations, a plain loop backwards) against ref.rand on the evaluated posterior with replaced noise, on the
+    literal and on the C oracle's posterior; 1e-12 of the draw's scale (the same sums in another order)"""
+    from oracle import seq_kalman as sk
+    k, dt, s2 = CASES[i]
+    model, y, _ = U.gp_case(k, ("regular", 0.0, dt, T), s2, seed=60 + i)
+    d = len(model["x0m"])
+    rng = np.random.default_rng(i)
+    eps = (rng.standard_normal((T, d)), rng.standard_normal(T), rng.standard_normal(d))
+    post = ref.posterior(model, y)
+    for Rn in (np.array([0.05]), rng.random(T) * 0.1, None):
+        lit = post if Rn is None else ref.replace_observation_noise_cov(post, np.broadcast_to(Rn, (T,)).copy())
+        want = ref.rand(lit, *eps)
+        sc = max(1.0, np.abs(want).max())
+        assert np.abs(U.posterior_draw(post, Rn, *eps) - want).max() <= 1e-12 * sc
+        assert np.abs(U.posterior_draw(sk.posterior(model, y), Rn, *eps) - want).max() <= 1e-9 * sc      # (the C oracle's posterior: tests/test_oracle_c.py's bar)
+
+
+def test_the_oracles_filter_and_evaluated_posterior_of_a_prefix_are_a_prefix():
+    """what tests/test_gpu_dense_powers_edges.py shares among the lengths of a class: both run forwards -- the first T steps do not see what follows"""
+    from oracle import seq_kalman as sk
+    from tests import _dense_powers_edges as E
+    blocks, d, y, _, _, _ = _edge_case("identical_d6")
+    N, T = 3000, 1777
+    _, fm, fP = sk.filter_(dict(blocks, T=N), y[:N], want_states=True)
+    _, fm1, fP1 = sk.filter_(dict(blocks, T=T), y[:T], want_states=True)
+    assert np.array_equal(fm[:T], fm1) and np.array_equal(fP[:T], fP1)
+    p, p1 = sk.posterior(dict(blocks, T=N), y[:N]), sk.posterior(dict(blocks, T=T), y[:T])
+    assert all(np.array_equal(p[k][:T], p1[k]) for k in ("A", "a", "Q"))
+    assert np.array_equal(p1["x0m"], fm[T - 1]) and np.allclose(p1["x0P"], fP[T - 1], rtol=0, atol=1e-15)
+
+
 @pytest.mark.parametrize("i", [0, 3, 4, 6])
 def test_an_emission_offset_per_step(i):
     """a GP with a mean function on a regular grid (lti_sde.jl:118-131): every block shared but the emission offset h_t = m(x_t).  The gains never see
