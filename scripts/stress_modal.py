@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Randomised check of the stationary-gain engine's ONE-LAUNCH path (TGP_OPT_STEADY = 3, csrc/tgp_modal.hip + tgp_steady_plan.hpp) against the
+"""Randomised check of the stationary-gain engine's ONE-LAUNCH path (TGP_OPT_STEADY = 3, csrc/tgp_modal.hip, the dense-power kernels of csrc/tgp_powers.hip + tgp_steady_plan.hpp) against the
 sequential C oracle: random kernels (sums of scaled, stretched Matern terms, d = 1..8), spacings 0.003..1, noise 1e-4..3, series lengths around
 every tile / workgroup / head boundary, shared or per-step new noise, transition and emission offsets, host or device arrays (device pointers
 on and off the 16-byte boundary).  Reports which engine served each case (the plan's verdict for the ones it declined) and holds the

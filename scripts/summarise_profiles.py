@@ -77,10 +77,10 @@ def label(name):
             mode = {"0": "logpdf", "1": "filter", "2": "posterior", "3": "materialise", "4": "scratch"}.get(m.group(4) or "", m.group(4) or "?")
             return f"k_apply_filter<{lay},{mode}>"
         return f"k_{m.group(1)}<{lay}>"
-    m = re.match(r"tgp_modal::k_smooth_one<", n)
+    m = re.match(r"tgp_powers::k_smooth_one<", n)
     if m:      # (as above: the larger launch is the posterior call)
         return "k_smooth_one<posterior>"
-    m = re.match(r"tgp_modal::(k_filter_one|k_rand_one|k_adjoint_one)<", n)
+    m = re.match(r"tgp_powers::(k_filter_one|k_rand_one|k_adjoint_one)<", n)
     if m:
         return m.group(1)
     m = re.match(r"tgp_sweep::k_sweep<(\d+), (true|false), (\d+), (true|false)>", n)

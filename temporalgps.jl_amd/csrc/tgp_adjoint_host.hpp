@@ -24,7 +24,7 @@ inline int record_size(int d) { return 3 * d * d + 8 * d + 8 + d * (d + 1) / 2; 
 
 // rec: the engine's record (record_size(d) doubles); yh: the first nyh observations (nyh >= 512 * head tiles).  Returns 0, or 1 when the
 // record says the engine did not apply / the arguments do not fit it.
-// head_steps >= 0: the head's length in steps when it is not a whole number of 512-step tiles (the one-launch adjoint, tgp_modal::adjoint_lti)
+// head_steps >= 0: the head's length in steps when it is not a whole number of 512-step tiles (the one-launch adjoint, tgp_powers::adjoint_lti)
 inline int finish(int d, const double* rec, const double* yh, int64_t nyh, const Out& out, int64_t head_steps = -1) {
     const int DD = d * d, NS = DD + 3 * d + 2;
     const double *SA = rec, *Sa = rec + DD, *Sk = rec + DD + d, *Srm = rec + DD + 2 * d;

@@ -23,6 +23,7 @@
 #include <chrono>
 #include "tgp_steady.hpp"
 #include "tgp_modal.hpp"
+#include "tgp_powers.hpp"
 #include "tgp_sweep.hpp"
 #include "tgp_wide.hpp"
 #include "tgp_adjoint_host.hpp"
@@ -2141,17 +2142,17 @@ int tgp_filter(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t 
 
 // posterior(model, y) of a Forward LTI model (lgssm.jl:193-221; scalar observations, one noise variance, no missing data, d <= 6): the
 // reverse-time transitions of the head on the host, everything behind it -- two constant fills and g_(t+1) = m_t - G mu_(t+1) -- by the
-// filter's ONE kernel (tgp_modal.hpp: PosteriorOut).
+// filter's ONE kernel (tgp_powers.hpp: PosteriorOut).
 static int posterior_lti_call(tgp_handle* h, const double* y, uint32_t flags, double* G, double* g, double* L, double* xfm, double* xfP, bool* served) {
     *served = false;
     tgp_plan::ModelHost mh;
     if (!h->opt_modal || chunk_engine_requested(h) || h->is_dense || !h->lti || h->p != 1 || h->ordering != 0 || h->sde || h->d > tgp_plan::kRandMaxD || !modal_host_model(h, mh)) return TGP_OK;
     tgp_plan::FilterPlan fp;
-    tgp_modal::plan_filter(mh, h->T, fp);
+    tgp_powers::plan_filter(mh, h->T, fp);
     if (fp.why != tgp_plan::kOk) return TGP_OK;
     const int d = h->d;
     const size_t dd = (size_t)d * d, nhs = (size_t)fp.nhs;
-    const long long nwg = tgp_modal::filter_workgroups(fp, h->T);
+    const long long nwg = tgp_powers::filter_workgroups(fp, h->T);
     const size_t need = nhs * (1 + 2 * dd) + (nhs + 1) * d + 2 * dd + (size_t)nwg + d + 8;
     TRY(ensure_pinned(h, need));
     double *yh = h->flt_host, *Gh = yh + nhs, *Lh = Gh + nhs * dd, *gh = Lh + nhs * dd, *Gss = gh + (nhs + 1) * d, *Lss = Gss + dd, *fin = Lss + dd,
@@ -2164,7 +2165,7 @@ static int posterior_lti_call(tgp_handle* h, const double* y, uint32_t flags, do
     HIPCHK(hipMemcpyAsync(yh, h->mv.y, nhs * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     double mu_end[tgp_plan::kRandMaxD], quad_head = 0.0;
-    if (!tgp_modal::plan_posterior_head(mh, fp, yh, Gh, gh, Lh, Gss, Lss, mu_end, &quad_head)) return TGP_OK;      // (the general engine reports it)
+    if (!tgp_powers::plan_posterior_head(mh, fp, yh, Gh, gh, Lh, Gss, Lss, mu_end, &quad_head)) return TGP_OK;      // (the general engine reports it)
     double *dG = nullptr, *dg = nullptr, *dL = nullptr;
     TRY(stage_out(h, h->bo1, G, nG, odev, &dG));
     TRY(stage_out(h, h->bo2, g, ng, odev, &dg));
@@ -2174,8 +2175,8 @@ static int posterior_lti_call(tgp_handle* h, const double* y, uint32_t flags, do
     HIPCHK(hipMemcpyAsync(dg, gh, (nhs + 1) * d * sizeof(double), hipMemcpyHostToDevice, h->stream));
     {
         LaunchScope ls(h, "k_filter_one");
-        const tgp_modal::PosteriorOut po{Gss, Lss, dG, dg, dL, fin};
-        const int rc = tgp_modal::filter_lti(h->stream, fp, mu_end, h->mv.y, h->T, nullptr, nullptr, part, &po);
+        const tgp_powers::PosteriorOut po{Gss, Lss, dG, dg, dL, fin};
+        const int rc = tgp_powers::filter_lti(h->stream, fp, mu_end, h->mv.y, h->T, nullptr, nullptr, part, &po);
         if (rc != 0) return h->fail(TGP_EHIP, std::string("tgp_posterior: launch: ") + hipGetErrorString((hipError_t)rc));
     }
     tm.kernels_done();
@@ -2712,7 +2713,7 @@ int tgp_rand(tgp_handle* h, const double* eps_t, const double* eps_e, const doub
         for (int k = 0; k <= i; ++k) acc += U[k + i * d] * eps_0[k];
         x0[i] = h->x0m[i] + acc;
     }
-    // LTI, Forward, scalar observations, d <= 6: ONE kernel over the draws on the dense powers of the transition (tgp_modal::rand_lti)
+    // LTI, Forward, scalar observations, d <= 6: ONE kernel over the draws on the dense powers of the transition (tgp_powers::rand_lti)
     const bool rand_one = !chunk_engine_requested(h) && !h->is_dense && h->opt_modal && h->lti && h->p == 1 && h->ordering == 0 && !h->sde && d <= tgp_plan::kRandMaxD && !h->hostm.empty();
     // ... wide LTI models (8 < d <= 63, tgp_wide.hip): ONE kernel on the open loop, chunks warmed up on the same draws
     const bool rand_wide = !rand_one && !chunk_engine_requested(h) && h->opt_group != 2 && h->opt_modal && h->opt_wide && !h->widem.empty() && h->wide_ht == nullptr &&
@@ -2745,7 +2746,7 @@ int tgp_rand(tgp_handle* h, const double* eps_t, const double* eps_e, const doub
         tgp_plan::ModelHost mh;
         tgp_plan::RandPlan rp;
         if (modal_host_model(h, mh)) {
-            tgp_modal::plan_rand(mh, rp);
+            tgp_powers::plan_rand(mh, rp);
             if (rp.why == tgp_plan::kOk && h->T >= 2) {
                 const void *pet = nullptr, *pee = nullptr;
                 TRY(stage_in(h, h->beps_t, eps_t, (size_t)h->T * d * sizeof(double), idev, &pet));
@@ -2755,7 +2756,7 @@ int tgp_rand(tgp_handle* h, const double* eps_t, const double* eps_e, const doub
                 TRY(stage_out(h, h->bo1, y_out, nT, odev, &dy));
                 {
                     LaunchScope ls(h, "k_rand_one");
-                    const int rc = tgp_modal::rand_lti(h->stream, rp, x0.data(), (const double*)pet, (const double*)pee, h->T, dy, nullptr);
+                    const int rc = tgp_powers::rand_lti(h->stream, rp, x0.data(), (const double*)pet, (const double*)pee, h->T, dy, nullptr);
                     if (rc != 0) return h->fail(TGP_EHIP, std::string("tgp_rand: launch: ") + hipGetErrorString((hipError_t)rc));
                 }
                 tm.kernels_done();

@@ -15,13 +15,13 @@ static int ensure_pinned(tgp_handle* h, size_t need) {
 static int adjoint_lti_call(tgp_handle* h, const double* y, uint32_t flags, double* lml_out, const tgp_adjoint::Out& o, bool* served) {
     *served = false;
     tgp_plan::ModelHost mh;
-    if (!h->opt_modal || chunk_engine_requested(h) || h->is_dense || !h->lti || h->p != 1 || h->ordering != 0 || h->sde || h->d > tgp_modal::kAdjointMaxD || !modal_host_model(h, mh)) return TGP_OK;
+    if (!h->opt_modal || chunk_engine_requested(h) || h->is_dense || !h->lti || h->p != 1 || h->ordering != 0 || h->sde || h->d > tgp_powers::kAdjointMaxD || !modal_host_model(h, mh)) return TGP_OK;
     tgp_plan::FilterPlan fp;
-    tgp_modal::plan_filter(mh, h->T, fp);
+    tgp_powers::plan_filter(mh, h->T, fp);
     if (fp.why != tgp_plan::kOk) return TGP_OK;
-    const long long nwg = tgp_modal::adjoint_workgroups(fp, h->T);
+    const long long nwg = tgp_powers::adjoint_workgroups(fp, h->T);
     if (nwg < 1) return TGP_OK;
-    const int d = h->d, ns = tgp_modal::adjoint_sums(d);
+    const int d = h->d, ns = tgp_powers::adjoint_sums(d);
     const size_t dd = (size_t)d * d, nhs = (size_t)fp.nhs, nrec = tgp_adjoint::record_size(d);
     const size_t need = nhs + (size_t)nwg * ns + d + nrec + 16;
     TRY(ensure_pinned(h, need));
@@ -40,7 +40,7 @@ static int adjoint_lti_call(tgp_handle* h, const double* y, uint32_t flags, doub
     long long* sflag = reinterpret_cast<long long*>(h->sm_sync + 16);
     const long long seq = ++h->smooth_seq;
     double quad_head = 0.0;
-    tgp_modal::HeadHandover hh;
+    tgp_powers::HeadHandover hh;
     if (overlap) {
         hh.head_in = yh;
         hh.head_in_flag = sflag;
@@ -50,17 +50,17 @@ static int adjoint_lti_call(tgp_handle* h, const double* y, uint32_t flags, doub
     } else {
         HIPCHK(hipMemcpyAsync(yh, h->mv.y, nhs * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
-        tgp_modal::plan_filter_head(mh, fp, yh, nullptr, nullptr, mu_end, &quad_head);
+        tgp_powers::plan_filter_head(mh, fp, yh, nullptr, nullptr, mu_end, &quad_head);
     }
     {
         LaunchScope ls(h, "k_adjoint_one");
-        const int rc = tgp_modal::adjoint_lti(h->stream, fp, overlap ? nullptr : mu_end, h->mv.y, h->T, part, psi, overlap ? &hh : nullptr);
+        const int rc = tgp_powers::adjoint_lti(h->stream, fp, overlap ? nullptr : mu_end, h->mv.y, h->T, part, psi, overlap ? &hh : nullptr);
         if (rc != 0) return h->fail(TGP_EHIP, std::string("tgp_logpdf_adjoint: launch: ") + hipGetErrorString((hipError_t)rc));
     }
     bool handshake_ok = true;
     if (overlap) {
         handshake_ok = tgp_modal::await_host_flag(sflag, 2 * seq, h->stream);
-        if (handshake_ok) tgp_modal::plan_filter_head(mh, fp, yh, nullptr, nullptr, mu_end, &quad_head);
+        if (handshake_ok) tgp_powers::plan_filter_head(mh, fp, yh, nullptr, nullptr, mu_end, &quad_head);
         __atomic_store_n(sflag + 1, 2 * seq, __ATOMIC_RELEASE);      // (also when the hand-over failed: workgroup 0 never waits for what will not come)
     }
     tm.kernels_done();
@@ -173,17 +173,17 @@ int tgp_logpdf_adjoint(tgp_handle* h, const double* y, uint32_t flags, double* l
 }
 
 // _filter of an LTI model (Forward, scalar observations, one noise variance, no missing data, d <= 6): the head on the host from its few
-// observations, everything behind it in ONE kernel (tgp_modal::filter_lti; DESIGN 3.13).  *served = false: the caller runs the general engine.
+// observations, everything behind it in ONE kernel (tgp_powers::filter_lti; DESIGN 3.13).  *served = false: the caller runs the general engine.
 static int filter_lti_call(tgp_handle* h, const double* y, uint32_t flags, double* m_out, double* P_out, double* lml_out, bool* served) {
     *served = false;
     tgp_plan::ModelHost mh;
     if (!h->opt_modal || chunk_engine_requested(h) || h->is_dense || !h->lti || h->p != 1 || h->ordering != 0 || h->sde || h->d > tgp_plan::kRandMaxD || !modal_host_model(h, mh)) return TGP_OK;
     tgp_plan::FilterPlan fp;
-    tgp_modal::plan_filter(mh, h->T, fp);
+    tgp_powers::plan_filter(mh, h->T, fp);
     if (fp.why != tgp_plan::kOk) return TGP_OK;
     const int d = h->d;
     const size_t dd = (size_t)d * d, nhs = (size_t)fp.nhs;
-    const long long nwg = tgp_modal::filter_workgroups(fp, h->T);
+    const long long nwg = tgp_powers::filter_workgroups(fp, h->T);
     const size_t need = nhs * (1 + d + dd) + (size_t)nwg + 8;
     TRY(ensure_pinned(h, need));
     double *yh = h->flt_host, *mh_out = yh + nhs, *Ph_out = mh_out + nhs * d, *part = Ph_out + nhs * dd;
@@ -195,7 +195,7 @@ static int filter_lti_call(tgp_handle* h, const double* y, uint32_t flags, doubl
     HIPCHK(hipMemcpyAsync(yh, h->mv.y, nhs * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     double mu_end[tgp_plan::kRandMaxD], quad_head = 0.0;
-    tgp_modal::plan_filter_head(mh, fp, yh, m_out ? mh_out : nullptr, P_out ? Ph_out : nullptr, mu_end, &quad_head);
+    tgp_powers::plan_filter_head(mh, fp, yh, m_out ? mh_out : nullptr, P_out ? Ph_out : nullptr, mu_end, &quad_head);
     double *dm = nullptr, *dP = nullptr;
     TRY(stage_out(h, h->bo1, m_out, nm, odev, &dm));
     TRY(stage_out(h, h->bo2, P_out, nP, odev, &dP));
@@ -203,7 +203,7 @@ static int filter_lti_call(tgp_handle* h, const double* y, uint32_t flags, doubl
     if (dP) HIPCHK(hipMemcpyAsync(dP, Ph_out, nhs * dd * sizeof(double), hipMemcpyHostToDevice, h->stream));
     {
         LaunchScope ls(h, "k_filter_one");
-        const int rc = tgp_modal::filter_lti(h->stream, fp, mu_end, h->mv.y, h->T, dm, dP, part);
+        const int rc = tgp_powers::filter_lti(h->stream, fp, mu_end, h->mv.y, h->T, dm, dP, part);
         if (rc != 0) return h->fail(TGP_EHIP, std::string("tgp_filter: launch: ") + hipGetErrorString((hipError_t)rc));
     }
     tm.kernels_done();
@@ -221,7 +221,7 @@ static int filter_lti_call(tgp_handle* h, const double* y, uint32_t flags, doubl
 
 // logpdf + posterior marginals of an LTI model WITHOUT a modal form (Forward, scalar observations, one noise variance, no missing data,
 // d <= 8; a defective closed loop: two summands with one length scale, ...): the head on the host, everything behind it in ONE kernel on the
-// dense powers of the closed loop and of the settled reverse-time transition (tgp_modal::smooth_lti, DESIGN 3.15).  *served = false: the
+// dense powers of the closed loop and of the settled reverse-time transition (tgp_powers::smooth_lti, DESIGN 3.15).  *served = false: the
 // five-launch engine runs the call.
 // Every block shared but the emission offset: a GP with a mean function on a regular grid (lti_sde.jl:118-131).  The gains never see the offset, so the
 // stationary structure holds; the dense-powers kernel subtracts it per step (SmoothCall::hh_t).
@@ -246,7 +246,7 @@ static int smooth_lti_call(tgp_handle* h, const double* y, uint32_t flags, const
     if (!h->opt_modal || h->smooth_state < 0 || chunk_engine_requested(h) || h->is_dense || !(h->lti || (offs && !rnd)) || h->p != 1 || h->ordering != 0 || h->sde ||
         h->d > tgp_plan::kRandMaxD || (!offs && !modal_host_model(h, mh)) || (!rnd && (mean_out != nullptr) != (var_out != nullptr)) || (mean_out && !Rnew))
         return TGP_OK;
-    if (rnd && (h->d > tgp_modal::kSmoothRandMaxD || !mean_out || var_out || !rnd->eps_t || !rnd->eps_e || !rnd->eps_0)) return TGP_OK;
+    if (rnd && (h->d > tgp_powers::kSmoothRandMaxD || !mean_out || var_out || !rnd->eps_t || !rnd->eps_e || !rnd->eps_0)) return TGP_OK;
     const bool post = mean_out != nullptr;      // (false: logpdf only -- the forward half alone, no halo behind a span)
     constexpr size_t HM = tgp_plan::kHeadMax;
     const size_t nwg_max = (size_t)(h->T / 1024) + 2;
@@ -260,25 +260,25 @@ static int smooth_lti_call(tgp_handle* h, const double* y, uint32_t flags, const
     double *mu_end = h->sm_sync, *xi = h->sm_sync + 8;
     long long* sflag = reinterpret_cast<long long*>(h->sm_sync + 16);      // [0] head inputs on the host, [1] mu_end, [2] xi, [3] head outputs
     tgp_plan::SmoothPlan sp;
-    tgp_modal::plan_smooth(mh, h->T, sp, tvb, post);
+    tgp_powers::plan_smooth(mh, h->T, sp, tvb, post);
     if (sp.why != tgp_plan::kOk) {
         if (post) h->smooth_state = -1;      // (a function of the model and T alone: the next call need not ask again)
         return TGP_OK;
     }
     const tgp_plan::FilterPlan& fp = sp.fp;
     const size_t nhs = (size_t)fp.nhs;
-    const long long nwg = tgp_modal::smooth_workgroups(sp, h->T, post);
+    const long long nwg = tgp_powers::smooth_workgroups(sp, h->T, post);
     if (nwg < 1 || (size_t)nwg > nwg_max) return TGP_OK;
     const bool idev = (flags & TGP_IN_DEVICE) != 0, odev = (flags & TGP_OUT_DEVICE) != 0, rshared = (flags & TGP_SHARED_R) != 0;
     const size_t nT = (size_t)h->T * sizeof(double);
-    // The head BESIDE the kernel (tgp_modal.hpp SmoothCall): the launch goes first; workgroup 0 hands the head's inputs to the host through
+    // The head BESIDE the kernel (tgp_powers.hpp SmoothCall): the launch goes first; workgroup 0 hands the head's inputs to the host through
     // pinned memory, the host answers with the head's end state, runs the head backwards once workgroup 0 has raised xi, and the last workgroup
     // writes the head's outputs: one launch, one synchronisation, no copy on any stream in between.  With synchronous launches: the same
     // steps one after the other, copies on the handle's stream.
     const bool overlap = tgp_modal::overlap_allowed();
     const long long seq = ++h->smooth_seq;
-    double rU[tgp_modal::kSmoothRandMaxD * tgp_modal::kSmoothRandMaxD], rv0[tgp_modal::kSmoothRandMaxD], rs0 = 0.0;
-    if (rnd && !tgp_modal::plan_smooth_rand_factors(sp, rnd->eps_0, rU, rv0, &rs0)) return TGP_OK;      // (a noise factor not positive definite: the evaluated route gives the verdict)
+    double rU[tgp_powers::kSmoothRandMaxD * tgp_powers::kSmoothRandMaxD], rv0[tgp_powers::kSmoothRandMaxD], rs0 = 0.0;
+    if (rnd && !tgp_powers::plan_smooth_rand_factors(sp, rnd->eps_0, rU, rv0, &rs0)) return TGP_OK;      // (a noise factor not positive definite: the evaluated route gives the verdict)
     CallTimer tm(h, /*clear=*/false);
     const void *pR = nullptr, *pet = nullptr, *pee = nullptr;
     if (post) TRY(stage_in(h, h->bRnew, Rnew, rshared ? sizeof(double) : nT, idev, &pR));
@@ -296,7 +296,7 @@ static int smooth_lti_call(tgp_handle* h, const double* y, uint32_t flags, const
     const double *yhead = hand ? hin : y, *rnhead = hand ? hin + nhs : Rnew;
     const double* hhhead = offs ? hin + 10 * nhs : nullptr;
     const double *eehead = rnd ? (hand ? hin + 2 * nhs : rnd->eps_e) : nullptr, *ethead = rnd ? (hand ? hin + 3 * nhs : rnd->eps_t) : nullptr;
-    tgp_modal::SmoothCall c;
+    tgp_powers::SmoothCall c;
     c.T = h->T;
     c.y = h->mv.y;
     c.Rnew = static_cast<const double*>(pR);
@@ -338,11 +338,11 @@ static int smooth_lti_call(tgp_handle* h, const double* y, uint32_t flags, const
             }
             HIPCHK(hipStreamSynchronize(h->stream));
         }
-        tgp_modal::plan_smooth_head_forward(mh, sp, yhead, mu_end, &quad_head, hhhead);
+        tgp_powers::plan_smooth_head_forward(mh, sp, yhead, mu_end, &quad_head, hhhead);
     }
     {
         LaunchScope ls(h, rnd ? "k_smooth_one<rand>" : (post ? "k_smooth_one<posterior>" : "k_smooth_one<logpdf>"));
-        const int rc = tgp_modal::smooth_lti(h->stream, sp, overlap ? nullptr : mu_end, c);
+        const int rc = tgp_powers::smooth_lti(h->stream, sp, overlap ? nullptr : mu_end, c);
         if (rc != 0) return h->fail(TGP_EHIP, std::string("tgp_posterior_marginals: launch: ") + hipGetErrorString((hipError_t)rc));
     }
     struct FlagGuard {      // (whatever path leaves from here on: no workgroup is left waiting for the host)
@@ -359,17 +359,17 @@ static int smooth_lti_call(tgp_handle* h, const double* y, uint32_t flags, const
     if (overlap) {
         if (hand) handshake_ok = await(sflag);
         if (handshake_ok) {
-            tgp_modal::plan_smooth_head_forward(mh, sp, yhead, mu_end, &quad_head, hhhead);
+            tgp_powers::plan_smooth_head_forward(mh, sp, yhead, mu_end, &quad_head, hhhead);
             __atomic_store_n(sflag + 1, 2 * seq, __ATOMIC_RELEASE);
         }
     }
-    const bool tables_ok = !post || tgp_modal::plan_smooth_head_tables(mh, sp);      // (beside the kernel)
+    const bool tables_ok = !post || tgp_powers::plan_smooth_head_tables(mh, sp);      // (beside the kernel)
     auto head_back = [&]() {
         if (rnd) {
-            tgp_modal::plan_smooth_head_backward_rand(mh, sp, yhead, xi, eehead, ethead, rnhead, !rshared, hout);
+            tgp_powers::plan_smooth_head_backward_rand(mh, sp, yhead, xi, eehead, ethead, rnhead, !rshared, hout);
             return;
         }
-        tgp_modal::plan_smooth_head_backward(mh, sp, yhead, xi, hout, hout + nhs);
+        tgp_powers::plan_smooth_head_backward(mh, sp, yhead, xi, hout, hout + nhs);
         for (size_t t = 0; t < nhs; ++t) hout[nhs + t] += rnhead[rshared ? 0 : t];
     };
     if (overlap && post && tables_ok && handshake_ok) {      // workgroup 0 is among the first to finish: its xi arrives long before the grid is through

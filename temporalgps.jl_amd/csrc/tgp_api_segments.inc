@@ -155,7 +155,7 @@ int tgp_steady_plan(int d, const double* A, const double* a, const double* Q, co
     return TGP_OK;
 }
 
-// Host-only (no GPU needed): the FILTER plan (tgp_plan::FilterPlan through tgp_modal::plan_filter) that k_adjoint_one, k_filter_one and the dense-powers
+// Host-only (no GPU needed): the FILTER plan (tgp_plan::FilterPlan through tgp_powers::plan_filter) that k_adjoint_one, k_filter_one and the dense-powers
 // smoother are laid out on -- head length and halo decide where their spans, tiles and workgroups begin and end (tests place their lengths by it).
 int tgp_filter_plan(int d, const double* A, const double* a, const double* Q, const double* H, const double* hh, const double* R, const double* x0m,
                     const double* x0P, int64_t T, int32_t* info) {
@@ -164,14 +164,14 @@ int tgp_filter_plan(int d, const double* A, const double* a, const double* Q, co
     mh.d = d;
     mh.A = A; mh.a = a; mh.Q = Q; mh.H = H; mh.hh = hh; mh.R = R; mh.x0m = x0m; mh.x0P = x0P;
     tgp_plan::FilterPlan fp;
-    tgp_modal::plan_filter(mh, T, fp);
+    tgp_powers::plan_filter(mh, T, fp);
     info[0] = fp.why; info[1] = fp.n0; info[2] = fp.nhs; info[3] = fp.halo;
     return TGP_OK;
 }
 
-// Host-only (no GPU needed): the plan of the dense-powers smoother (tgp_plan::SmoothPlan through tgp_modal::plan_smooth, the very call smooth_lti_call
+// Host-only (no GPU needed): the plan of the dense-powers smoother (tgp_plan::SmoothPlan through tgp_powers::plan_smooth, the very call smooth_lti_call
 // makes) -- k_smooth_one<logpdf> with want_posterior == 0, k_smooth_one<posterior> and k_smooth_one<rand> otherwise.  span and workgroups are
-// tgp_modal::smooth_span / smooth_workgroups; both stay 0 where the plan stopped before its halo was known, workgroups also where it declined.
+// tgp_powers::smooth_span / smooth_workgroups; both stay 0 where the plan stopped before its halo was known, workgroups also where it declined.
 int tgp_smooth_plan(int d, const double* A, const double* a, const double* Q, const double* H, const double* hh, const double* R, const double* x0m,
                     const double* x0P, int64_t T, int want_posterior, int32_t* info) {
     if (d < 1 || d > tgp_plan::kRandMaxD || !A || !a || !Q || !H || !hh || !R || !x0m || !x0P || T <= 0 || !info) return TGP_EINVAL;
@@ -182,15 +182,15 @@ int tgp_smooth_plan(int d, const double* A, const double* a, const double* Q, co
     static thread_local double tvb[tgp_plan::kTailMax];
     const bool post = want_posterior != 0;
     sp = tgp_plan::SmoothPlan{};
-    tgp_modal::plan_smooth(mh, T, sp, tvb, post);
+    tgp_powers::plan_smooth(mh, T, sp, tvb, post);
     info[0] = sp.why; info[1] = sp.fp.n0; info[2] = sp.fp.nhs; info[3] = sp.fp.halo; info[4] = sp.halo; info[5] = sp.n1;
-    info[6] = sp.halo > 0 ? (int32_t)tgp_modal::smooth_span(sp, post) : 0;
-    info[7] = sp.why == tgp_plan::kOk ? (int32_t)tgp_modal::smooth_workgroups(sp, T, post) : 0;
+    info[6] = sp.halo > 0 ? (int32_t)tgp_powers::smooth_span(sp, post) : 0;
+    info[7] = sp.why == tgp_plan::kOk ? (int32_t)tgp_powers::smooth_workgroups(sp, T, post) : 0;
     return TGP_OK;
 }
 
-// Host-only (no GPU needed): the plan k_rand_one is launched on (tgp_plan::RandPlan through tgp_modal::plan_rand: a function of the model alone; tgp_rand
-// takes the path when why == 0 and T >= 2).  span = tgp_modal::rand_span, workgroups = ceil(T / span): there is no head, the first workgroup starts at step 0.
+// Host-only (no GPU needed): the plan k_rand_one is launched on (tgp_plan::RandPlan through tgp_powers::plan_rand: a function of the model alone; tgp_rand
+// takes the path when why == 0 and T >= 2).  span = tgp_powers::rand_span, workgroups = ceil(T / span): there is no head, the first workgroup starts at step 0.
 int tgp_rand_plan(int d, const double* A, const double* a, const double* Q, const double* H, const double* hh, const double* R, const double* x0m,
                   const double* x0P, int64_t T, int32_t* info) {
     if (d < 1 || d > tgp_plan::kRandMaxD || !A || !a || !Q || !H || !hh || !R || !x0m || !x0P || T <= 0 || !info) return TGP_EINVAL;
@@ -199,11 +199,11 @@ int tgp_rand_plan(int d, const double* A, const double* a, const double* Q, cons
     mh.A = A; mh.a = a; mh.Q = Q; mh.H = H; mh.hh = hh; mh.R = R; mh.x0m = x0m; mh.x0P = x0P;
     static thread_local tgp_plan::RandPlan rp;
     rp = tgp_plan::RandPlan{};
-    tgp_modal::plan_rand(mh, rp);
+    tgp_powers::plan_rand(mh, rp);
     const bool ok = rp.why == tgp_plan::kOk;
     info[0] = rp.why; info[1] = rp.halo;
-    info[2] = ok ? (int32_t)tgp_modal::rand_span(rp) : 0;
-    info[3] = ok ? (int32_t)tgp_modal::rand_workgroups(rp, T) : 0;
+    info[2] = ok ? (int32_t)tgp_powers::rand_span(rp) : 0;
+    info[3] = ok ? (int32_t)tgp_powers::rand_workgroups(rp, T) : 0;
     return TGP_OK;
 }
 

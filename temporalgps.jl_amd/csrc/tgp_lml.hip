@@ -1,6 +1,7 @@
 // Streaming logpdf kernel of the stationary-gain engine (round 6) -- see tgp_lml.hpp.  gfx950 only (wave64, DPP scans, 160 KB of LDS per CU,
 // uniform coefficients through the kernel-argument segment).
 #include "tgp_lml.hpp"
+#include "tgp_lane.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -9,8 +10,6 @@
 namespace tgp_lml {
 
 namespace {
-
-typedef double v2d __attribute__((ext_vector_type(2)));
 
 // ---- kernel arguments: every coefficient is wave-uniform and reaches the lanes through scalar loads ---------------------------------
 template <int D, int N>
@@ -36,23 +35,6 @@ __device__ __forceinline__ constexpr int partner(int i) {
     return ((i ^ 1) < D) ? (i ^ 1) : i;
 }
 
-__device__ __forceinline__ void lds_sync() {      // one wave talking to itself through LDS (DS operations of a wave execute in order)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ double readlane_d(double x, int l) {      // l wave-uniform
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), l), hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
-    return __hiloint2double(hi, lo);
-}
-// DPP moves of a double (two v_mov_dpp; lanes without a source and rows outside the mask read zero).  gfx9 controls: row_shr:n 0x110 + n,
-// wave_shr:1 0x138, row_bcast:15 0x142, row_bcast:31 0x143
-template <int CTRL, int ROWMASK = 0xF>
-__device__ __forceinline__ double dpp_mov(double x) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, ROWMASK, 0xF, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, ROWMASK, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
 __device__ __forceinline__ double wave_sum(double x) {      // the sum over the wave, in every lane's SGPR copy (lane 63 holds it)
     x += dpp_mov<0x111>(x);
     x += dpp_mov<0x112>(x);

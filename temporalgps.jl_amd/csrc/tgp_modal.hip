@@ -3,6 +3,7 @@
 // whole-line output stores, uniform coefficients through the kernel-argument segment).
 #include "tgp_modal.hpp"
 #include "tgp_alloc.hpp"
+#include "tgp_lane.hpp"
 #include "tgp_lml.hpp"
 #include "tgp_post.hpp"
 
@@ -22,7 +23,6 @@ using tgp_plan::Modal;
 
 constexpr int kWJ = 8;      // rows of the WJ / WG tables (a lane of sixteen steps applies them in two halves)
 constexpr double kLog2Pi = 1.8378770664093454835606594728112;
-typedef double v2d __attribute__((ext_vector_type(2)));
 
 // ---- the packed tables of a call (doubles): [0] n1, then the fields at these offsets.  Per-step tables have n0 + 1 rows (row n0: the
 // stationary step; the head's steps behind n0 read that row).
@@ -79,33 +79,6 @@ template <int D>
 __device__ __forceinline__ void bmul(const double* __restrict__ pr, const double* __restrict__ pi, const double (&x)[D], double (&out)[D]) {
 #pragma unroll
     for (int i = 0; i < D; ++i) out[i] = fma(pr[i], x[i], pi[i] * x[partner<D>(i)]);
-}
-
-__device__ __forceinline__ void lds_sync() {      // one wave talking to itself through LDS (DS operations of a wave execute in order)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// The tables half of the host plan (per-step gains of the head, tail variances) may still be in the making when the kernel starts: the host
-// writes the packed tables into pinned memory and then the flag 2 seq (+ 1 if that half declined: the call is then re-run elsewhere and
-// whatever this kernel writes is discarded).  Workgroup 0 pulls them into device memory, all its waves at once (one PCIe round trip with
-// every load in flight; a DMA copy of the same bytes reaches the device ~20 us after the API call)
-// The wait is BOUNDED (round-4 advice): a host thread that dies between the launch and the flag, or a tool that makes the launch synchronous,
-// would otherwise leave the queue spinning for ever.  After kWaitTicks of the 100 MHz clock (two seconds: the host half takes microseconds)
-// the kernel goes on with whatever the table memory holds -- finite garbage at worst, every index comes from the arguments -- and poisons
-// its share of the sum of squares (`poison`, when given), so that the call's result is NaN and is discarded.
-constexpr long long kWaitTicks = 200000000ll;
-__device__ __noinline__ void wait_tables(const long long* flagc, long long seq, double* poison = nullptr) {
-    long long* flag = const_cast<long long*>(flagc);
-    const long long t0 = (long long)wall_clock64();
-    while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < 2 * seq) {
-        __builtin_amdgcn_s_sleep(16);
-        if ((long long)wall_clock64() - t0 > kWaitTicks) {
-            if (poison != nullptr) *poison = __builtin_nan("");
-            return;
-        }
-    }
 }
 
 template <int SUB, int D>
@@ -188,31 +161,7 @@ __device__ __forceinline__ void flush_row(double* __restrict__ p, long long half
 // ---- the head: steps [0, nhs) with gains of their own, sequentially, by ONE wave.  Nothing in the dependent chain of a step waits for memory:
 // the lanes fetch a block's per-step data ahead (lane l the data of step l of the block; the tables are read in place from pinned host memory, so a
 // fetch costs a PCIe round trip -- it overlaps the block in work) and a step picks its values out of the lanes' registers with v_readlane.
-__device__ __forceinline__ double readlane_d(double x, int l) {      // l wave-uniform
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), l), hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
-    return __hiloint2double(hi, lo);
-}
 
-// Data-parallel-primitive moves of a double (two 32-bit v_mov_dpp: no LDS round trip as ds_bpermute has).  Lanes without a source, and the
-// rows the mask leaves out, read zero.  gfx9 controls: row_shl:n 0x100 + n (lane l reads l + n of its row of 16), row_shr:n 0x110 + n
-// (reads l - n), wave_shl:1 0x130 / wave_shr:1 0x138 (the same across the whole wave), row_bcast:15 0x142 (lane 15 of a row to the next row),
-// row_bcast:31 0x143 (lane 31 to rows 2, 3), row_newbcast:n 0x150 + n (lane n of a row to its own row)
-template <int CTRL, int ROWMASK = 0xF>
-__device__ __forceinline__ double dpp_mov(double x) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, ROWMASK, 0xF, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, ROWMASK, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-// the sum over the wave, in lane 63 (rows by row_shr adds, then row_bcast:15 / :31 across them)
-__device__ __forceinline__ double wave_sum_to_lane63(double x) {
-    x += dpp_mov<0x111>(x);
-    x += dpp_mov<0x112>(x);
-    x += dpp_mov<0x114>(x);
-    x += dpp_mov<0x118>(x);
-    x += dpp_mov<0x142, 0xA>(x);
-    x += dpp_mov<0x143, 0xC>(x);
-    return x;
-}
 // one level of the in-row scans: z += (pr, pi) (*) z shifted by OFF lanes inside the row of 16 (DIR 0: from below, 1: from above)
 // (level K: OFF = 2^K lanes, the power M^(SUB 2^K) of the kernel arguments -- read member by member: a pointer into the by-value argument
 //  struct would make the compiler keep a copy of it in scratch memory)
@@ -1296,36 +1245,10 @@ void choose_geometry(int d, int halo, int* nw, int* sub) {
 }
 
 // This translation unit's host code is compiled for AVX2 + FMA (Makefile: the plan's small matrix products vectorise 4-wide -- an 8 x 8
-// product 36 ns instead of 150); a host without them gets the five-launch engine.
-static bool host_cpu_ok() {
+// product 36 ns instead of 150); a host without them gets the five-launch engine.  (tgp_powers.hip, built with the same flags, asks here too.)
+bool host_cpu_ok() {
     static const bool ok = __builtin_cpu_supports("avx2") && __builtin_cpu_supports("fma");
     return ok;
-}
-
-// The host plans other translation units need (tgp_api.hip: the filter / posterior / rand one-launch paths).  Defined HERE and only here: this
-// object's host code is built with -mavx2 -mfma, and the inline functions of tgp_steady_plan.hpp instantiated in a second object built with
-// other flags would be two definitions of one entity -- the linker keeps either (round-4 advice).  All behind the run-time CPU check: a
-// host without AVX2 gets a plan that declines (the older engines serve the call).
-void plan_filter(const tgp_plan::ModelHost& m, long long T, tgp_plan::FilterPlan& fp) {
-    if (!host_cpu_ok()) {
-        fp.why = tgp_plan::kEigFail;
-        return;
-    }
-    tgp_plan::build_filter_any(m, T, fp);
-}
-void plan_filter_head(const tgp_plan::ModelHost& m, const tgp_plan::FilterPlan& fp, const double* y, double* mout, double* Pout, double* mu_end, double* quad) {
-    tgp_plan::filter_head_any(m, fp, y, mout, Pout, mu_end, quad);      // (only ever called with a plan plan_filter accepted)
-}
-bool plan_posterior_head(const tgp_plan::ModelHost& m, const tgp_plan::FilterPlan& fp, const double* y, double* Gh, double* gh, double* Lh, double* Gss,
-                         double* Lss, double* mu_end, double* quad) {
-    return tgp_plan::posterior_head_any(m, fp, y, Gh, gh, Lh, Gss, Lss, mu_end, quad);
-}
-void plan_rand(const tgp_plan::ModelHost& m, tgp_plan::RandPlan& rp) {
-    if (!host_cpu_ok()) {
-        rp.why = tgp_plan::kEigFail;
-        return;
-    }
-    tgp_plan::build_rand_any(m, rp);
 }
 
 tgp_plan::Info plan_only(const tgp_plan::ModelHost& m, long long T, tgp_plan::Modal& md, tgp_plan::HeadTables& tab) {
@@ -1589,10 +1512,6 @@ bool plan(Engine* e, const tgp_plan::ModelHost& m, long long T, bool logpdf_only
     return true;
 }
 
-// Behind the launch: the tables half of the plan, if it was deferred.  false: it declined (the kernel has been released all the same -- whatever
-// it writes is to be discarded, the caller re-runs the call elsewhere after synchronising).
-namespace {
-}  // namespace
 // The host's side of a hand-over: spins on a flag in pinned memory the kernel raises.  Not bounded by the clock -- the kernel may not even
 // have started (a stream with work of the caller's in front of it) -- but by the stream: once it has drained (hipStreamQuery, every few
 // thousand spins) the kernel is through, and the flag is there or will never be (the kernel's own waits give up after two seconds and
@@ -1614,6 +1533,8 @@ void raise_flag(long long* f, long long v) {
 }
 }  // namespace
 
+// Behind the launch: the tables half of the plan, if it was deferred.  false: it declined (the kernel has been released all the same -- whatever
+// it writes is to be discarded, the caller re-runs the call elsewhere after synchronising).
 bool complete(Engine* e, long long T) {
     if (e->began && e->lml) {
         // the head's forward recursion, as soon as the kernel has handed its observations over (or the stream has drained)
@@ -1852,1719 +1773,6 @@ double finish(const Engine* e, long long T) {
     return -0.5 * ((double)T * kLog2Pi + logdet + quad);
 }
 
-// =================================================================================================================================
-// rand of an LTI model (lgssm.jl:65-91, the draws supplied): x_t = A x_{t-1} + a + Lq eps_t,  y_t = h' x_t + hh + sqrt(R) eta_t.
-// The same one-launch structure as k_steady_one, forwards only and on DENSE powers (the open-loop transition of a Matern-3/2 / -5/2 block is
-// a Jordan block: no modal form).  Workgroup g owns the outputs [g C, (g + 1) C), C = 8 tiles of 512 steps minus the halo; its tiles start
-// `halo` steps earlier from a zero state (g = 0: at step 0 from the drawn x0); a lane runs its 8 steps from zero, the lanes' end states are
-// scanned (rows of 16 by DPP moves with A^(8 2^k), across the rows through a per-lane table of A^(8 e) in LDS), the tiles are chained over
-// the <= 3 tiles before them, and the lane's start state reaches its 8 outputs through the rows h' A^(j+1).  Reads eps_t (8 d B/step) and
-// eps_e once, writes y once.
-// =================================================================================================================================
-namespace {
-template <int D>
-struct RArgs {
-    double A[D][D], a[D], Lq[D][D], h[D], hh, sR;
-    double P[6][D][D];       // A^(8 2^k)
-    double PT[2][D][D];      // A^512, A^1024
-    double WJ[kWJ][D];       // h' A^(j+1)
-    double x0[D];
-    long long T, C, nwg;
-    int halo;
-    const double *eps_t, *eps_e;
-    double* y;
-};
-
-// y <- M x (dense, M from the kernel arguments)
-#define TGP_MATVEC_ACC(M, X, Y)                                   \
-    _Pragma("unroll") for (int i_ = 0; i_ < D; ++i_) {            \
-        double v_ = Y[i_];                                        \
-        _Pragma("unroll") for (int k_ = 0; k_ < D; ++k_) v_ = fma(M[i_][k_], X[k_], v_); \
-        Y[i_] = v_;                                               \
-    }
-
-template <int D, int NW>
-__global__ __launch_bounds__(NW * 64, (D <= 4 ? 4 : 2)) void k_rand_one(const RArgs<D> by_value) {
-    (void)by_value;
-    const RArgs<D>& ka = *(const RArgs<D>*)__builtin_amdgcn_kernarg_segment_ptr();      // (read in place: see k_steady_one)
-    constexpr int SUB = kWJ, TILE = 64 * SUB;
-    __shared__ double sF[NW][D];
-    __shared__ double sPw[D][D][64];      // A^(8 e), e = 0 .. 63: entry [i][k][e]
-    constexpr int LV = SUB * D / 2;       // 16-byte pieces of draws per lane
-    __shared__ v2d sT[NW][16 * (LV + 1)];      // a quarter of a tile's draws on their way from memory order to the lanes (one spare piece per lane:
-                                               // the 16 reading lanes then start in 16 different groups of four banks)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long g;
-    {
-        const long long per = (ka.nwg + 7) / 8;      // consecutive workgroups (they share their halos' lines) on the same XCD
-        g = (long long)(blockIdx.x & 7) * per + (blockIdx.x >> 3);
-        if ((long long)(blockIdx.x >> 3) >= per || g >= ka.nwg) return;
-    }
-    const long long T = ka.T, c_lo = g * ka.C, c_hi = (c_lo + ka.C < T) ? c_lo + ka.C : T;
-    const bool first = g == 0;
-    const long long s0 = first ? 0 : c_lo - ka.halo;
-    const long long tile_t0 = s0 + (long long)wave * TILE, t0 = tile_t0 + (long long)lane * SUB;
-    const bool any_valid = tile_t0 < c_hi;      // (wave-uniform: a tile wholly behind the workgroup's range has nothing to do)
-    // ---- the per-lane power table: row i of A^(8 e) by the bits of e, rows shared out over the waves
-    {
-        const int uw = __builtin_amdgcn_readfirstlane(wave);
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            if (uw != i % NW) continue;      // (wave-uniform)
-            double row[D];
-#pragma unroll
-            for (int k = 0; k < D; ++k) row[k] = (k == i) ? 1.0 : 0.0;
-#pragma unroll
-            for (int b = 0; b < 6; ++b) {
-                double nr[D];
-#pragma unroll
-                for (int k = 0; k < D; ++k) {
-                    double v = 0.0;
-#pragma unroll
-                    for (int m = 0; m < D; ++m) v = fma(row[m], ka.P[b][m][k], v);
-                    nr[k] = v;
-                }
-                const bool bit = ((lane >> b) & 1) != 0;
-#pragma unroll
-                for (int k = 0; k < D; ++k) row[k] = bit ? nr[k] : row[k];
-            }
-#pragma unroll
-            for (int k = 0; k < D; ++k) sPw[i][k][lane] = row[k];
-        }
-    }
-    // ---- the lane's eight steps from a zero state
-    double y0[SUB], x[D];
-#pragma unroll
-    for (int i = 0; i < D; ++i) x[i] = 0.0;
-#pragma unroll
-    for (int j = 0; j < SUB; ++j) y0[j] = 0.0;
-    if (any_valid) {
-        const bool whole = t0 + SUB <= T && (reinterpret_cast<uintptr_t>(ka.eps_t) & 15) == 0 && (reinterpret_cast<uintptr_t>(ka.eps_e) & 15) == 0;
-        // a whole tile's draws are 64 SUB D consecutive doubles: fetched in memory order (every load instruction 1 KB of consecutive bytes;
-        // a lane fetching its own SUB D values, 16 bytes at a stride of 8 SUB D, keeps the address path busy four to eight times as long)
-        // and handed to their lanes through LDS, sixteen lanes' worth at a time
-        const bool tile_whole = tile_t0 + TILE <= T && (reinterpret_cast<uintptr_t>(ka.eps_t) & 15) == 0 && ((tile_t0 * D) & 1) == 0;      // (wave-uniform)
-        double evt[SUB * D];
-        if (tile_whole) {
-            const v2d* src = reinterpret_cast<const v2d*>(ka.eps_t + tile_t0 * D);
-            v2d ld[4][D];
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int i = 0; i < D; ++i) ld[r][i] = src[r * 16 * LV + i * 64 + lane];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-#pragma unroll
-                for (int i = 0; i < D; ++i) {
-                    const int idx = i * 64 + lane;
-                    sT[wave][idx + idx / LV] = ld[r][i];
-                }
-                lds_sync();
-                if ((lane >> 4) == r) {
-#pragma unroll
-                    for (int k = 0; k < LV; ++k) {
-                        const v2d w = sT[wave][(lane & 15) * (LV + 1) + k];
-                        evt[2 * k] = w.x;
-                        evt[2 * k + 1] = w.y;
-                    }
-                }
-                lds_sync();
-            }
-        }
-        double ee[SUB];
-        if (whole) {
-            const v2d* q = reinterpret_cast<const v2d*>(ka.eps_e + t0);
-#pragma unroll
-            for (int j = 0; j < SUB / 2; ++j) {
-                const v2d w = q[j];
-                ee[2 * j] = w.x;
-                ee[2 * j + 1] = w.y;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < SUB; ++j) ee[j] = t0 + j < T ? ka.eps_e[t0 + j] : 0.0;
-        }
-#pragma unroll
-        for (int j2 = 0; j2 < SUB; j2 += 2) {
-            // the draws of two steps: 2 d consecutive doubles (16-byte pieces where the series allows)
-            double ev[2 * D];
-            if (tile_whole) {
-#pragma unroll
-                for (int k = 0; k < 2 * D; ++k) ev[k] = evt[j2 * D + k];
-            } else if (whole) {
-                const v2d* q = reinterpret_cast<const v2d*>(ka.eps_t + (t0 + j2) * D);
-#pragma unroll
-                for (int k = 0; k < D; ++k) {
-                    const v2d w = q[k];
-                    ev[2 * k] = w.x;
-                    ev[2 * k + 1] = w.y;
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < 2 * D; ++k) ev[k] = (t0 + j2) * D + k < T * D ? ka.eps_t[(t0 + j2) * D + k] : 0.0;
-            }
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj) {
-                const int j = j2 + jj;
-                double nx[D];
-#pragma unroll
-                for (int i = 0; i < D; ++i) {
-                    double v = ka.a[i];
-#pragma unroll
-                    for (int k = 0; k <= i; ++k) v = fma(ka.Lq[i][k], ev[jj * D + k], v);      // (lower factor)
-                    nx[i] = v;
-                }
-                TGP_MATVEC_ACC(ka.A, x, nx);
-                double yy = fma(ka.sR, ee[j], ka.hh);
-#pragma unroll
-                for (int i = 0; i < D; ++i) {
-                    x[i] = nx[i];
-                    yy = fma(ka.h[i], nx[i], yy);
-                }
-                y0[j] = yy;
-            }
-        }
-    }
-    __syncthreads();      // (the table)
-    // ---- inclusive scan of the lanes' end states: x_l <- sum_{m <= l} A^(8 (l - m)) x_m
-    double st[D];
-    if (any_valid) {
-#define TGP_RAND_LEVEL(K)                                                                  \
-    do {                                                                                   \
-        double g_[D], n_[D];                                                               \
-        _Pragma("unroll") for (int i = 0; i < D; ++i) {                                    \
-            g_[i] = dpp_mov<0x110 + (1 << (K))>(x[i]);                                     \
-            n_[i] = x[i];                                                                  \
-        }                                                                                  \
-        TGP_MATVEC_ACC(ka.P[K], g_, n_);                                                   \
-        _Pragma("unroll") for (int i = 0; i < D; ++i) x[i] = n_[i];                        \
-    } while (0)
-        TGP_RAND_LEVEL(0);
-        TGP_RAND_LEVEL(1);
-        TGP_RAND_LEVEL(2);
-        TGP_RAND_LEVEL(3);
-#undef TGP_RAND_LEVEL
-        {
-            const int e1 = (lane & 15) + 1, e2 = lane >= 32 ? lane - 31 : 0;
-            double gv[D], nv[D];
-#pragma unroll
-            for (int i = 0; i < D; ++i) {
-                gv[i] = dpp_mov<0x142, 0xA>(x[i]);
-                nv[i] = x[i];
-            }
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int k = 0; k < D; ++k) nv[i] = fma(sPw[i][k][e1], gv[k], nv[i]);
-#pragma unroll
-            for (int i = 0; i < D; ++i) {
-                x[i] = nv[i];
-                gv[i] = dpp_mov<0x143, 0xC>(nv[i]);
-            }
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int k = 0; k < D; ++k) nv[i] = fma(sPw[i][k][e2], gv[k], nv[i]);
-#pragma unroll
-            for (int i = 0; i < D; ++i) x[i] = nv[i];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < D; ++i) st[i] = dpp_mov<0x138>(x[i]);      // the state in front of the lane's steps (lane 0: zero)
-    if (lane == 63) {
-#pragma unroll
-        for (int i = 0; i < D; ++i) sF[wave][i] = any_valid ? x[i] : 0.0;
-    }
-    __syncthreads();
-    if (!any_valid) return;
-    // ---- the tile's start state from the <= 3 tiles before it (workgroup 0: the drawn x0 sits at position -1), then the outputs
-    double zin[D];
-#pragma unroll
-    for (int i = 0; i < D; ++i) zin[i] = 0.0;
-#pragma unroll
-    for (int k = 1; k <= 3; ++k) {
-        const int src = wave - k;
-        if (src < -1 || (src == -1 && !first)) continue;      // (wave-uniform)
-        double xs[D];
-#pragma unroll
-        for (int i = 0; i < D; ++i) xs[i] = src >= 0 ? sF[src][i] : ka.x0[i];
-        if (k == 1) {
-#pragma unroll
-            for (int i = 0; i < D; ++i) zin[i] += xs[i];
-        } else {
-            TGP_MATVEC_ACC(ka.PT[k - 2], xs, zin);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < D; ++i)
-#pragma unroll
-        for (int k = 0; k < D; ++k) st[i] = fma(sPw[i][k][lane], zin[k], st[i]);
-    const bool aligned = (reinterpret_cast<uintptr_t>(ka.y) & 15) == 0;
-#pragma unroll
-    for (int j = 0; j < SUB; j += 2) {
-        double m0 = y0[j], m1 = y0[j + 1];
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            m0 = fma(ka.WJ[j][i], st[i], m0);
-            m1 = fma(ka.WJ[j + 1][i], st[i], m1);
-        }
-        const long long t = t0 + j;
-        if (t >= c_lo && t + 1 < c_hi && aligned) {
-            v2d w;
-            w.x = m0;
-            w.y = m1;
-            *reinterpret_cast<v2d*>(ka.y + t) = w;
-        } else {
-            if (t >= c_lo && t < c_hi) ka.y[t] = m0;
-            if (t + 1 >= c_lo && t + 1 < c_hi) ka.y[t + 1] = m1;
-        }
-    }
-}
-#undef TGP_MATVEC_ACC
-
-template <int D>
-int launch_rand(hipStream_t st, const tgp_plan::RandPlan& rp, const double* x0, const double* eps_t, const double* eps_e, long long T, double* y) {
-    constexpr int NW = 8, M = tgp_plan::kRandMaxD;
-    RArgs<D> ka;
-    static_assert(sizeof(RArgs<D>) <= 8192, "the kernel-argument segment (12 KB launch on gfx950: scripts/micro/bigarg.hip)");
-    std::memset(&ka, 0, sizeof ka);
-    for (int i = 0; i < D; ++i) {
-        ka.a[i] = rp.a[i];
-        ka.h[i] = rp.h[i];
-        ka.x0[i] = x0[i];
-        for (int k = 0; k < D; ++k) {
-            ka.A[i][k] = rp.A[i * D + k];
-            ka.Lq[i][k] = rp.Lq[i * D + k];
-            for (int b = 0; b < 6; ++b) ka.P[b][i][k] = rp.P[b][i * D + k];
-            for (int b = 0; b < 2; ++b) ka.PT[b][i][k] = rp.PT[b][i * D + k];
-        }
-    }
-    (void)M;
-    for (int j = 0; j < kWJ; ++j)
-        for (int i = 0; i < D; ++i) ka.WJ[j][i] = rp.WJ[j][i];
-    ka.hh = rp.hh;
-    ka.sR = rp.sR;
-    ka.T = T;
-    ka.halo = rp.halo;
-    ka.C = (long long)NW * 64 * kWJ - rp.halo;
-    ka.nwg = (T + ka.C - 1) / ka.C;
-    ka.eps_t = eps_t;
-    ka.eps_e = eps_e;
-    ka.y = y;
-    const long long per = (ka.nwg + 7) / 8;
-    hipLaunchKernelGGL((k_rand_one<D, NW>), dim3((unsigned)(per * 8)), dim3(NW * 64), 0, st, ka);
-    return (int)hipGetLastError();
-}
-}  // namespace
-
-int rand_lti(hipStream_t stream, const tgp_plan::RandPlan& plan, const double* x0, const double* eps_t, const double* eps_e, long long T, double* y,
-             const char** kname) {
-    if (kname) *kname = "k_rand_one";
-    switch (plan.d) {
-        case 1: return launch_rand<1>(stream, plan, x0, eps_t, eps_e, T, y);
-        case 2: return launch_rand<2>(stream, plan, x0, eps_t, eps_e, T, y);
-        case 3: return launch_rand<3>(stream, plan, x0, eps_t, eps_e, T, y);
-        case 4: return launch_rand<4>(stream, plan, x0, eps_t, eps_e, T, y);
-        case 5: return launch_rand<5>(stream, plan, x0, eps_t, eps_e, T, y);
-        case 6: return launch_rand<6>(stream, plan, x0, eps_t, eps_e, T, y);
-        case 7: return launch_rand<7>(stream, plan, x0, eps_t, eps_e, T, y);
-        case 8: return launch_rand<8>(stream, plan, x0, eps_t, eps_e, T, y);
-    }
-    return (int)hipErrorInvalidValue;
-}
-
-long long rand_span(const tgp_plan::RandPlan& rp) { return 8LL * 64 * kWJ - rp.halo; }      // (launch_rand's ka.C)
-long long rand_workgroups(const tgp_plan::RandPlan& rp, long long T) {
-    const long long C = rand_span(rp);
-    return (T + C - 1) / C;
-}
-
-// =================================================================================================================================
-// _filter of an LTI model behind its head (lgssm.jl:171-187): mu' = Phi mu + a + (A K) u, r = u - h' mu, m_t = mu_t + K r_t, P_t = P_ss.
-// k_rand_one's structure on the dense powers of the closed loop Phi = A - (A K) h': a first sweep of a lane's 8 steps from a zero state gives
-// its end state, the scan and the tile chaining its true start state, a second sweep from there the outputs.  Workgroup 0 starts at nhs from
-// the head's end state (computed on the host).  Reads y once, writes 8 (d + d^2) bytes per step.
-// =================================================================================================================================
-namespace {
-template <int D>
-struct FArgs {
-    double Phi[D][D], a[D], kA[D], K[D], h[D], hh;
-    double P[6][D][D], PT[2][D][D];
-    double Pss[D * D];
-    double Gss[D * D], Lss[D * D];      // posterior(model, y): the settled reverse-time transition and its noise, COLUMN-major as they leave
-    double mu0[D];
-    long long T, C, nwg, nhs;
-    int halo;
-    const double* y;
-    double *m, *Pc, *part;
-    double *Gc, *gc, *Lc, *fin;      // (all four or none) G, L [T][D D], g [T][D]; fin [D]: the last filtered mean
-};
-
-template <int D, int NW>
-__global__ __launch_bounds__(NW * 64, (D <= 3 ? 4 : 2)) void k_filter_one(const FArgs<D> by_value) {      // (d = 4 at four waves per SIMD: 18 registers spilled)
-    (void)by_value;
-    const FArgs<D>& ka = *(const FArgs<D>*)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr int SUB = kWJ, TILE = 64 * SUB;
-    __shared__ double sF[NW][D], sAcc[NW];
-    __shared__ double sPw[D][D][64];      // Phi^(8 e), e = 0 .. 63
-    __shared__ double sP[3][D * D];       // the settled covariance, G, L (the fills below index them per lane)
-    constexpr int LV = SUB * D / 2;        // 16-byte pieces of means per lane
-    __shared__ v2d sT[NW][16 * (LV + 1)];      // a quarter of a tile's means (or g) on their way from the lanes to memory order
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long g;
-    {
-        const long long per = (ka.nwg + 7) / 8;
-        g = (long long)(blockIdx.x & 7) * per + (blockIdx.x >> 3);
-        if ((long long)(blockIdx.x >> 3) >= per || g >= ka.nwg) return;
-    }
-    if (threadIdx.x < D * D) {
-        sP[0][threadIdx.x] = ka.Pss[threadIdx.x];
-        sP[1][threadIdx.x] = ka.Gss[threadIdx.x];
-        sP[2][threadIdx.x] = ka.Lss[threadIdx.x];
-    }
-    const long long T = ka.T, c_lo = ka.nhs + g * ka.C, c_hi = (c_lo + ka.C < T) ? c_lo + ka.C : T;
-    const bool first = g == 0;
-    const long long s0 = first ? ka.nhs : c_lo - ka.halo;
-    const long long tile_t0 = s0 + (long long)wave * TILE, t0 = tile_t0 + (long long)lane * SUB;
-    const bool any_valid = tile_t0 < c_hi;
-    {
-        const int uw = __builtin_amdgcn_readfirstlane(wave);
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            if (uw != i % NW) continue;
-            double row[D];
-#pragma unroll
-            for (int k = 0; k < D; ++k) row[k] = (k == i) ? 1.0 : 0.0;
-#pragma unroll
-            for (int b = 0; b < 6; ++b) {
-                double nr[D];
-#pragma unroll
-                for (int k = 0; k < D; ++k) {
-                    double v = 0.0;
-#pragma unroll
-                    for (int m = 0; m < D; ++m) v = fma(row[m], ka.P[b][m][k], v);
-                    nr[k] = v;
-                }
-                const bool bit = ((lane >> b) & 1) != 0;
-#pragma unroll
-                for (int k = 0; k < D; ++k) row[k] = bit ? nr[k] : row[k];
-            }
-#pragma unroll
-            for (int k = 0; k < D; ++k) sPw[i][k][lane] = row[k];
-        }
-    }
-    // ---- first sweep: the lane's 8 steps from a zero state
-    double u[SUB], x[D];
-#pragma unroll
-    for (int i = 0; i < D; ++i) x[i] = 0.0;
-#pragma unroll
-    for (int j = 0; j < SUB; ++j) u[j] = 0.0;
-    if (any_valid) {
-        if (t0 + SUB <= T && (reinterpret_cast<uintptr_t>(ka.y) & 15) == 0) {
-            const v2d* q = reinterpret_cast<const v2d*>(ka.y + t0);
-#pragma unroll
-            for (int j = 0; j < SUB / 2; ++j) {
-                const v2d w = q[j];
-                u[2 * j] = w.x - ka.hh;
-                u[2 * j + 1] = w.y - ka.hh;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < SUB; ++j) u[j] = t0 + j < T ? ka.y[t0 + j] - ka.hh : 0.0;
-        }
-#pragma unroll
-        for (int j = 0; j < SUB; ++j) {
-            double nx[D];
-#pragma unroll
-            for (int i = 0; i < D; ++i) {
-                double v = fma(ka.kA[i], u[j], ka.a[i]);
-#pragma unroll
-                for (int k = 0; k < D; ++k) v = fma(ka.Phi[i][k], x[k], v);
-                nx[i] = v;
-            }
-#pragma unroll
-            for (int i = 0; i < D; ++i) x[i] = nx[i];
-        }
-    }
-    __syncthreads();
-    double st[D];
-    if (any_valid) {
-#define TGP_FILT_LEVEL(K)                                                                  \
-    do {                                                                                   \
-        double g_[D], n_[D];                                                               \
-        _Pragma("unroll") for (int i = 0; i < D; ++i) {                                    \
-            g_[i] = dpp_mov<0x110 + (1 << (K))>(x[i]);                                     \
-            n_[i] = x[i];                                                                  \
-        }                                                                                  \
-        _Pragma("unroll") for (int i = 0; i < D; ++i)                                      \
-            _Pragma("unroll") for (int k = 0; k < D; ++k) n_[i] = fma(ka.P[K][i][k], g_[k], n_[i]); \
-        _Pragma("unroll") for (int i = 0; i < D; ++i) x[i] = n_[i];                        \
-    } while (0)
-        TGP_FILT_LEVEL(0);
-        TGP_FILT_LEVEL(1);
-        TGP_FILT_LEVEL(2);
-        TGP_FILT_LEVEL(3);
-#undef TGP_FILT_LEVEL
-        const int e1 = (lane & 15) + 1, e2 = lane >= 32 ? lane - 31 : 0;
-        double gv[D], nv[D];
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            gv[i] = dpp_mov<0x142, 0xA>(x[i]);
-            nv[i] = x[i];
-        }
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int k = 0; k < D; ++k) nv[i] = fma(sPw[i][k][e1], gv[k], nv[i]);
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            x[i] = nv[i];
-            gv[i] = dpp_mov<0x143, 0xC>(nv[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int k = 0; k < D; ++k) nv[i] = fma(sPw[i][k][e2], gv[k], nv[i]);
-#pragma unroll
-        for (int i = 0; i < D; ++i) x[i] = nv[i];
-    }
-#pragma unroll
-    for (int i = 0; i < D; ++i) st[i] = dpp_mov<0x138>(x[i]);
-    if (lane == 63) {
-#pragma unroll
-        for (int i = 0; i < D; ++i) sF[wave][i] = any_valid ? x[i] : 0.0;
-    }
-    __syncthreads();
-    double acc = 0.0;
-    if (any_valid) {
-        double zin[D];
-#pragma unroll
-        for (int i = 0; i < D; ++i) zin[i] = 0.0;
-#pragma unroll
-        for (int k = 1; k <= 3; ++k) {
-            const int src = wave - k;
-            if (src < -1 || (src == -1 && !first)) continue;
-            double xs[D];
-#pragma unroll
-            for (int i = 0; i < D; ++i) xs[i] = src >= 0 ? sF[src][i] : ka.mu0[i];
-            if (k == 1) {
-#pragma unroll
-                for (int i = 0; i < D; ++i) zin[i] += xs[i];
-            } else {
-#pragma unroll
-                for (int i = 0; i < D; ++i)
-#pragma unroll
-                    for (int m = 0; m < D; ++m) zin[i] = fma(ka.PT[k - 2][i][m], xs[m], zin[i]);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int k = 0; k < D; ++k) st[i] = fma(sPw[i][k][lane], zin[k], st[i]);
-        // ---- second sweep from the true start state: innovations, filtered means
-        const bool whole = t0 >= c_lo && t0 + SUB <= c_hi;
-        const bool m_al = ka.m != nullptr && (reinterpret_cast<uintptr_t>(ka.m) & 15) == 0;
-        // a tile wholly inside the workgroup's range (and short of the series' last step): its 512 D means -- or the 512 D values of g, one step
-        // to the right -- are one run of consecutive doubles; they leave in memory order through LDS (below) instead of lane by lane
-        const bool run_whole = tile_t0 >= c_lo && tile_t0 + TILE <= c_hi && tile_t0 + TILE < T;      // (wave-uniform)
-        double* const run = !run_whole ? nullptr : (ka.gc != nullptr ? ka.gc + (tile_t0 + 1) * D : (ka.m != nullptr ? ka.m + tile_t0 * D : nullptr));
-        const bool want_g = ka.gc != nullptr;
-        double oall[SUB * D];
-#pragma unroll
-        for (int j2 = 0; j2 < SUB; j2 += 2) {
-            double mf[2 * D];
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj) {
-                const int j = j2 + jj;
-                double r = u[j];
-#pragma unroll
-                for (int k = 0; k < D; ++k) r = fma(-ka.h[k], st[k], r);
-                const long long t = t0 + j;
-                if (t >= c_lo && t < c_hi) acc = fma(r, r, acc);
-                double nx[D];
-#pragma unroll
-                for (int i = 0; i < D; ++i) {
-                    mf[jj * D + i] = fma(ka.K[i], r, st[i]);
-                    double v = fma(ka.kA[i], u[j], ka.a[i]);
-#pragma unroll
-                    for (int k = 0; k < D; ++k) v = fma(ka.Phi[i][k], st[k], v);
-                    nx[i] = v;
-                }
-#pragma unroll
-                for (int i = 0; i < D; ++i) st[i] = nx[i];
-                if (run != nullptr) {
-#pragma unroll
-                    for (int i = 0; i < D; ++i) {
-                        double v = mf[jj * D + i];
-                        if (want_g) {
-#pragma unroll
-                            for (int k = 0; k < D; ++k) v = fma(-ka.Gss[k * D + i], nx[k], v);
-                        }
-                        oall[j * D + i] = v;
-                    }
-                } else if (ka.gc != nullptr && t >= c_lo && t < c_hi) {
-                    // step t + 1 of the reverse-time model (lgssm.jl:215-221, :231-238): g = m_t - G mu_(t+1)
-                    if (t + 1 < T) {
-#pragma unroll
-                        for (int i = 0; i < D; ++i) {
-                            double v = mf[jj * D + i];
-#pragma unroll
-                            for (int k = 0; k < D; ++k) v = fma(-ka.Gss[k * D + i], nx[k], v);
-                            ka.gc[(t + 1) * D + i] = v;
-                        }
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < D; ++i) ka.fin[i] = mf[jj * D + i];
-                    }
-                }
-            }
-            if (ka.m != nullptr && run == nullptr) {
-                const long long t = t0 + j2;
-                if (whole && m_al) {      // (t D is even: 16-byte pieces)
-                    v2d* q = reinterpret_cast<v2d*>(ka.m + t * D);
-#pragma unroll
-                    for (int k = 0; k < D; ++k) {
-                        v2d w;
-                        w.x = mf[2 * k];
-                        w.y = mf[2 * k + 1];
-                        q[k] = w;
-                    }
-                } else {
-#pragma unroll
-                    for (int jj = 0; jj < 2; ++jj)
-                        if (t + jj >= c_lo && t + jj < c_hi)
-#pragma unroll
-                            for (int i = 0; i < D; ++i) ka.m[(t + jj) * D + i] = mf[jj * D + i];
-                }
-            }
-        }
-        if (run != nullptr) {
-            // sixteen lanes' values at a time: in at 16-byte pieces per lane (one spare piece per lane: no bank conflicts), out as doubles in
-            // memory order -- every store instruction 512 consecutive bytes (g sits D doubles off the tile's start: 8-byte granularity)
-            const double* sTd = reinterpret_cast<const double*>(&sT[wave][0]);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if ((lane >> 4) == r) {
-#pragma unroll
-                    for (int k = 0; k < LV; ++k) {
-                        v2d w;
-                        w.x = oall[2 * k];
-                        w.y = oall[2 * k + 1];
-                        sT[wave][(lane & 15) * (LV + 1) + k] = w;
-                    }
-                }
-                lds_sync();
-#pragma unroll
-                for (int i = 0; i < 2 * D; ++i) {
-                    const int e = i * 64 + lane;      // of the 16 lanes' 128 D doubles
-                    run[r * 128 * D + e] = sTd[e + 2 * (e / (SUB * D))];
-                }
-                lds_sync();
-            }
-        }
-        // the covariances: the settled one, for every step the workgroup owns -- a whole tile as one run of 512 D^2 doubles, every store
-        // instruction 1 KB of consecutive bytes (a lane writing its own 8 D^2 values, 16 bytes at a 64 D^2-byte stride: 40 % slower)
-        constexpr int DD = D * D;
-        const bool tile_whole = tile_t0 >= c_lo && tile_t0 + TILE <= c_hi;      // (wave-uniform)
-#pragma unroll
-        for (int which = 0; which < 3; ++which) {
-            double* dst = which == 0 ? ka.Pc : (which == 1 ? ka.Gc : ka.Lc);
-            if (dst == nullptr) continue;
-            if (tile_whole && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-                v2d* q = reinterpret_cast<v2d*>(dst + tile_t0 * DD);
-#pragma unroll 4
-                for (int k = 0; k < SUB * DD / 2; ++k) {
-                    const int e = k * 64 + lane;
-                    v2d w;
-                    w.x = sP[which][(2 * e) % DD];
-                    w.y = sP[which][(2 * e + 1) % DD];
-                    q[e] = w;
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < SUB; ++j)
-                    if (t0 + j >= c_lo && t0 + j < c_hi)
-#pragma unroll
-                        for (int e = 0; e < DD; ++e) dst[(t0 + j) * DD + e] = sP[which][e];
-            }
-        }
-    }
-    acc = wave_sum_to_lane63(acc);
-    if (lane == 63) sAcc[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tsum = 0.0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) tsum += sAcc[w];
-        ka.part[g] = tsum;
-    }
-}
-
-template <int D>
-int launch_filter(hipStream_t st, const tgp_plan::FilterPlan& fp, const double* mu0, const double* y, long long T, double* m, double* Pc, double* part,
-                  const PosteriorOut* po) {
-    constexpr int NW = 8;
-    FArgs<D> ka;
-    static_assert(sizeof(FArgs<D>) <= 8192, "the kernel-argument segment (12 KB launch on gfx950: scripts/micro/bigarg.hip)");
-    std::memset(&ka, 0, sizeof ka);
-    for (int i = 0; i < D; ++i) {
-        ka.a[i] = fp.a[i];
-        ka.kA[i] = fp.kA[i];
-        ka.K[i] = fp.K[i];
-        ka.h[i] = fp.h[i];
-        ka.mu0[i] = mu0[i];
-        for (int k = 0; k < D; ++k) {
-            ka.Phi[i][k] = fp.Phi[i * D + k];
-            ka.Pss[i * D + k] = fp.Pss[i * D + k];
-            if (po) {
-                ka.Gss[i * D + k] = po->Gss[i * D + k];
-                ka.Lss[i * D + k] = po->Lss[i * D + k];
-            }
-            for (int b = 0; b < 6; ++b) ka.P[b][i][k] = fp.P[b][i * D + k];
-            for (int b = 0; b < 2; ++b) ka.PT[b][i][k] = fp.PT[b][i * D + k];
-        }
-    }
-    ka.hh = fp.hh;
-    ka.T = T;
-    ka.nhs = fp.nhs;
-    ka.halo = fp.halo;
-    ka.C = (long long)NW * 64 * kWJ - fp.halo;
-    ka.nwg = (T - fp.nhs + ka.C - 1) / ka.C;
-    ka.y = y;
-    ka.m = m;
-    ka.Pc = Pc;
-    ka.part = part;
-    if (po) {
-        ka.Gc = po->G;
-        ka.gc = po->g;
-        ka.Lc = po->L;
-        ka.fin = po->fin;
-    }
-    const long long per = (ka.nwg + 7) / 8;
-    hipLaunchKernelGGL((k_filter_one<D, NW>), dim3((unsigned)(per * 8)), dim3(NW * 64), 0, st, ka);
-    return (int)hipGetLastError();
-}
-}  // namespace
-
-long long filter_workgroups(const tgp_plan::FilterPlan& fp, long long T) {
-    const long long C = 8LL * 64 * kWJ - fp.halo;
-    return (T - fp.nhs + C - 1) / C;
-}
-
-int filter_lti(hipStream_t stream, const tgp_plan::FilterPlan& fp, const double* mu_start, const double* y, long long T, double* m_out, double* P_out,
-               double* part, const PosteriorOut* po) {
-    switch (fp.d) {
-        case 1: return launch_filter<1>(stream, fp, mu_start, y, T, m_out, P_out, part, po);
-        case 2: return launch_filter<2>(stream, fp, mu_start, y, T, m_out, P_out, part, po);
-        case 3: return launch_filter<3>(stream, fp, mu_start, y, T, m_out, P_out, part, po);
-        case 4: return launch_filter<4>(stream, fp, mu_start, y, T, m_out, P_out, part, po);
-        case 5: return launch_filter<5>(stream, fp, mu_start, y, T, m_out, P_out, part, po);
-        case 6: return launch_filter<6>(stream, fp, mu_start, y, T, m_out, P_out, part, po);
-        case 7: return launch_filter<7>(stream, fp, mu_start, y, T, m_out, P_out, part, po);
-        case 8: return launch_filter<8>(stream, fp, mu_start, y, T, m_out, P_out, part, po);
-    }
-    return (int)hipErrorInvalidValue;
-}
-
-// =================================================================================================================================
-// The adjoint (gradient) pass of an LTI model behind its head, in one launch.  k_filter_one's forward half gives a lane
-// its true start state; a second forward sweep keeps mu_j and r_j of its 8 steps; the adjoint psi = Phi' psi + h r / S runs the same way
-// backwards (zero-start sweep, reverse scan by DPP moves on the TRANSPOSED powers -- the same table read the other way --, chaining over the
-// <= 3 tiles behind); the last sweep walks the 8 steps backwards with the true psi and accumulates the d^2 + 3 d + 2 sums.  Spans carry a
-// halo at both ends.
-// =================================================================================================================================
-namespace {
-template <int D>
-struct GArgs {
-    double Phi[D][D], a[D], kA[D], h[D], hh, iS;
-    double P[6][D][D], PT[2][D][D];
-    double mu0[D];
-    long long T, C, nwg, nhs;
-    int halo;
-    const double* y;
-    double *part, *psi_out;
-    // the head beside the kernel (SmoothCall in tgp_modal.hpp): workgroup 0 hands the head's observations over through pinned memory and waits
-    // (bounded) for the predicted mean of step nhs; nullptr: mu0 above by value
-    double* head_in;
-    long long* head_in_flag;
-    const double* mu0p;
-    const long long* mu0_flag;
-    long long seq;
-};
-
-template <int D, int NW>
-__global__ __launch_bounds__(NW * 64, 2) void k_adjoint_one(const GArgs<D> by_value) {
-    (void)by_value;
-    const GArgs<D>& ka = *(const GArgs<D>*)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr int SUB = kWJ, TILE = 64 * SUB, NS = D * D + 3 * D + 2;
-    __shared__ double sF[NW][D], sB[NW][D], sAcc[NW][NS];
-    __shared__ double sPw[D][D][64];      // Phi^(8 e), e = 0 .. 63
-    __shared__ double sPoison;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) sPoison = 0.0;
-    long long g;
-    {
-        const long long per = (ka.nwg + 7) / 8;
-        g = (long long)(blockIdx.x & 7) * per + (blockIdx.x >> 3);
-        if ((long long)(blockIdx.x >> 3) >= per || g >= ka.nwg) return;
-    }
-    const long long T = ka.T, c_lo = ka.nhs + g * ka.C, c_hi = (c_lo + ka.C < T) ? c_lo + ka.C : T;
-    const bool first = g == 0;
-    const bool from_head = first || c_lo - ka.halo < ka.nhs;      // (a span shorter than a halo: the second workgroup starts behind the head too -- see k_smooth_one)
-    const long long s0 = from_head ? ka.nhs : c_lo - ka.halo;
-    const long long tile_t0 = s0 + (long long)wave * TILE, t0 = tile_t0 + (long long)lane * SUB;
-    const bool any_valid = tile_t0 < T && tile_t0 < c_hi + ka.halo;      // (wave-uniform: tiles behind the right-hand halo have nothing to do)
-    if (first && wave == NW - 1 && ka.head_in != nullptr) {      // the head's observations to the host, first thing
-        for (long long t = lane; t < ka.nhs; t += 64) ka.head_in[t] = ka.y[t];
-        __threadfence_system();
-        if (lane == 0) __hip_atomic_store(ka.head_in_flag, 2 * ka.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    {
-        const int uw = __builtin_amdgcn_readfirstlane(wave);
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            if (uw != i % NW) continue;
-            double row[D];
-#pragma unroll
-            for (int k = 0; k < D; ++k) row[k] = (k == i) ? 1.0 : 0.0;
-#pragma unroll
-            for (int b = 0; b < 6; ++b) {
-                double nr[D];
-#pragma unroll
-                for (int k = 0; k < D; ++k) {
-                    double v = 0.0;
-#pragma unroll
-                    for (int m = 0; m < D; ++m) v = fma(row[m], ka.P[b][m][k], v);
-                    nr[k] = v;
-                }
-                const bool bit = ((lane >> b) & 1) != 0;
-#pragma unroll
-                for (int k = 0; k < D; ++k) row[k] = bit ? nr[k] : row[k];
-            }
-#pragma unroll
-            for (int k = 0; k < D; ++k) sPw[i][k][lane] = row[k];
-        }
-    }
-    // ---- forward, zero start
-    double u[SUB], x[D];
-#pragma unroll
-    for (int i = 0; i < D; ++i) x[i] = 0.0;
-#pragma unroll
-    for (int j = 0; j < SUB; ++j) u[j] = 0.0;
-    if (any_valid) {
-        if (t0 + SUB <= T && (reinterpret_cast<uintptr_t>(ka.y) & 15) == 0) {
-            const v2d* q = reinterpret_cast<const v2d*>(ka.y + t0);
-#pragma unroll
-            for (int j = 0; j < SUB / 2; ++j) {
-                const v2d w = q[j];
-                u[2 * j] = w.x - ka.hh;
-                u[2 * j + 1] = w.y - ka.hh;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < SUB; ++j) u[j] = t0 + j < T ? ka.y[t0 + j] - ka.hh : 0.0;
-        }
-#pragma unroll
-        for (int j = 0; j < SUB; ++j) {
-            double nx[D];
-#pragma unroll
-            for (int i = 0; i < D; ++i) {
-                double v = fma(ka.kA[i], u[j], ka.a[i]);
-#pragma unroll
-                for (int k = 0; k < D; ++k) v = fma(ka.Phi[i][k], x[k], v);
-                nx[i] = v;
-            }
-#pragma unroll
-            for (int i = 0; i < D; ++i) x[i] = nx[i];
-        }
-    }
-    __syncthreads();
-    double st[D];
-    if (any_valid) {
-#define TGP_ADJ_FWD(K)                                                                     \
-    do {                                                                                   \
-        double g_[D], n_[D];                                                               \
-        _Pragma("unroll") for (int i = 0; i < D; ++i) {                                    \
-            g_[i] = dpp_mov<0x110 + (1 << (K))>(x[i]);                                     \
-            n_[i] = x[i];                                                                  \
-        }                                                                                  \
-        _Pragma("unroll") for (int i = 0; i < D; ++i)                                      \
-            _Pragma("unroll") for (int k = 0; k < D; ++k) n_[i] = fma(ka.P[K][i][k], g_[k], n_[i]); \
-        _Pragma("unroll") for (int i = 0; i < D; ++i) x[i] = n_[i];                        \
-    } while (0)
-        TGP_ADJ_FWD(0);
-        TGP_ADJ_FWD(1);
-        TGP_ADJ_FWD(2);
-        TGP_ADJ_FWD(3);
-#undef TGP_ADJ_FWD
-        const int e1 = (lane & 15) + 1, e2 = lane >= 32 ? lane - 31 : 0;
-        double gv[D], nv[D];
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            gv[i] = dpp_mov<0x142, 0xA>(x[i]);
-            nv[i] = x[i];
-        }
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int k = 0; k < D; ++k) nv[i] = fma(sPw[i][k][e1], gv[k], nv[i]);
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            x[i] = nv[i];
-            gv[i] = dpp_mov<0x143, 0xC>(nv[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int k = 0; k < D; ++k) nv[i] = fma(sPw[i][k][e2], gv[k], nv[i]);
-#pragma unroll
-        for (int i = 0; i < D; ++i) x[i] = nv[i];
-    }
-#pragma unroll
-    for (int i = 0; i < D; ++i) st[i] = dpp_mov<0x138>(x[i]);
-    if (lane == 63) {
-#pragma unroll
-        for (int i = 0; i < D; ++i) sF[wave][i] = any_valid ? x[i] : 0.0;
-    }
-    __syncthreads();
-    // ---- the true start state, then the lane's predicted means and innovations
-    double mus[SUB][D], r[SUB], psi[D];
-#pragma unroll
-    for (int i = 0; i < D; ++i) psi[i] = 0.0;
-#pragma unroll
-    for (int j = 0; j < SUB; ++j) {
-        r[j] = 0.0;
-#pragma unroll
-        for (int i = 0; i < D; ++i) mus[j][i] = 0.0;
-    }
-    if (any_valid) {
-        double zin[D];
-#pragma unroll
-        for (int i = 0; i < D; ++i) zin[i] = 0.0;
-        const bool from_host = from_head && wave < 3 && ka.mu0_flag != nullptr;      // (wave-uniform) the head's end state comes from the host, beside the kernel
-        if (from_host) wait_tables(ka.mu0_flag, ka.seq, &sPoison);
-#pragma unroll
-        for (int k = 1; k <= 3; ++k) {
-            const int src = wave - k;
-            if (src < -1 || (src == -1 && !from_head)) continue;
-            double xs[D];
-#pragma unroll
-            for (int i = 0; i < D; ++i) xs[i] = src >= 0 ? sF[src][i] : (from_host ? ka.mu0p[i] : ka.mu0[i]);
-            if (k == 1) {
-#pragma unroll
-                for (int i = 0; i < D; ++i) zin[i] += xs[i];
-            } else {
-#pragma unroll
-                for (int i = 0; i < D; ++i)
-#pragma unroll
-                    for (int m = 0; m < D; ++m) zin[i] = fma(ka.PT[k - 2][i][m], xs[m], zin[i]);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int k = 0; k < D; ++k) st[i] = fma(sPw[i][k][lane], zin[k], st[i]);
-#pragma unroll
-        for (int j = 0; j < SUB; ++j) {
-            double rr = u[j];
-#pragma unroll
-            for (int k = 0; k < D; ++k) {
-                mus[j][k] = st[k];
-                rr = fma(-ka.h[k], st[k], rr);
-            }
-            r[j] = t0 + j < T ? rr : 0.0;      // (steps behind the series' end: no innovation, no adjoint)
-            double nx[D];
-#pragma unroll
-            for (int i = 0; i < D; ++i) {
-                double v = fma(ka.kA[i], u[j], ka.a[i]);
-#pragma unroll
-                for (int k = 0; k < D; ++k) v = fma(ka.Phi[i][k], st[k], v);
-                nx[i] = v;
-            }
-#pragma unroll
-            for (int i = 0; i < D; ++i) st[i] = nx[i];
-        }
-        // ---- backward, zero psi behind the lane: psi <- Phi' psi + h r / S
-#pragma unroll
-        for (int j = SUB - 1; j >= 0; --j) {
-            const double c = r[j] * ka.iS;
-            double np[D];
-#pragma unroll
-            for (int i = 0; i < D; ++i) {
-                double v = ka.h[i] * c;
-#pragma unroll
-                for (int k = 0; k < D; ++k) v = fma(ka.Phi[k][i], psi[k], v);
-                np[i] = v;
-            }
-#pragma unroll
-            for (int i = 0; i < D; ++i) psi[i] = np[i];
-        }
-        // reverse scan: lane l <- sum_{m >= l} (Phi')^(8 (m - l)) psi_m
-#define TGP_ADJ_BWD(K)                                                                     \
-    do {                                                                                   \
-        double g_[D], n_[D];                                                               \
-        _Pragma("unroll") for (int i = 0; i < D; ++i) {                                    \
-            g_[i] = dpp_mov<0x100 + (1 << (K))>(psi[i]);                                   \
-            n_[i] = psi[i];                                                                \
-        }                                                                                  \
-        _Pragma("unroll") for (int i = 0; i < D; ++i)                                      \
-            _Pragma("unroll") for (int k = 0; k < D; ++k) n_[i] = fma(ka.P[K][k][i], g_[k], n_[i]); \
-        _Pragma("unroll") for (int i = 0; i < D; ++i) psi[i] = n_[i];                      \
-    } while (0)
-        TGP_ADJ_BWD(0);
-        TGP_ADJ_BWD(1);
-        TGP_ADJ_BWD(2);
-        TGP_ADJ_BWD(3);
-#undef TGP_ADJ_BWD
-        {
-            const int e1 = 16 - (lane & 15);      // rows 0 and 2 take the first lane of the row above them, 16 - p lanes away
-            double gv[D], nv[D];
-#pragma unroll
-            for (int i = 0; i < D; ++i) {
-                gv[i] = dpp_mov<0x15F, 0x5>(dpp_mov<0x130>(psi[i]));
-                nv[i] = psi[i];
-            }
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int k = 0; k < D; ++k) nv[i] = fma(sPw[k][i][e1], gv[k], nv[i]);
-#pragma unroll
-            for (int i = 0; i < D; ++i) psi[i] = nv[i];
-            const int e2 = lane < 32 ? 32 - lane : 0;      // the lower half takes lane 32
-            const double keep = lane < 32 ? 1.0 : 0.0;
-#pragma unroll
-            for (int i = 0; i < D; ++i) gv[i] = readlane_d(psi[i], 32) * keep;
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int k = 0; k < D; ++k) nv[i] = fma(sPw[k][i][e2], gv[k], nv[i]);
-#pragma unroll
-            for (int i = 0; i < D; ++i) psi[i] = nv[i];
-        }
-    }
-    double pin[D];      // the adjoint behind the lane's last step: its right neighbour's (lane 63: zero)
-#pragma unroll
-    for (int i = 0; i < D; ++i) pin[i] = dpp_mov<0x130>(psi[i]);
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < D; ++i) sB[wave][i] = any_valid ? psi[i] : 0.0;
-    }
-    __syncthreads();
-    double acc[NS];
-#pragma unroll
-    for (int e = 0; e < NS; ++e) acc[e] = 0.0;
-    if (any_valid) {
-        double zin[D];
-#pragma unroll
-        for (int i = 0; i < D; ++i) zin[i] = 0.0;
-#pragma unroll
-        for (int k = 1; k <= 3; ++k) {
-            const int src = wave + k;
-            if (src >= NW) continue;
-            if (k == 1) {
-#pragma unroll
-                for (int i = 0; i < D; ++i) zin[i] += sB[src][i];
-            } else {
-#pragma unroll
-                for (int i = 0; i < D; ++i)
-#pragma unroll
-                    for (int m = 0; m < D; ++m) zin[i] = fma(ka.PT[k - 2][m][i], sB[src][m], zin[i]);
-            }
-        }
-        const int eb = 63 - lane;
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int k = 0; k < D; ++k) pin[i] = fma(sPw[k][i][eb], zin[k], pin[i]);
-        // ---- the last sweep: the lane's steps backwards with the true adjoint; sums over the steps the workgroup owns
-#pragma unroll
-        for (int j = SUB - 1; j >= 0; --j) {
-            const long long t = t0 + j;
-            const double own = (t >= c_lo && t < c_hi) ? 1.0 : 0.0;
-            const double rj = r[j];
-#pragma unroll
-            for (int i = 0; i < D; ++i) {
-                const double pw = pin[i] * own;
-#pragma unroll
-                for (int k = 0; k < D; ++k) acc[i * D + k] = fma(pw, mus[j][k], acc[i * D + k]);
-                acc[D * D + i] += pw;
-                acc[D * D + D + i] = fma(pw, rj, acc[D * D + D + i]);
-                acc[D * D + 2 * D + i] = fma(rj * own, mus[j][i], acc[D * D + 2 * D + i]);
-            }
-            acc[D * D + 3 * D] = fma(rj, own, acc[D * D + 3 * D]);
-            acc[D * D + 3 * D + 1] = fma(rj * own, rj, acc[D * D + 3 * D + 1]);
-            const double c = rj * ka.iS;
-            double np[D];
-#pragma unroll
-            for (int i = 0; i < D; ++i) {
-                double v = ka.h[i] * c;
-#pragma unroll
-                for (int k = 0; k < D; ++k) v = fma(ka.Phi[k][i], pin[k], v);
-                np[i] = v;
-            }
-#pragma unroll
-            for (int i = 0; i < D; ++i) pin[i] = np[i];
-        }
-        if (first && wave == 0 && lane == 0) {
-#pragma unroll
-            for (int i = 0; i < D; ++i) ka.psi_out[i] = pin[i];      // d logpdf / d mu at step nhs: where the host's half takes over
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < NS; ++e) {
-        const double s = wave_sum_to_lane63(acc[e]);
-        if (lane == 63) sAcc[wave][e] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < NS) {
-        double tsum = 0.0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) tsum += sAcc[w][threadIdx.x];
-        ka.part[g * NS + threadIdx.x] = tsum + sPoison;      // (NaN once a bounded wait for the host ran out: the call's result is discarded)
-    }
-}
-
-template <int D>
-int launch_adjoint(hipStream_t st, const tgp_plan::FilterPlan& fp, const double* mu0, const double* y, long long T, double* part, double* psi_out, const HeadHandover* hh) {
-    constexpr int NW = 8;
-    GArgs<D> ka;
-    static_assert(sizeof(GArgs<D>) <= 4096, "the kernel-argument segment");
-    std::memset(&ka, 0, sizeof ka);
-    for (int i = 0; i < D; ++i) {
-        ka.a[i] = fp.a[i];
-        ka.kA[i] = fp.kA[i];
-        ka.h[i] = fp.h[i];
-        ka.mu0[i] = mu0 != nullptr ? mu0[i] : 0.0;
-        for (int k = 0; k < D; ++k) {
-            ka.Phi[i][k] = fp.Phi[i * D + k];
-            for (int b = 0; b < 6; ++b) ka.P[b][i][k] = fp.P[b][i * D + k];
-            for (int b = 0; b < 2; ++b) ka.PT[b][i][k] = fp.PT[b][i * D + k];
-        }
-    }
-    ka.hh = fp.hh;
-    ka.iS = fp.iS;
-    ka.T = T;
-    ka.nhs = fp.nhs;
-    ka.halo = fp.halo;
-    ka.C = (long long)NW * 64 * kWJ - 2LL * fp.halo;
-    ka.nwg = (T - fp.nhs + ka.C - 1) / ka.C;
-    ka.y = y;
-    ka.part = part;
-    ka.psi_out = psi_out;
-    if (hh != nullptr) {
-        ka.head_in = hh->head_in;
-        ka.head_in_flag = hh->head_in_flag;
-        ka.mu0p = hh->mu0;
-        ka.mu0_flag = hh->mu0_flag;
-        ka.seq = hh->seq;
-    }
-    const long long per = (ka.nwg + 7) / 8;
-    hipLaunchKernelGGL((k_adjoint_one<D, NW>), dim3((unsigned)(per * 8)), dim3(NW * 64), 0, st, ka);
-    return (int)hipGetLastError();
-}
-}  // namespace
-
-long long adjoint_workgroups(const tgp_plan::FilterPlan& fp, long long T) {
-    const long long C = 8LL * 64 * kWJ - 2LL * fp.halo;
-    return C > 0 ? (T - fp.nhs + C - 1) / C : -1;
-}
-
-int adjoint_lti(hipStream_t stream, const tgp_plan::FilterPlan& fp, const double* mu_start, const double* y, long long T, double* part, double* psi_out,
-                const HeadHandover* hh) {
-    switch (fp.d) {
-        case 1: return launch_adjoint<1>(stream, fp, mu_start, y, T, part, psi_out, hh);
-        case 2: return launch_adjoint<2>(stream, fp, mu_start, y, T, part, psi_out, hh);
-        case 3: return launch_adjoint<3>(stream, fp, mu_start, y, T, part, psi_out, hh);
-        case 4: return launch_adjoint<4>(stream, fp, mu_start, y, T, part, psi_out, hh);
-        case 5: return launch_adjoint<5>(stream, fp, mu_start, y, T, part, psi_out, hh);
-        case 6: return launch_adjoint<6>(stream, fp, mu_start, y, T, part, psi_out, hh);
-    }
-    return (int)hipErrorInvalidValue;
-}
-
-// =================================================================================================================================
-// logpdf + posterior marginals of an LTI model behind its head on DENSE powers in BOTH directions (round 5): the models the modal
-// plan declines (a defective closed loop: two summands with one length scale, ...).  k_adjoint_one's skeleton -- spans with a halo at both ends,
-// forward sweep from zero + DPP scan on the powers of Phi, reverse sweep from zero + reverse DPP scan, tiles chained through LDS -- with the
-// smoother's recursion in the innovations going backwards, xi_t = c r_t + G xi_(t+1), on the powers of G (a second per-lane table), and no
-// second sweep in either direction: the lane's true start state reaches its innovations through the rows h' Phi^j, its right-hand xi reaches
-// its outputs through the rows h' G^(7-j) (the WJ / WG trick of k_steady_one, dense).  mean_t = y_t - (R/S) r_t + h' xi_(t+1);
-// var_t = h' Ps h + R_new (constant but for the last n1 steps: tvb, pinned host memory, read in place by the last tiles).
-// =================================================================================================================================
-namespace {
-template <int D>
-struct SArgs {
-    double Phi[D][D], a[D], kA[D], h[D], hh, rS, vb;
-    double P[6][D][D], PT[2][D][D];
-    double G[D][D], c[D];
-    double GP[6][D][D], GPT[2][D][D];
-    double WJ[kWJ][D], WG[kWJ][D];
-    double mu0[D];
-    long long T, C, nwg, nhs, n1;
-    int halo, halo_r, rnew_per_step;      // halo_r: the halo behind a span (0 without the backward half)
-    const double *y, *Rnew, *tvb;
-    double *mean, *var, *part, *xi_out;
-    // the head beside the kernel (tgp_modal.hpp SmoothCall): all pinned host memory, flags hold 2 seq once raised
-    const double* mu0p;
-    const long long* mu0_flag;
-    long long* xi_flag;
-    double* head_in;
-    long long* head_in_flag;
-    const double* head_out;
-    const long long* head_out_flag;
-    long long seq;
-    // RAND: a draw from the posterior instead of its marginals (lgssm.jl:65-91 on the reverse-time model of :193-221).  With delta_t = x_t - m_t the
-    // reverse-time step x_(t-1) = G x_t + g_t + U' eps_t is the smoother's recursion with a noise input: xi_t = c r_t + G xi_(t+1) + U' eps_t,
-    // y_t = y_obs_t - (R / S) r_t + h' xi_(t+1) + sqrt(Rnew_t) eta_t.  U: the upper Cholesky factor of the settled L + 1e-9 I (U[k][i], k <= i);
-    // xi_T = U0' eps_0 (the draw of the final filtering state) enters step T - 1 as v0 = G xi_T and its output as s0 = h' xi_T.
-    const double* hhT;      // the emission offset per step (a mean function at the inputs, lti_sde.jl:118-131), or nullptr: hh above.  The gains do not see it.
-    const double *eps_t, *eps_e;
-    static constexpr int RD = D <= kSmoothRandMaxD ? D : 1;      // (the kernel-argument segment is full at d = 8: no room for what d > 4 never uses)
-    double U[RD][RD], v0[RD], s0;
-};
-
-template <int D, int NW, int MINW, bool RAND>
-__global__ __launch_bounds__(NW * 64, MINW) void k_smooth_one(const SArgs<D> by_value) {      // (RAND: `mean` receives the draw, `var` is unused)
-    (void)by_value;
-    const SArgs<D>& ka = *(const SArgs<D>*)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr int SUB = kWJ, TILE = 64 * SUB;
-    __shared__ double sF[NW][D], sB[NW][D], sAcc[NW];
-    __shared__ double sPw[D][D][64];       // Phi^(8 e), e = 0 .. 63
-    __shared__ double sPg[D][D][64];       // G^(8 e)
-    __shared__ double sPoison;             // NaN once a bounded wait ran out (wait_tables): the call's result is then discarded
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) sPoison = 0.0;
-    long long g;
-    {
-        const long long per = (ka.nwg + 7) / 8;
-        g = (long long)(blockIdx.x & 7) * per + (blockIdx.x >> 3);
-        if ((long long)(blockIdx.x >> 3) >= per || g >= ka.nwg) return;
-    }
-    const long long T = ka.T, c_lo = ka.nhs + g * ka.C, c_hi = (c_lo + ka.C < T) ? c_lo + ka.C : T;
-    const bool first = g == 0;
-    // a workgroup whose run-in would reach back into the head (a span shorter than a halo: the second workgroup) starts behind the head like the
-    // first, from the head's exact end state: its tiles still cover its range and the halo behind it
-    const bool from_head = first || c_lo - ka.halo < ka.nhs;
-    const long long s0 = from_head ? ka.nhs : c_lo - ka.halo;
-    const long long tile_t0 = s0 + (long long)wave * TILE, t0 = tile_t0 + (long long)lane * SUB;
-    const bool any_valid = tile_t0 < T && tile_t0 < c_hi + ka.halo_r;      // (wave-uniform: tiles behind the right-hand halo have nothing to do)
-    if (first && wave == NW - 1 && ka.head_in != nullptr) {      // the head's inputs to the host, first thing: its forward recursion runs there
-        for (long long t = lane; t < ka.nhs; t += 64) {
-            ka.head_in[t] = ka.y[t];
-            if (ka.rnew_per_step && ka.mean != nullptr) ka.head_in[ka.nhs + t] = ka.Rnew[t];
-        }
-        if (!ka.rnew_per_step && ka.mean != nullptr && lane == 0) ka.head_in[ka.nhs] = ka.Rnew[0];
-        if constexpr (RAND) {      // the head's draws: eta [nhs] behind y | Rnew, then eps [nhs][D]
-            for (long long t = lane; t < ka.nhs; t += 64) ka.head_in[2 * ka.nhs + t] = ka.eps_e[t];
-            for (long long e = lane; e < ka.nhs * D; e += 64) ka.head_in[3 * ka.nhs + e] = ka.eps_t[e];
-        }
-        if (ka.hhT != nullptr) {      // the head's emission offsets, behind everything else (offset 10 nhs)
-            for (long long t = lane; t < ka.nhs; t += 64) ka.head_in[10 * ka.nhs + t] = ka.hhT[t];
-        }
-        __threadfence_system();
-        if (lane == 0) __hip_atomic_store(ka.head_in_flag, 2 * ka.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    // ---- the observations first (they are on their way while the tables are built)
-    double u[SUB];
-#pragma unroll
-    for (int j = 0; j < SUB; ++j) u[j] = 0.0;
-    if (any_valid) {
-        if (ka.hhT != nullptr) {      // (kernel-uniform) an emission offset per step
-#pragma unroll
-            for (int j = 0; j < SUB; ++j) u[j] = t0 + j < T ? ka.y[t0 + j] - ka.hhT[t0 + j] : 0.0;
-        } else if (t0 + SUB <= T && (reinterpret_cast<uintptr_t>(ka.y) & 15) == 0) {
-            const v2d* q = reinterpret_cast<const v2d*>(ka.y + t0);
-#pragma unroll
-            for (int j = 0; j < SUB / 2; ++j) {
-                const v2d w = q[j];
-                u[2 * j] = w.x - ka.hh;
-                u[2 * j + 1] = w.y - ka.hh;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < SUB; ++j) u[j] = t0 + j < T ? ka.y[t0 + j] - ka.hh : 0.0;
-        }
-    }
-    {   // the per-lane power tables: row i of Phi^(8 lane) and of G^(8 lane), the 2 D rows dealt over the waves
-        const int uw = __builtin_amdgcn_readfirstlane(wave);
-#pragma unroll
-        for (int i2 = 0; i2 < 2 * D; ++i2) {
-            if (uw != i2 % NW) continue;
-            const int i = i2 % D;
-            const bool isg = i2 >= D;
-            if (isg && ka.mean == nullptr) continue;      // (logpdf only: no backward half)
-            double row[D];
-#pragma unroll
-            for (int k = 0; k < D; ++k) row[k] = (k == i) ? 1.0 : 0.0;
-#pragma unroll
-            for (int b = 0; b < 6; ++b) {
-                double nr[D];
-#pragma unroll
-                for (int k = 0; k < D; ++k) {
-                    double v = 0.0;
-#pragma unroll
-                    for (int m = 0; m < D; ++m) v = fma(row[m], isg ? ka.GP[b][m][k] : ka.P[b][m][k], v);
-                    nr[k] = v;
-                }
-                const bool bit = ((lane >> b) & 1) != 0;
-#pragma unroll
-                for (int k = 0; k < D; ++k) row[k] = bit ? nr[k] : row[k];
-            }
-            if (isg) {
-#pragma unroll
-                for (int k = 0; k < D; ++k) sPg[i][k][lane] = row[k];
-            } else {
-#pragma unroll
-                for (int k = 0; k < D; ++k) sPw[i][k][lane] = row[k];
-            }
-        }
-    }
-    // ---- forward, zero start: the lane's innovations r0 and its end state
-    double r[SUB], x[D];
-#pragma unroll
-    for (int i = 0; i < D; ++i) x[i] = 0.0;
-#pragma unroll
-    for (int j = 0; j < SUB; ++j) r[j] = 0.0;
-    if (any_valid) {
-#pragma unroll
-        for (int j = 0; j < SUB; ++j) {
-            double rr = u[j];
-#pragma unroll
-            for (int k = 0; k < D; ++k) rr = fma(-ka.h[k], x[k], rr);
-            r[j] = rr;
-            double nx[D];
-#pragma unroll
-            for (int i = 0; i < D; ++i) {
-                double v = fma(ka.kA[i], u[j], ka.a[i]);
-#pragma unroll
-                for (int k = 0; k < D; ++k) v = fma(ka.Phi[i][k], x[k], v);
-                nx[i] = v;
-            }
-#pragma unroll
-            for (int i = 0; i < D; ++i) x[i] = nx[i];
-        }
-    }
-    __syncthreads();
-    double st[D];
-    if (any_valid) {
-#define TGP_SM_FWD(K)                                                                      \
-    do {                                                                                   \
-        double g_[D], n_[D];                                                               \
-        _Pragma("unroll") for (int i = 0; i < D; ++i) {                                    \
-            g_[i] = dpp_mov<0x110 + (1 << (K))>(x[i]);                                     \
-            n_[i] = x[i];                                                                  \
-        }                                                                                  \
-        _Pragma("unroll") for (int i = 0; i < D; ++i)                                      \
-            _Pragma("unroll") for (int k = 0; k < D; ++k) n_[i] = fma(ka.P[K][i][k], g_[k], n_[i]); \
-        _Pragma("unroll") for (int i = 0; i < D; ++i) x[i] = n_[i];                        \
-    } while (0)
-        TGP_SM_FWD(0);
-        TGP_SM_FWD(1);
-        TGP_SM_FWD(2);
-        TGP_SM_FWD(3);
-#undef TGP_SM_FWD
-        const int e1 = (lane & 15) + 1, e2 = lane >= 32 ? lane - 31 : 0;
-        double gv[D], nv[D];
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            gv[i] = dpp_mov<0x142, 0xA>(x[i]);
-            nv[i] = x[i];
-        }
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int k = 0; k < D; ++k) nv[i] = fma(sPw[i][k][e1], gv[k], nv[i]);
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            x[i] = nv[i];
-            gv[i] = dpp_mov<0x143, 0xC>(nv[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int k = 0; k < D; ++k) nv[i] = fma(sPw[i][k][e2], gv[k], nv[i]);
-#pragma unroll
-        for (int i = 0; i < D; ++i) x[i] = nv[i];
-    }
-#pragma unroll
-    for (int i = 0; i < D; ++i) st[i] = dpp_mov<0x138>(x[i]);
-    if (lane == 63) {
-#pragma unroll
-        for (int i = 0; i < D; ++i) sF[wave][i] = any_valid ? x[i] : 0.0;
-    }
-    __syncthreads();
-    // ---- the true start state -> the true innovations (r = r0 - h' Phi^j st); the reverse sweep from zero
-    double xi[D], o0[SUB], acc = 0.0;
-#pragma unroll
-    for (int i = 0; i < D; ++i) xi[i] = 0.0;
-#pragma unroll
-    for (int j = 0; j < SUB; ++j) o0[j] = 0.0;
-    if (any_valid) {
-        double zin[D], mu0v[D];
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            zin[i] = 0.0;
-            mu0v[i] = ka.mu0[i];
-        }
-        if (from_head && wave < 3 && ka.mu0_flag != nullptr) {      // (wave-uniform) the head's end state comes from the host, beside the kernel
-            wait_tables(ka.mu0_flag, ka.seq, &sPoison);
-#pragma unroll
-            for (int i = 0; i < D; ++i) mu0v[i] = ka.mu0p[i];
-        }
-#pragma unroll
-        for (int k = 1; k <= 3; ++k) {
-            const int src = wave - k;
-            if (src < -1 || (src == -1 && !from_head)) continue;
-            double xs[D];
-#pragma unroll
-            for (int i = 0; i < D; ++i) xs[i] = src >= 0 ? sF[src][i] : mu0v[i];
-            if (k == 1) {
-#pragma unroll
-                for (int i = 0; i < D; ++i) zin[i] += xs[i];
-            } else {
-#pragma unroll
-                for (int i = 0; i < D; ++i)
-#pragma unroll
-                    for (int m = 0; m < D; ++m) zin[i] = fma(ka.PT[k - 2][i][m], xs[m], zin[i]);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int k = 0; k < D; ++k) st[i] = fma(sPw[i][k][lane], zin[k], st[i]);
-#pragma unroll
-        for (int j = 0; j < SUB; ++j) {
-            double rr = r[j];
-#pragma unroll
-            for (int k = 0; k < D; ++k) rr = fma(-ka.WJ[j][k], st[k], rr);
-            const long long t = t0 + j;
-            rr = t < T ? rr : 0.0;      // (steps behind the series' end: no innovation)
-            r[j] = rr;
-            if (t >= c_lo && t < c_hi) acc = fma(rr, rr, acc);
-            // h' m_t + hh_t = y_t - (R / S) r_t: what the smoother adds h' xi_(t+1) to  (a per-step offset is fetched again: the L2 has it)
-            o0[j] = fma(-ka.rS, rr, u[j] + ((ka.hhT != nullptr && t < T) ? ka.hhT[t] : ka.hh));
-        }
-        if (ka.mean != nullptr) {
-            double ee[RAND ? SUB : 1][RAND ? D : 1];      // (RAND) the lane's transition draws: 8 D consecutive doubles of eps_t
-            if constexpr (RAND) {
-#pragma unroll
-                for (int j = 0; j < SUB; ++j)
-#pragma unroll
-                    for (int k = 0; k < D; ++k) ee[j][k] = (t0 + j < T) ? ka.eps_t[(t0 + j) * D + k] : 0.0;
-            }
-#pragma unroll
-            for (int j = SUB - 1; j >= 0; --j) {
-                double o = o0[j];
-#pragma unroll
-                for (int k = 0; k < D; ++k) o = fma(ka.h[k], xi[k], o);
-                o0[j] = o;
-                double np[D];
-#pragma unroll
-                for (int i = 0; i < D; ++i) {
-                    double v = ka.c[i] * r[j];
-#pragma unroll
-                    for (int k = 0; k < D; ++k) v = fma(ka.G[i][k], xi[k], v);
-                    if constexpr (RAND) {      // + (U' eps)_i; the series' last step also takes G xi_T
-#pragma unroll
-                        for (int k = 0; k <= i; ++k) v = fma(ka.U[k][i], ee[j][k], v);
-                        if (t0 + j == T - 1) v += ka.v0[i];
-                    }
-                    np[i] = v;
-                }
-#pragma unroll
-                for (int i = 0; i < D; ++i) xi[i] = np[i];
-            }
-            // reverse scan: lane l <- sum_{m >= l} G^(8 (m - l)) xi_m
-#define TGP_SM_BWD(K)                                                                      \
-    do {                                                                                   \
-        double g_[D], n_[D];                                                               \
-        _Pragma("unroll") for (int i = 0; i < D; ++i) {                                    \
-            g_[i] = dpp_mov<0x100 + (1 << (K))>(xi[i]);                                    \
-            n_[i] = xi[i];                                                                 \
-        }                                                                                  \
-        _Pragma("unroll") for (int i = 0; i < D; ++i)                                      \
-            _Pragma("unroll") for (int k = 0; k < D; ++k) n_[i] = fma(ka.GP[K][i][k], g_[k], n_[i]); \
-        _Pragma("unroll") for (int i = 0; i < D; ++i) xi[i] = n_[i];                       \
-    } while (0)
-            TGP_SM_BWD(0);
-            TGP_SM_BWD(1);
-            TGP_SM_BWD(2);
-            TGP_SM_BWD(3);
-#undef TGP_SM_BWD
-            {
-                const int e1 = 16 - (lane & 15);      // rows 0 and 2 take the first lane of the row above them, 16 - p lanes away
-                double gv[D], nv[D];
-#pragma unroll
-                for (int i = 0; i < D; ++i) {
-                    gv[i] = dpp_mov<0x15F, 0x5>(dpp_mov<0x130>(xi[i]));
-                    nv[i] = xi[i];
-                }
-#pragma unroll
-                for (int i = 0; i < D; ++i)
-#pragma unroll
-                    for (int k = 0; k < D; ++k) nv[i] = fma(sPg[i][k][e1], gv[k], nv[i]);
-#pragma unroll
-                for (int i = 0; i < D; ++i) xi[i] = nv[i];
-                const int e2 = lane < 32 ? 32 - lane : 0;      // the lower half takes lane 32
-                const double keep = lane < 32 ? 1.0 : 0.0;
-#pragma unroll
-                for (int i = 0; i < D; ++i) gv[i] = readlane_d(xi[i], 32) * keep;
-#pragma unroll
-                for (int i = 0; i < D; ++i)
-#pragma unroll
-                    for (int k = 0; k < D; ++k) nv[i] = fma(sPg[i][k][e2], gv[k], nv[i]);
-#pragma unroll
-                for (int i = 0; i < D; ++i) xi[i] = nv[i];
-            }
-        }
-    }
-    if (ka.mean != nullptr) {      // (kernel-uniform)
-        double pin[D];      // xi behind the lane's last step: its right neighbour's (lane 63: zero)
-#pragma unroll
-        for (int i = 0; i < D; ++i) pin[i] = dpp_mov<0x130>(xi[i]);
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < D; ++i) sB[wave][i] = any_valid ? xi[i] : 0.0;
-        }
-        __syncthreads();
-        if (any_valid) {
-            double zin[D];
-#pragma unroll
-            for (int i = 0; i < D; ++i) zin[i] = 0.0;
-#pragma unroll
-            for (int k = 1; k <= 3; ++k) {
-                const int src = wave + k;
-                if (src >= NW) continue;
-                if (k == 1) {
-#pragma unroll
-                    for (int i = 0; i < D; ++i) zin[i] += sB[src][i];
-                } else {
-#pragma unroll
-                    for (int i = 0; i < D; ++i)
-#pragma unroll
-                        for (int m = 0; m < D; ++m) zin[i] = fma(ka.GPT[k - 2][i][m], sB[src][m], zin[i]);
-                }
-            }
-            const int eb = 63 - lane;
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int k = 0; k < D; ++k) pin[i] = fma(sPg[i][k][eb], zin[k], pin[i]);
-            if (first && wave == 0 && lane == 0) {      // xi at step nhs: where the host's half takes over (G^512 zin + the tile's own)
-#pragma unroll
-                for (int i = 0; i < D; ++i) {
-                    double v = xi[i];
-#pragma unroll
-                    for (int k = 0; k < D; ++k) v = fma(ka.GPT[0][i][k], zin[k], v);
-                    ka.xi_out[i] = v;
-                }
-                if (ka.xi_flag != nullptr) {
-                    __threadfence_system();
-                    __hip_atomic_store(ka.xi_flag, 2 * ka.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
-            }
-            // ---- outputs of the steps the workgroup owns
-            const bool whole = t0 >= c_lo && t0 + SUB <= c_hi;
-            const bool al = ((reinterpret_cast<uintptr_t>(ka.mean) | (RAND ? (uintptr_t)0 : reinterpret_cast<uintptr_t>(ka.var))) & 15) == 0;
-            const double rn0 = ka.rnew_per_step ? 0.0 : ka.Rnew[0];
-            const bool in_tail = t0 + SUB > T - ka.n1;
-            const bool wide = whole && al;      // (t0 is a multiple of 8: spans start on multiples of 16 behind nhs, itself one)
-#pragma unroll
-            for (int j2 = 0; j2 < SUB; j2 += 2) {
-                double om[2], ov[2];
-#pragma unroll
-                for (int jj = 0; jj < 2; ++jj) {
-                    const int j = j2 + jj;
-                    const long long t = t0 + j;
-                    double o = o0[j];
-#pragma unroll
-                    for (int k = 0; k < D; ++k) o = fma(ka.WG[j][k], pin[k], o);
-                    double v = 0.0;
-                    if constexpr (RAND) {      // the draw: + h' xi_T at the series' last step, + sqrt(Rnew_t) eta_t
-                        if (t == T - 1) o += ka.s0;
-                        if (t < T) o = fma(sqrt(ka.rnew_per_step ? ka.Rnew[t] : rn0), ka.eps_e[t], o);
-                    } else {
-                        v = ka.vb;
-                        if (in_tail && t < T && T - 1 - t < ka.n1) v = ka.tvb[T - 1 - t];
-                        if (ka.rnew_per_step) v += (t < T ? ka.Rnew[t] : 0.0);
-                        else v += rn0;
-                    }
-                    om[jj] = o;
-                    ov[jj] = v;
-                }
-                if (wide) {
-                    v2d w;
-                    w.x = om[0];
-                    w.y = om[1];
-                    reinterpret_cast<v2d*>(ka.mean + t0)[j2 / 2] = w;
-                    if constexpr (!RAND) {
-                        w.x = ov[0];
-                        w.y = ov[1];
-                        reinterpret_cast<v2d*>(ka.var + t0)[j2 / 2] = w;
-                    }
-                } else {
-#pragma unroll
-                    for (int jj = 0; jj < 2; ++jj) {
-                        const long long t = t0 + j2 + jj;
-                        if (t >= c_lo && t < c_hi) {
-                            ka.mean[t] = om[jj];
-                            if constexpr (!RAND) ka.var[t] = ov[jj];
-                        }
-                    }
-                }
-            }
-        }
-    }
-    if (ka.head_out_flag != nullptr && ka.mean != nullptr && g == ((ka.nwg + 7) / 8) / 2) {      // the head's outputs, by a workgroup from the middle of the dispatch (see k_steady_one)
-        if (wave < (RAND ? 1 : 2)) {
-            wait_tables(ka.head_out_flag, ka.seq, &sPoison);
-            double* dst = wave == 0 ? ka.mean : ka.var;
-            const double* src = ka.head_out + (wave == 0 ? 0 : ka.nhs);
-            for (long long t = lane; t < ka.nhs; t += 64) dst[t] = src[t];
-        }
-    }
-    acc = wave_sum_to_lane63(acc);
-    if (lane == 63) sAcc[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tsum = 0.0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) tsum += sAcc[w];
-        ka.part[g] = tsum + sPoison;
-    }
-}
-
-template <int D, int NW>
-int launch_smooth(hipStream_t st, const tgp_plan::SmoothPlan& sp, const double* mu0, const SmoothCall& c) {
-    const tgp_plan::FilterPlan& fp = sp.fp;
-    SArgs<D> ka;
-    static_assert(sizeof(SArgs<D>) <= 11264, "the kernel-argument segment (12 KB launch on gfx950: scripts/micro/bigarg.hip)");
-    std::memset(&ka, 0, sizeof ka);
-    for (int i = 0; i < D; ++i) {
-        ka.a[i] = fp.a[i];
-        ka.kA[i] = fp.kA[i];
-        ka.h[i] = fp.h[i];
-        ka.c[i] = sp.c[i];
-        ka.mu0[i] = mu0 != nullptr ? mu0[i] : 0.0;
-        for (int j = 0; j < kWJ; ++j) {
-            ka.WJ[j][i] = sp.WJ[j][i];
-            ka.WG[j][i] = sp.WG[j][i];
-        }
-        for (int k = 0; k < D; ++k) {
-            ka.Phi[i][k] = fp.Phi[i * D + k];
-            ka.G[i][k] = sp.G[i * D + k];
-            for (int b = 0; b < 6; ++b) {
-                ka.P[b][i][k] = fp.P[b][i * D + k];
-                ka.GP[b][i][k] = sp.GP[b][i * D + k];
-            }
-            for (int b = 0; b < 2; ++b) {
-                ka.PT[b][i][k] = fp.PT[b][i * D + k];
-                ka.GPT[b][i][k] = sp.GPT[b][i * D + k];
-            }
-        }
-    }
-    ka.hh = fp.hh;
-    ka.rS = sp.rS;
-    ka.vb = sp.vb;
-    ka.T = c.T;
-    ka.nhs = fp.nhs;
-    ka.n1 = sp.n1;
-    const bool post = c.mean != nullptr;
-    ka.halo = sp.halo;
-    ka.halo_r = post ? sp.halo : 0;
-    ka.C = smooth_span(sp, post);
-    ka.nwg = (c.T - fp.nhs + ka.C - 1) / ka.C;
-    ka.rnew_per_step = c.rnew_per_step;
-    ka.y = c.y;
-    ka.Rnew = c.Rnew;
-    ka.tvb = c.tvb;
-    ka.mean = c.mean;
-    ka.var = c.var;
-    ka.part = c.part;
-    ka.xi_out = c.xi_out;
-    ka.hhT = c.hh_t;
-    ka.mu0p = c.mu0;
-    ka.mu0_flag = c.mu0_flag;
-    ka.xi_flag = c.xi_flag;
-    ka.head_in = c.head_in;
-    ka.head_in_flag = c.head_in_flag;
-    ka.head_out = c.head_out;
-    ka.head_out_flag = c.head_out_flag;
-    ka.seq = c.seq;
-    const long long per = (ka.nwg + 7) / 8;
-    static const int minw_env = [] { const char* v = std::getenv("TGP_SMOOTH_MINW"); return v ? std::atoi(v) : 0; }();
-    const bool four = minw_env ? minw_env >= 4 : D <= 6;
-    if (c.eps_t != nullptr) {      // a draw from the posterior (d <= kSmoothRandMaxD: the lane's 8 d draws sit in registers)
-        if constexpr (D <= kSmoothRandMaxD) {
-            ka.eps_t = c.eps_t;
-            ka.eps_e = c.eps_e;
-            for (int i = 0; i < D; ++i) {
-                ka.v0[i] = c.v0[i];
-                for (int k = 0; k < D; ++k) ka.U[i][k] = c.U[i * D + k];
-            }
-            ka.s0 = c.s0;
-            hipLaunchKernelGGL((k_smooth_one<D, NW, 2, true>), dim3((unsigned)(per * 8)), dim3(NW * 64), 0, st, ka);
-            return (int)hipGetLastError();
-        } else {
-            return (int)hipErrorInvalidValue;
-        }
-    }
-    if (four && D <= 6) hipLaunchKernelGGL((k_smooth_one<D, NW, (D <= 6 ? 4 : 2), false>), dim3((unsigned)(per * 8)), dim3(NW * 64), 0, st, ka);
-    else hipLaunchKernelGGL((k_smooth_one<D, NW, 2, false>), dim3((unsigned)(per * 8)), dim3(NW * 64), 0, st, ka);
-    return (int)hipGetLastError();
-}
-}  // namespace
-
-// (sixteen waves per workgroup -- spans of 8192 steps, half the halo overhead, the tables' rows dealt over sixteen waves -- were measured
-//  SLOWER: fused call 0.228 against 0.177 ms at d = 6, T = 1e7: one workgroup per CU leaves nothing to run beside its barriers)
-long long smooth_span(const tgp_plan::SmoothPlan& sp, bool post) { return 8LL * 64 * kWJ - (post ? 2LL : 1LL) * sp.halo; }
-long long smooth_workgroups(const tgp_plan::SmoothPlan& sp, long long T, bool post) {
-    const long long C = smooth_span(sp, post);
-    return C > 0 ? (T - sp.fp.nhs + C - 1) / C : -1;
-}
-
-int smooth_lti(hipStream_t stream, const tgp_plan::SmoothPlan& sp, const double* mu_start, const SmoothCall& c) {
-    switch (sp.fp.d) {
-        case 1: return launch_smooth<1, 8>(stream, sp, mu_start, c);
-        case 2: return launch_smooth<2, 8>(stream, sp, mu_start, c);
-        case 3: return launch_smooth<3, 8>(stream, sp, mu_start, c);
-        case 4: return launch_smooth<4, 8>(stream, sp, mu_start, c);
-        case 5: return launch_smooth<5, 8>(stream, sp, mu_start, c);
-        case 6: return launch_smooth<6, 8>(stream, sp, mu_start, c);
-        case 7: return launch_smooth<7, 8>(stream, sp, mu_start, c);
-        case 8: return launch_smooth<8, 8>(stream, sp, mu_start, c);
-    }
-    return (int)hipErrorInvalidValue;
-}
-
 bool overlap_allowed() { return overlap_tables(); }
-
-void plan_smooth(const tgp_plan::ModelHost& m, long long T, tgp_plan::SmoothPlan& sp, double* tvb, bool post) {
-    if (!host_cpu_ok()) {
-        sp.why = tgp_plan::kEigFail;
-        return;
-    }
-    tgp_plan::build_smooth_any(m, T, sp, tvb, post);
-    // (halos would eat three quarters of a span.  Workgroup g >= 1 starts `halo` steps in front of its range; with a span shorter than a halo that
-    //  reaches back into the head -- or in front of the series: a memory fault found by the randomised sweep, T = 250 000, two Matern-1/2 of one
-    //  length scale, halo 1520 against spans of 1056.
-    //  Such a workgroup -- only the second one can be: 2 spans + a halo fit its tiles exactly when a span is shorter than a halo -- starts behind
-    //  the head like the first, from the head's exact end state (`from_head` in the kernels).
-    if (sp.why == tgp_plan::kOk && smooth_span(sp, post) < 1024) sp.why = tgp_plan::kSlowMixing;
-}
-void plan_smooth_head_forward(const tgp_plan::ModelHost& m, const tgp_plan::SmoothPlan& sp, const double* y, double* mu_end, double* quad, const double* hh_t) {
-    tgp_plan::smooth_head_forward_any(m, sp, y, mu_end, quad, hh_t);
-}
-bool plan_smooth_head_tables(const tgp_plan::ModelHost& m, const tgp_plan::SmoothPlan& sp) { return tgp_plan::smooth_head_tables_any(m, sp); }
-void plan_smooth_head_backward(const tgp_plan::ModelHost& m, const tgp_plan::SmoothPlan& sp, const double* y, const double* lam, double* mean, double* vb) {
-    tgp_plan::smooth_head_backward_any(m, sp, y, lam, mean, vb);
-}
-bool plan_smooth_rand_factors(const tgp_plan::SmoothPlan& sp, const double* eps0, double* U, double* v0, double* s0) {
-    return tgp_plan::smooth_rand_factors_any(sp, eps0, U, v0, s0);
-}
-void plan_smooth_head_backward_rand(const tgp_plan::ModelHost& m, const tgp_plan::SmoothPlan& sp, const double* y, const double* delta, const double* eps_e,
-                                    const double* eps_t, const double* rn, bool rn_per_step, double* out) {
-    tgp_plan::smooth_head_backward_rand_any(m, sp, y, delta, eps_e, eps_t, rn, rn_per_step, out);
-}
 
 }  // namespace tgp_modal

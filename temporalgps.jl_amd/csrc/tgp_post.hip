@@ -1,6 +1,7 @@
 // Streaming posterior kernel of the stationary-gain engine (round 6) -- see tgp_post.hpp.  gfx950 only (wave64, DPP scans, uniform coefficients
 // through the kernel-argument segment).
 #include "tgp_post.hpp"
+#include "tgp_lane.hpp"
 
 #include "tgp_lml.hpp"      // record_key: the workgroups' records are marked as k_lml_stream's are
 
@@ -11,7 +12,6 @@ namespace tgp_post {
 
 namespace {
 
-typedef double v2d __attribute__((ext_vector_type(2)));
 constexpr int N = kN, PPL = kN / 2, TILE = kTile;
 
 // ---- kernel arguments: every coefficient is wave-uniform and reaches the lanes through scalar loads ---------------------------------
@@ -35,23 +35,6 @@ struct PArgs {
 template <int D>
 __device__ __forceinline__ constexpr int partner(int i) {
     return ((i ^ 1) < D) ? (i ^ 1) : i;
-}
-__device__ __forceinline__ void lds_sync() {      // one wave talking to itself through LDS (DS operations of a wave execute in order)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ double readlane_d(double x, int l) {      // l wave-uniform
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), l), hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
-    return __hiloint2double(hi, lo);
-}
-// DPP moves of a double (lanes without a source and rows outside the mask read zero).  gfx9 controls: row_shl:n 0x100 + n, row_shr:n 0x110 + n,
-// wave_shl:1 0x130, wave_shr:1 0x138, row_bcast:15 0x142, row_bcast:31 0x143, row_newbcast:n 0x150 + n
-template <int CTRL, int ROWMASK = 0xF>
-__device__ __forceinline__ double dpp_mov(double x) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, ROWMASK, 0xF, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, ROWMASK, 0xF, true);
-    return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ double wave_sum(double x) {
     x += dpp_mov<0x111>(x);
@@ -81,8 +64,7 @@ __device__ __forceinline__ void store_out(double* dst, double v, bool through) {
     else *dst = v;
 }
 
-// a bounded wait for a flag in pinned host memory (tgp_modal.hip wait_tables): two seconds of the 100 MHz clock, then on with a poisoned sum
-constexpr long long kWaitTicks = 200000000ll;
+// a bounded wait for a flag in pinned host memory (kWaitTicks, as tgp_lane.hpp wait_tables): two seconds of the 100 MHz clock, then on with a poisoned sum
 __device__ __noinline__ bool wait_flag(const long long* flagc, long long seq) {      // false: timed out
     long long* flag = const_cast<long long*>(flagc);
     const long long t0 = (long long)wall_clock64();

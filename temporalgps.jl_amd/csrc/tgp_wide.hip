@@ -10,27 +10,17 @@
 #include <vector>
 
 #include "tgp_alloc.hpp"
+#include "tgp_lane.hpp"
 #include "tgp_wide_adjoint_host.hpp"
 
 namespace tgp_wide {
 
 namespace {
 
-typedef double v2d __attribute__((ext_vector_type(2)));
-
 struct ZArg {
     double z[64];      // the filtered mean behind the head, one component per lane (zero beyond d)
 };
 
-__device__ __forceinline__ void lds_sync() {      // one wave talking to itself through LDS (DS operations of a wave execute in order)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ double readlane_d(double x, int l) {      // l wave-uniform
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), l), hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
-    return __hiloint2double(hi, lo);
-}
 // the LDS kernels' inner product: a0 + (the lane's row phi) . (the state in the LDS line zb), on four accumulator chains
 template <int DP>
 __device__ __forceinline__ double lds_dot(const double (&phi)[DP], const double* zb, double a0) {

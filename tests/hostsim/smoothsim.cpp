@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE ONLY (never part of the product library, never a fallback).
-// The dense-powers one-launch smoother (tgp_modal.hip k_smooth_one + tgp_steady_plan.hpp build_smooth / smooth_head_*) run on the
+// The dense-powers one-launch smoother (tgp_powers.hip k_smooth_one + tgp_steady_plan.hpp build_smooth / smooth_head_*) run on the
 // host: the product's own plan and head functions, and a restatement of the kernel's orchestration -- spans with halos at both ends, a lane's
 // eight steps from a zero state, the in-row and across-row scan levels with the very tables the kernel uses (P[k], the per-lane table built
 // from the bits of the lane number, PT), the tiles chained over the three before / behind them, the WJ / WG rows -- lane by lane.

@@ -1,6 +1,6 @@
 """CPU tier: the two pure host functions the dense-powers one-launch kernels' edge suite places its lengths by -- tgp_smooth_plan (the plan of
-k_smooth_one<logpdf | posterior | rand>, tgp_modal::plan_smooth) and tgp_rand_plan (the plan of k_rand_one, tgp_modal::plan_rand) -- against tgp_filter_plan,
-against the geometry the kernels' launch code derives from a plan (csrc/tgp_modal.hip launch_smooth / launch_rand: span = 4096 - one or two halos,
+k_smooth_one<logpdf | posterior | rand>, tgp_powers::plan_smooth) and tgp_rand_plan (the plan of k_rand_one, tgp_powers::plan_rand) -- against tgp_filter_plan,
+against the geometry the kernels' launch code derives from a plan (csrc/tgp_powers.hip launch_smooth / launch_rand: span = 4096 - one or two halos,
 workgroups = ceil(steps behind the head / span)), and on the declines they document (include/tgp_hip.h)."""
 import numpy as np
 import pytest

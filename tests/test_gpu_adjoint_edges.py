@@ -3,7 +3,7 @@ against the oracle's exact sequential adjoint in long double (oracle/seq_adjoint
 50-digit gradient). Bars: logpdf 1e-10 relative to seq_kalman.logpdf, every entry of every block gradient 1e-8 of the largest entry of the
 reference gradient (the project's gradient bar, tests/test_gpu_gradient.py).
 
-Geometry of k_adjoint_one (csrc/tgp_modal.hip, d <= 6; launch_adjoint and the kernel's first lines), on the plan of tgp_plan::build_filter:
+Geometry of k_adjoint_one (csrc/tgp_powers.hip, d <= 6; launch_adjoint and the kernel's first lines), on the plan of tgp_plan::build_filter:
   * a span is 8 waves x 64 lanes x 8 steps = 4096 steps; a lane loads its 8 steps with 16-byte loads when t0 + 8 <= T and y is 16-byte aligned,
     one by one otherwise;
   * a workgroup owns C = 4096 - 2 halo steps behind the head (nhs steps, run on the host): [nhs + g C, nhs + (g + 1) C), and starts `halo` steps early from

@@ -1,4 +1,4 @@
-"""GPU tier: the five operations of the d <= 8 LTI interface that run on ONE kernel skeleton on dense matrix powers (csrc/tgp_modal.hip) -- placed on the
+"""GPU tier: the five operations of the d <= 8 LTI interface that run on ONE kernel skeleton on dense matrix powers (csrc/tgp_powers.hip) -- placed on the
 edges of that skeleton, against the oracle's sequential restatement of the reference (oracle/seq_kalman.py) entry by entry.
 
     kernel label               serves                                                                    span C
