@@ -147,11 +147,13 @@ typedef struct tgp_handle tgp_handle;
                            to 1e-12 of a state's size): a call whose warm-ups prove too short is repeated with longer ones, a model that mixes
                            too slowly goes to the general engine.  What the reference's predict path produces: posterior_lti_sde.jl:20-37,97-131,
                            missings.jl:25-41, lti_sde.jl:135-146.  The same models (T >= 2048) have tgp_posterior_rand_missing served by the
-                           engine's draw kernel (k_sweep_draw).  0: the general chunked-scan engine as before, and
-                           tgp_posterior_rand_missing answers TGP_EUNSUPPORTED for these models. */
+                           engine's draw kernel (k_sweep_draw), and those in LTI form tgp_logpdf_adjoint_missing by its adjoint kernel
+                           (k_sweep_adjoint).  0: the general chunked-scan engine as before; tgp_posterior_rand_missing and
+                           tgp_logpdf_adjoint_missing answer TGP_EUNSUPPORTED for these models. */
 #define TGP_OPT_SWEEP_CHUNK 15       /* tests: steps per chunk of the sweep engine (0 automatic) */
 #define TGP_OPT_SWEEP_WARMUP 16      /* tests: forward warm-up steps (0 automatic); a forced geometry is never repaired by longer warm-ups */
-#define TGP_OPT_SWEEP_WARMUP_BACK 17 /* tests: backward warm-up steps (0 automatic); in tgp_posterior_rand_missing: the draw's warm-up */
+#define TGP_OPT_SWEEP_WARMUP_BACK 17 /* tests: backward warm-up steps (0 automatic); in tgp_posterior_rand_missing: the draw's warm-up; in
+                                        tgp_logpdf_adjoint_missing: the adjoint's */
 #define TGP_OPT_STREAM_MIN_T 18 /* series length from which the STREAMING kernels of the stationary-gain engine serve a call: persistent
                                    waves with ~7 us more fixed latency and 1.3 - 2.7 x the throughput of k_steady_one.  -1 (default): the measured
                                    crossovers (logpdf 5e6, posterior marginals 3e6 steps at d = 3); 0: always (the tests); a length: from there on */
@@ -200,8 +202,9 @@ int64_t tgp_graph_replays(const tgp_handle* h);
    the stationary-gain engines, their one-launch kernels and the wide-state engine: T - n0 (n0: the head of steps with gains of their own);
    the general engine: the steps the forward pass of the last posterior-path call ran in the mean-only form. */
 int tgp_steady_steps(tgp_handle* h, int64_t* mean_only, int64_t* total);
-/* Diagnostics of TGP_OPT_SWEEP for the last tgp_logpdf / tgp_[logpdf_and_]posterior_marginals / tgp_posterior_rand_missing call. info [8]: served by
-   the sweep engine (0 / 1), steps per chunk, forward warm-up, backward warm-up (tgp_posterior_rand_missing: the draw's), waves, attempts (launches),
+/* Diagnostics of TGP_OPT_SWEEP for the last tgp_logpdf / tgp_[logpdf_and_]posterior_marginals / tgp_posterior_rand_missing / tgp_logpdf_adjoint_missing
+   call. info [8]: served by the sweep engine (0 / 1), steps per chunk, forward warm-up, backward warm-up (tgp_posterior_rand_missing: the draw's;
+   tgp_logpdf_adjoint_missing: the adjoint's, and dist[1] compares the adjoints of its hand-over), waves, attempts (launches),
    status bits of the last attempt (1 forward / 2 backward or draw warm-up too short, 4 not positive definite, 8 non-finite), state for the bound
    model (0 untried, 1 serves, -1 declined).  dist [2]: the largest relative distance between a warm-up's end state and the run that reproduces it,
    forwards / backwards (the checks' 1e-12 / 1e-11; tgp_posterior_rand_missing: dist[1] compares the sample states of the draw's hand-over).
@@ -285,6 +288,20 @@ int tgp_logpdf_grad_sde(tgp_handle* h, const double* y, const uint8_t* missing, 
  * TGP_EUNSUPPORTED when no engine applies (use tgp_logpdf_grad). */
 int tgp_logpdf_adjoint(tgp_handle* h, const double* y, uint32_t flags, double* lml_out, double* gA, double* ga,
                        double* gQ, double* gH, double* ghh, double* gR, double* gx0m, double* gx0P);
+/* The same gradient where the GAINS vary in time -- missing steps (`missing` as in tgp_logpdf), a noise variance or an emission offset per step --
+ * by one adjoint pass on the sweep engine (TGP_OPT_SWEEP; k_sweep_adjoint): Forward models with shared A, a, Q, H (not SDE-described),
+ * scalar observations, d <= 4, T >= 2048; a model without any gap is served too (tgp_logpdf_adjoint is the faster route for it).  ONE kernel: the
+ * engine's forward run with checkpoints, then the adjoint of the recursion backwards over every chunk, started from the next chunk's adjoint, which
+ * that chunk got from a warm-up over its own first steps from zero; the hand-over is checked on the adjoints (1e-11 in units of the stationary prior),
+ * a call whose warm-ups prove too short is repeated with longer ones (not under TGP_OPT_SWEEP_CHUNK / _WARMUP / _WARMUP_BACK, the last forcing the
+ * adjoint's warm-up).  Block outputs as in tgp_logpdf_adjoint (host pointers, any may be NULL); ghh and gR are the sums of the per-step gradients over
+ * the observed steps, whether the stream is shared or per step.  gh_steps, gR_steps [T]: d logpdf / d h_t and d logpdf / d R_t of every step, zero at
+ * missing steps; NULL to skip, device pointers with TGP_OUT_DEVICE.  Two calls on the same series give the same bits.
+ * TGP_EUNSUPPORTED, with no output byte written (host or device): SDE-described models, d > 4, p > 1, Reverse models, T < 2048, TGP_OPT_SWEEP = 0, an
+ * engine declined for the bound model, a forced geometry whose warm-ups are too short, an innovation variance that is not positive, non-finite values
+ * (tgp_sweep_info has the status).  The library does not fall back: use tgp_logpdf_grad. */
+int tgp_logpdf_adjoint_missing(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, double* gA, double* ga, double* gQ,
+                               double* gH, double* ghh, double* gR, double* gx0m, double* gx0P, double* gh_steps, double* gR_steps);
 /* The plan of the stationary-gain engine's ONE-LAUNCH path (TGP_OPT_STEADY = 3, the default), a pure host function: what
  * tgp_logpdf / tgp_[logpdf_and_]posterior_marginals build inside every call of a Forward LTI model with one noise variance and scalar
  * observations (d <= 8) before their single kernel -- the covariance half of lgssm.jl:99-238 (predict lgc.jl:46-52, update lgc.jl:247-257,

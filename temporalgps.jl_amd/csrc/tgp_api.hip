@@ -360,6 +360,7 @@ struct tgp_handle {
     int sweep_state = 0;          // 0 untried for the bound model, 1 served the last call, -1 does not apply
     int sweep_W = 0, sweep_Wb = 0;     // warm-ups the bound model's last served call needed (0: estimate)
     int sweep_Wd = 0;             // the same for the draw's warm-up (tgp_posterior_rand_missing; 0: the backward warm-up's estimate)
+    int sweep_Wa = 0;             // the same for the adjoint's warm-up (tgp_logpdf_adjoint_missing; 0: the forward warm-up's value)
     int sweep_fC = 0, sweep_fW = 0, sweep_fWb = 0;   // TGP_OPT_SWEEP_CHUNK / _WARMUP / _WARMUP_BACK (tests; 0 automatic)
     int64_t sweep_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // tgp_sweep_info
     double sweep_dist[2] = {0.0, 0.0};
@@ -1400,7 +1401,7 @@ int tgp_set_option(tgp_handle* h, int option, int64_t value) {
         if (value < 0 || value > (1 << 20)) return h->fail(TGP_EINVAL, "sweep geometry out of range");
         (option == TGP_OPT_SWEEP_CHUNK ? h->sweep_fC : option == TGP_OPT_SWEEP_WARMUP ? h->sweep_fW : h->sweep_fWb) = (int)value;
         h->sweep_state = 0;
-        h->sweep_W = h->sweep_Wb = h->sweep_Wd = 0;
+        h->sweep_W = h->sweep_Wb = h->sweep_Wd = h->sweep_Wa = 0;
         return TGP_OK;
     }
     if (option == TGP_OPT_SDE_CLOSED_FORM) {
@@ -1602,7 +1603,7 @@ int tgp_model_set(tgp_handle* h, int64_t T, int d, int p, int ordering, uint32_t
     h->served = Served::general;
     h->hostm.clear();
     h->sweep_state = 0;
-    h->sweep_W = h->sweep_Wb = h->sweep_Wd = 0;
+    h->sweep_W = h->sweep_Wb = h->sweep_Wd = h->sweep_Wa = 0;
     if (!h->binding_sde) { h->sde_coef_host.clear(); h->sde_A1Q1_host.clear(); }
     h->fold_valid = false;
     drop_reduction(h);

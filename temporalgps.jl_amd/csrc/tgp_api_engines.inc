@@ -371,6 +371,116 @@ int sweep_draw_call(tgp_handle* h, const double* y, const uint8_t* missing, uint
     return TGP_OK;
 }
 
+// The adjoint gradient on the engine (k_sweep_adjoint, DESIGN 4.8; LTI form): sweep_call's staging and repair loop around the adjoint kernel.  The adjoint
+// pass sits in the backward slots of tgp_sweep_info (its warm-up Wa is remembered apart from Wb and Wd; TGP_OPT_SWEEP_WARMUP_BACK forces it here).  The
+// per-step gradients go to the handle's own buffers and reach gh_steps / gR_steps behind the checks, the block gradients are written behind them too:
+// *served = false with *why set: the engine declined, no output was written.
+int sweep_adjoint_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, const tgp_sweep::AdjointOut& o,
+                       double* gh_steps, double* gR_steps, bool* served, std::string* why) {
+    *served = false;
+    if (!h->sweep) h->sweep = tgp_sweep::create();
+    static const bool dbg = getenv("TGP_STEADY_DEBUG") != nullptr;
+    const int d = h->d;
+    const size_t dd = (size_t)d * d;
+    const double* q = h->sweepm.data();
+    tgp_sweep::ModelHost mh;
+    mh.d = d;
+    mh.sde = false;
+    mh.A = q;
+    mh.a = q + dd;
+    mh.Q = q + dd + d;
+    mh.H = q + 2 * dd + d;
+    mh.hh = q[2 * dd + 2 * d];
+    mh.R = h->sweep_Rrep;
+    mh.x0m = h->x0m.data();
+    mh.x0P = h->x0P.data();
+    const bool odev = (flags & TGP_OUT_DEVICE) != 0;
+    const size_t nT = (size_t)h->T * sizeof(double);
+    const bool forced = h->sweep_fW || h->sweep_fWb || h->sweep_fC;
+    int W = h->sweep_W, Wa = h->sweep_Wa;
+    for (int64_t& v : h->sweep_info) v = 0;
+    auto replan = [&]() {
+        std::string w;
+        tgp_sweep::force_geometry(h->sweep, h->sweep_fC, h->sweep_fW, 0, 0, h->sweep_fWb);
+        if (tgp_sweep::plan(h->sweep, mh, h->T, W, h->sweep_Wb, h->num_cu, &w, 0, Wa)) return true;
+        if (dbg) fprintf(stderr, "[tgp sweep] does not apply: %s\n", w.c_str());
+        h->sweep_state = -1;
+        *why = "the sweep engine's plan declines the model (" + w + ")";
+        return false;
+    };
+    if (!replan()) return TGP_OK;
+    CallTimer tm(h, /*clear=*/false);
+    TRY(set_obs(h, y, missing, flags));
+    tm.inputs_done();
+    double *dgh = nullptr, *dgR = nullptr;
+    if (gh_steps) {
+        HIPCHK(h->bo1.ensure(nT));
+        dgh = h->bo1.d();
+    }
+    if (gR_steps) {
+        HIPCHK(h->bo2.ensure(nT));
+        dgR = h->bo2.d();
+    }
+    for (int attempt = 0; attempt < 4; ++attempt) {
+        if (attempt > 0 && !replan()) return TGP_OK;
+        tgp_sweep::Call c;
+        c.T = h->T;
+        c.y = h->mv.y;
+        c.mask = h->mv.missing;
+        c.R = h->mv.sR != 0 ? h->mv.R : nullptr;
+        c.hh = h->mv.sh != 0 ? h->mv.h : nullptr;
+        c.adjoint = true;
+        c.gh_steps = dgh;
+        c.gR_steps = dgR;
+        {
+            std::string err;
+            const char* kname = tgp_sweep::adjoint_kernel_name();
+            LaunchScope ls(h, kname);
+            if (tgp_sweep::enqueue(h->sweep, h->stream, c, &kname, &err) != 0) return h->fail(TGP_EHIP, err);
+        }
+        tm.kernels_done();
+        if (h->timing) (void)hipEventRecord(h->ev[3], h->stream);
+        HIPCHK(hipStreamSynchronize(h->stream));
+        resolve_profile(h);
+        int status = 0, w = 0, wa = 0;
+        const double lml = tgp_sweep::finish(h->sweep, &status, &w, nullptr, &h->sweep_dist[0], &h->sweep_dist[1], nullptr, &wa);
+        int C = 0;
+        int64_t nw = 0;
+        tgp_sweep::geometry(h->sweep, &C, nullptr, nullptr, &nw);
+        h->sweep_info[1] = C; h->sweep_info[2] = w; h->sweep_info[3] = wa; h->sweep_info[4] = nw; h->sweep_info[5] = attempt + 1; h->sweep_info[6] = status;
+        if (dbg) fprintf(stderr, "[tgp sweep adjoint] attempt %d: C %d W %d Wa %d waves %lld status %d dist %.3g / %.3g\n", attempt, C, w, wa, (long long)nw, status, h->sweep_dist[0], h->sweep_dist[1]);
+        if (status & 12) {      // not positive definite / non-finite values: the tangent scans report it the way they always have
+            if (status & 4) h->sweep_state = -1;
+            *why = (status & 4) ? "an innovation variance is not positive" : "non-finite values in the pass";
+            return TGP_OK;
+        }
+        if (status & 3) {       // a warm-up was too short: longer ones (a forced geometry is a test's: report, do not repair)
+            if (forced) {
+                *why = "a warm-up of the forced geometry is too short (tgp_sweep_info)";
+                return TGP_OK;
+            }
+            if (status & 1) W = 2 * w;
+            if (status & 2) Wa = 2 * wa;
+            continue;
+        }
+        if (gh_steps) HIPCHK(hipMemcpyAsync(gh_steps, dgh, nT, odev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+        if (gR_steps) HIPCHK(hipMemcpyAsync(gR_steps, dgR, nT, odev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+        if (gh_steps || gR_steps) HIPCHK(hipStreamSynchronize(h->stream));
+        tgp_sweep::adjoint_blocks(h->sweep, o);
+        read_timing(h);
+        note_served(h, Served::sweep, 0, lml, lml_out);
+        h->sweep_W = w;
+        h->sweep_Wa = wa;
+        h->sweep_state = 1;
+        h->sweep_info[0] = 1;
+        *served = true;
+        return TGP_OK;
+    }
+    h->sweep_state = -1;      // four attempts, warm-ups still too short: a model that mixes too slowly for this engine
+    *why = "the warm-ups stayed too short over four attempts";
+    return TGP_OK;
+}
+
 bool steady2_served(tgp_handle* h) {
     const bool ran = h->host_result[6] == tgp_steady::kStatusRan;
     h->steady2_state = ran ? 1 : -1;

@@ -474,6 +474,27 @@ int tgp_posterior_rand_missing(tgp_handle* h, const double* y, const uint8_t* mi
     return dense_finish(h, tm, nullptr);
 }
 
+// logpdf and its gradient with respect to the shared blocks, and to the noise variance and the emission offset of every step, where the gains vary in time
+// -- missing steps, a noise variance or an emission offset per step -- by ONE adjoint pass on the sweep engine (k_sweep_adjoint, DESIGN 4.8): what
+// sweep_eligible accepts in LTI form.  TGP_EUNSUPPORTED: no output was written, the caller takes tgp_logpdf_grad.
+int tgp_logpdf_adjoint_missing(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, double* gA, double* ga, double* gQ,
+                               double* gH, double* ghh, double* gR, double* gx0m, double* gx0P, double* gh_steps, double* gR_steps) {
+    StreamGuard stream_guard_(h);
+    TRY(check_ready(h, /*general=*/false));
+    if (!y) return h->fail(TGP_EINVAL, "tgp_logpdf_adjoint_missing: null argument");
+    if (h->sde || !sweep_eligible(h, flags))
+        return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_missing: Forward models with shared A, a, Q, H (not SDE-described), scalar observations, d <= 4 and "
+                                         "T >= 2048 on the sweep engine (TGP_OPT_SWEEP = 1, the engine not declined for the bound model); use tgp_logpdf_grad "
+                                         "otherwise");
+    tgp_sweep::AdjointOut o;
+    o.gA = gA; o.ga = ga; o.gQ = gQ; o.gH = gH; o.ghh = ghh; o.gR = gR; o.gx0m = gx0m; o.gx0P = gx0P;
+    bool served = false;
+    std::string why;
+    TRY(sweep_adjoint_call(h, y, missing, flags, lml_out, o, gh_steps, gR_steps, &served, &why));
+    if (served) return TGP_OK;
+    return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_missing: the sweep engine declines the gradient: " + why + " (use tgp_logpdf_grad)");
+}
+
 // Two observations per step of ONE latent value with independent noise are one observation of it:
 //     N(y; f, R) N(y*; f, R*) = N(ybar; f, Rbar) N(y - y*; 0, R + R*),   Rbar = R R* / (R + R*),   ybar = (R* y + R y*) / (R + R*)
 // -- what turns logpdf(replace_observation_noise_cov(posterior(model, y), R*), y*) (posterior_lti_sde.jl:62-78 -> lgssm.jl:147-151 on the

@@ -18,6 +18,11 @@
 // A draw from the posterior (k_sweep_draw) is the same forward half and, backwards, the reverse-time model's sample path instead of its
 // marginals: a state of d doubles walks back over the chunk from the next lane's sample state of ITS first step, which that lane composed during its
 // forward run over its first Wd steps from zero deviation (the walk forgets as the smoother does); the hand-over is checked on the sample states.
+//
+// The gradient of the log marginal likelihood (k_sweep_adjoint; LTI form) is the same forward half and, backwards, the adjoint of the
+// recursion: (l, L) = d logpdf / d (m, P) of a filtering state, as large as the state, walks back over the chunk from the next lane's adjoint in front
+// of ITS first step, which that lane got from a walk over its own first Wa steps from zero (the adjoint forgets at the filter's rate); the hand-over is
+// checked on the adjoints.  A lane sums the gradients with respect to the shared blocks over its steps, the wave adds its lanes' sums, the host the waves'.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -50,20 +55,33 @@ struct Call {
     const double* eps_e = nullptr;        // device [T]
     double eps_0[4] = {0.0, 0.0, 0.0, 0.0};      // the start x_(T-1): travels in the kernel arguments
     double* y_out = nullptr;              // device [T]
+    // the adjoint gradient instead (mean / var / y_out null): k_sweep_adjoint, LTI form
+    bool adjoint = false;
+    double* gh_steps = nullptr;           // device [T] or null: d logpdf / d h_t, d logpdf / d R_t of every step (zero at missing ones)
+    double* gR_steps = nullptr;
+};
+// where adjoint_blocks writes the gradient with respect to the shared blocks (host, column-major, any null; ghh / gR: the sums over the observed steps)
+struct AdjointOut {
+    double *gA = nullptr, *ga = nullptr, *gQ = nullptr, *gH = nullptr, *ghh = nullptr, *gR = nullptr, *gx0m = nullptr, *gx0P = nullptr;
 };
 
 // Chooses the geometry (chunk length, warm-ups) for this model and series; false: the engine declines (`why` says so).
 // w_hint / wb_hint: warm-ups a previous call on the same bound model needed (0: estimate from the model).
 // wd_hint: the draw's warm-up (0: the backward warm-up's value; a draw call that passes one may lengthen the chunk to hold it).
-bool plan(Engine* e, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, std::string* why, int wd_hint = 0);
+// wa_hint: the adjoint's warm-up (0: the forward warm-up's value; likewise).
+bool plan(Engine* e, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, std::string* why, int wd_hint = 0, int wa_hint = 0);
 int enqueue(Engine* e, hipStream_t stream, const Call& c, const char** kernel_name, std::string* err);
 const char* kernel_name(int d, bool sde, bool post, bool draw = false);
+const char* adjoint_kernel_name();
 // After the stream has been synchronised.  status bits: 1 forward warm-up too short, 2 backward warm-up too short, 4 not positive definite,
 // 8 non-finite values.  *w / *wb: the warm-ups the call ran with.  A draw: bit 2 and *dist_b are the draw warm-up's (*wd), the returned value is 0.
-double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* dist_b, int* wd = nullptr);
+// An adjoint call: bit 2 and *dist_b are the adjoint warm-up's (*wa), the returned value is the log marginal likelihood.
+double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* dist_b, int* wd = nullptr, int* wa = nullptr);
+// Behind finish of an adjoint call whose status is clean: the waves' sums, added in wave order.
+void adjoint_blocks(const Engine* e, const AdjointOut& out);
 // geometry of the last plan (diagnostics / tests)
 void geometry(const Engine* e, int* C, int* W, int* Wb, int64_t* nwaves, int* Wd = nullptr);
 // test hook: force the geometry of the next plan (0: automatic)
-void force_geometry(Engine* e, int C, int W, int Wb, int Wd = 0);
+void force_geometry(Engine* e, int C, int W, int Wb, int Wd = 0, int Wa = 0);
 
 }  // namespace tgp_sweep

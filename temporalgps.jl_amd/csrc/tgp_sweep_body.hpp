@@ -1072,4 +1072,184 @@ TGP_HD void backward_run_draw(const KArgs<D>& ka, const DrawArgs& da, const Mode
     }
 }
 
+// ---- the adjoint of the filter (k_sweep_adjoint): d logpdf / d (shared blocks, h_t, R_t) in one backward walk -------------------------
+// Reverse mode through predict / update above (LTI form).  The walk carries (l, L) = d logpdf / d (m_f, P_f) of the filtering state BEHIND the step in hand
+// -- L symmetric, packed: every entry of a covariance counts as a variable of its own and the derivative is kept symmetric, which is what makes the Q and
+// x0P gradients come out symmetrised (lgssm.logpdf_adjoint's convention) -- and is zero behind the series' last step.
+template <int D> struct Adj {
+    double l[D];
+    double L[SD<D>::DS];
+    TGP_HD void zero() {
+        TGP_UNROLL for (int i = 0; i < D; ++i) l[i] = 0.0;
+        TGP_UNROLL for (int i = 0; i < SD<D>::DS; ++i) L[i] = 0.0;
+    }
+};
+// a lane's sums over the steps of its chunk: gA full (column-major), gQ packed, the sums of the per-step gh_t and gR_t
+template <int D> struct AdjAcc {
+    static constexpr int N = D * D + D + SD<D>::DS + D + 2;
+    double gA[D * D], ga[D], gQ[SD<D>::DS], gH[D], gh, gR;
+    TGP_HD void zero() {
+        TGP_UNROLL for (int i = 0; i < D * D; ++i) gA[i] = 0.0;
+        TGP_UNROLL for (int i = 0; i < D; ++i) ga[i] = gH[i] = 0.0;
+        TGP_UNROLL for (int i = 0; i < SD<D>::DS; ++i) gQ[i] = 0.0;
+        gh = gR = 0.0;
+    }
+};
+
+// One step backwards.  xf: the filtering state in FRONT of step t; ad: the adjoint behind it on entry, in front of it on return.  A missing step
+// (obs == false; the padded steps behind the series' end are such) passes the adjoint through the predict alone: gh_t = gR_t = 0.
+template <int D, bool ACC>
+TGP_HD void adjoint_step(const ModelR<D, false>& mr, const State<D>& xf, double hh, double R, double y, bool obs, Adj<D>& ad, AdjAcc<D>* acc, double& gh_t,
+                         double& gR_t) {
+    constexpr int DS = SD<D>::DS;
+    double mp[D], Pp[DS], AP[D * D];
+    TGP_UNROLL for (int i = 0; i < D; ++i) mp[i] = xf.m[i];
+    TGP_UNROLL for (int i = 0; i < DS; ++i) Pp[i] = xf.P[i];
+    predict_r<D, false>(mr, mr.A, mp, Pp, AP);      // (the filter's own predict, to the bit)
+    double V[D];
+    TGP_UNROLL for (int j = 0; j < D; ++j) {
+        double a = 0.0;
+        TGP_UNROLL for (int k = 0; k < D; ++k) a = ::fma(mr.H[k], Pp[pidx(k, j)], a);
+        V[j] = a;
+    }
+    double s2 = R, hm = hh;
+    TGP_UNROLL for (int k = 0; k < D; ++k) {
+        s2 = ::fma(V[k], mr.H[k], s2);
+        hm = ::fma(mr.H[k], mp[k], hm);
+    }
+    const double S = obs ? s2 : 1.0;
+    const double iS = obs ? fast_rcp(S) : 0.0;      // (a missing step: every term of the update's adjoint below is a multiple of iS or v)
+    const double v = obs ? (y - hm) : 0.0;
+    const double viS = v * iS;
+    double LV[D], lV = 0.0, VLV = 0.0;
+    TGP_UNROLL for (int i = 0; i < D; ++i) {
+        double a = 0.0;
+        TGP_UNROLL for (int k = 0; k < D; ++k) a = ::fma(ad.L[pidx(i, k)], V[k], a);
+        LV[i] = a;
+        lV = ::fma(ad.l[i], V[i], lV);
+    }
+    TGP_UNROLL for (int i = 0; i < D; ++i) VLV = ::fma(V[i], LV[i], VLV);
+    const double vbar = (lV - v) * iS;
+    const double Sbar = ::fma(::fma(-lV, v, VLV) * iS, iS, -0.5 * ::fma(-viS, viS, iS));
+    double Vb[D];
+    TGP_UNROLL for (int i = 0; i < D; ++i) Vb[i] = ::fma(Sbar, mr.H[i], ::fma(ad.l[i], viS, -2.0 * iS * LV[i]));
+    gh_t = -vbar;
+    gR_t = Sbar;
+    double mb[D], Pb[DS];
+    TGP_UNROLL for (int i = 0; i < D; ++i) mb[i] = ::fma(-vbar, mr.H[i], ad.l[i]);
+    TGP_UNROLL for (int j = 0; j < D; ++j)
+        TGP_UNROLL for (int i = 0; i <= j; ++i) Pb[pidx(i, j)] = ::fma(0.5, ::fma(Vb[i], mr.H[j], mr.H[i] * Vb[j]), ad.L[pidx(i, j)]);
+    if constexpr (ACC) {
+        TGP_UNROLL for (int i = 0; i < D; ++i) {
+            double a = ::fma(Sbar, V[i], -vbar * mp[i]);
+            TGP_UNROLL for (int k = 0; k < D; ++k) a = ::fma(Pp[pidx(i, k)], Vb[k], a);
+            acc->gH[i] += a;
+            acc->ga[i] += mb[i];
+        }
+        acc->gh -= vbar;
+        acc->gR += Sbar;
+        TGP_UNROLL for (int i = 0; i < DS; ++i) acc->gQ[i] += Pb[i];
+        TGP_UNROLL for (int k = 0; k < D; ++k)      // gA += mb m' + 2 Pb (A P)
+            TGP_UNROLL for (int i = 0; i < D; ++i) {
+                double a = 0.0;
+                TGP_UNROLL for (int j = 0; j < D; ++j) a = ::fma(Pb[pidx(i, j)], AP[j + k * D], a);
+                acc->gA[i + k * D] += ::fma(2.0, a, mb[i] * xf.m[k]);
+            }
+    }
+    // l <- A' mb;  L <- A' Pb A
+    TGP_UNROLL for (int i = 0; i < D; ++i) {
+        double a = 0.0;
+        TGP_UNROLL for (int k = 0; k < D; ++k) a = ::fma(mr.A[k + i * D], mb[k], a);
+        ad.l[i] = a;
+    }
+    double AtP[D * D];
+    TGP_UNROLL for (int j = 0; j < D; ++j)
+        TGP_UNROLL for (int i = 0; i < D; ++i) {
+            double a = 0.0;
+            TGP_UNROLL for (int k = 0; k < D; ++k) a = ::fma(mr.A[k + i * D], Pb[pidx(k, j)], a);
+            AtP[i + j * D] = a;
+        }
+    TGP_UNROLL for (int j = 0; j < D; ++j)
+        TGP_UNROLL for (int i = 0; i <= j; ++i) {
+            double a = 0.0;
+            TGP_UNROLL for (int k = 0; k < D; ++k) a = ::fma(AtP[i + k * D], mr.A[k + j * D], a);
+            ad.L[pidx(i, j)] = a;
+        }
+}
+
+// How far apart two adjoints are: the dual of state_distance's scaling (l_i sqrt(P_ii), L_ij sqrt(P_ii P_jj), P the stationary prior), absolute -- the
+// adjoint of a step is O(1) in these units whatever the model's scale.  Compared with mc.tol_b.
+template <int D> TGP_HD double adjoint_distance(const ModelC<D>& mc, const Adj<D>& a, const Adj<D>& b) {
+    double sd[D], worst = 0.0;
+    TGP_UNROLL for (int i = 0; i < D; ++i) sd[i] = ::sqrt(mc.gP[pidx(i, i)]);
+    TGP_UNROLL for (int i = 0; i < D; ++i) {
+        const double r = ::fabs(a.l[i] - b.l[i]) * sd[i];
+        worst = r > worst ? r : worst;      // (a NaN on either side compares false everywhere: caught by the caller's finite test)
+    }
+    TGP_UNROLL for (int j = 0; j < D; ++j)
+        TGP_UNROLL for (int i = 0; i <= j; ++i) {
+            const double r = ::fabs(a.L[pidx(i, j)] - b.L[pidx(i, j)]) * (sd[i] * sd[j]);
+            worst = r > worst ? r : worst;
+        }
+    return worst;
+}
+
+// The adjoint walk of a lane over the blocks nblk - 1 .. 0 of its chunk (first step t0, a multiple of 8): the steps below hi are walked, from `ad` = the
+// adjoint behind step hi - 1; on return `ad` is the adjoint in front of step t0.  The filtering states of a block are recomputed from its checkpoint into
+// LDS as backward_run does (sF: [step][component][lane]); step j reads the state in front of it: step j - 1's, the checkpoint for j = 0.
+// ACC: the block gradients are summed into *acc, and gh_t / gR_t of every walked step are written where gh_steps / gR_steps are given (a lane's own steps:
+// plain stores).
+template <int D, int XS, int B, bool ACC>
+TGP_HD void adjoint_run(const KArgs<D>& ka, const ModelR<D, false>& mr, long long t0, int nblk, long long hi, Adj<D>& ad, AdjAcc<D>* acc, double* gh_steps,
+                        double* gR_steps, const double* ckpt, double* sF, int lane, bool& ok) {
+    constexpr int NS = SD<D>::NS, DS = SD<D>::DS;
+    const long long T = ka.T;
+    Inputs<D, false, XS, B> in, nx;
+    const long long tlast = t0 + (long long)(nblk - 1) * B;
+    load_inputs<D, false, XS, B>(ka, tlast, in);
+    State<D> ck, ckN;
+    {
+        const double* q = ckpt + (size_t)(nblk > 0 ? nblk - 1 : 0) * NS * 64 + lane;
+        TGP_UNROLL for (int k = 0; k < D; ++k) ck.m[k] = q[(size_t)k * 64];
+        TGP_UNROLL for (int k = 0; k < DS; ++k) ck.P[k] = q[(size_t)(D + k) * 64];
+    }
+    for (int b = nblk - 1; b >= 0; --b) {
+        const long long tb = t0 + (long long)b * B;
+        load_inputs<D, false, XS, B>(ka, tb - B, nx);      // the next block (block b - 1): in flight through this one
+        {
+            const double* q = ckpt + (size_t)(b > 0 ? b - 1 : 0) * NS * 64 + lane;
+            TGP_UNROLL for (int k = 0; k < D; ++k) ckN.m[k] = q[(size_t)k * 64];
+            TGP_UNROLL for (int k = 0; k < DS; ++k) ckN.P[k] = q[(size_t)(D + k) * 64];
+        }
+        TGP_ISSUE_BARRIER();
+        // ---- the block's filtering states, forwards from its checkpoint (the last step's is not needed: nothing walks from it)
+        State<D> x = ck;
+        TGP_UNROLL for (int j = 0; j + 1 < B; ++j) {
+            predict_r<D, false>(mr, mr.A, x.m, x.P);
+            update<D>(mr.H, (XS & 2) ? in.hh[j] : mr.hh, (XS & 1) ? in.R[j] : mr.R, in.y[j], in.obs(j, tb + j, T), x.m, x.P, (LmlAcc*)nullptr, ok);
+            TGP_UNROLL for (int k = 0; k < D; ++k) sF[(j * NS + k) * 64 + lane] = x.m[k];
+            TGP_UNROLL for (int k = 0; k < DS; ++k) sF[(j * NS + D + k) * 64 + lane] = x.P[k];
+        }
+        TGP_ISSUE_BARRIER();      // (the states are to be read back from LDS: backward_run)
+        TGP_UNROLL for (int j = B - 1; j >= 0; --j) {
+            const long long t = tb + j;
+            if (t < hi) {
+                State<D> xf = ck;
+                if (j > 0) {
+                    TGP_UNROLL for (int k = 0; k < D; ++k) xf.m[k] = sF[((j - 1) * NS + k) * 64 + lane];
+                    TGP_UNROLL for (int k = 0; k < DS; ++k) xf.P[k] = sF[((j - 1) * NS + D + k) * 64 + lane];
+                }
+                double gh_t, gR_t;
+                adjoint_step<D, ACC>(mr, xf, (XS & 2) ? in.hh[j] : mr.hh, (XS & 1) ? in.R[j] : mr.R, in.y[j], in.obs(j, t, T), ad, acc, gh_t, gR_t);
+                if constexpr (ACC) {
+                    if (gh_steps != nullptr) gh_steps[t] = gh_t;
+                    if (gR_steps != nullptr) gR_steps[t] = gR_t;
+                }
+            }
+        }
+        in = nx;
+        ck = ckN;
+    }
+}
+
 }  // namespace tgp_sweep

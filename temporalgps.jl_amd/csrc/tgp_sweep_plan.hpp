@@ -34,12 +34,14 @@ struct Plan {
     bool sde = false;
     int C = 0, W = 0, Wb = 0;
     int Wd = 0;                     // the draw's warm-up (k_sweep_draw): steps of a chunk's head the walk is composed over
+    int Wa = 0;                     // the adjoint's warm-up (k_sweep_adjoint): steps of a chunk's head the adjoint walks from zero
     int64_t T = 0, nchunks = 0, nwaves = 0;
     double mc[160];                 // the ModelC<d> of the call, as plain doubles (copied into the typed kernel argument)
 };
 struct Forced {                     // test hook: geometry of the next plan (0: automatic)
     int C = 0, W = 0, Wb = 0;
     int Wd = 0;
+    int Wa = 0;
 };
 
 namespace plan_detail {
@@ -192,7 +194,8 @@ template <int D> inline void host_sde_A(const double* q, double tau, double* A) 
 constexpr double kTol = 1e-12, kTolBack = 1e-11;
 constexpr int kMaxWarm = 4096;
 
-template <int D> inline bool plan_d(Plan* e, const Forced& f, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, std::string* why, int wd_hint) {
+template <int D> inline bool plan_d(Plan* e, const Forced& f, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, std::string* why, int wd_hint,
+                                        int wa_hint) {
     constexpr int B = Geo<D>::B;
     ModelC<D> mc;
     fill_model<D>(m, mc);
@@ -282,12 +285,19 @@ template <int D> inline bool plan_d(Plan* e, const Forced& f, const ModelHost& m
     // passes a longer one, and the chunk holds it
     int Wd = wd_hint > 0 ? up(wd_hint, 8) : Wb;
     if (wd_hint > 0) C = std::max<int64_t>(C, Wd);
+    // the adjoint's warm-up: the forward warm-up's value is the first guess (the adjoint recursion runs through the transposed closed loop of the filter
+    // and forgets at its rate); a call that found it short passes a longer one, and the chunk holds it
+    int Wa = wa_hint > 0 ? up(wa_hint, 8) : W;
+    if (wa_hint > 0) C = std::max<int64_t>(C, Wa);
     if (f.C > 0) C = up(f.C, 8);
     if (f.W > 0) W = up(f.W, 8);
     if (f.Wb > 0) Wb = up(f.Wb, 8);
     if (f.Wd > 0) Wd = up(f.Wd, 8);
+    if (f.Wa > 0) Wa = up(f.Wa, 8);
+    else if (wa_hint <= 0) Wa = up(W, 8);      // (the first guess follows a forced forward warm-up)
     if (Wb > C) Wb = (int)C;
     if (Wd > C) Wd = (int)C;
+    if (Wa > C) Wa = (int)C;
     if (W > kMaxWarm || (f.C == 0 && W > 4 * C)) {
         if (why) *why = "forward warm-up longer than four chunks";
         return false;
@@ -300,6 +310,7 @@ template <int D> inline bool plan_d(Plan* e, const Forced& f, const ModelHost& m
     e->W = W;
     e->Wb = Wb;
     e->Wd = Wd;
+    e->Wa = Wa;
     e->nchunks = (T + C - 1) / C;
     e->nwaves = (e->nchunks + kOwned - 1) / kOwned;
     static_assert(sizeof(ModelC<D>) <= sizeof(e->mc), "Plan::mc too small");
@@ -310,17 +321,19 @@ template <int D> inline bool plan_d(Plan* e, const Forced& f, const ModelHost& m
 }  // namespace plan_detail
 
 // Chooses the geometry (chunk length, warm-ups) for this model and series; false: the engine declines (`why` says so).
-// w_hint / wb_hint: warm-ups a previous call on the same bound model needed (0: estimate from the model).
-inline bool make_plan(Plan* p, const Forced& f, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, std::string* why, int wd_hint = 0) {
+// w_hint / wb_hint: warm-ups a previous call on the same bound model needed (0: estimate from the model); wd_hint / wa_hint: the same for the draw's and
+// the adjoint's warm-ups.
+inline bool make_plan(Plan* p, const Forced& f, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, std::string* why, int wd_hint = 0,
+                      int wa_hint = 0) {
     if (m.d < 1 || m.d > kMaxD || T < 1) {
         if (why) *why = "state dimension";
         return false;
     }
     switch (m.d) {
-        case 1: return plan_detail::plan_d<1>(p, f, m, T, w_hint, wb_hint, num_cu, why, wd_hint);
-        case 2: return plan_detail::plan_d<2>(p, f, m, T, w_hint, wb_hint, num_cu, why, wd_hint);
-        case 3: return plan_detail::plan_d<3>(p, f, m, T, w_hint, wb_hint, num_cu, why, wd_hint);
-        default: return plan_detail::plan_d<4>(p, f, m, T, w_hint, wb_hint, num_cu, why, wd_hint);
+        case 1: return plan_detail::plan_d<1>(p, f, m, T, w_hint, wb_hint, num_cu, why, wd_hint, wa_hint);
+        case 2: return plan_detail::plan_d<2>(p, f, m, T, w_hint, wb_hint, num_cu, why, wd_hint, wa_hint);
+        case 3: return plan_detail::plan_d<3>(p, f, m, T, w_hint, wb_hint, num_cu, why, wd_hint, wa_hint);
+        default: return plan_detail::plan_d<4>(p, f, m, T, w_hint, wb_hint, num_cu, why, wd_hint, wa_hint);
     }
 }
 

@@ -608,6 +608,30 @@ def logpdf_adjoint(model, y):
     return lml.value, g
 
 
+def logpdf_adjoint_missing(model, y, per_step=False):
+    """logpdf_adjoint where the gains vary in time -- NaNs in y (or a (y, mask) tuple), a noise variance or an emission offset per step -- by ONE adjoint
+    pass on the sweep engine (tgp_logpdf_adjoint_missing, k_sweep_adjoint): Forward models with shared A, a, Q, H, scalar observations, d <= 4, T >= 2048.
+    Returns (lml, g) with g as logpdf_adjoint gives it; "h" and "R" are the sums of the per-step gradients over the observed steps, whether the stream is
+    shared or per step.  per_step: g also holds "h_steps" and "R_steps" (T,), d logpdf / d h_t and d logpdf / d R_t, zero at missing steps (torch tensors
+    on the model's device where y is one).  Raises Unsupported where the engine declines (use logpdf_and_grad)."""
+    _check_inputs(model, y[0] if isinstance(y, tuple) else y)
+    hd = model.handle()
+    yy, mm, dev = _obs(y, model)
+    d = model.dim
+    g = dict(A=np.zeros((d, d)), a=np.zeros(d), Q=np.zeros((d, d)), H=np.zeros(d), h=np.zeros(1), R=np.zeros(1), x0m=np.zeros(d), x0P=np.zeros((d, d)))
+    steps = [_out(model, (model.T,), dev), _out(model, (model.T,), dev)] if per_step else [None, None]
+    lml = ctypes.c_double()
+    flags = (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0
+    hd.check(hd.lib.tgp_logpdf_adjoint_missing(hd.h, _lib.ptr(yy), _lib.ptr(mm), flags, ctypes.byref(lml),
+                                               *[_lib.ptr(g[k]) for k in ("A", "a", "Q", "H", "h", "R", "x0m", "x0P")], _lib.ptr(steps[0]), _lib.ptr(steps[1])))
+    for k in ("A", "Q", "x0P"):
+        g[k] = g[k].T.copy()          # column-major blocks -> [i][k]
+    g["h"], g["R"] = float(g["h"][0]), float(g["R"][0])
+    if per_step:
+        g["h_steps"], g["R_steps"] = steps
+    return lml.value, g
+
+
 def logpdf_and_grad_sde(model, y, tangents, rel_step=1e-6):
     """The same for a model whose transitions are described by their SDE (SDETransitions: irregular spacing, d <= 4).
     `tangents`: per parameter, the derivatives of F (d,d), x0P == P_inf (d,d), x0m (d,), H (d,), h (), R () and of the explicit

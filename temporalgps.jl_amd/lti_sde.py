@@ -855,6 +855,35 @@ def _logpdf_and_gradient_adjoint(fx, y):
     return lp, grad
 
 
+def _logpdf_and_gradient_sweep(fx, y):
+    """One adjoint pass on the sweep engine (L.logpdf_adjoint_missing: missing observations and / or one noise variance per observation, d <= 4,
+    T >= 2048) contracted with the exact block tangents.  One variance per observation: no "noise" entry (as on the "fd" route)."""
+    if not (isinstance(fx.x, RegularSpacing) and isinstance(fx.f.f.mean, (ZeroMean, ConstMean))):
+        raise NotImplementedError("logpdf_and_gradient(method='sweep'): RegularSpacing inputs with a ZeroMean or ConstMean only")
+    plist = parameters(fx.f.f.kernel)
+    names = [n for n, _, _ in plist] + (["noise"] if fx.sigma2.shape[0] == 1 else []) + (["mean.c"] if isinstance(fx.f.f.mean, ConstMean) else [])
+    lp, g = L.logpdf_adjoint_missing(fx.build_lgssm(), y)
+    grad = {}
+    for name, t in zip(names, _shared_block_tangents(fx, names, plist)):
+        grad[name] = float(sum(_contract(g[k], v) for k, v in t.items()))
+    return lp, grad
+
+
+def _sweep_gradient_applies(fx, y):
+    """the default policy's route to the sweep engine's adjoint pass: regular spacing, a ZeroMean or ConstMean, d <= 4, T >= 2048, and gains that vary in
+    time -- one noise variance per observation, or a NaN in a host y / a mask beside a device y.  Measured (profiles/sweep_adjoint_time.txt, 10 % missing,
+    3 - 5 parameters): 2.0 - 7.7 x the tangent scans' speed by medians at T = 3e3 ... 1e7 (DESIGN 4.8 has the table and its two outliers)."""
+    if not (isinstance(fx.x, RegularSpacing) and isinstance(fx.f.f.mean, (ZeroMean, ConstMean)) and len(fx.x) >= 2048):
+        return False
+    if fx.sigma2.shape[0] == 1:
+        if isinstance(y, tuple):
+            if y[1] is None:
+                return False
+        elif L._is_torch(y) or not np.isnan(np.asarray(y, dtype=np.float64)).any():
+            return False
+    return fx.build_lgssm().dim <= 4
+
+
 def _contract(a, b):
     """sum(a * b) of two same-shaped small arrays or scalars (np.sum of a product costs ~5 us a piece: a dozen per gradient)"""
     if isinstance(a, np.ndarray) and isinstance(b, np.ndarray):
@@ -962,15 +991,19 @@ def logpdf_and_gradient(fx, y, rel_step=None, method=None):
     noise; the per-step tangents of exp(F dt_k) are formed on the device (tgp_logpdf_grad_sde).
     method: None (default policy), "adjoint" (ONE reverse-time pass on the stationary-gain engine, exact block tangents on the host:
     regular spacing, homoscedastic noise, d <= 8, or the wide-state engine for 8 < d <= 63 where its plan applies -- cost independent of the
-    number of parameters), "tangent" (the forward-mode scans)
+    number of parameters), "sweep" (ONE adjoint pass on the sweep engine: regular spacing with NaNs in y and / or one noise variance per
+    observation, ZeroMean or ConstMean, d <= 4, T >= 2048; raises Unsupported where the device declines), "tangent" (the forward-mode scans)
     or "fd" (central differences of the device logpdf).
-    Default: the adjoint pass where it applies, else tangent scans up to state dimension 8; from d = 9 (e.g. ApproxPeriodicKernel, d = 14) the dual-number kernels are
+    Default: the adjoint pass where it applies -- on the stationary-gain engines, or on the sweep engine for d <= 4 and T >= 2048 with missing observations
+    or one noise variance per observation (profiles/sweep_adjoint_time.txt) --, else tangent scans up to state dimension 8; from d = 9 (e.g. ApproxPeriodicKernel, d = 14) the dual-number kernels are
     out-of-line private-memory code (d = 14, T = 2e5: 2.4 s for 4 parameters against 5.7 ms per logpdf), so central differences
     of the logpdf -- 9 evaluations on the group kernels, ~50 ms, relative accuracy ~1e-7 -- are used instead.
     Heteroscedastic noise (one variance per observation) on the "fd" route: the kernel's and the mean's parameters only -- there is no
     single noise parameter to differentiate, the result has no "noise" entry."""
-    if method not in (None, "tangent", "fd", "adjoint"):
-        raise ValueError("method must be None, 'adjoint', 'tangent' or 'fd'")
+    if method not in (None, "tangent", "fd", "adjoint", "sweep"):
+        raise ValueError("method must be None, 'adjoint', 'sweep', 'tangent' or 'fd'")
+    if method == "sweep":
+        return _logpdf_and_gradient_sweep(fx, y)
     if method == "adjoint" or (method is None and isinstance(fx.x, RegularSpacing) and fx.sigma2.shape[0] == 1
                                and isinstance(fx.f.f.mean, (ZeroMean, ConstMean)) and fx.build_lgssm().dim <= 8):
         try:
@@ -978,6 +1011,11 @@ def logpdf_and_gradient(fx, y, rel_step=None, method=None):
         except (L._lib.Unsupported, NotImplementedError):
             if method == "adjoint":
                 raise                       # (default policy: the covariance did not settle within the head etc. -> the tangent scans below)
+    if method is None and _sweep_gradient_applies(fx, y):
+        try:
+            return _logpdf_and_gradient_sweep(fx, y)
+        except L._lib.Unsupported:
+            pass                            # (the device declined: what the default did before -- the tangent scans, or NotImplementedError for per-step noise)
     if method == "fd" or (method is None and isinstance(fx.x, RegularSpacing) and fx.build_lgssm().dim >= 9):
         return _logpdf_and_gradient_fd(fx, y, rel_step=1e-4 if rel_step is None else rel_step)
     rel_step = 1e-6 if rel_step is None else rel_step
