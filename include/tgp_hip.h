@@ -202,9 +202,9 @@ int64_t tgp_graph_replays(const tgp_handle* h);
    the stationary-gain engines, their one-launch kernels and the wide-state engine: T - n0 (n0: the head of steps with gains of their own);
    the general engine: the steps the forward pass of the last posterior-path call ran in the mean-only form. */
 int tgp_steady_steps(tgp_handle* h, int64_t* mean_only, int64_t* total);
-/* Diagnostics of TGP_OPT_SWEEP for the last tgp_logpdf / tgp_[logpdf_and_]posterior_marginals / tgp_posterior_rand_missing / tgp_logpdf_adjoint_missing
-   call. info [8]: served by the sweep engine (0 / 1), steps per chunk, forward warm-up, backward warm-up (tgp_posterior_rand_missing: the draw's;
-   tgp_logpdf_adjoint_missing: the adjoint's, and dist[1] compares the adjoints of its hand-over), waves, attempts (launches),
+/* Diagnostics of TGP_OPT_SWEEP for the last tgp_logpdf / tgp_[logpdf_and_]posterior_marginals / tgp_posterior_rand_missing / tgp_logpdf_adjoint_missing /
+   tgp_logpdf_adjoint_sde call. info [8]: served by the sweep engine (0 / 1), steps per chunk, forward warm-up, backward warm-up (tgp_posterior_rand_missing: the draw's;
+   tgp_logpdf_adjoint_missing / _sde: the adjoint's, and dist[1] compares the adjoints of its hand-over), waves, attempts (launches),
    status bits of the last attempt (1 forward / 2 backward or draw warm-up too short, 4 not positive definite, 8 non-finite), state for the bound
    model (0 untried, 1 serves, -1 declined).  dist [2]: the largest relative distance between a warm-up's end state and the run that reproduces it,
    forwards / backwards (the checks' 1e-12 / 1e-11; tgp_posterior_rand_missing: dist[1] compares the sample states of the draw's hand-over).
@@ -289,7 +289,8 @@ int tgp_logpdf_grad_sde(tgp_handle* h, const double* y, const uint8_t* missing, 
 int tgp_logpdf_adjoint(tgp_handle* h, const double* y, uint32_t flags, double* lml_out, double* gA, double* ga,
                        double* gQ, double* gH, double* ghh, double* gR, double* gx0m, double* gx0P);
 /* The same gradient where the GAINS vary in time -- missing steps (`missing` as in tgp_logpdf), a noise variance or an emission offset per step --
- * by one adjoint pass on the sweep engine (TGP_OPT_SWEEP; k_sweep_adjoint): Forward models with shared A, a, Q, H (not SDE-described),
+ * by one adjoint pass on the sweep engine (TGP_OPT_SWEEP; k_sweep_adjoint): Forward models with shared A, a, Q, H (not SDE-described:
+ * tgp_logpdf_adjoint_sde below),
  * scalar observations, d <= 4, T >= 2048; a model without any gap is served too (tgp_logpdf_adjoint is the faster route for it).  ONE kernel: the
  * engine's forward run with checkpoints, then the adjoint of the recursion backwards over every chunk, started from the next chunk's adjoint, which
  * that chunk got from a warm-up over its own first steps from zero; the hand-over is checked on the adjoints (1e-11 in units of the stationary prior),
@@ -297,11 +298,30 @@ int tgp_logpdf_adjoint(tgp_handle* h, const double* y, uint32_t flags, double* l
  * adjoint's warm-up).  Block outputs as in tgp_logpdf_adjoint (host pointers, any may be NULL); ghh and gR are the sums of the per-step gradients over
  * the observed steps, whether the stream is shared or per step.  gh_steps, gR_steps [T]: d logpdf / d h_t and d logpdf / d R_t of every step, zero at
  * missing steps; NULL to skip, device pointers with TGP_OUT_DEVICE.  Two calls on the same series give the same bits.
- * TGP_EUNSUPPORTED, with no output byte written (host or device): SDE-described models, d > 4, p > 1, Reverse models, T < 2048, TGP_OPT_SWEEP = 0, an
+ * TGP_EUNSUPPORTED, with no output byte written (host or device): SDE-described models (tgp_logpdf_adjoint_sde serves them), d > 4, p > 1, Reverse models, T < 2048, TGP_OPT_SWEEP = 0, an
  * engine declined for the bound model, a forced geometry whose warm-ups are too short, an innovation variance that is not positive, non-finite values
  * (tgp_sweep_info has the status).  The library does not fall back: use tgp_logpdf_grad. */
 int tgp_logpdf_adjoint_missing(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, double* gA, double* ga, double* gQ,
                                double* gH, double* ghh, double* gR, double* gx0m, double* gx0P, double* gh_steps, double* gR_steps);
+/* The same gradient for a model described by its SDE and time stamps (tgp_model_set_sde: irregular spacing; the reference's AbstractVector inputs,
+ * lti_sde.jl:135-146) by one adjoint pass on the sweep engine (k_sweep_adjoint<sde>): Forward models whose exp(F tau) has the closed form
+ * (TGP_OPT_SDE_CLOSED_FORM = 1), shared a and H, scalar observations, d <= 4, T >= 2048; `missing`, a noise variance and an emission offset per step in
+ * any combination.  The kernel contracts every step's d logpdf / d A_t on the spot into sums over the closed form's coefficients and the host finishes
+ * with the transpose of the map F -> coefficients, so the gradient is exact (no finite difference of the exponential) and costs one pass whatever the
+ * number of hyper-parameters.  Outputs (host pointers, column-major, any may be NULL):
+ *   gF [d*d]     d logpdf / d F; entries outside the connected components of F's sparsity pattern (which the closed form never reads) are 0
+ *   gPinf [d*d]  d logpdf / d Pinf (the x0P tgp_model_set_sde was given), symmetrised; the prior's own share is gx0P, apart: a model whose x0P doubles
+ *                as Pinf adds the two
+ *   gA1 [d*d]    d logpdf / d A1 of the explicit first transition; 0 for a model bound without one (its first step is exp(F 1): that share is in gF).
+ *                There is no gQ1: Q1 = Pinf - A1 Pinf A1' is checked on the host and never read by the device
+ *   ga, gH, gx0m [d], ghh, gR [1], gx0P [d*d] (symmetrised), gh_steps, gR_steps [T]: as in tgp_logpdf_adjoint_missing
+ * Warm-ups, checks, repair, TGP_OPT_SWEEP_CHUNK / _WARMUP / _WARMUP_BACK and tgp_sweep_info as for tgp_logpdf_adjoint_missing.  Two calls on the same
+ * series give the same bits.
+ * TGP_EUNSUPPORTED, with no output byte written (host or device): models in LTI form (use tgp_logpdf_adjoint_missing), d > 4, p > 1, Reverse models,
+ * T < 2048, TGP_OPT_SWEEP = 0, no closed form, an engine declined for the bound model, a forced geometry whose warm-ups are too short, an innovation
+ * variance that is not positive, non-finite values.  The library does not fall back: use tgp_logpdf_grad_sde. */
+int tgp_logpdf_adjoint_sde(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, double* gF, double* gPinf, double* gA1,
+                           double* ga, double* gH, double* ghh, double* gR, double* gx0m, double* gx0P, double* gh_steps, double* gR_steps);
 /* The plan of the stationary-gain engine's ONE-LAUNCH path (TGP_OPT_STEADY = 3, the default), a pure host function: what
  * tgp_logpdf / tgp_[logpdf_and_]posterior_marginals build inside every call of a Forward LTI model with one noise variance and scalar
  * observations (d <= 8) before their single kernel -- the covariance half of lgssm.jl:99-238 (predict lgc.jl:46-52, update lgc.jl:247-257,

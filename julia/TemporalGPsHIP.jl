@@ -426,6 +426,27 @@ function logpdf_and_block_gradients_missing(m::DeviceLGSSM{Forward}, y::Abstract
     return lml[], per_step ? merge(g, (h_steps = hs, R_steps = Rs)) : g
 end
 
+"""The same for a model bound by its SDE and time stamps (tgp_logpdf_adjoint_sde: Forward, closed-form exp(F tau), scalar observations, d <= 4,
+T >= 2048). `F` is zero outside the connected components of the drift matrix, `Pinf` and `x0P` are separate (add them where x0P doubles as Pinf), `A1` is
+zero for a model bound without an explicit first transition. `nothing`: TGP_EUNSUPPORTED, take the tangent scans."""
+function logpdf_and_block_gradients_sde(m::DeviceLGSSM{Forward}, y::AbstractVector; per_step::Bool = false)
+    d = m.d
+    yv, mp, mask = _split_missing(y)
+    lml = Ref{Float64}(0.0)
+    gF, gPi, gA1, gP = (Matrix{Float64}(undef, d, d) for _ in 1:4)
+    ga, gH, gm = (Vector{Float64}(undef, d) for _ in 1:3)
+    gh, gR = Ref{Float64}(0.0), Ref{Float64}(0.0)
+    hs, Rs = per_step ? (Vector{Float64}(undef, m.T), Vector{Float64}(undef, m.T)) : (Float64[], Float64[])
+    rc = GC.@preserve yv mask hs Rs ccall((:tgp_logpdf_adjoint_sde, libtgp), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{UInt8}, UInt32, Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64},
+         Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        m.h.ptr, yv, mp, UInt32(0), lml, gF, gPi, gA1, ga, gH, gh, gR, gm, gP, per_step ? pointer(hs) : C_NULL, per_step ? pointer(Rs) : C_NULL)
+    rc == 4 && return nothing
+    check(m.h, rc)
+    g = (F = gF, Pinf = gPi, A1 = gA1, a = ga, H = gH, h = gh[], R = gR[], x0m = gm, x0P = gP)
+    return lml[], per_step ? merge(g, (h_steps = hs, R_steps = Rs)) : g
+end
+
 # ---- one series over the GPUs of a node, one process (tgp_create_multi: one handle + stream + RCCL communicator per device inside
 #      the library; SURVEY.md 8b "Threading", 8e). Rank r owns the contiguous segment tgp_multi_segment gives it; inputs and outputs
 #      are addressed per segment (pointer + offset into the caller's arrays: nothing is copied on the host).

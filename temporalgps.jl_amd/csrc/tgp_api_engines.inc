@@ -375,8 +375,9 @@ int sweep_draw_call(tgp_handle* h, const double* y, const uint8_t* missing, uint
 // pass sits in the backward slots of tgp_sweep_info (its warm-up Wa is remembered apart from Wb and Wd; TGP_OPT_SWEEP_WARMUP_BACK forces it here).  The
 // per-step gradients go to the handle's own buffers and reach gh_steps / gR_steps behind the checks, the block gradients are written behind them too:
 // *served = false with *why set: the engine declined, no output was written.
+// so (null: the LTI form): an SDE-described model -- k_sweep_adjoint_sde (DESIGN 4.9), the sums over the closed form's coefficients go to *so and `o` is unused.
 int sweep_adjoint_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, const tgp_sweep::AdjointOut& o,
-                       double* gh_steps, double* gR_steps, bool* served, std::string* why) {
+                       double* gh_steps, double* gR_steps, bool* served, std::string* why, const tgp_sweep::AdjointSdeOut* so = nullptr) {
     *served = false;
     if (!h->sweep) h->sweep = tgp_sweep::create();
     static const bool dbg = getenv("TGP_STEADY_DEBUG") != nullptr;
@@ -385,15 +386,20 @@ int sweep_adjoint_call(tgp_handle* h, const double* y, const uint8_t* missing, u
     const double* q = h->sweepm.data();
     tgp_sweep::ModelHost mh;
     mh.d = d;
-    mh.sde = false;
-    mh.A = q;
+    mh.sde = so != nullptr;
+    mh.A = so ? h->sde_A1Q1_host.data() : q;
     mh.a = q + dd;
-    mh.Q = q + dd + d;
+    mh.Q = so ? h->sde_A1Q1_host.data() + dd : q + dd + d;
     mh.H = q + 2 * dd + d;
     mh.hh = q[2 * dd + 2 * d];
     mh.R = h->sweep_Rrep;
     mh.x0m = h->x0m.data();
     mh.x0P = h->x0P.data();
+    if (so) {      // (the stationary covariance as tgp_model_set_sde took it: tgp_model_set_x0 may have replaced the prior since)
+        mh.coef = h->sde_coef_host.data();
+        mh.Pinf = h->sde_coef_host.data() + d + 2 * dd;
+        mh.tau_typ = h->sweep_tau;
+    }
     const bool odev = (flags & TGP_OUT_DEVICE) != 0;
     const size_t nT = (size_t)h->T * sizeof(double);
     const bool forced = h->sweep_fW || h->sweep_fWb || h->sweep_fC;
@@ -429,12 +435,13 @@ int sweep_adjoint_call(tgp_handle* h, const double* y, const uint8_t* missing, u
         c.mask = h->mv.missing;
         c.R = h->mv.sR != 0 ? h->mv.R : nullptr;
         c.hh = h->mv.sh != 0 ? h->mv.h : nullptr;
+        c.tau = so ? h->btau.d() : nullptr;
         c.adjoint = true;
         c.gh_steps = dgh;
         c.gR_steps = dgR;
         {
             std::string err;
-            const char* kname = tgp_sweep::adjoint_kernel_name();
+            const char* kname = so ? tgp_sweep::adjoint_sde_kernel_name() : tgp_sweep::adjoint_kernel_name();
             LaunchScope ls(h, kname);
             if (tgp_sweep::enqueue(h->sweep, h->stream, c, &kname, &err) != 0) return h->fail(TGP_EHIP, err);
         }
@@ -466,7 +473,8 @@ int sweep_adjoint_call(tgp_handle* h, const double* y, const uint8_t* missing, u
         if (gh_steps) HIPCHK(hipMemcpyAsync(gh_steps, dgh, nT, odev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
         if (gR_steps) HIPCHK(hipMemcpyAsync(gR_steps, dgR, nT, odev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
         if (gh_steps || gR_steps) HIPCHK(hipStreamSynchronize(h->stream));
-        tgp_sweep::adjoint_blocks(h->sweep, o);
+        if (so) tgp_sweep::adjoint_blocks_sde(h->sweep, *so);
+        else tgp_sweep::adjoint_blocks(h->sweep, o);
         read_timing(h);
         note_served(h, Served::sweep, 0, lml, lml_out);
         h->sweep_W = w;
@@ -479,6 +487,43 @@ int sweep_adjoint_call(tgp_handle* h, const double* y, const uint8_t* missing, u
     h->sweep_state = -1;      // four attempts, warm-ups still too short: a model that mixes too slowly for this engine
     *why = "the warm-ups stayed too short over four attempts";
     return TGP_OK;
+}
+
+// d logpdf / d F from the sums over the closed form's coefficients: the transpose of sde_closed_form's map.  coef = [lam d | N d*d | N^2 / 2 d*d | ...];
+// a connected component S of n rows has N = F_SS + lam I, lam = -tr F_SS / n:  gN = [n >= 2] gN1_SS + [n >= 3] (gN2_SS N' + N' gN2_SS) / 2,
+// gF_SS = gN - ((sum_S gl_i + tr gN) / n) I.  Entries outside the components are zero (the closed form does not read them).
+void sde_coef_to_gF(int d, const double* coef, const double* gl, const double* gN1, const double* gN2, double* gF) {
+    const double* N = coef + d;
+    std::vector<int> comp(d);
+    for (int i = 0; i < d; ++i) comp[i] = i;
+    auto find = [&](int i) { while (comp[i] != i) i = comp[i] = comp[comp[i]]; return i; };
+    for (int j = 0; j < d; ++j)
+        for (int i = 0; i < d; ++i)
+            if (i != j && N[i + j * d] != 0.0) comp[find(i)] = find(j);      // (off the diagonal N is F: the same components)
+    for (int i = 0; i < d * d; ++i) gF[i] = 0.0;
+    std::vector<char> seen(d, 0);
+    for (int r = 0; r < d; ++r) {
+        const int root = find(r);
+        if (seen[root]) continue;
+        seen[root] = 1;
+        std::vector<int> S;
+        for (int i = 0; i < d; ++i)
+            if (find(i) == root) S.push_back(i);
+        const int n = (int)S.size();
+        std::vector<double> gN((size_t)n * n, 0.0);
+        for (int jj = 0; jj < n; ++jj)
+            for (int ii = 0; ii < n; ++ii) {
+                double v = n >= 2 ? gN1[S[ii] + S[jj] * d] : 0.0;
+                if (n >= 3)
+                    for (int k = 0; k < n; ++k)
+                        v += 0.5 * (gN2[S[ii] + S[k] * d] * N[S[jj] + S[k] * d] + N[S[k] + S[ii] * d] * gN2[S[k] + S[jj] * d]);
+                gN[ii + jj * n] = v;
+            }
+        double tr = 0.0;
+        for (int ii = 0; ii < n; ++ii) tr += gl[S[ii]] + gN[ii + ii * n];
+        for (int jj = 0; jj < n; ++jj)
+            for (int ii = 0; ii < n; ++ii) gF[S[ii] + S[jj] * d] = gN[ii + jj * n] - (ii == jj ? tr / n : 0.0);
+    }
 }
 
 bool steady2_served(tgp_handle* h) {

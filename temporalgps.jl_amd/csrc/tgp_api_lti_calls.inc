@@ -495,6 +495,58 @@ int tgp_logpdf_adjoint_missing(tgp_handle* h, const double* y, const uint8_t* mi
     return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_missing: the sweep engine declines the gradient: " + why + " (use tgp_logpdf_grad)");
 }
 
+// The same for a model described by its SDE and time stamps (tgp_model_set_sde: irregular spacing) -- what sweep_eligible accepts in SDE form -- by the
+// engine's k_sweep_adjoint_sde (DESIGN 4.9).  The kernel leaves the sums over the closed form's coefficients (lam, N1, N2), Pinf and the explicit first
+// transition; the host finishes d logpdf / d F by the transpose of sde_closed_form's map.  A model bound without A1 takes exp(F 1) at step 0
+// (tgp_model_set_sde): that step's G_0 is contracted into the coefficient sums with tau = 1 and gA1 is zero.
+int tgp_logpdf_adjoint_sde(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, double* gF, double* gPinf, double* gA1,
+                           double* ga, double* gH, double* ghh, double* gR, double* gx0m, double* gx0P, double* gh_steps, double* gR_steps) {
+    StreamGuard stream_guard_(h);
+    TRY(check_ready(h, /*general=*/false));
+    if (!y) return h->fail(TGP_EINVAL, "tgp_logpdf_adjoint_sde: null argument");
+    if (!h->sde)
+        return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_sde: the model is not SDE-described (tgp_model_set_sde); use tgp_logpdf_adjoint_missing for models in "
+                                         "LTI form");
+    if (!sweep_eligible(h, flags))
+        return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_sde: Forward SDE-described models with closed-form transitions (TGP_OPT_SDE_CLOSED_FORM = 1), shared a "
+                                         "and H, scalar observations, d <= 4 and T >= 2048 on the sweep engine (TGP_OPT_SWEEP = 1, the engine not declined for the "
+                                         "bound model); use tgp_logpdf_grad_sde otherwise");
+    const int d = h->d, dd = d * d;
+    double buf[4 * 16 + 3 * 4 + 2 + 2 * 16];
+    tgp_sweep::AdjointSdeOut so;
+    so.gl = buf; so.gN1 = so.gl + d; so.gN2 = so.gN1 + dd; so.gPinf = so.gN2 + dd; so.gA1 = so.gPinf + dd; so.ga = so.gA1 + dd; so.gH = so.ga + d;
+    so.ghh = so.gH + d; so.gR = so.ghh + 1; so.gx0m = so.gR + 1; so.gx0P = so.gx0m + d;
+    bool served = false;
+    std::string why;
+    TRY(sweep_adjoint_call(h, y, missing, flags, lml_out, tgp_sweep::AdjointOut(), gh_steps, gR_steps, &served, &why, &so));
+    if (!served) return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_sde: the sweep engine declines the gradient: " + why + " (use tgp_logpdf_grad_sde)");
+    const double* coef = h->sde_coef_host.data();
+    if (!h->have_AQ1) {      // step 0 took A1 = E (I + N1 + N2), E = diag(e^(-lam_i)): its G_0 belongs to the coefficients
+        const double* A1 = h->sde_A1Q1_host.data();
+        for (int i = 0; i < d; ++i) {
+            const double e = std::exp(-coef[i]);
+            double s = 0.0;
+            for (int j = 0; j < d; ++j) {
+                s += so.gA1[i + j * d] * A1[i + j * d];
+                so.gN1[i + j * d] += e * so.gA1[i + j * d];
+                so.gN2[i + j * d] += e * so.gA1[i + j * d];
+            }
+            so.gl[i] -= s;
+        }
+        for (int i = 0; i < dd; ++i) so.gA1[i] = 0.0;
+    }
+    if (gF) sde_coef_to_gF(d, coef, so.gl, so.gN1, so.gN2, gF);
+    if (gPinf) std::memcpy(gPinf, so.gPinf, sizeof(double) * dd);
+    if (gA1) std::memcpy(gA1, so.gA1, sizeof(double) * dd);
+    if (ga) std::memcpy(ga, so.ga, sizeof(double) * d);
+    if (gH) std::memcpy(gH, so.gH, sizeof(double) * d);
+    if (ghh) *ghh = *so.ghh;
+    if (gR) *gR = *so.gR;
+    if (gx0m) std::memcpy(gx0m, so.gx0m, sizeof(double) * d);
+    if (gx0P) std::memcpy(gx0P, so.gx0P, sizeof(double) * dd);
+    return TGP_OK;
+}
+
 // Two observations per step of ONE latent value with independent noise are one observation of it:
 //     N(y; f, R) N(y*; f, R*) = N(ybar; f, Rbar) N(y - y*; 0, R + R*),   Rbar = R R* / (R + R*),   ybar = (R* y + R y*) / (R + R*)
 // -- what turns logpdf(replace_observation_noise_cov(posterior(model, y), R*), y*) (posterior_lti_sde.jl:62-78 -> lgssm.jl:147-151 on the

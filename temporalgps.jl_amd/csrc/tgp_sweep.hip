@@ -394,6 +394,168 @@ __global__ __launch_bounds__(64, 1) void k_sweep_adjoint(const AArgs<D> by_value
     }
 }
 
+// The adjoint gradient of an SDE-described model: k_sweep_adjoint's skeleton with the transitions built from the gaps and the sums over
+// (lam, N1, N2, Pinf) in place of (A, Q).  part[wave]: [lml, bits, dist_f, dist_b | gl d | gN1 d*d | gN2 d*d | gPinf packed | ga d | gH d | sum gh_t |
+// sum gR_t | gA1 d*d | gx0m d | gx0P packed].  d = 4: the gl and gN2 sums of a lane sit in LDS behind the block's states (SdeSums).
+template <int D> struct AdjPartsSde {
+    static constexpr int NG = AdjAccSde<D>::N + D * D + SD<D>::NS, STRIDE = 4 + NG;
+};
+
+template <int D, int XS>
+__global__ __launch_bounds__(64, 1) void k_sweep_adjoint_sde(const AArgs<D> by_value) {
+    (void)by_value;
+    const AArgs<D>& ar = *(const AArgs<D>*)__builtin_amdgcn_kernarg_segment_ptr();
+    const KArgs<D>& ka = ar.ka;
+    constexpr int B = SdeSums<D>::B, NS = SD<D>::NS, DS = SD<D>::DS;
+    constexpr bool LDS = SdeSums<D>::LDS;
+    constexpr int NL = SdeSums<D>::NL;
+    __shared__ double sF[B * NS * 64];      // the block's filtering states
+    __shared__ double sS[LDS ? NL * 64 : 1];      // (d = 4) the lanes' gl and gN2 sums
+    __shared__ double sA1[D * D];           // G_0 of the series' first step (one lane of wave 0)
+    const int lane = threadIdx.x;
+    const long long wave = blockIdx.x;
+    const long long T = ka.T;
+    const int C = ka.C;
+    const long long c = wave * kOwned + lane - 1;
+    const bool active = c >= 0 && c < ka.nchunks;
+    const long long t0 = active ? c * C : 0;
+    long long t1 = active ? t0 + C : 0;
+    t1 = t1 < T ? t1 : (active ? T : 0);
+    const long long t1r = (t1 + 7) & ~7ll;
+    const bool runs = active && lane >= 1;
+    const bool owned = runs && lane <= kOwned;
+    bool ok = true;
+
+    if constexpr (LDS) {
+#pragma unroll
+        for (int k = 0; k < NL; ++k) sS[k * 64 + lane] = 0.0;
+    }
+    if (lane < D * D) sA1[lane] = 0.0;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+
+    ModelR<D, true> mr;
+    mr.init(ka.mc);
+    State<D> gen, x0;
+    set_state<D>(gen, ka.mc.gm, ka.mc.gP);
+    set_state<D>(x0, ka.mc.x0m, ka.mc.x0P);
+    double* ck = ka.ckpt + (size_t)wave * (size_t)(C / B) * NS * 64;
+
+    // ---- forwards: the warm-up over the chunk's last W steps, the shift, the chunk with its checkpoints
+    State<D> x, e1;
+    LmlAcc acc;
+    {
+        const long long tw = t1r - ka.W;
+        x = tw <= 0 ? x0 : gen;
+        for (int seg = 0; seg < 2; ++seg) {      // (ONE call site for both runs: the loop body exists once)
+            const bool warm = seg == 0;
+            forward_run<D, true, XS, B>(ka, mr, warm ? tw : t0, warm ? ka.W / B : C / B, warm ? (tw > 0 ? tw : 0) : t0, warm ? t1r : (runs ? t1r : t0), x, acc, !warm,
+                                        warm ? (double*)nullptr : ck, lane, ok);
+            if (warm) {
+                e1 = x;
+#pragma unroll
+                for (int k = 0; k < D; ++k) x.m[k] = shfl_up1(e1.m[k]);
+#pragma unroll
+                for (int k = 0; k < DS; ++k) x.P[k] = shfl_up1(e1.P[k]);
+                if (t0 == 0) x = x0;
+                acc = LmlAcc();
+            }
+        }
+    }
+    double dist_f = 0.0, dist_b = 0.0;
+    bool finite = true;
+    if (owned) {
+        dist_f = state_distance<D>(ka.mc, x, e1);
+        finite = state_finite<D>(x) && state_finite<D>(e1);
+    }
+
+    // ---- backwards, the warm-up: the adjoint in front of the chunk's first step as its first Wa steps give it from zero
+    Adj<D> b1;
+    b1.zero();
+    {
+        const long long te = (t0 + ka.Wb < t1) ? t0 + ka.Wb : t1;
+        adjoint_run_sde<D, XS, B, false>(ka, mr, t0, ka.Wb / B, runs ? te : t0, b1, (AdjAccSde<D>*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr,
+                                         (double*)nullptr, ck, sF, lane, ok);
+    }
+    // ---- backwards, the chunk: from the next lane's adjoint in front of ITS first step (zero behind the series' last step)
+    Adj<D> ad;
+#pragma unroll
+    for (int k = 0; k < D; ++k) ad.l[k] = shfl_dn1(b1.l[k]);
+#pragma unroll
+    for (int k = 0; k < DS; ++k) ad.L[k] = shfl_dn1(b1.L[k]);
+    if (t1 == T) ad.zero();
+    AdjAccSde<D> ga;
+    ga.zero();
+    adjoint_run_sde<D, XS, B, true>(ka, mr, t0, C / B, owned ? t1 : t0, ad, &ga, sS + lane, sA1, ar.gh_steps, ar.gR_steps, ck, sF, lane, ok);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+
+    // ---- the wave's share: fixed-order sums over the lanes
+    constexpr int NG = AdjPartsSde<D>::NG;
+    double g[NG];
+    {
+        int n = 0;
+#pragma unroll
+        for (int k = 0; k < D; ++k) g[n++] = LDS ? sS[(LDS ? k : 0) * 64 + lane] : ga.gl[k];
+#pragma unroll
+        for (int k = 0; k < D * D; ++k) g[n++] = ga.gN1[k];
+#pragma unroll
+        for (int k = 0; k < D * D; ++k) g[n++] = LDS ? sS[(LDS ? D + k : 0) * 64 + lane] : ga.gN2[k];
+#pragma unroll
+        for (int k = 0; k < DS; ++k) g[n++] = ga.gPinf[k];
+#pragma unroll
+        for (int k = 0; k < D; ++k) g[n++] = ga.ga[k];
+#pragma unroll
+        for (int k = 0; k < D; ++k) g[n++] = ga.gH[k];
+        g[n++] = ga.gh;
+        g[n++] = ga.gR;
+        const bool first = owned && c == 0;      // the adjoint in front of step 0 is the gradient of the series' prior
+#pragma unroll
+        for (int k = 0; k < D * D; ++k) g[n++] = first ? sA1[k] : 0.0;
+#pragma unroll
+        for (int k = 0; k < D; ++k) g[n++] = first ? ad.l[k] : 0.0;
+#pragma unroll
+        for (int k = 0; k < DS; ++k) g[n++] = first ? ad.L[k] : 0.0;
+    }
+    if (owned) {
+        dist_b = adjoint_distance<D>(ka.mc, ad, b1);
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < D; ++k) s += ::fabs(ad.l[k]) + ::fabs(b1.l[k]);
+#pragma unroll
+        for (int k = 0; k < DS; ++k) s += ::fabs(ad.L[k]) + ::fabs(b1.L[k]);
+#pragma unroll
+        for (int k = 0; k < NG; ++k) s += ::fabs(g[k]);
+        finite = finite && (s < 1e300);
+    }
+    double lml = owned ? acc.total() : 0.0;
+    finite = finite && (::fabs(lml) < 1e300);
+    unsigned bits = 0;
+    if (owned && !(dist_f <= ka.mc.tol)) bits |= 1u;
+    if (owned && !(dist_b <= ka.mc.tol_b)) bits |= 2u;
+    if (!ok) bits |= 4u;
+    if (!finite) bits |= 8u;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        lml += __shfl_xor(lml, off, 64);
+        bits |= (unsigned)__shfl_xor((int)bits, off, 64);
+        const double of = __shfl_xor(dist_f, off, 64), ob = __shfl_xor(dist_b, off, 64);
+        dist_f = (of > dist_f) ? of : dist_f;
+        dist_b = (ob > dist_b) ? ob : dist_b;
+#pragma unroll
+        for (int k = 0; k < NG; ++k) g[k] += __shfl_xor(g[k], off, 64);
+    }
+    if (lane == 0) {
+        double* p = ka.part + (size_t)wave * AdjPartsSde<D>::STRIDE;
+        p[0] = lml;
+        p[1] = (double)bits;
+        p[2] = dist_f;
+        p[3] = dist_b;
+#pragma unroll
+        for (int k = 0; k < NG; ++k) p[4 + k] = g[k];
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------------ host side
 struct Engine {
     Plan p;
@@ -476,9 +638,19 @@ template <int D, int XS> void launch_adjoint(Engine* e, hipStream_t stream, cons
     hipLaunchKernelGGL((k_sweep_adjoint<D, XS>), dim3((unsigned)e->p.nwaves), dim3(64), 0, stream, ar);
 }
 
+template <int D, int XS> void launch_adjoint_sde(Engine* e, hipStream_t stream, const Call& c) {
+    AArgs<D> ar;
+    fill_args<D>(e, c, ar.ka);
+    ar.ka.Wb = e->p.Wa;
+    ar.gh_steps = c.gh_steps;
+    ar.gR_steps = c.gR_steps;
+    hipLaunchKernelGGL((k_sweep_adjoint_sde<D, XS>), dim3((unsigned)e->p.nwaves), dim3(64), 0, stream, ar);
+}
+
 template <int D, bool SDE, int XS> void launch_x(Engine* e, hipStream_t stream, const Call& c) {
     if (c.adjoint) {
-        if constexpr (!SDE) launch_adjoint<D, XS>(e, stream, c);      // (enqueue has refused the SDE form)
+        if constexpr (SDE) launch_adjoint_sde<D, XS>(e, stream, c);
+        else launch_adjoint<D, XS>(e, stream, c);
     } else if (c.y_out != nullptr) launch_draw<D, SDE, XS>(e, stream, c);
     else if (c.mean != nullptr) launch<D, SDE, XS, true>(e, stream, c);
     else launch<D, SDE, XS, false>(e, stream, c);
@@ -505,6 +677,7 @@ const char* kernel_name(int, bool sde, bool post, bool draw) {
 }
 
 const char* adjoint_kernel_name() { return "k_sweep_adjoint<lti>"; }
+const char* adjoint_sde_kernel_name() { return "k_sweep_adjoint<sde>"; }
 
 int enqueue(Engine* e, hipStream_t stream, const Call& c, const char** kname, std::string* err) {
     auto fail = [&](const char* what, hipError_t rc) {
@@ -514,12 +687,13 @@ int enqueue(Engine* e, hipStream_t stream, const Call& c, const char** kname, st
     const Plan& p = e->p;
     const bool draw = c.y_out != nullptr;
     const bool post = c.mean != nullptr || draw || c.adjoint;      // (the draw and the adjoint keep the posterior call's checkpoints)
-    if (c.adjoint && (p.sde || draw || c.mean != nullptr)) {
-        if (err) *err = "k_sweep_adjoint: the LTI form only, and no other output in the call";
+    if (c.adjoint && (draw || c.mean != nullptr)) {
+        if (err) *err = "k_sweep_adjoint: no other output in the call";
         return 1;
     }
     const int NS = p.d + p.d * (p.d + 1) / 2;
     e->part_stride = c.adjoint ? 4 + (p.d * p.d + 2 * p.d + (NS - p.d) + 2) + NS : 4;      // (AdjParts<d>::STRIDE: 4, AdjAcc<d>::N, an adjoint)
+    if (c.adjoint && p.sde) e->part_stride = 4 + (3 * p.d + 2 * p.d * p.d + (NS - p.d) + 2) + p.d * p.d + NS;      // (AdjPartsSde<d>::STRIDE)
     const size_t need_part = (size_t)p.nwaves * e->part_stride * sizeof(double);
     if (need_part > e->part_cap) {
         if (e->part) (void)tgp_alloc::host_free(e->part);
@@ -531,7 +705,7 @@ int enqueue(Engine* e, hipStream_t stream, const Call& c, const char** kname, st
         e->part_cap = cap;
     }
     if (post) {
-        const int B = p.d <= 3 ? 8 : 4;
+        const int B = (c.adjoint && p.sde) ? sde_adjoint_block(p.d) : (p.d <= 3 ? 8 : 4);
         const size_t need = (size_t)p.nwaves * (size_t)(p.C / B) * NS * 64 * sizeof(double);
         if (need > e->ckpt_cap) {
             if (e->ckpt) (void)tgp_alloc::dev_free(e->ckpt);
@@ -546,7 +720,7 @@ int enqueue(Engine* e, hipStream_t stream, const Call& c, const char** kname, st
         if (err) *err = "k_sweep_draw: a draw needs eps_t, eps_e and Rnew";
         return 1;
     }
-    if (kname) *kname = c.adjoint ? adjoint_kernel_name() : kernel_name(p.d, p.sde, post, draw);
+    if (kname) *kname = c.adjoint ? (p.sde ? adjoint_sde_kernel_name() : adjoint_kernel_name()) : kernel_name(p.d, p.sde, post, draw);
     switch (p.d) {
         case 1: launch_d<1>(e, stream, c); break;
         case 2: launch_d<2>(e, stream, c); break;
@@ -598,6 +772,32 @@ void adjoint_blocks(const Engine* e, const AdjointOut& o) {
     if (o.gR) *o.gR = gs[1];
     if (o.gx0m) std::memcpy(o.gx0m, gm, sizeof(double) * d);
     if (o.gx0P) unpack(gP, o.gx0P);
+}
+
+void adjoint_blocks_sde(const Engine* e, const AdjointSdeOut& o) {
+    const int d = e->p.d, dd = d * d, ds = d * (d + 1) / 2, ng = e->part_stride - 4;
+    std::vector<double> g((size_t)ng, 0.0);
+    for (int64_t i = 0; i < e->p.nwaves; ++i) {      // fixed order: two calls on the same series give the same bits
+        const double* q = e->part + (size_t)i * e->part_stride + 4;
+        for (int k = 0; k < ng; ++k) g[(size_t)k] += q[k];
+    }
+    const double *gl = g.data(), *gN1 = gl + d, *gN2 = gN1 + dd, *gPi = gN2 + dd, *ga = gPi + ds, *gH = ga + d, *gs = gH + d, *gA1 = gs + 2, *gm = gA1 + dd,
+                 *gP = gm + d;
+    auto unpack = [d](const double* packed, double* full) {
+        for (int j = 0; j < d; ++j)
+            for (int i = 0; i < d; ++i) full[i + j * d] = packed[pidx(i, j)];
+    };
+    std::memcpy(o.gl, gl, sizeof(double) * d);
+    std::memcpy(o.gN1, gN1, sizeof(double) * dd);
+    std::memcpy(o.gN2, gN2, sizeof(double) * dd);
+    unpack(gPi, o.gPinf);
+    std::memcpy(o.ga, ga, sizeof(double) * d);
+    std::memcpy(o.gH, gH, sizeof(double) * d);
+    *o.ghh = gs[0];
+    *o.gR = gs[1];
+    std::memcpy(o.gA1, gA1, sizeof(double) * dd);
+    std::memcpy(o.gx0m, gm, sizeof(double) * d);
+    unpack(gP, o.gx0P);
 }
 
 }  // namespace tgp_sweep

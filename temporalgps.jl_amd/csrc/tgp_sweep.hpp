@@ -23,6 +23,8 @@
 // recursion: (l, L) = d logpdf / d (m, P) of a filtering state, as large as the state, walks back over the chunk from the next lane's adjoint in front
 // of ITS first step, which that lane got from a walk over its own first Wa steps from zero (the adjoint forgets at the filter's rate); the hand-over is
 // checked on the adjoints.  A lane sums the gradients with respect to the shared blocks over its steps, the wave adds its lanes' sums, the host the waves'.
+// SDE-described models (k_sweep_adjoint_sde): the same walk with the transitions built from the gaps; d logpdf / d A_t of a step is contracted
+// on the spot into sums over the closed form's coefficients (lam, N1, N2) and the stationary covariance.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -55,7 +57,7 @@ struct Call {
     const double* eps_e = nullptr;        // device [T]
     double eps_0[4] = {0.0, 0.0, 0.0, 0.0};      // the start x_(T-1): travels in the kernel arguments
     double* y_out = nullptr;              // device [T]
-    // the adjoint gradient instead (mean / var / y_out null): k_sweep_adjoint, LTI form
+    // the adjoint gradient instead (mean / var / y_out null): k_sweep_adjoint (LTI form), k_sweep_adjoint_sde (SDE form)
     bool adjoint = false;
     double* gh_steps = nullptr;           // device [T] or null: d logpdf / d h_t, d logpdf / d R_t of every step (zero at missing ones)
     double* gR_steps = nullptr;
@@ -63,6 +65,13 @@ struct Call {
 // where adjoint_blocks writes the gradient with respect to the shared blocks (host, column-major, any null; ghh / gR: the sums over the observed steps)
 struct AdjointOut {
     double *gA = nullptr, *ga = nullptr, *gQ = nullptr, *gH = nullptr, *ghh = nullptr, *gR = nullptr, *gx0m = nullptr, *gx0P = nullptr;
+};
+
+// the same for an SDE-described model (host, column-major, none null): the sums over the closed form's coefficients (lam per row, N1, N2 = N^2 / 2), the
+// stationary covariance (symmetric), the explicit first transition; the caller finishes d logpdf / d F by the transpose of its own coefficient map
+struct AdjointSdeOut {
+    double *gl = nullptr, *gN1 = nullptr, *gN2 = nullptr, *gPinf = nullptr, *gA1 = nullptr, *ga = nullptr, *gH = nullptr, *ghh = nullptr, *gR = nullptr,
+           *gx0m = nullptr, *gx0P = nullptr;
 };
 
 // Chooses the geometry (chunk length, warm-ups) for this model and series; false: the engine declines (`why` says so).
@@ -73,12 +82,14 @@ bool plan(Engine* e, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int
 int enqueue(Engine* e, hipStream_t stream, const Call& c, const char** kernel_name, std::string* err);
 const char* kernel_name(int d, bool sde, bool post, bool draw = false);
 const char* adjoint_kernel_name();
+const char* adjoint_sde_kernel_name();
 // After the stream has been synchronised.  status bits: 1 forward warm-up too short, 2 backward warm-up too short, 4 not positive definite,
 // 8 non-finite values.  *w / *wb: the warm-ups the call ran with.  A draw: bit 2 and *dist_b are the draw warm-up's (*wd), the returned value is 0.
 // An adjoint call: bit 2 and *dist_b are the adjoint warm-up's (*wa), the returned value is the log marginal likelihood.
 double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* dist_b, int* wd = nullptr, int* wa = nullptr);
 // Behind finish of an adjoint call whose status is clean: the waves' sums, added in wave order.
 void adjoint_blocks(const Engine* e, const AdjointOut& out);
+void adjoint_blocks_sde(const Engine* e, const AdjointSdeOut& out);
 // geometry of the last plan (diagnostics / tests)
 void geometry(const Engine* e, int* C, int* W, int* Wb, int64_t* nwaves, int* Wd = nullptr);
 // test hook: force the geometry of the next plan (0: automatic)

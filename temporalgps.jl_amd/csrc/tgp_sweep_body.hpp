@@ -1252,4 +1252,201 @@ TGP_HD void adjoint_run(const KArgs<D>& ka, const ModelR<D, false>& mr, long lon
     }
 }
 
+// ---- the same adjoint for SDE-described models (k_sweep_adjoint_sde): irregular spacing ---------------------------------------------------
+// The transition of step t >= 1 is A_t = E (I + tau N1 + tau^2 N2), E = diag(e^(-lam_i tau)), its covariance half runs through Pinf (predict_r<D, true>:
+// P_p = A (P - Pinf) A' + Pinf); step 0's is the explicit A1.  G_t = d logpdf / d A_t = mb m' + 2 Pb (A (P - Pinf)) is never stored: it is contracted on the
+// spot into the sums over (lam, N1, N2) -- gl_i -= tau sum_j G_ij A_ij, gN1_ij += tau e_i G_ij, gN2_ij += tau^2 e_i G_ij (a tie, tau = 0, adds nothing) --
+// and Pinf collects Pb - A' Pb A.  Step 0 gives gA1 = G_0 (one lane of one wave, once: written through a pointer, not summed).
+// LDS: the lane's gl and gN2 sums live in shared memory ([component][lane] behind sG) instead of registers (d = 4: the register budget).
+TGP_HD constexpr int sde_adjoint_block(int d) { return d <= 2 ? 8 : (d == 3 ? 4 : 2); }
+template <int D> struct SdeSums {
+    static constexpr bool LDS = D >= 4;
+    static constexpr int NL = D + D * D;      // doubles per lane behind sG: gl, gN2
+    // steps per block of this pass (Geo<D>::B for the others): shorter blocks at d >= 3 -- half the inputs in flight, half the states in LDS -- are what
+    // keeps the kernel under 512 registers without spills; the forward run writes its checkpoints at this pass's own spacing
+    static constexpr int B = sde_adjoint_block(D);
+};
+template <int D> struct AdjAccSde {
+    static constexpr int N = D + 2 * D * D + SD<D>::DS + 2 * D + 2;
+    double gl[D], gN1[D * D], gN2[D * D], gPinf[SD<D>::DS], ga[D], gH[D], gh, gR;
+    TGP_HD void zero() {
+        TGP_UNROLL for (int i = 0; i < D * D; ++i) gN1[i] = gN2[i] = 0.0;
+        TGP_UNROLL for (int i = 0; i < D; ++i) gl[i] = ga[i] = gH[i] = 0.0;
+        TGP_UNROLL for (int i = 0; i < SD<D>::DS; ++i) gPinf[i] = 0.0;
+        gh = gR = 0.0;
+    }
+};
+
+// A_t as step_A<D, true> builds it (the same operations: the same bits), with the exponentials kept
+template <int D> TGP_HD void step_A_sde(const ModelC<D>& mc, const ModelR<D, true>& mr, double tau, bool first, double* A, double* e) {
+    e[0] = ::exp(-mr.lam[0] * tau);
+    TGP_UNROLL for (int i = 1; i < D; ++i) e[i] = (mr.lam[i] == mr.lam[i - 1]) ? e[i - 1] : ::exp(-mr.lam[i] * tau);
+    const double t2 = tau * tau;
+    TGP_UNROLL for (int j = 0; j < D; ++j)
+        TGP_UNROLL for (int i = 0; i < D; ++i) A[i + j * D] = e[i] * ::fma(t2, mr.N2[i + j * D], ::fma(tau, mr.N1[i + j * D], i == j ? 1.0 : 0.0));
+    if (first) {
+        TGP_UNROLL for (int i = 0; i < D * D; ++i) A[i] = mc.A[i];
+    }
+}
+
+// One step backwards (adjoint_step's roles).  tau: the gap in front of step t; first: t == 0.  gA1 (ACC): where step 0 writes G_0, D * D doubles.
+// sG (ACC, SdeSums<D>::LDS): this lane's slot of the shared sums, component k at sG[k * 64].
+template <int D, bool ACC>
+TGP_HD void adjoint_step_sde(const ModelC<D>& mc, const ModelR<D, true>& mr, const State<D>& xf, double tau, bool first, double hh, double R, double y, bool obs,
+                             Adj<D>& ad, AdjAccSde<D>* acc, double* sG, double* gA1, double& gh_t, double& gR_t) {
+    constexpr int DS = SD<D>::DS;
+    double A[D * D], e[D];
+    step_A_sde<D>(mc, mr, tau, first, A, e);
+    // the filter's own predict, to the bit (predict_r<D, true> without AP_out), with A (P - Pinf) kept
+    double mp[D], Pp[DS], AX[D * D];
+    TGP_UNROLL for (int i = 0; i < D; ++i) {
+        double a = mr.a[i];
+        TGP_UNROLL for (int k = 0; k < D; ++k) a = ::fma(A[i + k * D], xf.m[k], a);
+        mp[i] = a;
+    }
+    {
+        double Dm[DS];
+        TGP_UNROLL for (int i = 0; i < DS; ++i) Dm[i] = xf.P[i] - mr.Qg[i];
+        mul_A_sym<D>(A, Dm, AX);
+        mul_AXAt_plus<D>(AX, A, mr.Qg, Pp);
+    }
+    double V[D];
+    TGP_UNROLL for (int j = 0; j < D; ++j) {
+        double a = 0.0;
+        TGP_UNROLL for (int k = 0; k < D; ++k) a = ::fma(mr.H[k], Pp[pidx(k, j)], a);
+        V[j] = a;
+    }
+    double s2 = R, hm = hh;
+    TGP_UNROLL for (int k = 0; k < D; ++k) {
+        s2 = ::fma(V[k], mr.H[k], s2);
+        hm = ::fma(mr.H[k], mp[k], hm);
+    }
+    const double S = obs ? s2 : 1.0;
+    const double iS = obs ? fast_rcp(S) : 0.0;
+    const double v = obs ? (y - hm) : 0.0;
+    const double viS = v * iS;
+    double LV[D], lV = 0.0, VLV = 0.0;
+    TGP_UNROLL for (int i = 0; i < D; ++i) {
+        double a = 0.0;
+        TGP_UNROLL for (int k = 0; k < D; ++k) a = ::fma(ad.L[pidx(i, k)], V[k], a);
+        LV[i] = a;
+        lV = ::fma(ad.l[i], V[i], lV);
+    }
+    TGP_UNROLL for (int i = 0; i < D; ++i) VLV = ::fma(V[i], LV[i], VLV);
+    const double vbar = (lV - v) * iS;
+    const double Sbar = ::fma(::fma(-lV, v, VLV) * iS, iS, -0.5 * ::fma(-viS, viS, iS));
+    double Vb[D];
+    TGP_UNROLL for (int i = 0; i < D; ++i) Vb[i] = ::fma(Sbar, mr.H[i], ::fma(ad.l[i], viS, -2.0 * iS * LV[i]));
+    gh_t = -vbar;
+    gR_t = Sbar;
+    double mb[D], Pb[DS];
+    TGP_UNROLL for (int i = 0; i < D; ++i) mb[i] = ::fma(-vbar, mr.H[i], ad.l[i]);
+    TGP_UNROLL for (int j = 0; j < D; ++j)
+        TGP_UNROLL for (int i = 0; i <= j; ++i) Pb[pidx(i, j)] = ::fma(0.5, ::fma(Vb[i], mr.H[j], mr.H[i] * Vb[j]), ad.L[pidx(i, j)]);
+    // l <- A' mb;  L <- A' Pb A
+    TGP_UNROLL for (int i = 0; i < D; ++i) {
+        double a = 0.0;
+        TGP_UNROLL for (int k = 0; k < D; ++k) a = ::fma(A[k + i * D], mb[k], a);
+        ad.l[i] = a;
+    }
+    double AtP[D * D];
+    TGP_UNROLL for (int j = 0; j < D; ++j)
+        TGP_UNROLL for (int i = 0; i < D; ++i) {
+            double a = 0.0;
+            TGP_UNROLL for (int k = 0; k < D; ++k) a = ::fma(A[k + i * D], Pb[pidx(k, j)], a);
+            AtP[i + j * D] = a;
+        }
+    TGP_UNROLL for (int j = 0; j < D; ++j)
+        TGP_UNROLL for (int i = 0; i <= j; ++i) {
+            double a = 0.0;
+            TGP_UNROLL for (int k = 0; k < D; ++k) a = ::fma(AtP[i + k * D], A[k + j * D], a);
+            ad.L[pidx(i, j)] = a;
+        }
+    if constexpr (ACC) {
+        TGP_UNROLL for (int i = 0; i < D; ++i) {
+            double a = ::fma(Sbar, V[i], -vbar * mp[i]);
+            TGP_UNROLL for (int k = 0; k < D; ++k) a = ::fma(Pp[pidx(i, k)], Vb[k], a);
+            acc->gH[i] += a;
+            acc->ga[i] += mb[i];
+        }
+        acc->gh -= vbar;
+        acc->gR += Sbar;
+        TGP_UNROLL for (int i = 0; i < DS; ++i) acc->gPinf[i] += Pb[i] - ad.L[i];
+        const double tc = first ? 0.0 : tau, tc2 = tc * tc;      // (step 0's gap entry is a marker, not a gap)
+        TGP_UNROLL for (int i = 0; i < D; ++i) {
+            double ga_i = 0.0;
+            const double w1 = tc * e[i], w2 = tc2 * e[i];
+            TGP_UNROLL for (int k = 0; k < D; ++k) {      // G[i][k] = mb_i m_k + 2 sum_j Pb_ij (A (P - Pinf))_jk
+                double a = 0.0;
+                TGP_UNROLL for (int j = 0; j < D; ++j) a = ::fma(Pb[pidx(i, j)], AX[j + k * D], a);
+                const double G = ::fma(2.0, a, mb[i] * xf.m[k]);
+                ga_i = ::fma(G, A[i + k * D], ga_i);
+                acc->gN1[i + k * D] = ::fma(w1, G, acc->gN1[i + k * D]);
+                if constexpr (SdeSums<D>::LDS) sG[(D + i + k * D) * 64] = ::fma(w2, G, sG[(D + i + k * D) * 64]);
+                else acc->gN2[i + k * D] = ::fma(w2, G, acc->gN2[i + k * D]);
+                if (first) gA1[i + k * D] = G;
+            }
+            if constexpr (SdeSums<D>::LDS) sG[i * 64] = ::fma(-tc, ga_i, sG[i * 64]);
+            else acc->gl[i] = ::fma(-tc, ga_i, acc->gl[i]);
+        }
+    }
+}
+
+// The adjoint walk of a lane over its chunk (adjoint_run's roles and layout), SDE form.
+template <int D, int XS, int B, bool ACC>
+TGP_HD void adjoint_run_sde(const KArgs<D>& ka, const ModelR<D, true>& mr, long long t0, int nblk, long long hi, Adj<D>& ad, AdjAccSde<D>* acc, double* sG, double* gA1,
+                            double* gh_steps, double* gR_steps, const double* ckpt, double* sF, int lane, bool& ok) {
+    constexpr int NS = SD<D>::NS, DS = SD<D>::DS;
+    const long long T = ka.T;
+    Inputs<D, true, XS, B> in, nx;
+    const long long tlast = t0 + (long long)(nblk - 1) * B;
+    load_inputs<D, true, XS, B>(ka, tlast, in);
+    State<D> ck, ckN;
+    {
+        const double* q = ckpt + (size_t)(nblk > 0 ? nblk - 1 : 0) * NS * 64 + lane;
+        TGP_UNROLL for (int k = 0; k < D; ++k) ck.m[k] = q[(size_t)k * 64];
+        TGP_UNROLL for (int k = 0; k < DS; ++k) ck.P[k] = q[(size_t)(D + k) * 64];
+    }
+    for (int b = nblk - 1; b >= 0; --b) {
+        const long long tb = t0 + (long long)b * B;
+        load_inputs<D, true, XS, B>(ka, tb - B, nx);      // the next block (block b - 1): in flight through this one
+        {
+            const double* q = ckpt + (size_t)(b > 0 ? b - 1 : 0) * NS * 64 + lane;
+            TGP_UNROLL for (int k = 0; k < D; ++k) ckN.m[k] = q[(size_t)k * 64];
+            TGP_UNROLL for (int k = 0; k < DS; ++k) ckN.P[k] = q[(size_t)(D + k) * 64];
+        }
+        TGP_ISSUE_BARRIER();
+        // ---- the block's filtering states, forwards from its checkpoint (the last step's is not needed: nothing walks from it)
+        State<D> x = ck;
+        TGP_UNROLL for (int j = 0; j + 1 < B; ++j) {
+            double A[D * D];
+            step_A<D, true>(ka.mc, mr, in.tau[j], tb + j == 0, A);
+            predict_r<D, true>(mr, A, x.m, x.P);
+            update<D>(mr.H, (XS & 2) ? in.hh[j] : mr.hh, (XS & 1) ? in.R[j] : mr.R, in.y[j], in.obs(j, tb + j, T), x.m, x.P, (LmlAcc*)nullptr, ok);
+            TGP_UNROLL for (int k = 0; k < D; ++k) sF[(j * NS + k) * 64 + lane] = x.m[k];
+            TGP_UNROLL for (int k = 0; k < DS; ++k) sF[(j * NS + D + k) * 64 + lane] = x.P[k];
+        }
+        TGP_ISSUE_BARRIER();      // (the states are to be read back from LDS: backward_run)
+        TGP_UNROLL for (int j = B - 1; j >= 0; --j) {
+            const long long t = tb + j;
+            if (t < hi) {
+                State<D> xf = ck;
+                if (j > 0) {
+                    TGP_UNROLL for (int k = 0; k < D; ++k) xf.m[k] = sF[((j - 1) * NS + k) * 64 + lane];
+                    TGP_UNROLL for (int k = 0; k < DS; ++k) xf.P[k] = sF[((j - 1) * NS + D + k) * 64 + lane];
+                }
+                double gh_t, gR_t;
+                adjoint_step_sde<D, ACC>(ka.mc, mr, xf, in.tau[j], t == 0, (XS & 2) ? in.hh[j] : mr.hh, (XS & 1) ? in.R[j] : mr.R, in.y[j], in.obs(j, t, T), ad, acc,
+                                         sG, gA1, gh_t, gR_t);
+                if constexpr (ACC) {
+                    if (gh_steps != nullptr) gh_steps[t] = gh_t;
+                    if (gR_steps != nullptr) gR_steps[t] = gR_t;
+                }
+            }
+        }
+        in = nx;
+        ck = ckN;
+    }
+}
+
 }  // namespace tgp_sweep

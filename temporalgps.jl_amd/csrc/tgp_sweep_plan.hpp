@@ -24,7 +24,8 @@ struct ModelHost {
     const double* H = nullptr;      // [d]
     double hh = 0.0, R = 0.0;       // shared values (ignored where a per-step stream is given; R also feeds the warm-up estimate)
     const double* x0m = nullptr;    // [d]
-    const double* x0P = nullptr;    // [d*d]  (SDE: also Pinf)
+    const double* x0P = nullptr;    // [d*d]  (SDE: also Pinf, unless Pinf is given)
+    const double* Pinf = nullptr;   // SDE, optional: [d*d] the stationary covariance of a model whose prior was replaced (tgp_model_set_x0)
     const double* coef = nullptr;   // SDE: [lambda d | N d*d | N^2/2 d*d | ...] as ModelView::sde
     double tau_typ = 0.0;           // SDE: a typical gap (the warm-up estimate)
 };
@@ -203,10 +204,11 @@ template <int D> inline bool plan_d(Plan* e, const Forced& f, const ModelHost& m
     mc.tol_b = kTolBack;
     double Aty[D * D], Qty[D * D];      // a typical step's transition (the warm-up estimate)
     if (m.sde) {
-        // the warm-up starts from Pinf = x0P; the first transition must be consistent with it (Q1 = Pinf - A1 Pinf A1')
+        // the warm-up starts from Pinf (x0P where none is given); the first transition must be consistent with it (Q1 = Pinf - A1 Pinf A1')
+        const double* Ps = m.Pinf ? m.Pinf : m.x0P;
         double Pinf[D * D];
         for (int j = 0; j < D; ++j)
-            for (int i = 0; i < D; ++i) Pinf[i + j * D] = 0.5 * (m.x0P[i + j * D] + m.x0P[j + i * D]);
+            for (int i = 0; i < D; ++i) Pinf[i + j * D] = 0.5 * (Ps[i + j * D] + Ps[j + i * D]);
         double worst = 0.0, scale = 0.0;
         for (int j = 0; j < D; ++j)
             for (int i = 0; i < D; ++i) {

@@ -632,6 +632,34 @@ def logpdf_adjoint_missing(model, y, per_step=False):
     return lml.value, g
 
 
+def logpdf_adjoint_sde(model, y, per_step=False):
+    """logpdf_adjoint_missing for a model whose transitions are described by their SDE (SDETransitions: irregular spacing) -- ONE adjoint pass on the sweep
+    engine (tgp_logpdf_adjoint_sde, k_sweep_adjoint<sde>): Forward, closed-form exp(F tau), shared H, scalar observations, d <= 4, T >= 2048; NaNs in y (or a
+    (y, mask) tuple), a noise variance and an emission offset per step in any combination.  Returns (lml, g) with g a dict F (d,d) -- zero outside the
+    connected components of F --, Pinf (d,d) and x0P (d,d) (symmetrised, separate: a model whose x0P doubles as Pinf adds them), A1 (d,d) (zero for a model
+    bound without an explicit first transition), a (d,), H (d,), h (), R () (sums over the observed steps), x0m (d,); per_step adds "h_steps" and "R_steps"
+    (T,) as logpdf_adjoint_missing does.  Raises Unsupported where the engine declines (use logpdf_and_grad_sde)."""
+    _check_inputs(model, y[0] if isinstance(y, tuple) else y)
+    if not isinstance(model.transitions, SDETransitions):
+        raise _lib.Unsupported(_lib.EUNSUPPORTED, "logpdf_adjoint_sde needs SDE-described transitions (use logpdf_adjoint_missing)")
+    hd = model.handle()
+    yy, mm, dev = _obs(y, model)
+    d = model.dim
+    g = dict(F=np.zeros((d, d)), Pinf=np.zeros((d, d)), A1=np.zeros((d, d)), a=np.zeros(d), H=np.zeros(d), h=np.zeros(1), R=np.zeros(1), x0m=np.zeros(d),
+             x0P=np.zeros((d, d)))
+    steps = [_out(model, (model.T,), dev), _out(model, (model.T,), dev)] if per_step else [None, None]
+    lml = ctypes.c_double()
+    flags = (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0
+    hd.check(hd.lib.tgp_logpdf_adjoint_sde(hd.h, _lib.ptr(yy), _lib.ptr(mm), flags, ctypes.byref(lml),
+                                           *[_lib.ptr(g[k]) for k in ("F", "Pinf", "A1", "a", "H", "h", "R", "x0m", "x0P")], _lib.ptr(steps[0]), _lib.ptr(steps[1])))
+    for k in ("F", "Pinf", "A1", "x0P"):
+        g[k] = g[k].T.copy()          # column-major blocks -> [i][k]
+    g["h"], g["R"] = float(g["h"][0]), float(g["R"][0])
+    if per_step:
+        g["h_steps"], g["R_steps"] = steps
+    return lml.value, g
+
+
 def logpdf_and_grad_sde(model, y, tangents, rel_step=1e-6):
     """The same for a model whose transitions are described by their SDE (SDETransitions: irregular spacing, d <= 4).
     `tangents`: per parameter, the derivatives of F (d,d), x0P == P_inf (d,d), x0m (d,), H (d,), h (), R () and of the explicit

@@ -869,6 +869,42 @@ def _logpdf_and_gradient_sweep(fx, y):
     return lp, grad
 
 
+def _logpdf_and_gradient_sweep_sde(fx, y):
+    """Plain-array (irregularly spaced) inputs: the model is bound through its SDE as _logpdf_and_gradient_sde binds it, ONE adjoint pass on the sweep engine
+    (L.logpdf_adjoint_sde, k_sweep_adjoint<sde>: d <= 4, T >= 2048) gives d logpdf / d (F, H, Pinf, x0P, A1, h, R), contracted with the exact tangents of
+    those O(1) blocks.  x0P doubles as Pinf: the two gradients are added.  One variance per observation: no "noise" entry."""
+    kernel = fx.f.f.kernel
+    if not isinstance(fx.f.f.mean, (ZeroMean, ConstMean)):
+        raise NotImplementedError("logpdf_and_gradient(method='sweep'): a ZeroMean or ConstMean only")
+    if not hasattr(kernel, "sde_blocks") or kernel.sde_blocks()[0].shape[0] > 4:
+        raise NotImplementedError("logpdf_and_gradient(method='sweep') on irregular inputs: kernels with state dimension <= 4")
+    plist = parameters(kernel)
+    names = [n for n, _, _ in plist] + (["noise"] if fx.sigma2.shape[0] == 1 else []) + (["mean.c"] if isinstance(fx.f.f.mean, ConstMean) else [])
+    model = build_lgssm(kernel, fx.x, fx.sigma2, fx.f.f.mean, fx.f.storage.device, device_components=True)
+    if not isinstance(model.transitions, L.SDETransitions):
+        raise NotImplementedError("logpdf_and_gradient: could not bind the model through its SDE")
+    lp, g = L.logpdf_adjoint_sde(model, y)
+    gP = g["Pinf"] + g["x0P"]
+    grad = {}
+    for name, t in zip(names, _sde_param_tangents(fx, names, plist)):
+        if "F" not in t:
+            grad[name] = float(sum(_contract(g[k], v) for k, v in t.items()))
+            continue
+        grad[name] = (_contract(g["F"], np.asarray(t["F"], float)) + _contract(g["H"], np.asarray(t["H"], float))
+                      + _contract(gP, _symmetric_from_upper(t["x0P"])) + _contract(g["A1"], np.asarray(t["A1"], float)))
+    return lp, grad
+
+
+def _sweep_sde_gradient_applies(fx):
+    """the default policy's route to the sweep engine's adjoint pass for plain-array inputs: a ZeroMean or ConstMean, d <= 4, T >= 2048.  Measured
+    (profiles/sweep_adjoint_sde_time.txt, gaps U(0.05, 0.15), 10 % missing, 3 - 5 parameters): 1.13 - 2.45 x the tangent scans' speed by the medians of the
+    whole call at T = 3e3 ... 1e7, 2.3 - 15 x on a model bound once (DESIGN 4.9 has the table)."""
+    kernel = fx.f.f.kernel
+    if isinstance(fx.x, RegularSpacing) or not isinstance(fx.f.f.mean, (ZeroMean, ConstMean)) or len(fx.x) < 2048:
+        return False
+    return hasattr(kernel, "sde_blocks") and kernel.sde_blocks()[0].shape[0] <= 4
+
+
 def _sweep_gradient_applies(fx, y):
     """the default policy's route to the sweep engine's adjoint pass: regular spacing, a ZeroMean or ConstMean, d <= 4, T >= 2048, and gains that vary in
     time -- one noise variance per observation, or a NaN in a host y / a mask beside a device y.  Measured (profiles/sweep_adjoint_time.txt, 10 % missing,
@@ -992,10 +1028,12 @@ def logpdf_and_gradient(fx, y, rel_step=None, method=None):
     method: None (default policy), "adjoint" (ONE reverse-time pass on the stationary-gain engine, exact block tangents on the host:
     regular spacing, homoscedastic noise, d <= 8, or the wide-state engine for 8 < d <= 63 where its plan applies -- cost independent of the
     number of parameters), "sweep" (ONE adjoint pass on the sweep engine: regular spacing with NaNs in y and / or one noise variance per
-    observation, ZeroMean or ConstMean, d <= 4, T >= 2048; raises Unsupported where the device declines), "tangent" (the forward-mode scans)
+    observation, or plain-array (irregularly spaced) inputs bound through their SDE; ZeroMean or ConstMean, d <= 4, T >= 2048; raises Unsupported where the
+    device declines), "tangent" (the forward-mode scans)
     or "fd" (central differences of the device logpdf).
     Default: the adjoint pass where it applies -- on the stationary-gain engines, or on the sweep engine for d <= 4 and T >= 2048 with missing observations
-    or one noise variance per observation (profiles/sweep_adjoint_time.txt) --, else tangent scans up to state dimension 8; from d = 9 (e.g. ApproxPeriodicKernel, d = 14) the dual-number kernels are
+    or one noise variance per observation (profiles/sweep_adjoint_time.txt) or with plain-array inputs and no rel_step given
+    (profiles/sweep_adjoint_sde_time.txt) --, else tangent scans up to state dimension 8; from d = 9 (e.g. ApproxPeriodicKernel, d = 14) the dual-number kernels are
     out-of-line private-memory code (d = 14, T = 2e5: 2.4 s for 4 parameters against 5.7 ms per logpdf), so central differences
     of the logpdf -- 9 evaluations on the group kernels, ~50 ms, relative accuracy ~1e-7 -- are used instead.
     Heteroscedastic noise (one variance per observation) on the "fd" route: the kernel's and the mean's parameters only -- there is no
@@ -1003,6 +1041,8 @@ def logpdf_and_gradient(fx, y, rel_step=None, method=None):
     if method not in (None, "tangent", "fd", "adjoint", "sweep"):
         raise ValueError("method must be None, 'adjoint', 'sweep', 'tangent' or 'fd'")
     if method == "sweep":
+        if not isinstance(fx.x, RegularSpacing):
+            return _logpdf_and_gradient_sweep_sde(fx, y)
         return _logpdf_and_gradient_sweep(fx, y)
     if method == "adjoint" or (method is None and isinstance(fx.x, RegularSpacing) and fx.sigma2.shape[0] == 1
                                and isinstance(fx.f.f.mean, (ZeroMean, ConstMean)) and fx.build_lgssm().dim <= 8):
@@ -1018,6 +1058,11 @@ def logpdf_and_gradient(fx, y, rel_step=None, method=None):
             pass                            # (the device declined: what the default did before -- the tangent scans, or NotImplementedError for per-step noise)
     if method == "fd" or (method is None and isinstance(fx.x, RegularSpacing) and fx.build_lgssm().dim >= 9):
         return _logpdf_and_gradient_fd(fx, y, rel_step=1e-4 if rel_step is None else rel_step)
+    if method is None and rel_step is None and _sweep_sde_gradient_applies(fx):
+        try:
+            return _logpdf_and_gradient_sweep_sde(fx, y)
+        except L._lib.Unsupported:
+            pass                            # (the device declined: the tangent scans below, as before)
     rel_step = 1e-6 if rel_step is None else rel_step
     if not isinstance(fx.x, RegularSpacing):
         # any plain array of inputs -- uniformly spaced or not -- is the reference's AbstractVector path (lti_sde.jl:135-146:
