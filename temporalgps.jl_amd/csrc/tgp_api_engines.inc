@@ -118,6 +118,14 @@ int modal_call(tgp_handle* h, const double* y, uint32_t flags, const double* Rne
         const auto tp4 = std::chrono::steady_clock::now();
         auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
         fprintf(stderr, "[tgp modal host] plan core %.1f us, staging + launch %.1f, tables + copies %.1f, wait %.1f\n", us(tp0, tp1), us(tp1, tp2), us(tp2, tp3), us(tp3, tp4));
+        if (by_records) {      // a streaming call that ended on its records: where its time went behind the launch's return, on the same clock
+            long long ns[3];
+            tgp_modal::debug_stamps(h->modal, ns);
+            const long long t2 = std::chrono::duration_cast<std::chrono::nanoseconds>(tp2.time_since_epoch()).count();
+            auto since = [&](long long t) { return t ? (double)(t - t2) * 1e-3 : -1.0; };
+            fprintf(stderr, "[tgp modal host] us behind the launch's return: head observation seen %.1f, first record seen %.1f, last record seen %.1f\n", since(ns[0]), since(ns[1]),
+                    since(ns[2]));
+        }
     }
     read_timing(h);
     resolve_profile(h);

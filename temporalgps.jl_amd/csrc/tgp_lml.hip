@@ -383,6 +383,8 @@ __global__ __launch_bounds__(kNW * 64, (N == 16 ? 4 : 2)) void k_lml_stream(cons
     }
     __syncthreads();
     if (stamp) ka.part[kStampOff + 8 * blockIdx.x + 3] = (double)wall_clock64();
+    constexpr int NL = record_lines(D);
+    unsigned long long* sLine = reinterpret_cast<unsigned long long*>(sPost + kNW * PW);      // [NL][8]: the workgroup's record, packed (behind sPost)
     if (threadIdx.x == 0) {
         // the runs of this workgroup close each other: run w starts from the end state of run w - 1; run 0 is the host's to close
         double tot = sPost[0], el[D];
@@ -404,25 +406,27 @@ __global__ __launch_bounds__(kNW * 64, (N == 16 ? 4 : 2)) void k_lml_stream(cons
 #pragma unroll
             for (int i = 0; i < D; ++i) el[i] = p[2 + D + i];
         }
-        // the workgroup's record: 1 + 2 D (value, check) pairs, each ONE 16-byte write-through store -- check = the value's bits ^ the call's key, so
-        // the host knows a pair of THIS call when it sees one and needs no stream synchronisation to read the records (tgp_lml.hpp await_records)
-        v2d* out = reinterpret_cast<v2d*>(ka.part) + (size_t)blockIdx.x * (1 + 2 * D);
-        const long long key = (long long)record_key(ka.seq);
-        auto put = [&](int k, double v) {
-            v2d rec;
-            rec.x = v;
-            rec.y = __longlong_as_double(__double_as_longlong(v) ^ key);
-            v2d* dst = out + k;
-            asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(dst), "v"(rec) : "memory");
-        };
-        put(0, tot);
+        // the workgroup's record: its 1 + 2 D values (Q, V, E) packed into NL lines of seven values and a check word -- the values' bits ^ the call's
+        // key, so the host knows a line of THIS call when it sees one and needs no stream synchronisation to read the records (tgp_lml_record.hpp)
+        double vals[1 + 2 * D];
+        vals[0] = tot;
 #pragma unroll
         for (int i = 0; i < D; ++i) {
-            put(1 + i, sPost[2 + i]);
-            put(1 + D + i, el[i]);
+            vals[1 + i] = sPost[2 + i];
+            vals[1 + D + i] = el[i];
         }
-        if (stamp) ka.part[kStampOff + 8 * blockIdx.x + 4] = (double)wall_clock64();
+        record_pack(1 + 2 * D, vals, record_key(ka.seq), sLine);
     }
+    // ... and out of LDS as ONE aligned 64-byte write per line: threads 0 ... 4 NL - 1 (lanes of wave 0, like thread 0: its LDS writes are theirs to read
+    // behind lds_sync) store sixteen consecutive bytes each, write-through, in one instruction
+    // (thread 0 alone issued 1 + 2 D single-lane stores here: seven small writes to host memory per workgroup at d = 3, 1 715 per launch at T = 1e7)
+    if (threadIdx.x < 4 * NL) {
+        lds_sync();
+        const v2d rec = reinterpret_cast<const v2d*>(sLine)[threadIdx.x];
+        v2d* dst = reinterpret_cast<v2d*>(ka.part) + (blockIdx.x * (4 * NL) + threadIdx.x);      // (32-bit: at most kMaxWG records of twelve pieces)
+        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(dst), "v"(rec) : "memory");
+    }
+    if (stamp) ka.part[kStampOff + 8 * blockIdx.x + 4] = (double)wall_clock64();
 }
 
 #undef ka
@@ -491,9 +495,9 @@ void fill(LArgs<D, N>& ka, const tgp_plan::Modal& md) {
     }
 }
 
-// LDS of a workgroup: the eight slices and the runs' (Q, active, V, E); a CU has 160 KB, and a request above half of that keeps the CU to one workgroup
+// LDS of a workgroup: the eight slices, the runs' (Q, active, V, E) and the packed record's lines; a CU has 160 KB, and a request above half of that keeps the CU to one workgroup
 constexpr size_t kLdsCu = 160 * 1024, kLdsAlone = kLdsCu / 2 + 1024, kLdsMax = 136 * 1024;
-constexpr size_t lds_used(int d, int n) { return (size_t)kNW * 64 * (n / 2) * 16 + (size_t)kNW * (2 + 2 * d) * sizeof(double); }
+constexpr size_t lds_used(int d, int n) { return (size_t)kNW * 64 * (n / 2) * 16 + (size_t)kNW * (2 + 2 * d) * sizeof(double) + (size_t)record_lines(d) * kLineWords * 8; }
 static_assert(lds_used(tgp_plan::kMaxD, 32) <= kLdsMax && kLdsAlone <= kLdsMax && 2 * lds_used(tgp_plan::kMaxD, 16) <= kLdsCu, "the CU's LDS");
 // Do the tiles' loads carry the non-temporal hint?  No: the posterior call reads the same series microseconds later, and behind plain loads it finds
 // it in the caches -- k_post_stream 49.5 -> 43.2 us at d = 3, T = 1e7, this kernel + 1 us (measured on the whole step)
@@ -657,27 +661,34 @@ int enqueue(hipStream_t stream, const tgp_plan::Modal& md, const Geometry& g, lo
 }
 
 double finish(const tgp_plan::Modal& md, const Geometry& g, const double* part, const double* z0, const double* Wt) {
-    const int d = md.d, pw = 1 + 2 * d;
+    const int d = md.d, nl = record_lines(d);
     double s = 0.0;
     double stv[tgp_plan::kMaxD];
     for (int i = 0; i < d; ++i) stv[i] = z0[i];
     for (int w = 0; w < g.nwg; ++w) {
-        const double* p = part + (size_t)w * pw * 2;      // (value, check) pairs
+        const double* p = part + (size_t)w * nl * kLineWords;      // the workgroup's record: nl lines (tgp_lml_record.hpp)
         double lin = 0.0, quad = 0.0;
         for (int i = 0; i < d; ++i) {
-            lin += stv[i] * p[2 * (1 + i)];
+            lin += stv[i] * record_value(p, 1 + i);
             double v = 0.0;
             for (int k = 0; k < d; ++k) v += Wt[i * d + k] * stv[k];
             quad += stv[i] * v;
         }
-        s += p[0] - 2.0 * lin + quad;
-        for (int i = 0; i < d; ++i) stv[i] = p[2 * (1 + d + i)];
+        s += record_value(p, 0) - 2.0 * lin + quad;
+        for (int i = 0; i < d; ++i) stv[i] = record_value(p, 1 + d + i);
     }
     return s;
 }
 
 bool records_there(const Geometry& g, int d, const double* part, long long seq, size_t* next) {
-    return records_there((size_t)g.nwg * (1 + 2 * d), part, seq, next);
+    const size_t n = (size_t)g.nwg * record_lines(d);
+    const unsigned long long key = record_key(seq);
+    const volatile unsigned long long* q = reinterpret_cast<const volatile unsigned long long*>(part);
+    size_t k = *next;
+    while (k < n && record_line_ok(q + k * kLineWords, key)) ++k;
+    *next = k;
+    if (k == n) __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    return k == n;
 }
 bool records_there(size_t n, const double* part, long long seq, size_t* next) {
     const unsigned long long key = record_key(seq);

@@ -14,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "tgp_lml_record.hpp"
 #include "tgp_steady_plan.hpp"
 
 namespace tgp_lml {
@@ -34,20 +35,20 @@ struct Geometry {
 // R runs over the G tiles behind the head; every run starts with a whole tile (>= halo) unless the series is shorter than that (then ONE run)
 Geometry choose_geometry(const tgp_plan::Modal& md, long long T);
 
-// pinned host memory the launch writes: part [nwg][1 + 2 d] (value, check) PAIRS (Q, V, E per workgroup; check = the value's bits ^ record_key(seq): a pair
-// of this call is known when seen), head_in [nhs], flags [0]: head_in is there
+// pinned host memory the launch writes: part [nwg][record_lines(d)] LINES of 64 bytes (Q, V, E per workgroup, seven values and a check word to the line:
+// tgp_lml_record.hpp) -- an area of this kernel's own, on a 64-byte boundary, cleared when it is allocated --, head_in [nhs], flags [0]: head_in is there
 struct Buffers {
     double* part = nullptr;
     double* head_in = nullptr;
     long long* flags = nullptr;
 };
-constexpr size_t kStampOff = 2 * (size_t)kMaxWG * (1 + 2 * tgp_plan::kMaxD);      // development stamps (TGP_LML_DBG) behind the largest record table
+constexpr size_t kStampOff = (size_t)kMaxWG * kLineWords * record_lines(tgp_plan::kMaxD);      // development stamps (TGP_LML_DBG) behind the largest record table
 inline size_t part_doubles(int) { return kStampOff + 8 * (size_t)kMaxWG; }
-__host__ __device__ inline unsigned long long record_key(long long seq) { return (unsigned long long)seq * 0x9E3779B97F4A7C15ull + 0x632BE59BD9B4E019ull; }
-// Have all records of call `seq` arrived?  *next: the first pair not yet seen (0 at the first call; the scan resumes there).  With every record there
+// Have all records of call `seq` arrived?  *next: the first LINE not yet seen (0 at the first call; the scan resumes there).  With every record there
 // the kernel has read all of y and written all it writes: the host may go on without synchronising the stream (which stays ordered).
 bool records_there(const Geometry& g, int d, const double* part, long long seq, size_t* next);
-// ... the same over the first n pairs of any record table of call `seq` (the streaming posterior kernel's: one pair per workgroup, tgp_post.hpp)
+// ... and the first n (value, check) PAIRS of a pair table of call `seq` (the streaming posterior kernel's: one pair per workgroup, tgp_post.hpp; check =
+// the value's bits ^ record_key(seq))
 bool records_there(size_t n, const double* part, long long seq, size_t* next);
 
 // Wt = sum_{t < n} w_t' w_t (d x d, row-major), n = Geometry::first_tile -- data-free, O(d^2 log n) on the host

@@ -1035,12 +1035,16 @@ struct Engine {
     bool lml = false;
     tgp_lml::Geometry lg{};
     double lWt[tgp_plan::kMaxD * tgp_plan::kMaxD];
+    void* lpart_raw = nullptr;         // (the block lpart lies in, as allocated)
+    double* lpart = nullptr;           // pinned, on a 64-byte boundary, this kernel's alone: the workgroups' records as LINES (tgp_lml_record.hpp) and the TGP_LML_DBG stamps
     bool lml_records = false;          // the host may take the launched kernel's end from its records in pinned memory (tgp_lml.hpp records_there)
     // the streaming posterior kernel (tgp_post.hip): the last launch was k_post_stream (its sums are (value, check) records in `part`); the host
     // may take that launch's end from the records (every output byte written through and acknowledged in front of them: tgp_post.hpp records_end)
     bool post_stream = false, post_records = false;
     void* pxch = nullptr;              // device memory: the exchange records of the streaming posterior kernel's runs (tgp_post.hpp)
     long long stream_min_T = -1;       // TGP_OPT_STREAM_MIN_T
+    // TGP_STEADY_DEBUG, a streaming call: the host's clock (steady_clock, ns) when it first saw a head observation, a record, the last record (0: never)
+    long long dbg_ns[3] = {0, 0, 0};
     // the core of the last plan, kept while the model and the length stand (the reference's own sequence -- logpdf(model, y), then posterior(model, y) --
     // plans the same model twice): key = the model's blocks as handed over
     std::vector<double> memo_key;
@@ -1058,7 +1062,38 @@ inline double* hh_out(Engine* e) { return e->hhead + 2 * kHH; }
 inline double* hh_z0(Engine* e) { return e->hhead + 4 * kHH; }
 inline double* hh_zeta(Engine* e) { return e->hhead + 4 * kHH + 8; }
 inline long long* hh_flag(Engine* e) { return reinterpret_cast<long long*>(e->hhead + 4 * kHH + 16); }
+
+// ---- TGP_STEADY_DEBUG (read once): where a streaming call's time goes between the launch and the last record, on the host's clock.  In front of the
+// launch head_in[0] is set to a word no series holds; the kernel's head wave replaces it first thing, so the first look that finds another word there
+// has seen the kernel running.  await_done stamps the first and the last record.  (profiles/lml_call_tail_time.txt)
+// Development only: both streaming kernels' head waves store head_in[0 .. nhs) in every launch, whatever the series' length, so the word is replaced before
+// the head's forward recursion reads it; a launch that fails leaves it there, and the head then computed from it is discarded with the call's error.
+inline bool steady_debug() {
+    static const bool on = std::getenv("TGP_STEADY_DEBUG") != nullptr;
+    return on;
+}
+inline long long host_ns() { return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+constexpr long long kDbgUnseen = 0x7FF8C0DEC0DEC0DEll;      // (a NaN with a payload of its own)
+inline void dbg_arm(Engine* e) {
+    e->dbg_ns[0] = e->dbg_ns[1] = e->dbg_ns[2] = 0;
+    __atomic_store_n(reinterpret_cast<long long*>(hh_in(e)), kDbgUnseen, __ATOMIC_RELEASE);
+}
+inline void dbg_await_head(Engine* e) {      // (bounded by the stream, as await_host_flag is)
+    const long long* p = reinterpret_cast<const long long*>(hh_in(e));
+    for (unsigned spin = 1; __atomic_load_n(p, __ATOMIC_ACQUIRE) == kDbgUnseen; ++spin) {
+        if ((spin & 4095u) == 0) {
+            const hipError_t q = hipStreamQuery(e->stream);
+            (void)hipGetLastError();
+            if (q != hipErrorNotReady) return;
+        }
+        __builtin_ia32_pause();
+    }
+    e->dbg_ns[0] = host_ns();
+}
 }  // namespace
+void debug_stamps(const Engine* e, long long ns[3]) {
+    for (int k = 0; k < 3; ++k) ns[k] = e->dbg_ns[k];
+}
 
 Engine* create() { return new Engine(); }
 void set_stream_min_T(Engine* e, long long v) {
@@ -1077,6 +1112,7 @@ void destroy(Engine* e) {
     if (e->hhead) (void)tgp_alloc::host_free(e->hhead);
     if (e->dflat) (void)tgp_alloc::dev_free(e->dflat);
     if (e->part) (void)tgp_alloc::host_free(e->part);
+    if (e->lpart_raw) (void)tgp_alloc::host_free(e->lpart_raw);
     if (e->pxch) (void)tgp_alloc::dev_free(e->pxch);
     delete e;
 }
@@ -1151,6 +1187,7 @@ int launch(Engine* e, hipStream_t st, const Call& c, const char** kname) {
         e->hh_pending = true;
         e->post_stream = true;
         e->post_records = post_records_enabled() && tgp_post::records_end(pc);
+        if (steady_debug()) dbg_arm(e);
         return tgp_post::enqueue(st, e->md, g, pc, kname);
     }
     e->post_stream = false;
@@ -1451,17 +1488,18 @@ bool plan(Engine* e, const tgp_plan::ModelHost& m, long long T, bool logpdf_only
     if (logpdf_only && lml_stream_enabled() && stream_serves(e, T, kLmlMinT)) {
         // the streaming logpdf kernel: no tables (the head runs on the host from build_core's gains), no wait inside the kernel
         e->lg = tgp_lml::choose_geometry(e->md, T);
-        const size_t need = tgp_lml::part_doubles(e->md.d) + 64;      // (the records and the development stamps of TGP_LML_DBG)
-        if (need > e->part_cap) {
-            if (e->part) (void)tgp_alloc::host_free(e->part);
-            e->part = nullptr;
-            e->part_cap = 0;
-            if (tgp_alloc::host_malloc(reinterpret_cast<void**>(&e->part), need * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+        if (!e->lpart) {
+            // the records' own area (its lines never mix with the pair records of k_post_stream in `part`), the largest table and the development stamps
+            // of TGP_LML_DBG; cleared: the allocator hands out parked pinned blocks as they were left, and a zeroed line passes for no call's
+            // (a line is ONE aligned 64-byte write: the area starts on the block's first 64-byte boundary, wherever the allocator's block starts)
+            const size_t need = (tgp_lml::part_doubles(e->md.d) + 64) * sizeof(double);
+            if (tgp_alloc::host_malloc(&e->lpart_raw, need + 64, hipHostMallocDefault) != hipSuccess) {
+                e->lpart_raw = nullptr;
                 e->info.why = tgp_plan::kEigFail;
                 return false;
             }
-            std::memset(e->part, 0, need * sizeof(double));
-            e->part_cap = need;
+            std::memset(e->lpart_raw, 0, need + 64);
+            e->lpart = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(e->lpart_raw) + 63) & ~(uintptr_t)63);
         }
         if (e->memo_Wt_n != e->lg.first_tile) {
             tgp_lml::quad_table(e->md, e->lg.first_tile, e->lWt);
@@ -1540,6 +1578,7 @@ bool complete(Engine* e, long long T) {
         // the head's forward recursion, as soon as the kernel has handed its observations over (or the stream has drained)
         // (false: the stream has drained without the flag -- a short series, whose head wave raises none: the kernel's end has delivered the data.
         //  A launch that failed is the caller's stream synchronisation's to report; the head of garbage is then discarded with the rest)
+        if (steady_debug()) dbg_await_head(e);
         (void)await_host_flag(hh_flag(e), 2 * e->seq, e->stream);
         tgp_plan::modal_head_forward_any(e->mh, e->md, *e->tab, hh_in(e), e->hr, hh_z0(e), &e->host_quad);
         return true;
@@ -1569,6 +1608,7 @@ bool complete(Engine* e, long long T) {
         ship_stage(e, 2, why);      // (the head's variances in that stage are not there yet: with the head on the host nobody on the device reads them)
     }
     if (head) {
+        if (steady_debug() && e->post_stream) dbg_await_head(e);      // (behind the tail's tables: seen no later than this)
         ok = await_host_flag(f, v, e->stream);
         if (ok) tgp_plan::modal_head_forward_any(e->mh, e->md, *e->tab, hh_in(e), e->hr, hh_z0(e), &e->host_quad);
         raise_flag(f + 1, v);
@@ -1599,7 +1639,7 @@ bool complete(Engine* e, long long T) {
     return true;
 }
 
-// The kernel of a logpdf-only call produces nothing but the workgroups' records in pinned memory, each pair of them marked with the call's key: once
+// The kernel of a logpdf-only call produces nothing but the workgroups' records in pinned memory, each 64-byte line of them marked with the call's key: once
 // every record is there the kernel has read all of y and written all it writes, and the host goes on without hipStreamSynchronize (the kernel's own
 // end -- the release at the end of the dispatch, the queue's barrier packet, the completion signal -- is ~4 us the caller need not wait for; the
 // stream stays ordered: whatever is enqueued next runs behind the kernel).  false: the stream drained or failed without them -- synchronise.
@@ -1609,14 +1649,26 @@ bool complete(Engine* e, long long T) {
 bool await_done(Engine* e) {
     if (!e || !e->began) return false;
     if (e->lml ? !e->lml_records : !(e->post_stream && e->post_records)) return false;
-    const size_t n = e->lml ? (size_t)e->lg.nwg * (1 + 2 * e->md.d) : (size_t)e->nwg_local;
+    // (the logpdf kernel's records are lines in its own area, checked a line at a time; the posterior kernel's are pairs, one per workgroup)
+    const size_t n = e->lml ? (size_t)e->lg.nwg * tgp_lml::record_lines(e->md.d) : (size_t)e->nwg_local;
+    auto there = [&](size_t* next) { return e->lml ? tgp_lml::records_there(e->lg, e->md.d, e->lpart, e->seq, next) : tgp_lml::records_there(n, e->part, e->seq, next); };
     size_t next = 0;
+    const bool dbg = steady_debug();
     for (unsigned spin = 1;; ++spin) {
-        if (tgp_lml::records_there(n, e->part, e->seq, &next)) return true;
+        if (dbg && e->dbg_ns[1] == 0) {      // (any record of this call, whichever workgroup's)
+            const unsigned long long key = tgp_lml::record_key(e->seq);
+            const volatile unsigned long long* q = reinterpret_cast<const volatile unsigned long long*>(e->lml ? e->lpart : e->part);
+            for (size_t k = 0; k < n && e->dbg_ns[1] == 0; ++k)
+                if (e->lml ? tgp_lml::record_line_ok(q + k * tgp_lml::kLineWords, key) : (q[2 * k] ^ q[2 * k + 1]) == key) e->dbg_ns[1] = host_ns();
+        }
+        if (there(&next)) {
+            if (dbg) e->dbg_ns[2] = host_ns();
+            return true;
+        }
         if ((spin & 4095u) == 0) {
             const hipError_t q = hipStreamQuery(e->stream);
             (void)hipGetLastError();
-            if (q != hipErrorNotReady) return tgp_lml::records_there(n, e->part, e->seq, &next);
+            if (q != hipErrorNotReady) return there(&next);
         }
         __builtin_ia32_pause();
     }
@@ -1648,7 +1700,7 @@ int enqueue(Engine* e, hipStream_t stream, const Call& c, const char** kname, st
             return (int)hipErrorInvalidValue;
         }
         tgp_lml::Buffers b;
-        b.part = e->part;
+        b.part = e->lpart;
         b.head_in = hh_in(e);
         b.flags = hh_flag(e);
         e->lml_records = lml_records_enabled();
@@ -1657,6 +1709,7 @@ int enqueue(Engine* e, hipStream_t stream, const Call& c, const char** kname, st
         e->stream = stream;
         e->owns_head = true;
         e->nwg_local = e->lg.nwg;
+        if (steady_debug()) dbg_arm(e);
         r = tgp_lml::enqueue(stream, e->md, e->lg, c.T, c.y, b, e->seq, e->lWt, kname);
         if (r != 0 && err) *err = std::string("tgp_lml: launch: ") + hipGetErrorString((hipError_t)r);
         return r;
@@ -1680,7 +1733,7 @@ int enqueue(Engine* e, hipStream_t stream, const Call& c, const char** kname, st
 // and (the launch that holds the head) the head's sum of r^2 / S_t; fixed summation order.
 void finish_parts(const Engine* e, double* ssq, double* head_quad) {
     if (e->lml) {
-        *ssq = tgp_lml::finish(e->md, e->lg, e->part, e->hhead + 4 * kHH, e->lWt);
+        *ssq = tgp_lml::finish(e->md, e->lg, e->lpart, e->hhead + 4 * kHH, e->lWt);
         *head_quad = e->host_quad;
         return;
     }
@@ -1733,7 +1786,7 @@ double finish(const Engine* e, long long T) {
                 (s1 - s0) * 0.01, (e0 - s0) * 0.01, (esum / n - s0) * 0.01, (e1 - s0) * 0.01, elast, (q[1] - s0) * 0.01, (q[2 * (R / 2) + 1] - s0) * 0.01);
     }
     if (e->lml && std::getenv("TGP_LML_DBG") != nullptr) {
-        const double* q = e->part + tgp_lml::kStampOff;
+        const double* q = e->lpart + tgp_lml::kStampOff;
         double s0 = 1e300, s1 = 0, l1 = 0, c1 = 0, b1 = 0, e1 = 0;
         for (int g = 0; g < e->lg.nwg && g < 512; ++g) {
             s0 = std::min(s0, q[8 * g]);

@@ -37,6 +37,8 @@ bool plan(Engine*, const tgp_plan::ModelHost&, long long T, bool logpdf_only = f
 void set_stream_min_T(Engine*, long long min_T);
 // the host's wait for a logpdf-only call's kernel: true once its last workgroup has said so through pinned memory (false: use the stream)
 bool await_done(Engine*);
+// TGP_STEADY_DEBUG, the last streaming call: the host's clock (steady_clock, ns) at its first sight of a head observation, of a record, of the last record
+void debug_stamps(const Engine*, long long ns[3]);
 // Enqueues the kernel of the planned call on `stream` (no synchronisation); *kname names it for the profile.
 int enqueue(Engine*, hipStream_t stream, const Call&, const char** kname, std::string* err);
 // Right behind enqueue: the tables half of the plan when plan() left it for now (the kernel's head wave and last tiles wait for it).

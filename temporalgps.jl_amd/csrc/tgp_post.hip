@@ -622,7 +622,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void k_post_stream(const PArgs<D> by_v
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         raise_head_flag();
     }
-    // The workgroup's record: ONE 16-byte write-through store of (sum, the sum's bits ^ the call's key), the pair k_lml_stream writes -- issued once
+    // The workgroup's record: ONE 16-byte write-through store of (sum, the sum's bits ^ the call's key -- tgp_lml::record_key, the key k_lml_stream's lines carry) -- issued once
     // every wave of the workgroup has all its output stores acknowledged, so that a host that sees the record of every workgroup has mean and var in memory
     // and needs no stream synchronisation (tgp_modal.hip await_done)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
