@@ -14,7 +14,9 @@ namespace {
 // ---- kernel arguments: every coefficient is wave-uniform and reaches the lanes through scalar loads ---------------------------------
 template <int D, int N>
 struct LArgs {
-    double fd[D], fo[D], fb[D], fc[D], fw[D];      // z' = fd z + fo z_partner + fb y + fc (fc = fa - fb hh),  r = (y - hh) - fw . z
+    // the normal form (tgp_stream_form.hpp): u = y - hh,  r = u - fw . z,  z' = fd z + fo z_partner + e u -- e = 1 on a slot's first component and on an
+    // unpaired one; on a slot's second component e = fb: 0 in a conjugate pair, 1 where the slot holds two real modes
+    double fd[D], fo[D], fb[D], fw[D];
     double hh;
     double lvr[6][D], lvi[6][D];                   // M^(N 2^k), k < 6: the block form (re, signed im)
     double wj[N][D];                               // fw' M^j (a row): step j of a lane sees the lane's start state through it
@@ -33,6 +35,16 @@ struct LArgs {
 template <int D>
 __device__ __forceinline__ constexpr int partner(int i) {
     return ((i ^ 1) < D) ? (i ^ 1) : i;
+}
+// The odd last component has no partner: no second term anywhere -- recursion, scans, powers.
+// (P x)_i of a block form (re, signed im), plus c
+template <int D>
+__device__ __forceinline__ double block_fma(int i, double re, double im, const double (&x)[D], double c) {
+    return partner<D>(i) != i ? fma(re, x[i], fma(im, x[partner<D>(i)], c)) : fma(re, x[i], c);
+}
+template <int D>
+__device__ __forceinline__ double block_mul(int i, double re, double im, const double (&x)[D]) {
+    return partner<D>(i) != i ? fma(re, x[i], im * x[partner<D>(i)]) : re * x[i];
 }
 
 __device__ __forceinline__ double wave_sum(double x) {      // the sum over the wave, in every lane's SGPR copy (lane 63 holds it)
@@ -130,11 +142,16 @@ __global__ __launch_bounds__(kNW * 64, (N == 16 ? 4 : 2)) void k_lml_stream(cons
                 double xr = 1.0, xi = 0.0;
 #pragma unroll
                 for (int k = 0; k < 6; ++k) {
-                    const double lr = ka.lvr[k][i], li = ka.lvi[k][i];
+                    const double lr = ka.lvr[k][i];
                     const bool bit = ((ex >> k) & 1) != 0;
-                    const double nr = fma(xr, lr, -(xi * li)), ni = fma(xr, li, xi * lr);
-                    xr = bit ? nr : xr;
-                    xi = bit ? ni : xi;
+                    if (partner<D>(i) != i) {
+                        const double li = ka.lvi[k][i];
+                        const double nr = fma(xr, lr, -(xi * li)), ni = fma(xr, li, xi * lr);
+                        xr = bit ? nr : xr;
+                        xi = bit ? ni : xi;
+                    } else {      // (a real mode of its own: a real power)
+                        xr = bit ? xr * lr : xr;
+                    }
                 }
                 pr[i] = xr;
                 pi[i] = xi;
@@ -200,8 +217,8 @@ __global__ __launch_bounds__(kNW * 64, (N == 16 ? 4 : 2)) void k_lml_stream(cons
             if (staged) issue_loads(tile_t0 + TILE);      // the next tile's observations travel while this one is in work
             // ---- ONE sweep from a zero start (a whole tile): the innovations r0 of the lane's steps are never kept -- what the lane's true
             // start state st makes of them is a quadratic form,  sum_j (r0_j - w_j . st)^2 = q - 2 st . v + st' WN st  with  q = sum r0^2,
-            // v = sum_j w_j r0_j (w_j = fw' M^j from the argument table, WN = sum_j w_j' w_j data-free) -- 17 instructions per step at d = 3 where the
-            // two-sweep form below spends 23.  A tile with steps beyond the series' end (one per launch at most) takes the two sweeps.
+            // v = sum_j w_j r0_j (w_j = fw' M^j from the argument table, WN = sum_j w_j' w_j data-free) -- 14 instructions per step at d = 3 in the
+            // normal form (17 in the plan's coordinates), where two sweeps spent 23. A tile with steps beyond the series' end (one per launch at most) takes the two sweeps.
             constexpr int CH = N == 16 ? 4 : 8;
             const long long nv = t_hi - tile_t0;      // valid steps of the tile (wave-uniform)
             const bool full = nv >= TILE;
@@ -222,7 +239,8 @@ __global__ __launch_bounds__(kNW * 64, (N == 16 ? 4 : 2)) void k_lml_stream(cons
                 if (full) {      // (wave-uniform)
 #pragma unroll
                     for (int j = 0; j < CH; ++j) {
-                        double r = u[j] - ka.hh;
+                        const double ut = u[j] - ka.hh;
+                        double r = ut;
 #pragma unroll
                         for (int i = 0; i < D; ++i) r = fma(-ka.fw[i], z[i], r);
                         q = fma(r, r, q);
@@ -230,14 +248,15 @@ __global__ __launch_bounds__(kNW * 64, (N == 16 ? 4 : 2)) void k_lml_stream(cons
                         for (int i = 0; i < D; ++i) v[i] = fma(ka.wj[jc + j][i], r, v[i]);
                         double nz[D];
 #pragma unroll
-                        for (int i = 0; i < D; ++i) nz[i] = fma(ka.fd[i], z[i], fma(ka.fo[i], z[partner<D>(i)], fma(ka.fb[i], u[j], ka.fc[i])));
+                        for (int i = 0; i < D; ++i) nz[i] = block_fma<D>(i, ka.fd[i], ka.fo[i], z, (partner<D>(i) != i && (i & 1)) ? ka.fb[i] * ut : ut);
 #pragma unroll
                         for (int i = 0; i < D; ++i) z[i] = nz[i];
                     }
                 } else {         // the series' last tile: innovations of steps that do not exist do not count
 #pragma unroll
                     for (int j = 0; j < CH; ++j) {
-                        double r = u[j] - ka.hh;
+                        const double ut = u[j] - ka.hh;
+                        double r = ut;
 #pragma unroll
                         for (int i = 0; i < D; ++i) r = fma(-ka.fw[i], z[i], r);
                         r = jc + j < nvalid ? r : 0.0;
@@ -246,7 +265,7 @@ __global__ __launch_bounds__(kNW * 64, (N == 16 ? 4 : 2)) void k_lml_stream(cons
                         for (int i = 0; i < D; ++i) v[i] = fma(ka.wj[jc + j][i], r, v[i]);
                         double nz[D];
 #pragma unroll
-                        for (int i = 0; i < D; ++i) nz[i] = fma(ka.fd[i], z[i], fma(ka.fo[i], z[partner<D>(i)], fma(ka.fb[i], u[j], ka.fc[i])));
+                        for (int i = 0; i < D; ++i) nz[i] = block_fma<D>(i, ka.fd[i], ka.fo[i], z, (partner<D>(i) != i && (i & 1)) ? ka.fb[i] * ut : ut);
 #pragma unroll
                         for (int i = 0; i < D; ++i) z[i] = nz[i];
                     }
@@ -256,7 +275,7 @@ __global__ __launch_bounds__(kNW * 64, (N == 16 ? 4 : 2)) void k_lml_stream(cons
             {
                 double add[D];
 #pragma unroll
-                for (int i = 0; i < D; ++i) add[i] = fma(ka.lvr[0][i], zin[i], ka.lvi[0][i] * zin[partner<D>(i)]);
+                for (int i = 0; i < D; ++i) add[i] = block_mul<D>(i, ka.lvr[0][i], ka.lvi[0][i], zin);
 #pragma unroll
                 for (int i = 0; i < D; ++i) z[i] += (lane == 0) ? add[i] : 0.0;
             }
@@ -269,7 +288,7 @@ __global__ __launch_bounds__(kNW * 64, (N == 16 ? 4 : 2)) void k_lml_stream(cons
     do {                                                                                                             \
         double g_[D];                                                                                                \
         _Pragma("unroll") for (int i = 0; i < D; ++i) g_[i] = dpp_mov<0x110 + (1 << (K))>(z[i]);                    \
-        _Pragma("unroll") for (int i = 0; i < D; ++i) z[i] = fma(ka.lvr[K][i], g_[i], fma(ka.lvi[K][i], g_[partner<D>(i)], z[i])); \
+        _Pragma("unroll") for (int i = 0; i < D; ++i) z[i] = block_fma<D>(i, ka.lvr[K][i], ka.lvi[K][i], g_, z[i]);            \
     } while (0)
             TGP_LML_ROW_LEVEL(0);
             TGP_LML_ROW_LEVEL(1);
@@ -281,16 +300,16 @@ __global__ __launch_bounds__(kNW * 64, (N == 16 ? 4 : 2)) void k_lml_stream(cons
 #pragma unroll
                 for (int i = 0; i < D; ++i) g[i] = dpp_mov<0x142, 0xA>(z[i]);      // rows 1, 3: the total of the row below
 #pragma unroll
-                for (int i = 0; i < D; ++i) z[i] = fma(mpr[i], g[i], fma(mpi[i], g[partner<D>(i)], z[i]));
+                for (int i = 0; i < D; ++i) z[i] = block_fma<D>(i, mpr[i], mpi[i], g, z[i]);
 #pragma unroll
                 for (int i = 0; i < D; ++i) g[i] = dpp_mov<0x143, 0xC>(z[i]);      // rows 2, 3: everything up to lane 31 ...
                 double g3[D];
 #pragma unroll
-                for (int i = 0; i < D; ++i) g3[i] = fma(ka.lvr[4][i], g[i], ka.lvi[4][i] * g[partner<D>(i)]);      // ... which row 3 sees through M^(16 N) more
+                for (int i = 0; i < D; ++i) g3[i] = block_mul<D>(i, ka.lvr[4][i], ka.lvi[4][i], g);      // ... which row 3 sees through M^(16 N) more
 #pragma unroll
                 for (int i = 0; i < D; ++i) g[i] = lane >= 48 ? g3[i] : g[i];
 #pragma unroll
-                for (int i = 0; i < D; ++i) z[i] = fma(mpr[i], g[i], fma(mpi[i], g[partner<D>(i)], z[i]));
+                for (int i = 0; i < D; ++i) z[i] = block_fma<D>(i, mpr[i], mpi[i], g, z[i]);
             }
             if (D == 5) asm volatile("" : "+s"(kap));      // (as in front of the scan, for d = 5)
             // the tile's true end state: the inclusive value of its last lane with a step in it
@@ -458,7 +477,6 @@ void fill(LArgs<D, N>& ka, const tgp_plan::Modal& md) {
         ka.fd[i] = md.fd[i];
         ka.fo[i] = md.fo[i];
         ka.fb[i] = md.fb[i];
-        ka.fc[i] = md.fa[i] - md.fb[i] * md.hh;
         ka.fw[i] = md.fw[i];
     }
     ka.hh = md.hh;

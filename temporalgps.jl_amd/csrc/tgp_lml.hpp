@@ -5,7 +5,8 @@
 // The steps behind the head are cut into R runs, one per wave; a wave streams its run tile by tile (64 lanes x N consecutive steps) through
 // its own LDS slice and carries the filter state from tile to tile exactly.  Inside a tile a lane's zero-start end state is a table product
 // (the recursion from zero), the lanes' start states come from one DPP scan, and the second sweep is the reference's recursion itself in the modal
-// coordinates of the stationary closed loop: r = u - fw . z, z' = M z + fb u + fa.  A run does not know the state it starts from: it starts
+// coordinates of the stationary closed loop, input-normalised (tgp_stream_form.hpp: every Modal handed to this unit is that form's, and the records,
+// Wt and z0 are in its coordinates): r = u - fw . z, z' = M z + e u, u = y - hh.  A run does not know the state it starts from: it starts
 // from zero and also accumulates V = sum_t w_t r_t over its first tile (w_t = fw' M^t: how a start state moves the innovations), so that
 //     sum r^2 (start state s) = Q - 2 s . V + s' Wt s,   Wt = sum_t w_t' w_t  (data-free, from the host),
 // to rounding once the tile is longer than the `halo` of the plan.  The waves of a workgroup apply that to each other after the one barrier
@@ -56,7 +57,7 @@ void quad_table(const tgp_plan::Modal& md, long long n, double* Wt);
 // Enqueues the kernel on `stream` (no synchronisation).  0 or a hipError_t.
 int enqueue(hipStream_t stream, const tgp_plan::Modal& md, const Geometry& g, long long T, const double* y, const Buffers& b, long long seq, const double* Wt,
             const char** kname);
-// After flags[1] (or the stream) says the kernel is through: sum r^2 over the steps [nhs, T) given the head's end state z0 (modal coordinates)
+// After flags[1] (or the stream) says the kernel is through: sum r^2 over the steps [nhs, T) given the head's end state z0 (the kernel's coordinates: tgp_stream_form::state_in)
 double finish(const tgp_plan::Modal& md, const Geometry& g, const double* part, const double* z0, const double* Wt);
 
 }  // namespace tgp_lml

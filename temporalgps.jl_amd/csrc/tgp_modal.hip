@@ -6,6 +6,7 @@
 #include "tgp_lane.hpp"
 #include "tgp_lml.hpp"
 #include "tgp_post.hpp"
+#include "tgp_stream_form.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -1052,6 +1053,9 @@ struct Engine {
     bool memo_ok = false;
     unsigned long long memo_stamp = 0; // of the thread's plan workspace when the core was built (another engine's plan on this thread, another thread: no hit)
     Modal memo_md{};
+    // the input-normalised form of md the two streaming kernels run on (tgp_stream_form.hpp); !sf.ok: it declined, k_steady_one serves the call.  Built with
+    // the plan's core and kept with it
+    tgp_stream_form::Form sf{}, memo_sf{};
     tgp_plan::Info memo_info{};
     long long memo_Wt_n = -1;          // lWt holds quad_table(md, memo_Wt_n)
 };
@@ -1062,6 +1066,10 @@ inline double* hh_out(Engine* e) { return e->hhead + 2 * kHH; }
 inline double* hh_z0(Engine* e) { return e->hhead + 4 * kHH; }
 inline double* hh_zeta(Engine* e) { return e->hhead + 4 * kHH + 8; }
 inline long long* hh_flag(Engine* e) { return reinterpret_cast<long long*>(e->hhead + 4 * kHH + 16); }
+// ... and behind the flags the same two states in the streaming kernels' coordinates: what k_post_stream reads and writes (k_steady_one: the plan's, above)
+inline double* hh_kz0(Engine* e) { return e->hhead + 4 * kHH + 20; }
+inline double* hh_kzeta(Engine* e) { return e->hhead + 4 * kHH + 28; }
+constexpr size_t kHHDoubles = 4 * kHH + 36;
 
 // ---- TGP_STEADY_DEBUG (read once): where a streaming call's time goes between the launch and the last record, on the host's clock.  In front of the
 // launch head_in[0] is set to a word no series holds; the kernel's head wave replaces it first thing, so the first look that finds another word there
@@ -1137,7 +1145,7 @@ static bool head_scans_enabled() {      // TGP_MODAL_HEAD_SCANS=0: the sequentia
 // buffer on a 16-byte boundary; segments, in-kernel heads and odd pointers stay on k_steady_one.
 static bool use_post_stream(const Engine* e, const Call& c) {
     if (c.mean == nullptr || !e->hosthead || c.seg_lo != 0 || (c.seg_hi >= 0 && c.seg_hi < c.T)) return false;
-    if (!tgp_post::applies(e->md, c.T) || !stream_serves(e, c.T, kPostMinT)) return false;
+    if (!e->sf.ok || !tgp_post::applies(e->md, c.T) || !stream_serves(e, c.T, kPostMinT)) return false;
     auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     return al(c.y) && al(c.mean) && al(c.var) && (!c.rnew_per_step || al(c.Rnew));
 }
@@ -1159,7 +1167,7 @@ int launch(Engine* e, hipStream_t st, const Call& c, const char** kname) {
             if (tgp_alloc::dev_malloc(&e->pxch, tgp_post::xch_bytes()) != hipSuccess) return (int)hipErrorOutOfMemory;
             if (hipMemsetAsync(e->pxch, 0, tgp_post::xch_bytes(), st) != hipSuccess) return (int)hipGetLastError();
         }
-        const tgp_post::Geometry g = tgp_post::choose_geometry(e->md, c.T);
+        const tgp_post::Geometry g = tgp_post::choose_geometry(e->sf.md, c.T);
         tgp_post::Call pc;
         pc.T = c.T;
         pc.y = c.y;
@@ -1172,8 +1180,8 @@ int launch(Engine* e, hipStream_t st, const Call& c, const char** kname) {
         pc.flag = reinterpret_cast<const long long*>(e->hflat + e->flat_cap);
         pc.part = e->part;
         pc.head_in = hh_in(e);
-        pc.z0p = hh_z0(e);
-        pc.zeta_out = hh_zeta(e);
+        pc.z0p = hh_kz0(e);            // (the kernel's coordinates: `complete` maps the head's states on their way in and out)
+        pc.zeta_out = hh_kzeta(e);
         pc.head_out = hh_out(e);
         pc.hflag = hh_flag(e);
         pc.seq = e->seq;
@@ -1188,7 +1196,7 @@ int launch(Engine* e, hipStream_t st, const Call& c, const char** kname) {
         e->post_stream = true;
         e->post_records = post_records_enabled() && tgp_post::records_end(pc);
         if (steady_debug()) dbg_arm(e);
-        return tgp_post::enqueue(st, e->md, g, pc, kname);
+        return tgp_post::enqueue(st, e->sf.md, g, pc, kname);
     }
     e->post_stream = false;
     KArgs<D> ka;
@@ -1435,6 +1443,7 @@ void memo_store(Engine* e, const tgp_plan::ModelHost& m, long long T) {
     model_words(m, [&](const double* p, size_t n) { e->memo_key.insert(e->memo_key.end(), p, p + n); });
     e->memo_T = T;
     e->memo_md = e->md;
+    e->memo_sf = e->sf;
     e->memo_info = e->info;
     e->memo_stamp = tgp_plan::work_stamp_any(m.d);
     e->memo_ok = true;
@@ -1463,7 +1472,7 @@ bool plan(Engine* e, const tgp_plan::ModelHost& m, long long T, bool logpdf_only
         for (int s2 = 0; s2 < 3; ++s2) reinterpret_cast<long long*>(e->hflat + e->flat_cap)[s2] = 0;      // (the stages' flags)
     }
     if (!e->hhead) {
-        const size_t n = 4 * kHH + 16 + 4;
+        const size_t n = kHHDoubles;
         if (tgp_alloc::host_malloc(reinterpret_cast<void**>(&e->hhead), n * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
             e->info = tgp_plan::Info{};
             e->info.why = tgp_plan::kEigFail;
@@ -1474,20 +1483,22 @@ bool plan(Engine* e, const tgp_plan::ModelHost& m, long long T, bool logpdf_only
     ++e->seq;
     if (memo_hit(e, m, T)) {
         e->md = e->memo_md;
+        e->sf = e->memo_sf;
         e->info = e->memo_info;
     } else {
         e->memo_ok = false;
         e->memo_Wt_n = -1;
         e->info = tgp_plan::build_core_any(m, T, e->md, *e->tab);
         if (e->info.why != tgp_plan::kOk) return false;
+        (void)tgp_stream_form::build(e->md, e->sf);
         memo_store(e, m, T);
     }
     layout_tables(e);
     e->mh = m;
     e->hh_T = T;
-    if (logpdf_only && lml_stream_enabled() && stream_serves(e, T, kLmlMinT)) {
+    if (logpdf_only && e->sf.ok && lml_stream_enabled() && stream_serves(e, T, kLmlMinT)) {
         // the streaming logpdf kernel: no tables (the head runs on the host from build_core's gains), no wait inside the kernel
-        e->lg = tgp_lml::choose_geometry(e->md, T);
+        e->lg = tgp_lml::choose_geometry(e->sf.md, T);
         if (!e->lpart) {
             // the records' own area (its lines never mix with the pair records of k_post_stream in `part`), the largest table and the development stamps
             // of TGP_LML_DBG; cleared: the allocator hands out parked pinned blocks as they were left, and a zeroed line passes for no call's
@@ -1502,7 +1513,7 @@ bool plan(Engine* e, const tgp_plan::ModelHost& m, long long T, bool logpdf_only
             e->lpart = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(e->lpart_raw) + 63) & ~(uintptr_t)63);
         }
         if (e->memo_Wt_n != e->lg.first_tile) {
-            tgp_lml::quad_table(e->md, e->lg.first_tile, e->lWt);
+            tgp_lml::quad_table(e->sf.md, e->lg.first_tile, e->lWt);      // (in the kernel's coordinates, like its records)
             e->memo_Wt_n = e->memo_ok ? e->lg.first_tile : -1;
         }
         e->deferred = false;
@@ -1611,6 +1622,7 @@ bool complete(Engine* e, long long T) {
         if (steady_debug() && e->post_stream) dbg_await_head(e);      // (behind the tail's tables: seen no later than this)
         ok = await_host_flag(f, v, e->stream);
         if (ok) tgp_plan::modal_head_forward_any(e->mh, e->md, *e->tab, hh_in(e), e->hr, hh_z0(e), &e->host_quad);
+        if (ok && e->post_stream) tgp_stream_form::state_in(e->sf, hh_z0(e), hh_kz0(e));
         raise_flag(f + 1, v);
     }
     if (e->post && why == tgp_plan::kOk) {
@@ -1623,6 +1635,7 @@ bool complete(Engine* e, long long T) {
             const int nhs = e->md.nhs;
             double *om = hh_out(e), *ov = om + nhs;
             const double* in = hh_in(e);
+            if (e->post_stream) tgp_stream_form::zeta_out(e->sf, hh_kzeta(e), hh_zeta(e));
             tgp_plan::modal_head_backward_any(e->md, *e->tab, in, e->hr, hh_zeta(e), om, ov);
             for (int t = 0; t < nhs; ++t) ov[t] += in[nhs + (e->rnew_per_step ? t : 0)];
         }
@@ -1710,7 +1723,7 @@ int enqueue(Engine* e, hipStream_t stream, const Call& c, const char** kname, st
         e->owns_head = true;
         e->nwg_local = e->lg.nwg;
         if (steady_debug()) dbg_arm(e);
-        r = tgp_lml::enqueue(stream, e->md, e->lg, c.T, c.y, b, e->seq, e->lWt, kname);
+        r = tgp_lml::enqueue(stream, e->sf.md, e->lg, c.T, c.y, b, e->seq, e->lWt, kname);
         if (r != 0 && err) *err = std::string("tgp_lml: launch: ") + hipGetErrorString((hipError_t)r);
         return r;
     }
@@ -1733,7 +1746,9 @@ int enqueue(Engine* e, hipStream_t stream, const Call& c, const char** kname, st
 // and (the launch that holds the head) the head's sum of r^2 / S_t; fixed summation order.
 void finish_parts(const Engine* e, double* ssq, double* head_quad) {
     if (e->lml) {
-        *ssq = tgp_lml::finish(e->md, e->lg, e->lpart, e->hhead + 4 * kHH, e->lWt);
+        double z0k[tgp_plan::kMaxD];      // the head's end state as the records see it
+        tgp_stream_form::state_in(e->sf, e->hhead + 4 * kHH, z0k);
+        *ssq = tgp_lml::finish(e->sf.md, e->lg, e->lpart, z0k, e->lWt);
         *head_quad = e->host_quad;
         return;
     }

@@ -17,8 +17,10 @@ constexpr int N = kN, PPL = kN / 2, TILE = kTile;
 // ---- kernel arguments: every coefficient is wave-uniform and reaches the lanes through scalar loads ---------------------------------
 template <int D>
 struct PArgs {
-    double fd[D], fo[D], fb[D], fa[D], fw[D];      // forward:  z' = fd z + fo z_partner + fb u + fa,  r = u - fw . z
-    double gd[D], go[D], gc[D], gw[D];             // backward: zeta' = gd zeta + go zeta_partner + gc r,  mean = y - rS r + gw . zeta
+    // the normal form (tgp_stream_form.hpp): the input enters a slot's first component and an unpaired one with coefficient 1; a slot's second component
+    // with fb (gc): 0 in a conjugate pair, 1 where the slot holds two real modes.  No constant.
+    double fd[D], fo[D], fb[D], fw[D];             // forward:  u = y - hh,  z' = fd z + fo z_partner + e u,  r = u - fw . z
+    double gd[D], go[D], gc[D], gw[D];             // backward: zeta' = gd zeta + go zeta_partner + e r,  mean = y - rS r + gw . zeta
     double lfr[6][D], lfi[6][D];                   // M^(N 2^k), k < 6: the block form (re, signed im)
     double lgr[6][D], lgi[6][D];                   // Mg^(N 2^k)
     double WJ[N][D], WG[N][D];                     // fw' M^j; gw' Mg^(N-1-j)
@@ -35,6 +37,20 @@ struct PArgs {
 template <int D>
 __device__ __forceinline__ constexpr int partner(int i) {
     return ((i ^ 1) < D) ? (i ^ 1) : i;
+}
+// The odd last component has no partner: no second term anywhere -- recursions, scans, the lanes' powers.  (tgp_lml.hip)
+template <int D>
+__device__ __forceinline__ double block_fma(int i, double re, double im, const double (&x)[D], double c) {
+    return partner<D>(i) != i ? fma(re, x[i], fma(im, x[partner<D>(i)], c)) : fma(re, x[i], c);
+}
+template <int D>
+__device__ __forceinline__ double block_mul(int i, double re, double im, const double (&x)[D]) {
+    return partner<D>(i) != i ? fma(re, x[i], im * x[partner<D>(i)]) : re * x[i];
+}
+// the input `in` as component i sees it: e in
+template <int D>
+__device__ __forceinline__ double input_of(int i, double e, double in) {
+    return (partner<D>(i) != i && (i & 1)) ? e * in : in;
 }
 __device__ __forceinline__ double wave_sum(double x) {
     x += dpp_mov<0x111>(x);
@@ -106,13 +122,21 @@ __global__ __launch_bounds__(kNW * 64, 2) void k_post_stream(const PArgs<D> by_v
             const int tb = job / D, i = job % D;
             const int ex = tb == 0 ? (lane & 15) + 1 : (tb == 1 ? 16 - (lane & 15) : 63 - lane);
             double xr = 1.0, xi = 0.0;
+            if (partner<D>(D - 1) == D - 1 && i == D - 1) {      // (wave-uniform) a real mode of its own: a real power, its imaginary table is never read
 #pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                const double lr = tb == 0 ? ka.lfr[k][i] : ka.lgr[k][i], li = tb == 0 ? ka.lfi[k][i] : ka.lgi[k][i];
-                const bool bit = ((ex >> k) & 1) != 0;
-                const double nr = fma(xr, lr, -(xi * li)), ni = fma(xr, li, xi * lr);
-                xr = bit ? nr : xr;
-                xi = bit ? ni : xi;
+                for (int k = 0; k < 6; ++k) {
+                    const double lr = tb == 0 ? ka.lfr[k][i] : ka.lgr[k][i];
+                    xr = ((ex >> k) & 1) != 0 ? xr * lr : xr;
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 6; ++k) {
+                    const double lr = tb == 0 ? ka.lfr[k][i] : ka.lgr[k][i], li = tb == 0 ? ka.lfi[k][i] : ka.lgi[k][i];
+                    const bool bit = ((ex >> k) & 1) != 0;
+                    const double nr = fma(xr, lr, -(xi * li)), ni = fma(xr, li, xi * lr);
+                    xr = bit ? nr : xr;
+                    xi = bit ? ni : xi;
+                }
             }
             sPw[tb][0][i][lane] = xr;
             sPw[tb][1][i][lane] = xi;
@@ -229,7 +253,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void k_post_stream(const PArgs<D> by_v
             {
                 double add[D];
 #pragma unroll
-                for (int i = 0; i < D; ++i) add[i] = fma(ka.lfr[0][i], zin[i], ka.lfi[0][i] * zin[partner<D>(i)]);
+                for (int i = 0; i < D; ++i) add[i] = block_mul<D>(i, ka.lfr[0][i], ka.lfi[0][i], zin);
 #pragma unroll
                 for (int i = 0; i < D; ++i) z[i] += (lane == 0) ? add[i] : 0.0;
             }
@@ -237,7 +261,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void k_post_stream(const PArgs<D> by_v
     do {                                                                                                               \
         double g_[D];                                                                                                  \
         _Pragma("unroll") for (int i = 0; i < D; ++i) g_[i] = dpp_mov<(CTRL) + (1 << (K))>(Z[i]);                     \
-        _Pragma("unroll") for (int i = 0; i < D; ++i) Z[i] = fma(ka.LR[K][i], g_[i], fma(ka.LI[K][i], g_[partner<D>(i)], Z[i])); \
+        _Pragma("unroll") for (int i = 0; i < D; ++i) Z[i] = block_fma<D>(i, ka.LR[K][i], ka.LI[K][i], g_, Z[i]);               \
     } while (0)
             TGP_POST_ROW_LEVEL(0x110, lfr, lfi, 0, z);
             TGP_POST_ROW_LEVEL(0x110, lfr, lfi, 1, z);
@@ -247,15 +271,15 @@ __global__ __launch_bounds__(kNW * 64, 2) void k_post_stream(const PArgs<D> by_v
 #pragma unroll
             for (int i = 0; i < D; ++i) g[i] = dpp_mov<0x142, 0xA>(z[i]);      // rows 1, 3: the total of the row below
 #pragma unroll
-            for (int i = 0; i < D; ++i) z[i] = fma(sPw[0][0][i][lane], g[i], fma(sPw[0][1][i][lane], g[partner<D>(i)], z[i]));
+            for (int i = 0; i < D; ++i) z[i] = block_fma<D>(i, sPw[0][0][i][lane], partner<D>(i) != i ? sPw[0][1][i][lane] : 0.0, g, z[i]);
 #pragma unroll
             for (int i = 0; i < D; ++i) g[i] = dpp_mov<0x143, 0xC>(z[i]);      // rows 2, 3: everything up to lane 31 ...
 #pragma unroll
-            for (int i = 0; i < D; ++i) g3[i] = fma(ka.lfr[4][i], g[i], ka.lfi[4][i] * g[partner<D>(i)]);      // ... which row 3 sees through M^(16 N) more
+            for (int i = 0; i < D; ++i) g3[i] = block_mul<D>(i, ka.lfr[4][i], ka.lfi[4][i], g);      // ... which row 3 sees through M^(16 N) more
 #pragma unroll
             for (int i = 0; i < D; ++i) g[i] = lane >= 48 ? g3[i] : g[i];
 #pragma unroll
-            for (int i = 0; i < D; ++i) z[i] = fma(sPw[0][0][i][lane], g[i], fma(sPw[0][1][i][lane], g[partner<D>(i)], z[i]));
+            for (int i = 0; i < D; ++i) z[i] = block_fma<D>(i, sPw[0][0][i][lane], partner<D>(i) != i ? sPw[0][1][i][lane] : 0.0, g, z[i]);
 #pragma unroll
             for (int i = 0; i < D; ++i) end[i] = readlane_d(z[i], 63);
 #pragma unroll
@@ -277,16 +301,16 @@ __global__ __launch_bounds__(kNW * 64, 2) void k_post_stream(const PArgs<D> by_v
 #pragma unroll
             for (int i = 0; i < D; ++i) g[i] = dpp_mov<0x15F, 0x5>(dpp_mov<0x130>(zeta[i]));
 #pragma unroll
-            for (int i = 0; i < D; ++i) zeta[i] = fma(sPw[1][0][i][lane], g[i], fma(sPw[1][1][i][lane], g[partner<D>(i)], zeta[i]));
+            for (int i = 0; i < D; ++i) zeta[i] = block_fma<D>(i, sPw[1][0][i][lane], partner<D>(i) != i ? sPw[1][1][i][lane] : 0.0, g, zeta[i]);
             // the lower half takes lane 32 (complete by now); row 0 sees it through Mg^(16 N) more
 #pragma unroll
             for (int i = 0; i < D; ++i) g[i] = readlane_d(zeta[i], 32);
 #pragma unroll
-            for (int i = 0; i < D; ++i) g3[i] = fma(ka.lgr[4][i], g[i], ka.lgi[4][i] * g[partner<D>(i)]);
+            for (int i = 0; i < D; ++i) g3[i] = block_mul<D>(i, ka.lgr[4][i], ka.lgi[4][i], g);
 #pragma unroll
             for (int i = 0; i < D; ++i) g[i] = lane < 16 ? g3[i] : (lane < 32 ? g[i] : 0.0);
 #pragma unroll
-            for (int i = 0; i < D; ++i) zeta[i] = fma(sPw[1][0][i][lane], g[i], fma(sPw[1][1][i][lane], g[partner<D>(i)], zeta[i]));
+            for (int i = 0; i < D; ++i) zeta[i] = block_fma<D>(i, sPw[1][0][i][lane], partner<D>(i) != i ? sPw[1][1][i][lane] : 0.0, g, zeta[i]);
 #pragma unroll
             for (int i = 0; i < D; ++i) left[i] = readlane_d(zeta[i], 0);
 #pragma unroll
@@ -318,7 +342,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void k_post_stream(const PArgs<D> by_v
                 for (int j = 0; j < 8; ++j) {
                     double nz[D];
 #pragma unroll
-                    for (int i = 0; i < D; ++i) nz[i] = fma(ka.fd[i], z[i], fma(ka.fo[i], z[partner<D>(i)], fma(ka.fb[i], u[j], ka.fa[i])));
+                    for (int i = 0; i < D; ++i) nz[i] = block_fma<D>(i, ka.fd[i], ka.fo[i], z, input_of<D>(i, ka.fb[i], u[j]));
 #pragma unroll
                     for (int i = 0; i < D; ++i) z[i] = nz[i];
                 }
@@ -431,7 +455,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void k_post_stream(const PArgs<D> by_v
         auto finish_prev = [&](v2d* sY, long long tile_t0, const double (&zr)[D], int ln) -> int {
             double zst[D];
 #pragma unroll
-            for (int i = 0; i < D; ++i) zst[i] = fma(sPw[2][0][i][lane], zr[i], fma(sPw[2][1][i][lane], zr[partner<D>(i)], zh[i]));
+            for (int i = 0; i < D; ++i) zst[i] = block_fma<D>(i, sPw[2][0][i][lane], partner<D>(i) != i ? sPw[2][1][i][lane] : 0.0, zr, zh[i]);
             double mm[N];
 #pragma unroll
             for (int j = 0; j < N; ++j) {
@@ -503,10 +527,10 @@ __global__ __launch_bounds__(kNW * 64, 2) void k_post_stream(const PArgs<D> by_v
                 r[j] = rr;
                 double nz[D];
 #pragma unroll
-                for (int i = 0; i < D; ++i) nz[i] = fma(ka.fd[i], z[i], fma(ka.fo[i], z[partner<D>(i)], fma(ka.fb[i], u, ka.fa[i])));
+                for (int i = 0; i < D; ++i) nz[i] = block_fma<D>(i, ka.fd[i], ka.fo[i], z, input_of<D>(i, ka.fb[i], u));
 #pragma unroll
                 for (int i = 0; i < D; ++i) z[i] = nz[i];
-                if ((j & 3) == 3) __builtin_amdgcn_sched_barrier(0);      // (left alone, the scheduler computes every fb u + fa ahead and spills)
+                if ((j & 3) == 3) __builtin_amdgcn_sched_barrier(0);      // (left alone, the scheduler computes every y - hh ahead and spills)
             }
             double zend[D];
             fwd_scan(z, zin, zend);      // (z: the lane's start state)
@@ -540,7 +564,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void k_post_stream(const PArgs<D> by_v
                 yv[j] = m;
                 double nz[D];
 #pragma unroll
-                for (int i = 0; i < D; ++i) nz[i] = fma(ka.gd[i], zeta[i], fma(ka.go[i], zeta[partner<D>(i)], ka.gc[i] * rj));
+                for (int i = 0; i < D; ++i) nz[i] = block_fma<D>(i, ka.gd[i], ka.go[i], zeta, input_of<D>(i, ka.gc[i], rj));
 #pragma unroll
                 for (int i = 0; i < D; ++i) zeta[i] = nz[i];
                 if ((j & 3) == 0) __builtin_amdgcn_sched_barrier(0);
@@ -664,7 +688,7 @@ int launch(hipStream_t st, const tgp_plan::Modal& md, const Geometry& g, const C
     std::memset(&a, 0, sizeof a);
     const int np = md.npair;
     for (int i = 0; i < D; ++i) {
-        a.fd[i] = md.fd[i]; a.fo[i] = md.fo[i]; a.fb[i] = md.fb[i]; a.fa[i] = md.fa[i]; a.fw[i] = md.fw[i];
+        a.fd[i] = md.fd[i]; a.fo[i] = md.fo[i]; a.fb[i] = md.fb[i]; a.fw[i] = md.fw[i];
         a.gd[i] = md.gd[i]; a.go[i] = md.go[i]; a.gc[i] = md.gc[i]; a.gw[i] = md.gw[i];
     }
     double pr[kMaxD], pi[kMaxD], qr[kMaxD], qi[kMaxD];

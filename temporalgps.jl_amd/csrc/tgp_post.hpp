@@ -8,6 +8,7 @@
 //   * the backward recursion needs the NEXT tile's innovations: a tile's outputs are finished one tile late, from the left-edge state of the tile behind
 //     it (tiles are longer than the halo: whatever lies further right has decayed by 2^-64); a run's last tile takes it from a `ghost` pass over the
 //     first halo steps of the next run, a run's first tile its entry state from a state-only pass over the halo steps in front of it.
+// The Modal handed to this unit is the input-normalised form of tgp_stream_form.hpp; z0p and zeta_out are in its coordinates (tgp_modal.hip maps them).
 // Same host protocol as k_steady_one with the head on the host (tgp_modal.hip `complete`): head_in / z0p / zeta_out / head_out and their flags, the
 // tail variances out of the pinned tables behind their stage flag, sum r^2 per workgroup into `part` -- as a (value, check) record behind the workgroup's
 // last acknowledged output store: mean and var are stored write-through, and the host may end the call on the records.
