@@ -148,7 +148,15 @@ typedef struct tgp_handle tgp_handle;
                            too slowly goes to the general engine.  What the reference's predict path produces: posterior_lti_sde.jl:20-37,97-131,
                            missings.jl:25-41, lti_sde.jl:135-146.  The same models (T >= 2048) have tgp_posterior_rand_missing served by the
                            engine's draw kernel (k_sweep_draw), and those in LTI form tgp_logpdf_adjoint_missing by its adjoint kernel
-                           (k_sweep_adjoint).  0: the general chunked-scan engine as before; tgp_posterior_rand_missing and
+                           (k_sweep_adjoint).  5 <= d <= 8 in LTI form (shared A, a, Q, H; not tgp_model_set_sde), T >= 2048: tgp_logpdf /
+                           tgp_[logpdf_and_]posterior_marginals run on the GROUP sweep (tgp_sweep_group.hip) -- the same algorithm,
+                           checks and repair with a chunk spread over 8 lanes, lane j holding column j of every matrix; kernels
+                           k_sweep_group<lti,logpdf> / k_sweep_group<lti,posterior>; the draw and the adjoint stay at d <= 4.  Under 1 the group
+                           sweep takes only the (d, call) pairs that beat the general engine at T = 1e6 and 1e7 (profiles/sweep_group_time.txt):
+                           tgp_logpdf at d = 6, 7, 8; 2: every pair, tgp_logpdf at d = 5 and the posterior calls included (tests, A/B timing;
+                           the lane sweep is the same under 1 and 2).  Both step aside
+                           on an explicit request for the general engine (TGP_REUSE_REDUCE, TGP_OPT_CHUNK, TGP_OPT_VARIANT, TGP_OPT_STEADY 0 / 1,
+                           TGP_OPT_GRAPH).  0: the general chunked-scan engine as before; tgp_posterior_rand_missing and
                            tgp_logpdf_adjoint_missing answer TGP_EUNSUPPORTED for these models. */
 #define TGP_OPT_SWEEP_CHUNK 15       /* tests: steps per chunk of the sweep engine (0 automatic) */
 #define TGP_OPT_SWEEP_WARMUP 16      /* tests: forward warm-up steps (0 automatic); a forced geometry is never repaired by longer warm-ups */

@@ -25,6 +25,7 @@
 #include "tgp_modal.hpp"
 #include "tgp_powers.hpp"
 #include "tgp_sweep.hpp"
+#include "tgp_sweep_group.hpp"
 #include "tgp_wide.hpp"
 #include "tgp_adjoint_host.hpp"
 #include "tgp_alloc.hpp"
@@ -353,10 +354,13 @@ struct tgp_handle {
     // TGP_OPT_SWEEP (default 1): the sweep engine (tgp_sweep.hip) serves tgp_logpdf / tgp_[logpdf_and_]posterior_marginals of Forward
     // models with scalar observations, d <= 4, shared A / a / Q / H (or closed-form SDE transitions) whose gains vary in time: a mask, a noise
     // variance or an emission offset per step, irregular spacing.  One launch; a call whose warm-ups prove too short is repeated with longer
-    // ones (remembered for the bound model), a model it does not serve goes on to the general engine.
+    // ones (remembered for the bound model), a model it does not serve goes on to the general engine.  5 <= d <= 8 in LTI form: the group sweep
+    // (tgp_sweep_group.hip), the same algorithm with a chunk spread over 8 lanes; it shares the state, hints and forced geometry below.
+    // 1: the group sweep takes the measured winners only (sweep_group_default_route); 2: every (d, call) pair.
     int opt_sweep = 1;
     long long opt_stream_min_T = -1;      // TGP_OPT_STREAM_MIN_T
     tgp_sweep::Engine* sweep = nullptr;
+    tgp_sweep_group::Engine* sweep_group = nullptr;
     int sweep_state = 0;          // 0 untried for the bound model, 1 served the last call, -1 does not apply
     int sweep_W = 0, sweep_Wb = 0;     // warm-ups the bound model's last served call needed (0: estimate)
     int sweep_Wd = 0;             // the same for the draw's warm-up (tgp_posterior_rand_missing; 0: the backward warm-up's estimate)
@@ -1320,6 +1324,7 @@ int tgp_destroy(tgp_handle* h) {
     if (h->steady2) tgp_steady::destroy(h->steady2);
     if (h->modal) tgp_modal::destroy(h->modal);
     if (h->sweep) tgp_sweep::destroy(h->sweep);
+    if (h->sweep_group) tgp_sweep_group::destroy(h->sweep_group);
     if (h->host_result) (void)tgp_alloc::host_free(h->host_result);
     if (h->adj_host) (void)tgp_alloc::host_free(h->adj_host);
     if (h->flt_host) (void)tgp_alloc::host_free(h->flt_host);
@@ -1382,7 +1387,7 @@ int tgp_set_option(tgp_handle* h, int option, int64_t value) {
         return TGP_OK;
     }
     if (option == TGP_OPT_SWEEP) {
-        h->opt_sweep = value != 0;
+        h->opt_sweep = value <= 0 ? 0 : (value >= 2 ? 2 : 1);      // (2: the group sweep for every (d, call) pair, not only the measured winners)
         h->sweep_state = 0;
         return TGP_OK;
     }
@@ -2011,6 +2016,11 @@ int tgp_logpdf(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t 
         TRY(sweep_call(h, y, missing, flags, nullptr, nullptr, nullptr, out, &served));
         if (served) return TGP_OK;
     }
+    if (sweep_group_eligible(h, flags, /*post=*/false)) {      // the same at 5 <= d <= 8 (tgp_sweep_group.hip)
+        bool served = false;
+        TRY(sweep_group_call(h, y, missing, flags, nullptr, nullptr, nullptr, out, &served));
+        if (served) return TGP_OK;
+    }
     if (wide_eligible(h, y, missing)) {      // wide LTI models (8 < d <= 63): the stationary closed loop across the chip (tgp_wide.hip)
         bool served = false;
         TRY(wide_call(h, y, flags, nullptr, nullptr, nullptr, out, &served));
@@ -2340,6 +2350,11 @@ int tgp_posterior_marginals(tgp_handle* h, const double* y, const uint8_t* missi
     if (sweep_eligible(h, flags)) {
         bool served = false;
         TRY(sweep_call(h, y, missing, flags, Rnew, mean_out, var_out, lml_out, &served));
+        if (served) return TGP_OK;
+    }
+    if (sweep_group_eligible(h, flags, /*post=*/true)) {      // the same at 5 <= d <= 8 (tgp_sweep_group.hip)
+        bool served = false;
+        TRY(sweep_group_call(h, y, missing, flags, Rnew, mean_out, var_out, lml_out, &served));
         if (served) return TGP_OK;
     }
     if (wide_eligible(h, y, missing)) {      // wide LTI models: tgp_wide.hip

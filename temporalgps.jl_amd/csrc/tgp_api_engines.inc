@@ -156,12 +156,23 @@ bool sweep_eligible(const tgp_handle* h, uint32_t flags) {
     if (h->sde) return h->sde_closed && h->opt_sde_closed && !h->sde_coef_host.empty() && h->mv.sa == 0;
     return h->mv.sA == 0 && h->mv.sa == 0 && h->mv.sQ == 0;
 }
-// Runs the call on the engine.  *served = false: it declined (nothing the caller must undo); the caller goes on to the general engine.
-int sweep_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, double* mean_out, double* var_out,
-               double* lml_out, bool* served) {
-    *served = false;
-    if (!h->sweep) h->sweep = tgp_sweep::create();
-    static const bool dbg = getenv("TGP_STEADY_DEBUG") != nullptr;
+// The group sweep (tgp_sweep_group.hip, DESIGN 4.10): the same conditions at 5 <= d <= 8, LTI form only (an SDE-described model's transition differs
+// per chunk and cannot be the wave-wide broadcast the group kernels read).  Both engines share sweep_state, the forced geometry and tgp_sweep_info.
+// Default routing (TGP_OPT_SWEEP = 1) takes only the (d, call) pairs whose median beat the general engine's at T = 1e6 AND 1e7
+// (profiles/sweep_group_time.txt): logpdf at d = 6, 7, 8.  logpdf at d = 5 loses at 1e7 and the posterior kernel loses at every d at one length at
+// least: those run here under TGP_OPT_SWEEP = 2 only (tests, A/B timing).
+bool sweep_group_default_route(int d, bool post) { return !post && d >= 6; }
+bool sweep_group_eligible(const tgp_handle* h, uint32_t flags, bool post) {
+    if (!h->opt_sweep || h->sweep_state < 0 || h->is_dense || h->p != 1 || h->ordering != 0 || h->sde) return false;
+    if (h->d < tgp_sweep::kGroupMinD || h->d > tgp_sweep::kGroupMaxD) return false;
+    if (h->opt_sweep < 2 && !sweep_group_default_route(h->d, post)) return false;
+    if ((flags & TGP_REUSE_REDUCE) || h->opt_chunk != 0 || h->variant_opt != 0 || !h->opt_steady2 || h->opt_graph != 0) return false;
+    if (h->T < tgp_sweep::kGroupMinT || h->mv.T != h->T || h->mv.sH != 0 || h->sweepm.empty()) return false;
+    return h->mv.sA == 0 && h->mv.sa == 0 && h->mv.sQ == 0;
+}
+
+// The host model the plans of both engines read, from the staged blocks of the bound model
+tgp_sweep::ModelHost sweep_host_model(const tgp_handle* h) {
     const int d = h->d;
     const size_t dd = (size_t)d * d;
     const double* q = h->sweepm.data();
@@ -178,6 +189,28 @@ int sweep_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t 
     mh.x0P = h->x0P.data();
     mh.coef = h->sde ? h->sde_coef_host.data() : nullptr;
     mh.tau_typ = h->sweep_tau;
+    return mh;
+}
+
+// What sweep_run needs of an engine: the lane sweep (tgp_sweep.hip) and the group sweep (tgp_sweep_group.hip) behind one call sequence.  Plain function
+// pointers on the handle (no allocation on the call path); `post`: the call asks for the posterior marginals.
+struct SweepEngineOps {
+    const char* tag;
+    const char* kname;
+    bool post;
+    bool (*plan)(tgp_handle* h, const tgp_sweep::ModelHost& mh, bool post, int W, int Wb, std::string* why);      // (with the handle's forced geometry)
+    int (*enqueue)(tgp_handle* h, const tgp_sweep::Call& c, const char** kname, std::string* err);
+    double (*finish)(tgp_handle* h, int* status, int* w, int* wb, double* dist_f, double* dist_b);
+    void (*geometry)(tgp_handle* h, int* C, int64_t* nwaves);
+};
+
+// Runs a logpdf / posterior call on one of the sweep engines: staging ONCE, up to four attempts with doubled warm-ups, the engine switched off for the
+// bound model where it cannot serve it.  *served = false: it declined (nothing the caller must undo); the caller goes on to the general engine.
+int sweep_run(tgp_handle* h, const SweepEngineOps& eng, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, double* mean_out,
+              double* var_out, double* lml_out, bool* served) {
+    *served = false;
+    static const bool dbg = getenv("TGP_STEADY_DEBUG") != nullptr;
+    const tgp_sweep::ModelHost mh = sweep_host_model(h);
     const bool idev = (flags & TGP_IN_DEVICE) != 0, odev = (flags & TGP_OUT_DEVICE) != 0;
     const bool rshared = (flags & TGP_SHARED_R) != 0;
     const size_t nT = (size_t)h->T * sizeof(double);
@@ -186,9 +219,8 @@ int sweep_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t 
     // inputs and outputs are staged ONCE, in front of the attempts (round-5 advice: a host-resident series was uploaded again by every retry)
     {
         std::string why;
-        tgp_sweep::force_geometry(h->sweep, h->sweep_fC, h->sweep_fW, h->sweep_fWb);
-        if (!tgp_sweep::plan(h->sweep, mh, h->T, W, Wb, h->num_cu, &why)) {
-            if (dbg) fprintf(stderr, "[tgp sweep] does not apply: %s\n", why.c_str());
+        if (!eng.plan(h, mh, eng.post, W, Wb, &why)) {
+            if (dbg) fprintf(stderr, "[tgp %s] does not apply: %s\n", eng.tag, why.c_str());
             h->sweep_state = -1;
             return TGP_OK;
         }
@@ -204,9 +236,8 @@ int sweep_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t 
     for (int attempt = 0; attempt < 4; ++attempt) {
         if (attempt > 0) {
             std::string why;
-            tgp_sweep::force_geometry(h->sweep, h->sweep_fC, h->sweep_fW, h->sweep_fWb);
-            if (!tgp_sweep::plan(h->sweep, mh, h->T, W, Wb, h->num_cu, &why)) {
-                if (dbg) fprintf(stderr, "[tgp sweep] does not apply: %s\n", why.c_str());
+            if (!eng.plan(h, mh, eng.post, W, Wb, &why)) {
+                if (dbg) fprintf(stderr, "[tgp %s] does not apply: %s\n", eng.tag, why.c_str());
                 h->sweep_state = -1;
                 return TGP_OK;
             }
@@ -224,21 +255,21 @@ int sweep_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t 
         c.var = dv;
         {
             std::string err;
-            const char* kname = tgp_sweep::kernel_name(d, h->sde, dm != nullptr);
+            const char* kname = eng.kname;
             LaunchScope ls(h, kname);
-            if (tgp_sweep::enqueue(h->sweep, h->stream, c, &kname, &err) != 0) return h->fail(TGP_EHIP, err);
+            if (eng.enqueue(h, c, &kname, &err) != 0) return h->fail(TGP_EHIP, err);
         }
         tm.kernels_done();
         if (h->timing) (void)hipEventRecord(h->ev[3], h->stream);
         HIPCHK(hipStreamSynchronize(h->stream));
         resolve_profile(h);
         int status = 0, w = 0, wb = 0;
-        const double lml = tgp_sweep::finish(h->sweep, &status, &w, &wb, &h->sweep_dist[0], &h->sweep_dist[1]);
+        const double lml = eng.finish(h, &status, &w, &wb, &h->sweep_dist[0], &h->sweep_dist[1]);
         int C = 0;
         int64_t nw = 0;
-        tgp_sweep::geometry(h->sweep, &C, nullptr, nullptr, &nw);
+        eng.geometry(h, &C, &nw);
         h->sweep_info[1] = C; h->sweep_info[2] = w; h->sweep_info[3] = wb; h->sweep_info[4] = nw; h->sweep_info[5] = attempt + 1; h->sweep_info[6] = status;
-        if (dbg) fprintf(stderr, "[tgp sweep] attempt %d: C %d W %d Wb %d waves %lld status %d dist %.3g / %.3g\n", attempt, C, w, wb, (long long)nw, status, h->sweep_dist[0], h->sweep_dist[1]);
+        if (dbg) fprintf(stderr, "[tgp %s] attempt %d: C %d W %d Wb %d waves %lld status %d dist %.3g / %.3g\n", eng.tag, attempt, C, w, wb, (long long)nw, status, h->sweep_dist[0], h->sweep_dist[1]);
         if (status & 12) {      // not positive definite / non-finite values: the general engine reports it the way it always has
             if (status & 4) h->sweep_state = -1;      // (a property of the model, not of this series: later calls do not pay for a launch that cannot serve them)
             return TGP_OK;
@@ -263,6 +294,38 @@ int sweep_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t 
     }
     h->sweep_state = -1;      // four attempts, warm-ups still too short: a model that mixes too slowly for this engine
     return TGP_OK;
+}
+
+// The lane sweep (d <= 4; LTI and SDE form)
+int sweep_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, double* mean_out, double* var_out,
+               double* lml_out, bool* served) {
+    if (!h->sweep) h->sweep = tgp_sweep::create();
+    const SweepEngineOps eng = {
+        "sweep", tgp_sweep::kernel_name(h->d, h->sde, mean_out != nullptr), mean_out != nullptr,
+        [](tgp_handle* hh, const tgp_sweep::ModelHost& mh, bool, int W, int Wb, std::string* why) {
+            tgp_sweep::force_geometry(hh->sweep, hh->sweep_fC, hh->sweep_fW, hh->sweep_fWb);
+            return tgp_sweep::plan(hh->sweep, mh, hh->T, W, Wb, hh->num_cu, why);
+        },
+        [](tgp_handle* hh, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep::enqueue(hh->sweep, hh->stream, c, kname, err); },
+        [](tgp_handle* hh, int* status, int* w, int* wb, double* df, double* db) { return tgp_sweep::finish(hh->sweep, status, w, wb, df, db); },
+        [](tgp_handle* hh, int* C, int64_t* nw) { tgp_sweep::geometry(hh->sweep, C, nullptr, nullptr, nw); }};
+    return sweep_run(h, eng, y, missing, flags, Rnew, mean_out, var_out, lml_out, served);
+}
+
+// The group sweep (5 <= d <= 8; LTI form)
+int sweep_group_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, double* mean_out, double* var_out,
+                     double* lml_out, bool* served) {
+    if (!h->sweep_group) h->sweep_group = tgp_sweep_group::create();
+    const SweepEngineOps eng = {
+        "sweep group", tgp_sweep_group::kernel_name(mean_out != nullptr), mean_out != nullptr,
+        [](tgp_handle* hh, const tgp_sweep::ModelHost& mh, bool post, int W, int Wb, std::string* why) {
+            tgp_sweep_group::force_geometry(hh->sweep_group, hh->sweep_fC, hh->sweep_fW, hh->sweep_fWb);
+            return tgp_sweep_group::plan(hh->sweep_group, mh, hh->T, W, Wb, hh->num_cu, post, why);
+        },
+        [](tgp_handle* hh, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep_group::enqueue(hh->sweep_group, hh->stream, c, kname, err); },
+        [](tgp_handle* hh, int* status, int* w, int* wb, double* df, double* db) { return tgp_sweep_group::finish(hh->sweep_group, status, w, wb, df, db); },
+        [](tgp_handle* hh, int* C, int64_t* nw) { tgp_sweep_group::geometry(hh->sweep_group, C, nullptr, nullptr, nw); }};
+    return sweep_run(h, eng, y, missing, flags, Rnew, mean_out, var_out, lml_out, served);
 }
 
 // rand of the posterior on the engine (k_sweep_draw, DESIGN 4.7): sweep_call's staging and repair loop around the draw kernel.  The draw pass sits in

@@ -1,0 +1,619 @@
+// The group sweep: see tgp_sweep_group.hpp (what and why) and DESIGN 4.10 (geometry, LDS budget, register counts).  gfx950 only.
+// One wave per workgroup; a wave's LDS: A (512 B), the 8 groups' exchange tiles (8 x 82 doubles) and, in a posterior call, the filtering states of
+// one checkpoint block per group (8 B (d + d (d + 1) / 2) doubles: 13.5 KB at d = 6, B = 8; 11 KB at d = 8, B = 4) -- at most 19.6 KB, so that 8
+// workgroups = two waves per SIMD stay resident in a CU's 160 KB.
+//
+// The column layout and its building blocks are tgp_group.hpp's (GroupLane::predict, group_sum, gather) and tgp_group_smooth.hpp's (the 8-lane
+// Cholesky solve); the recursions are tgp_sweep_body.hpp's update / smooth_step (a missing step: predict only; the RTS step in gain form).
+// Lanes j >= d of a group hold zeros in every column they own, contribute exact zeros to every group sum and never write the tile rows >= d.
+#include "tgp_sweep_group.hpp"
+#include "tgp_alloc.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+namespace tgp_sweep_group {
+
+using tgp_sweep::fast_rcp;
+using tgp_sweep::fast_sqrt_rsqrt;
+using tgp_sweep::GroupModelC;
+using tgp_sweep::kJitter;
+using tgp_sweep::LmlAcc;
+
+struct GArgs {
+    GroupModelC mc;
+    tgp_sweep::Streams st;
+    long long T;
+    int C, W, Wb, owned;
+    long long nchunks;
+    double* mean;
+    double* var;
+    double* ckpt;      // [wave][block][group][NS]: the state in front of every block of B steps (posterior calls)
+    double* part;      // [wave][4]: share of the log marginal likelihood, status bits, forward / backward distance (pinned host memory)
+};
+static_assert(sizeof(GArgs) <= 4096, "the kernel's argument segment");
+
+constexpr int G = tgp_sweep::kGroupLanes;
+constexpr int kTileLD = G * G + 2 * G + 2;      // tgp_group.hpp GroupGeom::LD: an 8 x 8 matrix (i + 8 col), two 8-vectors, 2 doubles of padding
+constexpr int V0 = G * G, V1 = G * G + G;
+
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+template <int CTRL> __device__ __forceinline__ double dpp_move(double x) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xF, 0xF, false);
+    return __hiloint2double(hi, lo);
+}
+// sum over the 8 lanes of a group, every lane ending with the same bits (tgp_group.hpp group_sum)
+__device__ __forceinline__ double group_sum(double x) {
+    x += dpp_move<0xB1>(x);       // quad_perm:[1,0,3,2]
+    x += dpp_move<0x4E>(x);       // quad_perm:[2,3,0,1]
+    x += dpp_move<0x141>(x);      // row_half_mirror
+    return x;
+}
+__device__ __forceinline__ double group_max(double x) {
+    double o = dpp_move<0xB1>(x);
+    x = o > x ? o : x;
+    o = dpp_move<0x4E>(x);
+    x = o > x ? o : x;
+    o = dpp_move<0x141>(x);
+    return o > x ? o : x;
+}
+
+#define TGP_GU _Pragma("unroll")
+
+// a state by columns: lane j holds element j of the mean and column j of the covariance
+template <int D> struct GState {
+    double m;
+    double P[D];
+};
+
+// The 8 steps of a row of the observation stream, one per lane of the group (a 64-byte row per stream and group); handed out step by step with a
+// shuffle inside the group.  XS bit 0: the noise variance is per step, bit 1: the emission offset is.
+template <int XS> struct Row {
+    double y, R, hh;
+    unsigned mk;
+};
+template <int XS> __device__ __forceinline__ void load_row(const GArgs& ka, long long tb, int j, Row<XS>& r) {
+    const long long t = tgp_sweep::clamp_t(tb + j, ka.T);
+    r.y = ka.st.y[t];
+    r.R = (XS & 1) ? ka.st.R[t] : 0.0;
+    r.hh = (XS & 2) ? ka.st.hh[t] : 0.0;
+    r.mk = ka.st.mask != nullptr ? (unsigned)ka.st.mask[t] : 0u;
+}
+
+// KEEP_A: the logpdf kernels (<= 202 registers) unroll the eight steps of a row, and the optimiser keeps A (read from LDS as a wave-wide broadcast) in
+// registers across them; the posterior kernels keep their step loops rolled (forward_run, backward_run).
+template <int D, int XS, bool KEEP_A> struct Lane {
+    static constexpr int NS = D + D * (D + 1) / 2;
+    int j;                // lane inside the group == the column it owns
+    bool act;             // j < D
+    double* tile;         // the group's exchange tile
+    const double* sA;     // A in LDS, row-major [8 i + k], zero outside d x d
+    double Qc[D], H[D], Hj, aj, hh, R;
+
+    // y[:, j] = A x[:, j]
+    __device__ __forceinline__ void mul_A(const double* x, double* y) const {
+        TGP_GU for (int i = 0; i < D; ++i) {
+            double acc = 0.0;
+            TGP_GU for (int k = 0; k < D; ++k) acc = fma(sA[G * i + k], x[k], acc);
+            y[i] = acc;
+        }
+    }
+    // every lane gets the D elements of a vector held one element per lane
+    __device__ __forceinline__ void gather(double vj, double* v, int at) const {
+        wave_sync();
+        tile[at + j] = vj;
+        wave_sync();
+        TGP_GU for (int k = 0; k < D; ++k) v[k] = tile[at + k];
+    }
+    // tile[i + 8 j] = c[i]: lane j writes column j (rows < D only)
+    __device__ __forceinline__ void publish(const double* c) const {
+        wave_sync();
+        TGP_GU for (int i = 0; i < D; ++i) tile[i + G * j] = c[i];
+        wave_sync();
+    }
+    // predict (lgc.jl:46-52):  m <- A m + a,  P <- A P A' + Q.  W = A P is lane-local; its transpose and the gather of m share ONE trip through
+    // the tile; column j of A P A' is A (row j of W)'.  AP (optional): column j of A P of the INCOMING covariance (what invert_dynamics multiplies again).
+    __device__ __forceinline__ void predict(GState<D>& x, double* AP = nullptr) const {
+        double W[D], row[D], v[D];
+        mul_A(x.P, W);
+        if (AP) { TGP_GU for (int i = 0; i < D; ++i) AP[i] = W[i]; }
+        wave_sync();
+        TGP_GU for (int i = 0; i < D; ++i) tile[i + G * j] = W[i];
+        tile[V0 + j] = x.m;
+        wave_sync();
+        TGP_GU for (int k = 0; k < D; ++k) {
+            row[k] = act ? tile[j + G * k] : 0.0;      // rows >= D of the tile are never written
+            v[k] = tile[V0 + k];
+        }
+        mul_A(row, x.P);
+        TGP_GU for (int i = 0; i < D; ++i) x.P[i] += Qc[i];
+        double acc = 0.0;
+        TGP_GU for (int k = 0; k < D; ++k) acc = fma(sA[G * j + k], v[k], acc);
+        x.m = acc + aj;
+    }
+    // posterior_and_lml of a ScalarOutputLGC (lgc.jl:247-257); obs == false: the step is missing, nothing changes (tgp_sweep_body.hpp update)
+    __device__ __forceinline__ void update(GState<D>& x, double y, double Rt, double ht, bool obs, LmlAcc* acc, bool& ok) const {
+        double vj = 0.0;      // V = P H, element j (by symmetry lane-local)
+        TGP_GU for (int i = 0; i < D; ++i) vj = fma(x.P[i], H[i], vj);
+        const double s2 = group_sum(Hj * vj) + Rt;
+        const double hm = group_sum(Hj * x.m) + ht;
+        const double S = obs ? s2 : 1.0;
+        ok = ok && (S > 0.0);
+        const double iS = obs ? fast_rcp(S) : 0.0;
+        const double v = obs ? (y - hm) : 0.0;
+        const double viS = v * iS;
+        x.m = fma(vj, viS, x.m);
+        double V[D];
+        gather(vj, V, V1);
+        const double w = vj * iS;
+        TGP_GU for (int i = 0; i < D; ++i) x.P[i] = fma(-V[i], w, x.P[i]);
+        if (acc) {
+            acc->q = fma(v, viS, acc->q);
+            acc->prod *= S;
+            acc->n += obs ? 1.0 : 0.0;
+        }
+    }
+    // one step of the filter with step k of a row's inputs
+    __device__ __forceinline__ void fstep(GState<D>& x, const Row<XS>& r, int k, long long t, long long T, LmlAcc* acc, bool& ok) const {
+        const double y = __shfl(r.y, k, G);
+        const double Rt = (XS & 1) ? __shfl(r.R, k, G) : R;
+        const double ht = (XS & 2) ? __shfl(r.hh, k, G) : hh;
+        const bool obs = t < T && __shfl((int)r.mk, k, G) == 0;      // (steps behind the series are missing: the runs pad their last row)
+        predict(x);
+        update(x, y, Rt, ht, obs, acc, ok);
+    }
+
+    // One step of the reverse-time recursion (lgssm.jl:231-238 + :111-115; tgp_sweep_body.hpp smooth_step in the column layout): xf = filtering
+    // state of step t, xs = smoothing state of step t + 1 on entry, of step t on return.  G = Pf A' (Pp + 1e-10 I)^-1 by the 8-lane Cholesky of
+    // tgp_group_smooth.hpp; gain form  ms = mf + G (ms+ - mp),  Ps = Pf + G (Ps+ - Pp - 1e-10 I) G'.
+    __device__ __forceinline__ void smooth_step(const GState<D>& xf, GState<D>& xs, bool& ok) const {
+        GState<D> xp = xf;
+        double AP[D];
+        predict(xp, AP);
+        // ---- upper Cholesky factor of Pp + jitter I, one row per step: lane i finishes U[i][i] and hands its column above the diagonal to everybody
+        double Uc[D], rinv[D];
+        TGP_GU for (int i = 0; i < D; ++i) Uc[i] = 0.0;
+        TGP_GU for (int i = 0; i < D; ++i) {
+            double acc = xp.P[i] + ((i == j) ? kJitter : 0.0);
+            wave_sync();
+            if (j == i) {
+                double dg = acc;
+                TGP_GU for (int k = 0; k < i; ++k) dg = fma(-Uc[k], Uc[k], dg);
+                double s, rs;
+                fast_sqrt_rsqrt(dg, s, rs);
+                TGP_GU for (int k = 0; k < i; ++k) tile[V0 + k] = Uc[k];
+                tile[V1 + 0] = dg;
+                tile[V1 + 1] = s;
+                tile[V1 + 2] = rs;
+            }
+            wave_sync();
+            const double dg = tile[V1 + 0], di = tile[V1 + 1];
+            rinv[i] = tile[V1 + 2];
+            ok = ok && (dg > 0.0);
+            TGP_GU for (int k = 0; k < i; ++k) acc = fma(-tile[V0 + k], Uc[k], acc);
+            Uc[i] = (j == i) ? di : ((j > i && act) ? acc * rinv[i] : 0.0);
+        }
+        // ---- column j of G' = (Pp + jitter I)^-1 (A Pf):  U' z = AP[:, j],  U w = z   (U published: tile[i + 8 k] = U[i][k])
+        publish(Uc);
+        double Xc[D];
+        TGP_GU for (int i = 0; i < D; ++i) {
+            double acc = AP[i];
+            TGP_GU for (int k = 0; k < i; ++k) acc = fma(-tile[k + G * i], Xc[k], acc);
+            Xc[i] = acc * rinv[i];
+        }
+        TGP_GU for (int i = D - 1; i >= 0; --i) {
+            double acc = Xc[i];
+            TGP_GU for (int k = i + 1; k < D; ++k) acc = fma(-tile[i + G * k], Xc[k], acc);
+            Xc[i] = acc * rinv[i];
+        }
+        if (!act) { TGP_GU for (int i = 0; i < D; ++i) Xc[i] = 0.0; }
+        // ---- the mean: (G dm)_j = sum_k G'[k][j] dm_k
+        double dm[D];
+        gather(xs.m - xp.m, dm, V0);
+        double accm = xf.m;
+        TGP_GU for (int k = 0; k < D; ++k) accm = fma(Xc[k], dm[k], accm);
+        xs.m = accm;
+        // ---- the covariance: N = G Dm (column j lane-local with G' published: G[i][k] = tile[k + 8 i]), then column j of N G' = N (G')[:, j]
+        double Dm[D], N[D];
+        TGP_GU for (int i = 0; i < D; ++i) Dm[i] = act ? xs.P[i] - xp.P[i] - ((i == j) ? kJitter : 0.0) : 0.0;
+        publish(Xc);
+        TGP_GU for (int i = 0; i < D; ++i) {
+            double acc = 0.0;
+            TGP_GU for (int k = 0; k < D; ++k) acc = fma(tile[k + G * i], Dm[k], acc);
+            N[i] = acc;
+        }
+        publish(N);
+        TGP_GU for (int i = 0; i < D; ++i) {
+            double acc = xf.P[i];
+            TGP_GU for (int k = 0; k < D; ++k) acc = fma(tile[i + G * k], Xc[k], acc);
+            xs.P[i] = act ? acc : 0.0;
+        }
+    }
+    // emission predict of a smoothing state without the replaced noise (the caller adds it): mean = H' m + h, var = H' P H
+    __device__ __forceinline__ void emit(const GState<D>& xs, double ht, double& mean, double& var) const {
+        double pj = 0.0;
+        TGP_GU for (int i = 0; i < D; ++i) pj = fma(xs.P[i], H[i], pj);
+        mean = group_sum(Hj * xs.m) + ht;
+        var = group_sum(Hj * pj);
+    }
+
+    // packed state records (checkpoints in HBM, a block's filtering states in LDS): [m d | upper triangle, column by column]
+    __device__ __forceinline__ void store_packed(double* q, const GState<D>& x) const {
+        if (act) {
+            q[j] = x.m;
+            TGP_GU for (int i = 0; i < D; ++i)
+                if (i <= j) q[D + j * (j + 1) / 2 + i] = x.P[i];
+        }
+    }
+    __device__ __forceinline__ void load_packed(const double* q, GState<D>& x) const {
+        x.m = 0.0;
+        TGP_GU for (int i = 0; i < D; ++i) x.P[i] = 0.0;
+        if (act) {
+            x.m = q[j];
+            TGP_GU for (int i = 0; i < D; ++i) {
+                const int lo = i < j ? i : j, hi = i < j ? j : i;
+                x.P[i] = q[D + hi * (hi + 1) / 2 + lo];
+            }
+        }
+    }
+    // how far apart two states are, relative to the size of a state (tgp_sweep_body.hpp state_distance): this lane's column, then the group's maximum
+    __device__ __forceinline__ double distance(const GroupModelC& mc, const GState<D>& a, const GState<D>& b) const {
+        double worst = 0.0;
+        if (act) {
+            const double sj = mc.sd[j];
+            worst = ::fabs(a.m - b.m) / (sj + ::fabs(a.m) + ::fabs(b.m));
+            TGP_GU for (int i = 0; i < D; ++i) {
+                const double r = ::fabs(a.P[i] - b.P[i]) / (mc.sd[i] * sj);
+                worst = r > worst ? r : worst;
+            }
+        }
+        return group_max(worst);
+    }
+    __device__ __forceinline__ bool finite(const GState<D>& x) const {
+        double s = ::fabs(x.m);
+        TGP_GU for (int i = 0; i < D; ++i) s += ::fabs(x.P[i]);
+        return group_sum(s) < 1e300;      // (false for NaN as well)
+    }
+};
+
+// One forward run of a group: `nrows` rows of 8 steps from step ts on (a multiple of 8, possibly negative); the rows that start in [lo, hi) are
+// processed, whole (steps behind the series' end are missing).  ck (null: none): the state in front of every block of B steps is kept, block
+// (t - ck_t0) / B of the group's checkpoint array (stride ck_ld doubles).
+template <int D, int XS, int B, bool KA>
+__device__ __forceinline__ void forward_run(const GArgs& ka, const Lane<D, XS, KA>& ln, long long ts, int nrows, long long lo, long long hi, GState<D>& x, LmlAcc& acc,
+                                            bool want_lml, double* ck, long long ck_t0, size_t ck_ld, bool& ok) {
+    Row<XS> in, nx;
+    load_row<XS>(ka, ts, ln.j, in);
+    for (int r = 0; r < nrows; ++r) {
+        const long long tb = ts + 8ll * r;
+        load_row<XS>(ka, tb + 8, ln.j, nx);      // in flight while this row computes (behind the last row: clamped, unused)
+        if (tb >= lo && tb < hi) {
+            // (rolled in the posterior kernels: a step is hundreds of instructions, and eight copies of it only stretch the live ranges)
+#pragma unroll(KA ? 8 : 1)
+            for (int k = 0; k < 8; ++k) {
+                if (ck != nullptr && k % B == 0) ln.store_packed(ck + (size_t)((tb + k - ck_t0) / B) * ck_ld, x);
+                ln.fstep(x, in, k, tb + k, ka.T, &acc, ok);
+            }
+        }
+        if (want_lml) acc.flush();
+        else acc.prod = 1.0;
+        in = nx;
+    }
+}
+
+// One backward run of a group over the rows nrows - 1 .. 0 of its chunk (first step t0): the steps below hi are smoothed.  fresh: the run starts at
+// step hi - 1 from that step's filtering state (the end of the series, or a warm-up); otherwise xs holds the smoothing state of step hi (the next
+// group's first step).  On return xs is the smoothing state of step t0.  EMIT: mean / var of the steps are written, a 64-byte row per group.
+// The filtering states of a block are recomputed from its checkpoint into LDS (sF: [step][NS] of this group).
+template <int D, int XS, int B, bool EMIT, bool KA>
+__device__ __forceinline__ void backward_run(const GArgs& ka, const Lane<D, XS, KA>& ln, long long t0, int nrows, long long hi, bool fresh, GState<D>& xs,
+                                             const double* ck, size_t ck_ld, double* sF, bool& ok) {
+    constexpr int NS = Lane<D, XS, KA>::NS;
+    Row<XS> in, nx;
+    load_row<XS>(ka, t0 + 8ll * (nrows - 1), ln.j, in);
+    for (int r = nrows - 1; r >= 0; --r) {
+        const long long tb = t0 + 8ll * r;
+        load_row<XS>(ka, tb - 8, ln.j, nx);      // the next row (row r - 1): in flight through this one
+        double om = 0.0, ov = 0.0, rn = 0.0;
+        if (EMIT) rn = ka.st.Rnew[ka.st.rnew_per_step ? tgp_sweep::clamp_t(tb + ln.j, ka.T) : 0];
+#pragma nounroll
+        for (int s = 8 / B - 1; s >= 0; --s) {
+            const long long tsb = tb + s * B;
+            if (tsb < hi) {
+                // ---- the block's filtering states, forwards from its checkpoint
+                GState<D> x;
+                ln.load_packed(ck + (size_t)((tsb - t0) / B) * ck_ld, x);
+                wave_sync();
+#pragma nounroll
+                for (int k = 0; k < B; ++k) {
+                    ln.fstep(x, in, s * B + k, tsb + k, ka.T, (LmlAcc*)nullptr, ok);
+                    ln.store_packed(sF + k * NS, x);
+                }
+                wave_sync();
+                // ---- backwards through the block
+#pragma nounroll
+                for (int k = B - 1; k >= 0; --k) {
+                    const long long t = tsb + k;
+                    if (t < hi) {
+                        GState<D> xf;
+                        ln.load_packed(sF + k * NS, xf);
+                        if (fresh && t == hi - 1) xs = xf;
+                        else ln.smooth_step(xf, xs, ok);
+                        if (EMIT) {
+                            double mu, vr;
+                            ln.emit(xs, (XS & 2) ? __shfl(in.hh, s * B + k, G) : ln.hh, mu, vr);
+                            om = (ln.j == s * B + k) ? mu : om;
+                            ov = (ln.j == s * B + k) ? vr : ov;
+                        }
+                    }
+                }
+            }
+        }
+        if (EMIT && tb + ln.j < hi) {
+            ka.mean[tb + ln.j] = om;
+            ka.var[tb + ln.j] = ov + rn;
+        }
+        in = nx;
+    }
+}
+
+// (no register cap: under amdgpu_waves_per_eu(2) the posterior kernels spill from d = 6 on -- 28 to 560 bytes of scratch -- and a sequential
+//  recursion pays for every spilled value in its dependent chain; the counts are in profiles/sweep_group_resources.txt)
+template <int D, int XS, bool POST>
+__global__ __launch_bounds__(64) void k_sweep_group(const GArgs by_value) {
+    (void)by_value;
+    const GArgs& ka = *(const GArgs*)__builtin_amdgcn_kernarg_segment_ptr();      // (read in place: tgp_sweep.hip k_sweep)
+    constexpr int B = tgp_sweep::group_block(D), NS = Lane<D, XS, !POST>::NS, NG = tgp_sweep::kGroupsPerWave;
+    __shared__ __attribute__((aligned(16))) double sA[G * G];
+    __shared__ double tiles[NG * kTileLD];
+    __shared__ double sF[POST ? NG * B * NS : 1];
+    const int lane = threadIdx.x, g = lane / G;
+    const long long wave = blockIdx.x;
+    sA[lane] = ka.mc.A[lane];
+    __syncthreads();
+
+    Lane<D, XS, !POST> ln;
+    ln.j = lane % G;
+    ln.act = ln.j < D;
+    ln.tile = tiles + g * kTileLD;
+    ln.sA = sA;
+    const int j = ln.j;
+    TGP_GU for (int i = 0; i < D; ++i) {
+        ln.Qc[i] = ln.act ? ka.mc.Q[i + G * j] : 0.0;
+        ln.H[i] = ka.mc.H[i];
+    }
+    ln.Hj = ln.act ? ka.mc.H[j] : 0.0;
+    ln.aj = ln.act ? ka.mc.a[j] : 0.0;
+    ln.hh = ka.mc.hh;
+    ln.R = ka.mc.R;
+
+    const long long T = ka.T;
+    const int C = ka.C;
+    const tgp_sweep::GroupSpan span = tgp_sweep::group_span(wave, g, ka.owned, ka.nchunks, C, T);
+    const long long t0 = span.t0, t1 = span.t1;
+    const long long t1r = (t1 + 7) & ~7ll;                 // the runs work in whole rows: the steps behind the series' end are missing ones
+    const bool runs = span.runs;                           // group 0 only warms up for group 1
+    const bool owned = span.owned;                         // (posterior calls) group 7 only warms up backwards for group 6
+    bool ok = true;
+
+    GState<D> gen, x0;
+    gen.m = ln.act ? ka.mc.gm[j] : 0.0;
+    x0.m = ln.act ? ka.mc.x0m[j] : 0.0;
+    TGP_GU for (int i = 0; i < D; ++i) {
+        gen.P[i] = ln.act ? ka.mc.gP[i + G * j] : 0.0;
+        x0.P[i] = ln.act ? ka.mc.x0P[i + G * j] : 0.0;
+    }
+    const size_t ck_ld = (size_t)NG * NS;
+    double* ck = POST ? ka.ckpt + (size_t)wave * (size_t)(C / B) * ck_ld + (size_t)g * NS : nullptr;
+    double* sFg = sF + (POST ? g * B * NS : 0);
+
+    // ---- forwards.  Pass 0: the last W steps of the chunk from the stationary prior (from x0 where they reach the series' first step); its end
+    // state is the NEXT group's start state.  Pass 1: the chunk from the previous group's end state (checkpoints, log marginal likelihood).
+    GState<D> x, e1;
+    LmlAcc acc;
+    {
+        const long long tw = t1r - ka.W;
+        x = tw <= 0 ? x0 : gen;
+        forward_run<D, XS, B, !POST>(ka, ln, tw, ka.W / 8, tw > 0 ? tw : 0, t1r, x, acc, false, (double*)nullptr, 0, 0, ok);
+        e1 = x;
+        x.m = __shfl_up(e1.m, G, 64);
+        TGP_GU for (int i = 0; i < D; ++i) x.P[i] = __shfl_up(e1.P[i], G, 64);
+        if (t0 == 0) x = x0;
+        acc = LmlAcc();
+        forward_run<D, XS, B, !POST>(ka, ln, t0, C / 8, t0, runs ? t1r : t0, x, acc, true, ck, t0, ck_ld, ok);
+    }
+    double dist_f = 0.0, dist_b = 0.0;
+    bool finite = true;
+    {
+        const double df = ln.distance(ka.mc, x, e1);
+        const bool fin = ln.finite(x) && ln.finite(e1);
+        if (owned) {
+            dist_f = df;
+            finite = fin;
+        }
+    }
+
+    if (POST) {
+        // ---- backwards, the warm-up: the smoothing state of the chunk's first step as its first Wb steps give it from the filtering state behind
+        // them (exact where they reach the series' last step) -- what the PREVIOUS group continues from
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // (the checkpoints are read back by other lanes of the group)
+        const long long te = (t0 + ka.Wb < t1) ? t0 + ka.Wb : t1;
+        GState<D> b1 = gen;
+        backward_run<D, XS, B, false, !POST>(ka, ln, t0, ka.Wb / 8, runs ? te : t0, true, b1, ck, ck_ld, sFg, ok);
+        // ---- backwards, the chunk: from the next group's smoothing state of ITS first step; mean and variance of every step
+        GState<D> xs;
+        xs.m = __shfl_down(b1.m, G, 64);
+        TGP_GU for (int i = 0; i < D; ++i) xs.P[i] = __shfl_down(b1.P[i], G, 64);
+        backward_run<D, XS, B, true, !POST>(ka, ln, t0, C / 8, owned ? t1 : t0, t1 == T, xs, ck, ck_ld, sFg, ok);
+        const double db = ln.distance(ka.mc, xs, b1);
+        const bool fin = ln.finite(xs) && ln.finite(b1);
+        if (owned) {
+            dist_b = db;
+            finite = finite && fin;
+        }
+    }
+
+    // ---- the wave's share: fixed-order sums over the groups (every lane of a group holds the same sums: lane 0 of each contributes)
+    double lml = (owned && j == 0) ? acc.total() : 0.0;
+    finite = finite && (::fabs(lml) < 1e300);
+    unsigned bits = 0;
+    if (owned && !(dist_f <= ka.mc.tol)) bits |= 1u;
+    if (owned && POST && !(dist_b <= ka.mc.tol_b)) bits |= 2u;
+    if (!ok) bits |= 4u;
+    if (!finite) bits |= 8u;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        lml += __shfl_xor(lml, off, 64);
+        bits |= (unsigned)__shfl_xor((int)bits, off, 64);
+        const double of = __shfl_xor(dist_f, off, 64), ob = __shfl_xor(dist_b, off, 64);
+        dist_f = (of > dist_f) ? of : dist_f;
+        dist_b = (ob > dist_b) ? ob : dist_b;
+    }
+    if (lane == 0) {
+        double* p = ka.part + (size_t)wave * 4;
+        p[0] = lml;
+        p[1] = (double)bits;
+        p[2] = dist_f;
+        p[3] = dist_b;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------ host side
+struct Engine {
+    tgp_sweep::GroupPlan p;
+    tgp_sweep::Forced forced;
+    double* part = nullptr;      // pinned: the waves' shares
+    size_t part_cap = 0;
+    void* ckpt = nullptr;
+    size_t ckpt_cap = 0;
+};
+
+Engine* create() { return new Engine(); }
+void destroy(Engine* e) {
+    if (!e) return;
+    if (e->part) (void)tgp_alloc::host_free(e->part);
+    if (e->ckpt) (void)tgp_alloc::dev_free(e->ckpt);
+    delete e;
+}
+void force_geometry(Engine* e, int C, int W, int Wb) {
+    e->forced.C = C;
+    e->forced.W = W;
+    e->forced.Wb = Wb;
+}
+void geometry(const Engine* e, int* C, int* W, int* Wb, int64_t* nwaves) {
+    if (C) *C = e->p.C;
+    if (W) *W = e->p.W;
+    if (Wb) *Wb = e->p.Wb;
+    if (nwaves) *nwaves = e->p.nwaves;
+}
+bool plan(Engine* e, const tgp_sweep::ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why) {
+    return tgp_sweep::plan_group(&e->p, e->forced, m, T, w_hint, wb_hint, num_cu, post, why);
+}
+const char* kernel_name(bool post) { return post ? "k_sweep_group<lti,posterior>" : "k_sweep_group<lti,logpdf>"; }
+
+namespace {
+
+template <int D, int XS> void launch_x(const Engine* e, hipStream_t stream, const GArgs& ka, bool post) {
+    if (post) hipLaunchKernelGGL((k_sweep_group<D, XS, true>), dim3((unsigned)e->p.nwaves), dim3(64), 0, stream, ka);
+    else hipLaunchKernelGGL((k_sweep_group<D, XS, false>), dim3((unsigned)e->p.nwaves), dim3(64), 0, stream, ka);
+}
+template <int D> void launch_d(const Engine* e, hipStream_t stream, const GArgs& ka, bool post) {
+    const int xs = (ka.st.R != nullptr ? 1 : 0) | (ka.st.hh != nullptr ? 2 : 0);
+    switch (xs) {
+        case 0: launch_x<D, 0>(e, stream, ka, post); break;
+        case 1: launch_x<D, 1>(e, stream, ka, post); break;
+        case 2: launch_x<D, 2>(e, stream, ka, post); break;
+        default: launch_x<D, 3>(e, stream, ka, post); break;
+    }
+}
+
+}  // namespace
+
+int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char** kname, std::string* err) {
+    auto fail = [&](const char* what, hipError_t rc) {
+        if (err) *err = std::string(what) + ": " + hipGetErrorString(rc);
+        return 1;
+    };
+    const tgp_sweep::GroupPlan& p = e->p;
+    const bool post = c.mean != nullptr;
+    if (post != p.post || c.T != p.T || (post && (c.var == nullptr || c.Rnew == nullptr))) {
+        if (err) *err = "k_sweep_group: the call does not match its plan";
+        return 1;
+    }
+    const size_t need_part = (size_t)p.nwaves * 4 * sizeof(double);
+    if (need_part > e->part_cap) {
+        if (e->part) (void)tgp_alloc::host_free(e->part);
+        e->part = nullptr;
+        e->part_cap = 0;
+        const size_t cap = std::max<size_t>(need_part, 1 << 16);
+        hipError_t rc = tgp_alloc::host_malloc((void**)&e->part, cap, hipHostMallocDefault);
+        if (rc != hipSuccess) return fail("hipHostMalloc", rc);
+        e->part_cap = cap;
+    }
+    if (post) {
+        const int NS = p.d + p.d * (p.d + 1) / 2;
+        const size_t need = (size_t)p.nwaves * (size_t)(p.C / p.B) * tgp_sweep::kGroupsPerWave * NS * sizeof(double);
+        if (need > e->ckpt_cap) {
+            if (e->ckpt) (void)tgp_alloc::dev_free(e->ckpt);
+            e->ckpt = nullptr;
+            e->ckpt_cap = 0;
+            hipError_t rc = tgp_alloc::dev_malloc(&e->ckpt, need);
+            if (rc != hipSuccess) return fail("hipMalloc", rc);
+            e->ckpt_cap = need;
+        }
+    }
+    GArgs ka;
+    ka.mc = p.mc;
+    ka.st.y = c.y;
+    ka.st.mask = c.mask;
+    ka.st.R = c.R;
+    ka.st.hh = c.hh;
+    ka.st.tau = nullptr;
+    ka.st.Rnew = c.Rnew;
+    ka.st.rnew_per_step = c.rnew_per_step;
+    ka.T = p.T;
+    ka.C = p.C;
+    ka.W = p.W;
+    ka.Wb = p.Wb;
+    ka.owned = p.owned;
+    ka.nchunks = p.nchunks;
+    ka.mean = c.mean;
+    ka.var = c.var;
+    ka.ckpt = static_cast<double*>(e->ckpt);
+    ka.part = e->part;
+    if (kname) *kname = kernel_name(post);
+    switch (p.d) {
+        case 5: launch_d<5>(e, stream, ka, post); break;
+        case 6: launch_d<6>(e, stream, ka, post); break;
+        case 7: launch_d<7>(e, stream, ka, post); break;
+        default: launch_d<8>(e, stream, ka, post); break;
+    }
+    hipError_t rc = hipGetLastError();
+    if (rc != hipSuccess) return fail("k_sweep_group launch", rc);
+    return 0;
+}
+
+double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* dist_b) {
+    double lml = 0.0, df = 0.0, db = 0.0;
+    unsigned bits = 0;
+    for (int64_t i = 0; i < e->p.nwaves; ++i) {      // fixed order: the same sum for the same geometry
+        const double* q = e->part + (size_t)i * 4;
+        lml += q[0];
+        bits |= (unsigned)q[1];
+        df = std::max(df, q[2]);
+        db = std::max(db, q[3]);
+    }
+    if (status) *status = (int)bits;
+    if (w) *w = e->p.W;
+    if (wb) *wb = e->p.Wb;
+    if (dist_f) *dist_f = df;
+    if (dist_b) *dist_b = db;
+    return lml;
+}
+
+}  // namespace tgp_sweep_group

@@ -195,6 +195,52 @@ template <int D> inline void host_sde_A(const double* q, double tau, double* A) 
 constexpr double kTol = 1e-12, kTolBack = 1e-11;
 constexpr int kMaxWarm = 4096;
 
+// The stationary prior of an LTI model (where a warm-up starts from): Aty / Qty = the transition with Q symmetrised, gm the stationary mean, Ps the
+// stationary covariance.  false: the transition has none.
+template <int D> inline bool stationary_prior(const ModelHost& m, double* Aty, double* Qty, double* gm, double* Ps) {
+    for (int i = 0; i < D * D; ++i) { Aty[i] = m.A[i]; Qty[i] = 0.5 * (m.Q[i] + m.Q[(i % D) * D + i / D]); }
+    if (!lyapunov<D>(Aty, Qty, Ps)) return false;
+    // stationary mean: (I - A) gm = a, by fixed-point iteration (spectral radius < 1)
+    for (int i = 0; i < D; ++i) gm[i] = 0.0;
+    for (int it = 0; it < 100000; ++it) {
+        double nx[D], ch = 0.0;
+        for (int i = 0; i < D; ++i) {
+            double acc = m.a[i];
+            for (int k = 0; k < D; ++k) acc += Aty[i + k * D] * gm[k];
+            nx[i] = acc;
+            ch = std::max(ch, std::fabs(acc - gm[i]));
+        }
+        std::memcpy(gm, nx, sizeof nx);
+        if (ch == 0.0 || ch < 1e-300) break;
+        double mx = 0.0;
+        for (int i = 0; i < D; ++i) mx = std::max(mx, std::fabs(gm[i]));
+        if (ch <= 1e-15 * mx) break;
+    }
+    return true;
+}
+
+// The warm-up lengths (multiples of 8) where the caller has none (W / Wb <= 0 on entry): the forgetting-rate estimate with its margin.
+// false: the filter does not forget within kMaxWarm steps.
+template <int D> inline bool estimate_warmups(const double* Aty, const double* Qty, const double* H, double R, int& W, int& Wb, std::string* why) {
+    if (W <= 0 || Wb <= 0) {
+        // (the estimate is for a series observed at every step with the representative noise: missing steps and larger noise slow the forgetting
+        //  -- hence the margin -- and the checks decide: a call that finds its warm-ups short is repeated with longer ones and the bound model
+        //  remembers them.  Measured at the bench model with 10 % missing: 1e-12 forwards needs 100 steps, the estimate says 96 + margin.)
+        const double Rrep = R > 0.0 && R < 1e14 ? R : 1.0;
+        const int nf = forget_steps<D>(Aty, Qty, H, Rrep, kTol, kMaxWarm);
+        const int nb = forget_steps<D>(Aty, Qty, H, Rrep, kTolBack, kMaxWarm);
+        if (nf == 0 || nb == 0) {
+            if (why) *why = "the filter does not forget a state within 4096 steps";
+            return false;
+        }
+        if (W <= 0) W = nf + nf / 8 + 8;
+        if (Wb <= 0) Wb = nb + nb / 8 + 8;
+    }
+    W = (W + 7) / 8 * 8;
+    Wb = (Wb + 7) / 8 * 8;
+    return true;
+}
+
 template <int D> inline bool plan_d(Plan* e, const Forced& f, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, std::string* why, int wd_hint,
                                         int wa_hint) {
     constexpr int B = Geo<D>::B;
@@ -234,50 +280,18 @@ template <int D> inline bool plan_d(Plan* e, const Forced& f, const ModelHost& m
                 Qty[i + j * D] = Pinf[i + j * D] - a;
             }
     } else {
-        for (int i = 0; i < D * D; ++i) { Aty[i] = m.A[i]; Qty[i] = 0.5 * (m.Q[i] + m.Q[(i % D) * D + i / D]); }
-        double Ps[D * D];
-        if (!lyapunov<D>(Aty, Qty, Ps)) {
+        double gm[D], Ps[D * D];
+        if (!stationary_prior<D>(m, Aty, Qty, gm, Ps)) {
             if (why) *why = "the transition has no stationary covariance";
             return false;
-        }
-        // stationary mean: (I - A) gm = a, by fixed-point iteration (spectral radius < 1)
-        double gm[D] = {};
-        for (int it = 0; it < 100000; ++it) {
-            double nx[D], ch = 0.0;
-            for (int i = 0; i < D; ++i) {
-                double acc = m.a[i];
-                for (int k = 0; k < D; ++k) acc += Aty[i + k * D] * gm[k];
-                nx[i] = acc;
-                ch = std::max(ch, std::fabs(acc - gm[i]));
-            }
-            std::memcpy(gm, nx, sizeof gm);
-            if (ch == 0.0 || ch < 1e-300) break;
-            double mx = 0.0;
-            for (int i = 0; i < D; ++i) mx = std::max(mx, std::fabs(gm[i]));
-            if (ch <= 1e-15 * mx) break;
         }
         for (int i = 0; i < D; ++i) mc.gm[i] = gm[i];
         for (int j = 0; j < D; ++j)
             for (int i = 0; i <= j; ++i) mc.gP[pidx(i, j)] = 0.5 * (Ps[i + j * D] + Ps[j + i * D]);
     }
     int W = w_hint, Wb = wb_hint;
-    if (W <= 0 || Wb <= 0) {
-        // (the estimate is for a series observed at every step with the representative noise: missing steps and larger noise slow the forgetting
-        //  -- hence the margin -- and the checks decide: a call that finds its warm-ups short is repeated with longer ones and the bound model
-        //  remembers them.  Measured at the bench model with 10 % missing: 1e-12 forwards needs 100 steps, the estimate says 96 + margin.)
-        const double Rrep = m.R > 0.0 && m.R < 1e14 ? m.R : 1.0;
-        const int nf = forget_steps<D>(Aty, Qty, m.H, Rrep, kTol, kMaxWarm);
-        const int nb = forget_steps<D>(Aty, Qty, m.H, Rrep, kTolBack, kMaxWarm);
-        if (nf == 0 || nb == 0) {
-            if (why) *why = "the filter does not forget a state within 4096 steps";
-            return false;
-        }
-        if (W <= 0) W = nf + nf / 8 + 8;
-        if (Wb <= 0) Wb = nb + nb / 8 + 8;
-    }
+    if (!estimate_warmups<D>(Aty, Qty, m.H, m.R, W, Wb, why)) return false;
     auto up = [](int v, int q) { return (v + q - 1) / q * q; };
-    W = up(W, 8);
-    Wb = up(Wb, 8);
     // chunk length: the machine holds 4 waves per CU (their LDS), every wave 62 chunks of its own; a chunk holds the backward warm-up
     const int64_t slots = (int64_t)std::max(num_cu, 1) * 4 * kOwned;
     int64_t C = up((int)std::min<int64_t>((T + slots - 1) / slots, 1 << 20), 8);
@@ -336,6 +350,141 @@ inline bool make_plan(Plan* p, const Forced& f, const ModelHost& m, int64_t T, i
         case 2: return plan_detail::plan_d<2>(p, f, m, T, w_hint, wb_hint, num_cu, why, wd_hint, wa_hint);
         case 3: return plan_detail::plan_d<3>(p, f, m, T, w_hint, wb_hint, num_cu, why, wd_hint, wa_hint);
         default: return plan_detail::plan_d<4>(p, f, m, T, w_hint, wb_hint, num_cu, why, wd_hint, wa_hint);
+    }
+}
+
+// ---- the group sweep (tgp_sweep_group.hip): the same algorithm at 5 <= d <= 8, a chunk spread over 8 lanes ---------------------------
+// A wave holds 8 groups = 8 consecutive chunks.  Group 0 only warms up for group 1; in a posterior call group 7 only warms up (backwards) for group 6.
+constexpr int kGroupMinD = 5, kGroupMaxD = 8;
+constexpr int kGroupLanes = 8, kGroupsPerWave = 8;
+// waves resident per CU: two per SIMD by LDS and registers, but one where the posterior kernel takes more than 256 registers (d >= 6:
+// profiles/sweep_group_resources.txt) -- the grid is sized for what is resident, one round of waves
+constexpr int group_waves_per_cu(int d, bool post) { return (post && d >= 6) ? 4 : 8; }
+constexpr int64_t kGroupMinT = 2048;           // shorter series stay on the general engine
+constexpr int group_owned(bool post) { return post ? kGroupsPerWave - 2 : kGroupsPerWave - 1; }
+// steps per checkpoint block: the block's filtering states (d + d (d + 1) / 2 doubles per step and group) sit in LDS during the backward run
+constexpr int group_block(int d) { return d <= 6 ? 8 : 4; }
+
+// The steps [t0, t1) of group g (0 .. 7) of a wave, as the kernel and the tests compute them: the wave's groups hold the chunks
+// wave * owned - 1 .. wave * owned + 6.  runs: the group runs its chunk (group 0 only warms up); owned: it writes output and sums.
+struct GroupSpan {
+    long long t0, t1;
+    bool runs, owned;
+};
+TGP_HD GroupSpan group_span(long long wave, int g, int owned, long long nchunks, int C, long long T) {
+    const long long c = wave * owned + g - 1;
+    const bool active = c >= 0 && c < nchunks;
+    GroupSpan s;
+    s.t0 = active ? c * C : 0;
+    s.t1 = active ? s.t0 + C : 0;
+    s.t1 = s.t1 < T ? s.t1 : (active ? T : 0);
+    s.runs = active && g >= 1;
+    s.owned = s.runs && g <= owned;
+    return s;
+}
+
+// The model's shared blocks as the group kernels read them: padded to 8 whatever d is (the padding is zero), A row-major (read from LDS as a
+// broadcast), the symmetric blocks full and column-major (lane j reads column j).
+struct GroupModelC {
+    double A[64];                     // [8 i + k]
+    double a[8], H[8], x0m[8], gm[8];
+    double Q[64], x0P[64], gP[64];    // [i + 8 j]
+    double sd[8];                     // sqrt(gP[i][i]): the scale of a state's element i (the hand-over checks)
+    double hh, R, tol, tol_b;
+};
+
+struct GroupPlan {
+    int d = 0, B = 0, owned = 0;
+    bool post = false;
+    int C = 0, W = 0, Wb = 0;
+    int64_t T = 0, nchunks = 0, nwaves = 0;
+    GroupModelC mc;
+};
+
+namespace plan_detail {
+
+template <int D> inline bool plan_group_d(GroupPlan* e, const Forced& f, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post,
+                                          std::string* why) {
+    double Aty[D * D], Qty[D * D], gm[D], Ps[D * D];
+    if (!stationary_prior<D>(m, Aty, Qty, gm, Ps)) {
+        if (why) *why = "the transition has no stationary covariance";
+        return false;
+    }
+    int W = w_hint, Wb = wb_hint;
+    if (!estimate_warmups<D>(Aty, Qty, m.H, m.R, W, Wb, why)) return false;
+    auto up = [](int v, int q) { return (v + q - 1) / q * q; };
+    // chunk length: group_waves_per_cu waves per CU, every wave `owned` chunks of its own; a chunk holds the backward warm-up.  A multiple of 8 (the rows
+    // of the observation stream), hence of the checkpoint block.
+    const int owned = group_owned(post);
+    const int64_t slots = (int64_t)std::max(num_cu, 1) * group_waves_per_cu(D, post) * owned;
+    int64_t C = up((int)std::min<int64_t>((T + slots - 1) / slots, 1 << 20), 8);
+    C = std::max<int64_t>(C, 64);
+    C = std::max<int64_t>(C, Wb);
+    if (f.C > 0) C = up(f.C, 8);
+    if (f.W > 0) W = up(f.W, 8);
+    if (f.Wb > 0) Wb = up(f.Wb, 8);
+    if (Wb > C) Wb = (int)C;
+    if (W > kMaxWarm || (f.C == 0 && W > 4 * C)) {
+        if (why) *why = "forward warm-up longer than four chunks";
+        return false;
+    }
+    const int64_t nchunks = (T + C - 1) / C;
+    if (nchunks < owned) {
+        if (why) *why = "fewer chunks than one wave owns";
+        return false;
+    }
+    e->d = D;
+    e->B = group_block(D);
+    e->owned = owned;
+    e->post = post;
+    e->T = T;
+    e->C = (int)C;
+    e->W = W;
+    e->Wb = Wb;
+    e->nchunks = nchunks;
+    e->nwaves = (nchunks + owned - 1) / owned;
+    GroupModelC& mc = e->mc;
+    std::memset(&mc, 0, sizeof mc);
+    for (int i = 0; i < D; ++i) {
+        mc.a[i] = m.a[i];
+        mc.H[i] = m.H[i];
+        mc.x0m[i] = m.x0m[i];
+        mc.gm[i] = gm[i];
+        for (int k = 0; k < D; ++k) mc.A[8 * i + k] = m.A[i + k * D];
+    }
+    for (int j = 0; j < D; ++j)
+        for (int i = 0; i < D; ++i) {
+            const int lo = std::min(i, j), hi = std::max(i, j);
+            mc.Q[i + 8 * j] = Qty[i + j * D];
+            mc.x0P[i + 8 * j] = m.x0P[lo + hi * D];      // Symmetric(P): the upper triangle is what the reference reads (lgc.jl:50)
+            mc.gP[i + 8 * j] = 0.5 * (Ps[i + j * D] + Ps[j + i * D]);
+        }
+    for (int i = 0; i < D; ++i) mc.sd[i] = std::sqrt(mc.gP[i + 8 * i]);
+    mc.hh = m.hh;
+    mc.R = m.R;
+    mc.tol = kTol;
+    mc.tol_b = kTolBack;
+    return true;
+}
+
+}  // namespace plan_detail
+
+// The geometry of a group-sweep call (LTI form); false: the engine declines (`why` says so).  post: a posterior call (6 of a wave's 8 groups own
+// output instead of 7).  w_hint / wb_hint as make_plan's.
+inline bool plan_group(GroupPlan* p, const Forced& f, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why) {
+    if (m.d < kGroupMinD || m.d > kGroupMaxD || m.sde) {
+        if (why) *why = "state dimension";
+        return false;
+    }
+    if (T < kGroupMinT) {
+        if (why) *why = "series shorter than 2048 steps";
+        return false;
+    }
+    switch (m.d) {
+        case 5: return plan_detail::plan_group_d<5>(p, f, m, T, w_hint, wb_hint, num_cu, post, why);
+        case 6: return plan_detail::plan_group_d<6>(p, f, m, T, w_hint, wb_hint, num_cu, post, why);
+        case 7: return plan_detail::plan_group_d<7>(p, f, m, T, w_hint, wb_hint, num_cu, post, why);
+        default: return plan_detail::plan_group_d<8>(p, f, m, T, w_hint, wb_hint, num_cu, post, why);
     }
 }
 

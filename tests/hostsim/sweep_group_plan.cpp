@@ -1,0 +1,54 @@
+// Stand-alone host program around tgp_sweep_plan.hpp's plan_group (tests/test_sweep_group_plan.py): no GPU, no HIP.
+//   sweep_group_plan MODEL_FILE T num_cu post fC fW fWb w_hint wb_hint
+// MODEL_FILE: text, d then the blocks column-major: A d*d, a d, Q d*d, H d, hh, R, x0m d, x0P d*d.
+// Prints "declined: <why>" or "ok d B owned C W Wb nchunks nwaves" followed by one line "span wave g t0 t1 runs owned" per group of every wave
+// (group_span: the expression the kernel uses).
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "../../temporalgps.jl_amd/csrc/tgp_sweep_plan.hpp"
+
+int main(int argc, char** argv) {
+    if (argc != 10) return 2;
+    FILE* f = std::fopen(argv[1], "r");
+    if (!f) return 2;
+    int d = 0;
+    if (std::fscanf(f, "%d", &d) != 1 || d < 1 || d > 16) return 2;
+    const size_t dd = (size_t)d * d;
+    std::vector<double> v(3 * dd + 3 * (size_t)d + 2);
+    for (double& x : v)
+        if (std::fscanf(f, "%lf", &x) != 1) return 2;
+    std::fclose(f);
+    tgp_sweep::ModelHost m;
+    m.d = d;
+    m.A = v.data();
+    m.a = m.A + dd;
+    m.Q = m.a + d;
+    m.H = m.Q + dd;
+    m.hh = m.H[d];
+    m.R = m.H[d + 1];
+    m.x0m = m.H + d + 2;
+    m.x0P = m.x0m + d;
+    const long long T = std::atoll(argv[2]);
+    const int num_cu = std::atoi(argv[3]);
+    const bool post = std::atoi(argv[4]) != 0;
+    tgp_sweep::Forced fc;
+    fc.C = std::atoi(argv[5]);
+    fc.W = std::atoi(argv[6]);
+    fc.Wb = std::atoi(argv[7]);
+    tgp_sweep::GroupPlan p;
+    std::string why;
+    if (!tgp_sweep::plan_group(&p, fc, m, T, std::atoi(argv[8]), std::atoi(argv[9]), num_cu, post, &why)) {
+        std::printf("declined: %s\n", why.c_str());
+        return 0;
+    }
+    std::printf("ok %d %d %d %d %d %d %lld %lld\n", p.d, p.B, p.owned, p.C, p.W, p.Wb, (long long)p.nchunks, (long long)p.nwaves);
+    for (long long w = 0; w < p.nwaves; ++w)
+        for (int g = 0; g < tgp_sweep::kGroupsPerWave; ++g) {
+            const tgp_sweep::GroupSpan s = tgp_sweep::group_span(w, g, p.owned, p.nchunks, p.C, p.T);
+            std::printf("span %lld %d %lld %lld %d %d\n", w, g, s.t0, s.t1, (int)s.runs, (int)s.owned);
+        }
+    return 0;
+}
