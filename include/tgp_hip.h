@@ -151,17 +151,18 @@ typedef struct tgp_handle tgp_handle;
                            (k_sweep_adjoint).  5 <= d <= 8 in LTI form (shared A, a, Q, H; not tgp_model_set_sde), T >= 2048: tgp_logpdf /
                            tgp_[logpdf_and_]posterior_marginals run on the GROUP sweep (tgp_sweep_group.hip) -- the same algorithm,
                            checks and repair with a chunk spread over 8 lanes, lane j holding column j of every matrix; kernels
-                           k_sweep_group<lti,logpdf> / k_sweep_group<lti,posterior>; the draw and the adjoint stay at d <= 4.  Under 1 the group
+                           k_sweep_group<lti,logpdf> / k_sweep_group<lti,posterior>; the gradient has an entry point of its own there,
+                           tgp_logpdf_adjoint_group (k_sweep_group_adjoint<lti>; served under 1 and 2 alike); the draw stays at d <= 4.  Under 1 the group
                            sweep takes only the (d, call) pairs that beat the general engine at T = 1e6 and 1e7 (profiles/sweep_group_time.txt):
                            tgp_logpdf at d = 6, 7, 8; 2: every pair, tgp_logpdf at d = 5 and the posterior calls included (tests, A/B timing;
                            the lane sweep is the same under 1 and 2).  Both step aside
                            on an explicit request for the general engine (TGP_REUSE_REDUCE, TGP_OPT_CHUNK, TGP_OPT_VARIANT, TGP_OPT_STEADY 0 / 1,
-                           TGP_OPT_GRAPH).  0: the general chunked-scan engine as before; tgp_posterior_rand_missing and
-                           tgp_logpdf_adjoint_missing answer TGP_EUNSUPPORTED for these models. */
+                           TGP_OPT_GRAPH).  0: the general chunked-scan engine as before; tgp_posterior_rand_missing,
+                           tgp_logpdf_adjoint_missing and tgp_logpdf_adjoint_group answer TGP_EUNSUPPORTED for these models. */
 #define TGP_OPT_SWEEP_CHUNK 15       /* tests: steps per chunk of the sweep engine (0 automatic) */
 #define TGP_OPT_SWEEP_WARMUP 16      /* tests: forward warm-up steps (0 automatic); a forced geometry is never repaired by longer warm-ups */
 #define TGP_OPT_SWEEP_WARMUP_BACK 17 /* tests: backward warm-up steps (0 automatic); in tgp_posterior_rand_missing: the draw's warm-up; in
-                                        tgp_logpdf_adjoint_missing: the adjoint's */
+                                        tgp_logpdf_adjoint_missing / _group: the adjoint's */
 #define TGP_OPT_STREAM_MIN_T 18 /* series length from which the STREAMING kernels of the stationary-gain engine serve a call: persistent
                                    waves with ~7 us more fixed latency and 1.3 - 2.7 x the throughput of k_steady_one.  -1 (default): the measured
                                    crossovers (logpdf 5e6, posterior marginals 3e6 steps at d = 3); 0: always (the tests); a length: from there on */
@@ -211,8 +212,8 @@ int64_t tgp_graph_replays(const tgp_handle* h);
    the general engine: the steps the forward pass of the last posterior-path call ran in the mean-only form. */
 int tgp_steady_steps(tgp_handle* h, int64_t* mean_only, int64_t* total);
 /* Diagnostics of TGP_OPT_SWEEP for the last tgp_logpdf / tgp_[logpdf_and_]posterior_marginals / tgp_posterior_rand_missing / tgp_logpdf_adjoint_missing /
-   tgp_logpdf_adjoint_sde call. info [8]: served by the sweep engine (0 / 1), steps per chunk, forward warm-up, backward warm-up (tgp_posterior_rand_missing: the draw's;
-   tgp_logpdf_adjoint_missing / _sde: the adjoint's, and dist[1] compares the adjoints of its hand-over), waves, attempts (launches),
+   tgp_logpdf_adjoint_group / tgp_logpdf_adjoint_sde call. info [8]: served by the sweep engine (0 / 1), steps per chunk, forward warm-up, backward warm-up (tgp_posterior_rand_missing: the draw's;
+   tgp_logpdf_adjoint_missing / _group / _sde: the adjoint's, and dist[1] compares the adjoints of its hand-over), waves, attempts (launches),
    status bits of the last attempt (1 forward / 2 backward or draw warm-up too short, 4 not positive definite, 8 non-finite), state for the bound
    model (0 untried, 1 serves, -1 declined).  dist [2]: the largest relative distance between a warm-up's end state and the run that reproduces it,
    forwards / backwards (the checks' 1e-12 / 1e-11; tgp_posterior_rand_missing: dist[1] compares the sample states of the draw's hand-over).
@@ -311,6 +312,18 @@ int tgp_logpdf_adjoint(tgp_handle* h, const double* y, uint32_t flags, double* l
  * (tgp_sweep_info has the status).  The library does not fall back: use tgp_logpdf_grad. */
 int tgp_logpdf_adjoint_missing(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, double* gA, double* ga, double* gQ,
                                double* gH, double* ghh, double* gR, double* gx0m, double* gx0P, double* gh_steps, double* gR_steps);
+/* The same gradient at state dimensions 5 <= d <= 8 by one adjoint pass on the GROUP sweep (k_sweep_group_adjoint<lti>): a chunk spread over
+ * 8 lanes, lane j holding column j of every matrix, of the adjoint (l, L) too; k_sweep_group<lti,posterior>'s geometry (6 of a wave's 8 groups own
+ * output) and forward half, then the adjoint of the recursion backwards with the hand-over, check (1e-11) and repair of tgp_logpdf_adjoint_missing.
+ * Arguments, outputs, TGP_IN_DEVICE / TGP_OUT_DEVICE and tgp_sweep_info exactly as there; TGP_OPT_SWEEP_WARMUP_BACK forces the adjoint's warm-up.  An
+ * explicit call: served under TGP_OPT_SWEEP = 1 and 2 alike, whatever the default routing of the engine's other calls; a model without any gap is
+ * served too.  Two calls on the same series give the same bits.
+ * TGP_EUNSUPPORTED, with no output byte written (host or device): d < 5 (use tgp_logpdf_adjoint_missing), d > 8, SDE-described models, p > 1, Reverse
+ * models, T < 2048, TGP_OPT_SWEEP = 0, an explicit request for the general engine (TGP_OPT_CHUNK, ...), an engine declined for the bound model, a
+ * forced geometry whose warm-ups are too short, an innovation variance that is not positive, non-finite values.  The library does not fall back: use
+ * tgp_logpdf_grad. */
+int tgp_logpdf_adjoint_group(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, double* gA, double* ga, double* gQ,
+                             double* gH, double* ghh, double* gR, double* gx0m, double* gx0P, double* gh_steps, double* gR_steps);
 /* The same gradient for a model described by its SDE and time stamps (tgp_model_set_sde: irregular spacing; the reference's AbstractVector inputs,
  * lti_sde.jl:135-146) by one adjoint pass on the sweep engine (k_sweep_adjoint<sde>): Forward models whose exp(F tau) has the closed form
  * (TGP_OPT_SDE_CLOSED_FORM = 1), shared a and H, scalar observations, d <= 4, T >= 2048; `missing`, a noise variance and an emission offset per step in

@@ -405,7 +405,8 @@ function logpdf_and_block_gradients(m::DeviceLGSSM{Forward}, y::AbstractVector{<
 end
 
 """The same where the gains vary in time -- `missing` entries of `y`, a noise variance or an emission offset per step -- by ONE adjoint pass on the
-sweep engine (tgp_logpdf_adjoint_missing: Forward models with shared A, a, Q, H, scalar observations, d <= 4, T >= 2048). `h` and `R` are the sums of
+sweep engine (tgp_logpdf_adjoint_missing: Forward models with shared A, a, Q, H, scalar observations, d <= 4, T >= 2048; tgp_logpdf_adjoint_group on the
+group sweep at 5 <= d <= 8). `h` and `R` are the sums of
 the per-step gradients over the observed steps; `per_step = true` adds `h_steps` and `R_steps` (length T, zero at missing steps).
 `nothing`: TGP_EUNSUPPORTED, take `logpdf_and_grad`."""
 function logpdf_and_block_gradients_missing(m::DeviceLGSSM{Forward}, y::AbstractVector; per_step::Bool = false)
@@ -416,10 +417,18 @@ function logpdf_and_block_gradients_missing(m::DeviceLGSSM{Forward}, y::Abstract
     ga, gH, gm = (Vector{Float64}(undef, d) for _ in 1:3)
     gh, gR = Ref{Float64}(0.0), Ref{Float64}(0.0)
     hs, Rs = per_step ? (Vector{Float64}(undef, m.T), Vector{Float64}(undef, m.T)) : (Float64[], Float64[])
-    rc = GC.@preserve yv mask hs Rs ccall((:tgp_logpdf_adjoint_missing, libtgp), Cint,
-        (Ptr{Cvoid}, Ptr{Float64}, Ptr{UInt8}, UInt32, Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64},
-         Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
-        m.h.ptr, yv, mp, UInt32(0), lml, gA, ga, gQ, gH, gh, gR, gm, gP, per_step ? pointer(hs) : C_NULL, per_step ? pointer(Rs) : C_NULL)
+    # (5 <= d <= 8: the group sweep's entry point, the same argument list; a ccall's symbol must be a literal)
+    rc = GC.@preserve yv mask hs Rs if 5 <= d <= 8
+        ccall((:tgp_logpdf_adjoint_group, libtgp), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Ptr{UInt8}, UInt32, Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64},
+             Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+            m.h.ptr, yv, mp, UInt32(0), lml, gA, ga, gQ, gH, gh, gR, gm, gP, per_step ? pointer(hs) : C_NULL, per_step ? pointer(Rs) : C_NULL)
+    else
+        ccall((:tgp_logpdf_adjoint_missing, libtgp), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Ptr{UInt8}, UInt32, Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64},
+             Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+            m.h.ptr, yv, mp, UInt32(0), lml, gA, ga, gQ, gH, gh, gR, gm, gP, per_step ? pointer(hs) : C_NULL, per_step ? pointer(Rs) : C_NULL)
+    end
     rc == 4 && return nothing
     check(m.h, rc)
     g = (A = gA, a = ga, Q = gQ, H = gH, h = gh[], R = gR[], x0m = gm, x0P = gP)

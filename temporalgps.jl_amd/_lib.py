@@ -55,6 +55,7 @@ _SIGS = {
     "tgp_logpdf_grad_sde": (ctypes.c_int, [_vp, _vp, _vp, _u32, ctypes.c_int] + [_vp] * 10 + [ctypes.c_double, _dp, _vp]),
     "tgp_logpdf_adjoint": (ctypes.c_int, [_vp, _vp, _u32, _dp] + [_vp] * 8),
     "tgp_logpdf_adjoint_missing": (ctypes.c_int, [_vp, _vp, _vp, _u32, _dp] + [_vp] * 10),
+    "tgp_logpdf_adjoint_group": (ctypes.c_int, [_vp, _vp, _vp, _u32, _dp] + [_vp] * 10),
     "tgp_logpdf_adjoint_sde": (ctypes.c_int, [_vp, _vp, _vp, _u32, _dp] + [_vp] * 11),
     "tgp_adjoint_record_size": (ctypes.c_int, [ctypes.c_int]),
     "tgp_steady_plan": (ctypes.c_int, [ctypes.c_int] + [_vp] * 8 + [_i64, _vp, _vp, _vp, _vp]),
@@ -229,7 +230,7 @@ class Handle:
 
     def sweep_info(self):
         """diagnostics of the sweep engine (TGP_OPT_SWEEP) for the last logpdf / posterior-marginals / posterior-draw / adjoint-gradient call (a draw:
-        Wb and dist_b are the draw warm-up's; logpdf_adjoint_missing / logpdf_adjoint_sde: the adjoint warm-up's)"""
+        Wb and dist_b are the draw warm-up's; logpdf_adjoint_missing / logpdf_adjoint_group / logpdf_adjoint_sde: the adjoint warm-up's)"""
         import numpy as np
         info, dist = np.zeros(8, dtype=np.int64), np.zeros(2)
         self.check(self.lib.tgp_sweep_info(self.h, info.ctypes.data, dist.ctypes.data))

@@ -162,10 +162,11 @@ bool sweep_eligible(const tgp_handle* h, uint32_t flags) {
 // (profiles/sweep_group_time.txt): logpdf at d = 6, 7, 8.  logpdf at d = 5 loses at 1e7 and the posterior kernel loses at every d at one length at
 // least: those run here under TGP_OPT_SWEEP = 2 only (tests, A/B timing).
 bool sweep_group_default_route(int d, bool post) { return !post && d >= 6; }
-bool sweep_group_eligible(const tgp_handle* h, uint32_t flags, bool post) {
+// explicit_call: an entry point of the engine's own (tgp_logpdf_adjoint_group), which the default routing does not filter.
+bool sweep_group_eligible(const tgp_handle* h, uint32_t flags, bool post, bool explicit_call = false) {
     if (!h->opt_sweep || h->sweep_state < 0 || h->is_dense || h->p != 1 || h->ordering != 0 || h->sde) return false;
     if (h->d < tgp_sweep::kGroupMinD || h->d > tgp_sweep::kGroupMaxD) return false;
-    if (h->opt_sweep < 2 && !sweep_group_default_route(h->d, post)) return false;
+    if (!explicit_call && h->opt_sweep < 2 && !sweep_group_default_route(h->d, post)) return false;
     if ((flags & TGP_REUSE_REDUCE) || h->opt_chunk != 0 || h->variant_opt != 0 || !h->opt_steady2 || h->opt_graph != 0) return false;
     if (h->T < tgp_sweep::kGroupMinT || h->mv.T != h->T || h->mv.sH != 0 || h->sweepm.empty()) return false;
     return h->mv.sA == 0 && h->mv.sa == 0 && h->mv.sQ == 0;
@@ -442,35 +443,26 @@ int sweep_draw_call(tgp_handle* h, const double* y, const uint8_t* missing, uint
     return TGP_OK;
 }
 
-// The adjoint gradient on the engine (k_sweep_adjoint, DESIGN 4.8; LTI form): sweep_call's staging and repair loop around the adjoint kernel.  The adjoint
-// pass sits in the backward slots of tgp_sweep_info (its warm-up Wa is remembered apart from Wb and Wd; TGP_OPT_SWEEP_WARMUP_BACK forces it here).  The
-// per-step gradients go to the handle's own buffers and reach gh_steps / gR_steps behind the checks, the block gradients are written behind them too:
+// What sweep_adjoint_run needs of an engine: the lane sweep's adjoint kernels and the group sweep's behind one call sequence (SweepEngineOps' twin; Wa: the
+// adjoint's warm-up, in the engines' backward slot).
+struct SweepAdjointOps {
+    const char* tag;
+    const char* kname;
+    bool (*plan)(tgp_handle* h, const tgp_sweep::ModelHost& mh, int W, int Wa, std::string* why);      // (with the handle's forced geometry)
+    int (*enqueue)(tgp_handle* h, const tgp_sweep::Call& c, const char** kname, std::string* err);
+    double (*finish)(tgp_handle* h, int* status, int* w, int* wa, double* dist_f, double* dist_b);
+    void (*geometry)(tgp_handle* h, int* C, int64_t* nwaves);
+};
+
+// The adjoint gradient on one of the sweep engines: sweep_run's staging and repair loop around an adjoint kernel.  The adjoint pass sits in the backward
+// slots of tgp_sweep_info (its warm-up Wa is remembered apart from Wb and Wd; TGP_OPT_SWEEP_WARMUP_BACK forces it here).  The per-step gradients go to the
+// handle's own buffers and reach gh_steps / gR_steps behind the checks, the block gradients are written behind them too (write_blocks):
 // *served = false with *why set: the engine declined, no output was written.
-// so (null: the LTI form): an SDE-described model -- k_sweep_adjoint_sde (DESIGN 4.9), the sums over the closed form's coefficients go to *so and `o` is unused.
-int sweep_adjoint_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, const tgp_sweep::AdjointOut& o,
-                       double* gh_steps, double* gR_steps, bool* served, std::string* why, const tgp_sweep::AdjointSdeOut* so = nullptr) {
+template <class WriteBlocks>
+int sweep_adjoint_run(tgp_handle* h, const SweepAdjointOps& eng, const tgp_sweep::ModelHost& mh, bool sde, const double* y, const uint8_t* missing, uint32_t flags,
+                      double* lml_out, double* gh_steps, double* gR_steps, bool* served, std::string* why, WriteBlocks&& write_blocks) {
     *served = false;
-    if (!h->sweep) h->sweep = tgp_sweep::create();
     static const bool dbg = getenv("TGP_STEADY_DEBUG") != nullptr;
-    const int d = h->d;
-    const size_t dd = (size_t)d * d;
-    const double* q = h->sweepm.data();
-    tgp_sweep::ModelHost mh;
-    mh.d = d;
-    mh.sde = so != nullptr;
-    mh.A = so ? h->sde_A1Q1_host.data() : q;
-    mh.a = q + dd;
-    mh.Q = so ? h->sde_A1Q1_host.data() + dd : q + dd + d;
-    mh.H = q + 2 * dd + d;
-    mh.hh = q[2 * dd + 2 * d];
-    mh.R = h->sweep_Rrep;
-    mh.x0m = h->x0m.data();
-    mh.x0P = h->x0P.data();
-    if (so) {      // (the stationary covariance as tgp_model_set_sde took it: tgp_model_set_x0 may have replaced the prior since)
-        mh.coef = h->sde_coef_host.data();
-        mh.Pinf = h->sde_coef_host.data() + d + 2 * dd;
-        mh.tau_typ = h->sweep_tau;
-    }
     const bool odev = (flags & TGP_OUT_DEVICE) != 0;
     const size_t nT = (size_t)h->T * sizeof(double);
     const bool forced = h->sweep_fW || h->sweep_fWb || h->sweep_fC;
@@ -478,9 +470,8 @@ int sweep_adjoint_call(tgp_handle* h, const double* y, const uint8_t* missing, u
     for (int64_t& v : h->sweep_info) v = 0;
     auto replan = [&]() {
         std::string w;
-        tgp_sweep::force_geometry(h->sweep, h->sweep_fC, h->sweep_fW, 0, 0, h->sweep_fWb);
-        if (tgp_sweep::plan(h->sweep, mh, h->T, W, h->sweep_Wb, h->num_cu, &w, 0, Wa)) return true;
-        if (dbg) fprintf(stderr, "[tgp sweep] does not apply: %s\n", w.c_str());
+        if (eng.plan(h, mh, W, Wa, &w)) return true;
+        if (dbg) fprintf(stderr, "[tgp %s] does not apply: %s\n", eng.tag, w.c_str());
         h->sweep_state = -1;
         *why = "the sweep engine's plan declines the model (" + w + ")";
         return false;
@@ -506,27 +497,27 @@ int sweep_adjoint_call(tgp_handle* h, const double* y, const uint8_t* missing, u
         c.mask = h->mv.missing;
         c.R = h->mv.sR != 0 ? h->mv.R : nullptr;
         c.hh = h->mv.sh != 0 ? h->mv.h : nullptr;
-        c.tau = so ? h->btau.d() : nullptr;
+        c.tau = sde ? h->btau.d() : nullptr;
         c.adjoint = true;
         c.gh_steps = dgh;
         c.gR_steps = dgR;
         {
             std::string err;
-            const char* kname = so ? tgp_sweep::adjoint_sde_kernel_name() : tgp_sweep::adjoint_kernel_name();
+            const char* kname = eng.kname;
             LaunchScope ls(h, kname);
-            if (tgp_sweep::enqueue(h->sweep, h->stream, c, &kname, &err) != 0) return h->fail(TGP_EHIP, err);
+            if (eng.enqueue(h, c, &kname, &err) != 0) return h->fail(TGP_EHIP, err);
         }
         tm.kernels_done();
         if (h->timing) (void)hipEventRecord(h->ev[3], h->stream);
         HIPCHK(hipStreamSynchronize(h->stream));
         resolve_profile(h);
         int status = 0, w = 0, wa = 0;
-        const double lml = tgp_sweep::finish(h->sweep, &status, &w, nullptr, &h->sweep_dist[0], &h->sweep_dist[1], nullptr, &wa);
+        const double lml = eng.finish(h, &status, &w, &wa, &h->sweep_dist[0], &h->sweep_dist[1]);
         int C = 0;
         int64_t nw = 0;
-        tgp_sweep::geometry(h->sweep, &C, nullptr, nullptr, &nw);
+        eng.geometry(h, &C, &nw);
         h->sweep_info[1] = C; h->sweep_info[2] = w; h->sweep_info[3] = wa; h->sweep_info[4] = nw; h->sweep_info[5] = attempt + 1; h->sweep_info[6] = status;
-        if (dbg) fprintf(stderr, "[tgp sweep adjoint] attempt %d: C %d W %d Wa %d waves %lld status %d dist %.3g / %.3g\n", attempt, C, w, wa, (long long)nw, status, h->sweep_dist[0], h->sweep_dist[1]);
+        if (dbg) fprintf(stderr, "[tgp %s] attempt %d: C %d W %d Wa %d waves %lld status %d dist %.3g / %.3g\n", eng.tag, attempt, C, w, wa, (long long)nw, status, h->sweep_dist[0], h->sweep_dist[1]);
         if (status & 12) {      // not positive definite / non-finite values: the tangent scans report it the way they always have
             if (status & 4) h->sweep_state = -1;
             *why = (status & 4) ? "an innovation variance is not positive" : "non-finite values in the pass";
@@ -544,8 +535,7 @@ int sweep_adjoint_call(tgp_handle* h, const double* y, const uint8_t* missing, u
         if (gh_steps) HIPCHK(hipMemcpyAsync(gh_steps, dgh, nT, odev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
         if (gR_steps) HIPCHK(hipMemcpyAsync(gR_steps, dgR, nT, odev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
         if (gh_steps || gR_steps) HIPCHK(hipStreamSynchronize(h->stream));
-        if (so) tgp_sweep::adjoint_blocks_sde(h->sweep, *so);
-        else tgp_sweep::adjoint_blocks(h->sweep, o);
+        write_blocks();
         read_timing(h);
         note_served(h, Served::sweep, 0, lml, lml_out);
         h->sweep_W = w;
@@ -558,6 +548,64 @@ int sweep_adjoint_call(tgp_handle* h, const double* y, const uint8_t* missing, u
     h->sweep_state = -1;      // four attempts, warm-ups still too short: a model that mixes too slowly for this engine
     *why = "the warm-ups stayed too short over four attempts";
     return TGP_OK;
+}
+
+// The adjoint gradient on the lane sweep (k_sweep_adjoint, DESIGN 4.8; LTI form).
+// so (null: the LTI form): an SDE-described model -- k_sweep_adjoint_sde (DESIGN 4.9), the sums over the closed form's coefficients go to *so and `o` is unused.
+int sweep_adjoint_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, const tgp_sweep::AdjointOut& o,
+                       double* gh_steps, double* gR_steps, bool* served, std::string* why, const tgp_sweep::AdjointSdeOut* so = nullptr) {
+    *served = false;
+    if (!h->sweep) h->sweep = tgp_sweep::create();
+    const int d = h->d;
+    const size_t dd = (size_t)d * d;
+    const double* q = h->sweepm.data();
+    tgp_sweep::ModelHost mh;
+    mh.d = d;
+    mh.sde = so != nullptr;
+    mh.A = so ? h->sde_A1Q1_host.data() : q;
+    mh.a = q + dd;
+    mh.Q = so ? h->sde_A1Q1_host.data() + dd : q + dd + d;
+    mh.H = q + 2 * dd + d;
+    mh.hh = q[2 * dd + 2 * d];
+    mh.R = h->sweep_Rrep;
+    mh.x0m = h->x0m.data();
+    mh.x0P = h->x0P.data();
+    if (so) {      // (the stationary covariance as tgp_model_set_sde took it: tgp_model_set_x0 may have replaced the prior since)
+        mh.coef = h->sde_coef_host.data();
+        mh.Pinf = h->sde_coef_host.data() + d + 2 * dd;
+        mh.tau_typ = h->sweep_tau;
+    }
+    const SweepAdjointOps eng = {
+        "sweep adjoint", so ? tgp_sweep::adjoint_sde_kernel_name() : tgp_sweep::adjoint_kernel_name(),
+        [](tgp_handle* hh, const tgp_sweep::ModelHost& m, int W, int Wa, std::string* w) {
+            tgp_sweep::force_geometry(hh->sweep, hh->sweep_fC, hh->sweep_fW, 0, 0, hh->sweep_fWb);
+            return tgp_sweep::plan(hh->sweep, m, hh->T, W, hh->sweep_Wb, hh->num_cu, w, 0, Wa);
+        },
+        [](tgp_handle* hh, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep::enqueue(hh->sweep, hh->stream, c, kname, err); },
+        [](tgp_handle* hh, int* status, int* w, int* wa, double* df, double* db) { return tgp_sweep::finish(hh->sweep, status, w, nullptr, df, db, nullptr, wa); },
+        [](tgp_handle* hh, int* C, int64_t* nw) { tgp_sweep::geometry(hh->sweep, C, nullptr, nullptr, nw); }};
+    return sweep_adjoint_run(h, eng, mh, so != nullptr, y, missing, flags, lml_out, gh_steps, gR_steps, served, why, [&]() {
+        if (so) tgp_sweep::adjoint_blocks_sde(h->sweep, *so);
+        else tgp_sweep::adjoint_blocks(h->sweep, o);
+    });
+}
+
+// The same at 5 <= d <= 8 on the group sweep (k_sweep_group_adjoint, DESIGN 4.11; LTI form): the posterior call's geometry with Wa in its backward slot.
+int sweep_group_adjoint_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, const tgp_sweep::AdjointOut& o,
+                             double* gh_steps, double* gR_steps, bool* served, std::string* why) {
+    *served = false;
+    if (!h->sweep_group) h->sweep_group = tgp_sweep_group::create();
+    const SweepAdjointOps eng = {
+        "sweep group adjoint", tgp_sweep_group::adjoint_kernel_name(),
+        [](tgp_handle* hh, const tgp_sweep::ModelHost& m, int W, int Wa, std::string* w) {
+            tgp_sweep_group::force_geometry(hh->sweep_group, hh->sweep_fC, hh->sweep_fW, hh->sweep_fWb);
+            return tgp_sweep_group::plan(hh->sweep_group, m, hh->T, W, Wa, hh->num_cu, /*post=*/true, w, /*adjoint=*/true);
+        },
+        [](tgp_handle* hh, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep_group::enqueue(hh->sweep_group, hh->stream, c, kname, err); },
+        [](tgp_handle* hh, int* status, int* w, int* wa, double* df, double* db) { return tgp_sweep_group::finish(hh->sweep_group, status, w, wa, df, db); },
+        [](tgp_handle* hh, int* C, int64_t* nw) { tgp_sweep_group::geometry(hh->sweep_group, C, nullptr, nullptr, nw); }};
+    return sweep_adjoint_run(h, eng, sweep_host_model(h), false, y, missing, flags, lml_out, gh_steps, gR_steps, served, why,
+                             [&]() { tgp_sweep_group::adjoint_blocks(h->sweep_group, o); });
 }
 
 // d logpdf / d F from the sums over the closed form's coefficients: the transpose of sde_closed_form's map.  coef = [lam d | N d*d | N^2 / 2 d*d | ...];

@@ -495,6 +495,26 @@ int tgp_logpdf_adjoint_missing(tgp_handle* h, const double* y, const uint8_t* mi
     return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_missing: the sweep engine declines the gradient: " + why + " (use tgp_logpdf_grad)");
 }
 
+// The same at state dimensions 5 .. 8 by the group sweep's adjoint kernel (k_sweep_group_adjoint, DESIGN 4.11): what sweep_group_eligible accepts, whatever
+// the default routing of the engine's other calls (an explicit call; TGP_OPT_SWEEP >= 1).  tgp_logpdf_adjoint_missing's arguments and outputs.
+int tgp_logpdf_adjoint_group(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, double* gA, double* ga, double* gQ,
+                             double* gH, double* ghh, double* gR, double* gx0m, double* gx0P, double* gh_steps, double* gR_steps) {
+    StreamGuard stream_guard_(h);
+    TRY(check_ready(h, /*general=*/false));
+    if (!y) return h->fail(TGP_EINVAL, "tgp_logpdf_adjoint_group: null argument");
+    if (!sweep_group_eligible(h, flags, /*post=*/true, /*explicit_call=*/true))
+        return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_group: Forward models with shared A, a, Q, H (not SDE-described), scalar observations, 5 <= d <= 8 "
+                                         "and T >= 2048 on the group sweep (TGP_OPT_SWEEP >= 1, the engine not declined for the bound model); use "
+                                         "tgp_logpdf_adjoint_missing at d <= 4 and tgp_logpdf_grad otherwise");
+    tgp_sweep::AdjointOut o;
+    o.gA = gA; o.ga = ga; o.gQ = gQ; o.gH = gH; o.ghh = ghh; o.gR = gR; o.gx0m = gx0m; o.gx0P = gx0P;
+    bool served = false;
+    std::string why;
+    TRY(sweep_group_adjoint_call(h, y, missing, flags, lml_out, o, gh_steps, gR_steps, &served, &why));
+    if (served) return TGP_OK;
+    return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_group: the group sweep declines the gradient: " + why + " (use tgp_logpdf_grad)");
+}
+
 // The same for a model described by its SDE and time stamps (tgp_model_set_sde: irregular spacing) -- what sweep_eligible accepts in SDE form -- by the
 // engine's k_sweep_adjoint_sde (DESIGN 4.9).  The kernel leaves the sums over the closed form's coefficients (lam, N1, N2), Pinf and the explicit first
 // transition; the host finishes d logpdf / d F by the transpose of sde_closed_form's map.  A model bound without A1 takes exp(F 1) at step 0

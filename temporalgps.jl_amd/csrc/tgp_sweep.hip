@@ -752,27 +752,7 @@ double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* d
     return lml;
 }
 
-void adjoint_blocks(const Engine* e, const AdjointOut& o) {
-    const int d = e->p.d, dd = d * d, ds = d * (d + 1) / 2, ng = e->part_stride - 4;
-    std::vector<double> g((size_t)ng, 0.0);
-    for (int64_t i = 0; i < e->p.nwaves; ++i) {      // fixed order: two calls on the same series give the same bits
-        const double* q = e->part + (size_t)i * e->part_stride + 4;
-        for (int k = 0; k < ng; ++k) g[(size_t)k] += q[k];
-    }
-    const double *gA = g.data(), *ga = gA + dd, *gQ = ga + d, *gH = gQ + ds, *gs = gH + d, *gm = gs + 2, *gP = gm + d;
-    auto unpack = [d](const double* packed, double* full) {
-        for (int j = 0; j < d; ++j)
-            for (int i = 0; i < d; ++i) full[i + j * d] = packed[pidx(i, j)];
-    };
-    if (o.gA) std::memcpy(o.gA, gA, sizeof(double) * dd);
-    if (o.ga) std::memcpy(o.ga, ga, sizeof(double) * d);
-    if (o.gQ) unpack(gQ, o.gQ);
-    if (o.gH) std::memcpy(o.gH, gH, sizeof(double) * d);
-    if (o.ghh) *o.ghh = gs[0];
-    if (o.gR) *o.gR = gs[1];
-    if (o.gx0m) std::memcpy(o.gx0m, gm, sizeof(double) * d);
-    if (o.gx0P) unpack(gP, o.gx0P);
-}
+void adjoint_blocks(const Engine* e, const AdjointOut& o) { adjoint_blocks_from_parts(e->part, e->p.nwaves, e->part_stride, e->p.d, o); }
 
 void adjoint_blocks_sde(const Engine* e, const AdjointSdeOut& o) {
     const int d = e->p.d, dd = d * d, ds = d * (d + 1) / 2, ng = e->part_stride - 4;

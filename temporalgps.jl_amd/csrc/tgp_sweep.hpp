@@ -74,6 +74,31 @@ struct AdjointSdeOut {
            *gx0m = nullptr, *gx0P = nullptr;
 };
 
+// The gradient with respect to the shared blocks from the waves' records of an adjoint call (pinned host memory, `stride` doubles per wave: 4 status words,
+// then gA d*d | ga d | gQ packed | gH d | sum gh_t | sum gR_t | gx0m d | gx0P packed): added in wave order -- two calls on the same series give the same
+// bits -- and the packed blocks unpacked to full symmetric ones.  Both sweep engines leave this record (tgp_sweep.hip, tgp_sweep_group.hip).
+inline void adjoint_blocks_from_parts(const double* part, int64_t nwaves, int stride, int d, const AdjointOut& o) {
+    const int dd = d * d, ds = d * (d + 1) / 2, ng = stride - 4;
+    double g[group_adjoint_sums(kGroupMaxD)] = {0.0};      // (the largest record: d = 8)
+    for (int64_t i = 0; i < nwaves; ++i) {
+        const double* q = part + (size_t)i * stride + 4;
+        for (int k = 0; k < ng; ++k) g[k] += q[k];
+    }
+    const double *gA = g, *ga = gA + dd, *gQ = ga + d, *gH = gQ + ds, *gs = gH + d, *gm = gs + 2, *gP = gm + d;
+    auto unpack = [d](const double* packed, double* full) {
+        for (int j = 0; j < d; ++j)
+            for (int i = 0; i < d; ++i) full[i + j * d] = packed[pidx(i, j)];
+    };
+    if (o.gA) std::memcpy(o.gA, gA, sizeof(double) * dd);
+    if (o.ga) std::memcpy(o.ga, ga, sizeof(double) * d);
+    if (o.gQ) unpack(gQ, o.gQ);
+    if (o.gH) std::memcpy(o.gH, gH, sizeof(double) * d);
+    if (o.ghh) *o.ghh = gs[0];
+    if (o.gR) *o.gR = gs[1];
+    if (o.gx0m) std::memcpy(o.gx0m, gm, sizeof(double) * d);
+    if (o.gx0P) unpack(gP, o.gx0P);
+}
+
 // Chooses the geometry (chunk length, warm-ups) for this model and series; false: the engine declines (`why` says so).
 // w_hint / wb_hint: warm-ups a previous call on the same bound model needed (0: estimate from the model).
 // wd_hint: the draw's warm-up (0: the backward warm-up's value; a draw call that passes one may lengthen the chunk to hold it).

@@ -1,7 +1,8 @@
 // The group sweep: see tgp_sweep_group.hpp (what and why) and DESIGN 4.10 (geometry, LDS budget, register counts).  gfx950 only.
 // One wave per workgroup; a wave's LDS: A (512 B), the 8 groups' exchange tiles (8 x 82 doubles) and, in a posterior call, the filtering states of
 // one checkpoint block per group (8 B (d + d (d + 1) / 2) doubles: 13.5 KB at d = 6, B = 8; 11 KB at d = 8, B = 4) -- at most 19.6 KB, so that 8
-// workgroups = two waves per SIMD stay resident in a CU's 160 KB.
+// workgroups = two waves per SIMD stay resident in a CU's 160 KB.  An adjoint call (k_sweep_group_adjoint) has the posterior call's LDS: a block's slots hold
+// the states in FRONT of its steps.
 //
 // The column layout and its building blocks are tgp_group.hpp's (GroupLane::predict, group_sum, gather) and tgp_group_smooth.hpp's (the 8-lane
 // Cholesky solve); the recursions are tgp_sweep_body.hpp's update / smooth_step (a missing step: predict only; the RTS step in gain form).
@@ -69,6 +70,16 @@ __device__ __forceinline__ double group_max(double x) {
 template <int D> struct GState {
     double m;
     double P[D];
+};
+
+// a lane's sums of the block gradients over the steps of its group's chunk (k_sweep_group_adjoint): column j of gA and of gQ (full, not packed),
+// element j of ga and gH, the sums of the per-step gh_t and gR_t (the same in every lane of the group)
+template <int D> struct GAcc {
+    double gA[D], gQ[D], ga, gH, gh, gR;
+    __device__ __forceinline__ void zero() {
+        TGP_GU for (int i = 0; i < D; ++i) gA[i] = gQ[i] = 0.0;
+        ga = gH = gh = gR = 0.0;
+    }
 };
 
 // The 8 steps of a row of the observation stream, one per lane of the group (a 64-byte row per stream and group); handed out step by step with a
@@ -279,6 +290,97 @@ template <int D, int XS, bool KEEP_A> struct Lane {
         TGP_GU for (int i = 0; i < D; ++i) s += ::fabs(x.P[i]);
         return group_sum(s) < 1e300;      // (false for NaN as well)
     }
+
+    // ---- the adjoint of the filter (k_sweep_group_adjoint): tgp_sweep_body.hpp adjoint_step in the column layout.  An adjoint
+    // (l, L) = d logpdf / d (m, P) is held like a state: lane j holds l_j (GState::m) and column j of L (GState::P; L is symmetric).
+    // One step backwards.  xf: the filtering state in FRONT of step t; ad: the adjoint behind it on entry, in front of it on return.  A missing step
+    // (obs == false; the padded steps behind the series' end are such) passes the adjoint through the predict alone: gh_t = gR_t = 0.
+    // ACC: the step's share of the block gradients is added to acc (column j of gA and gQ, element j of ga and gH, the sums of gh_t and gR_t).
+    template <bool ACC>
+    __device__ __forceinline__ void adjoint_step(const GState<D>& xf, double y, double Rt, double ht, bool obs, GState<D>& ad, GAcc<D>* acc, double& gh_t,
+                                                 double& gR_t) const {
+        GState<D> xp = xf;
+        double AP[D];
+        predict(xp, AP);      // (the filter's own predict, to the bit)
+        double vj = 0.0;      // V = Pp H, element j
+        TGP_GU for (int i = 0; i < D; ++i) vj = fma(xp.P[i], H[i], vj);
+        const double s2 = group_sum(Hj * vj) + Rt;
+        const double hm = group_sum(Hj * xp.m) + ht;
+        const double S = obs ? s2 : 1.0;
+        const double iS = obs ? fast_rcp(S) : 0.0;      // (a missing step: every term of the update's adjoint below is a multiple of iS or v)
+        const double v = obs ? (y - hm) : 0.0;
+        const double viS = v * iS;
+        double V[D];
+        gather(vj, V, V1);
+        double lvj = 0.0;      // (L V)_j = sum_i L[i][j] V_i: lane-local by symmetry
+        TGP_GU for (int i = 0; i < D; ++i) lvj = fma(ad.P[i], V[i], lvj);
+        const double lV = group_sum(ad.m * vj);
+        const double VLV = group_sum(vj * lvj);
+        const double vbar = (lV - v) * iS;
+        const double Sbar = fma(fma(-lV, v, VLV) * iS, iS, -0.5 * fma(-viS, viS, iS));
+        const double vbj = fma(Sbar, Hj, fma(ad.m, viS, -2.0 * iS * lvj));
+        gh_t = -vbar;
+        gR_t = Sbar;
+        double Vb[D];
+        gather(vbj, Vb, V0);
+        const double mbj = fma(-vbar, Hj, ad.m);
+        double Pb[D];      // column j of Pb = L + (Vb H' + H Vb') / 2
+        TGP_GU for (int i = 0; i < D; ++i) Pb[i] = fma(0.5, fma(Vb[i], Hj, H[i] * vbj), ad.P[i]);
+        if (ACC) {
+            double a = fma(Sbar, vj, -vbar * xp.m);
+            TGP_GU for (int i = 0; i < D; ++i) a = fma(xp.P[i], Vb[i], a);
+            acc->gH += a;
+            acc->ga += mbj;
+            acc->gh -= vbar;
+            acc->gR += Sbar;
+            TGP_GU for (int i = 0; i < D; ++i) acc->gQ[i] += Pb[i];
+        }
+        // Pb and mb through the tile (ONE trip, as predict's): every lane reads the whole of Pb, a wave-wide broadcast per element (rows and columns
+        // < D only: a padding lane's column is zero, the rows >= D are never written)
+        wave_sync();
+        TGP_GU for (int i = 0; i < D; ++i) tile[i + G * j] = Pb[i];
+        tile[V0 + j] = mbj;
+        wave_sync();
+        double mb[D], Ac[D], u[D], w[D];
+        TGP_GU for (int k = 0; k < D; ++k) {
+            mb[k] = tile[V0 + k];
+            Ac[k] = sA[G * k + j];      // column j of A (zero in a padding lane)
+        }
+        TGP_GU for (int i = 0; i < D; ++i) {
+            double au = 0.0, aw = 0.0;
+            TGP_GU for (int k = 0; k < D; ++k) {
+                const double p = tile[i + G * k];
+                if (ACC) au = fma(p, AP[k], au);
+                aw = fma(p, Ac[k], aw);
+            }
+            u[i] = au;
+            w[i] = aw;
+        }
+        if (ACC) { TGP_GU for (int i = 0; i < D; ++i) acc->gA[i] += fma(2.0, u[i], mb[i] * xf.m); }      // gA += mb m' + 2 Pb (A P), column j
+        // l <- A' mb;  L <- A' Pb A, column j = A' w
+        double al = 0.0;
+        TGP_GU for (int k = 0; k < D; ++k) al = fma(Ac[k], mb[k], al);
+        ad.m = al;
+        TGP_GU for (int i = 0; i < D; ++i) {
+            double a = 0.0;
+            TGP_GU for (int k = 0; k < D; ++k) a = fma(sA[G * k + i], w[k], a);
+            ad.P[i] = a;
+        }
+    }
+    // How far apart two adjoints are (tgp_sweep_body.hpp adjoint_distance): |dl_i| sd_i, |dL_ij| sd_i sd_j, absolute; this lane's column, then the
+    // group's maximum.  Compared with mc.tol_b.
+    __device__ __forceinline__ double adjoint_distance(const GroupModelC& mc, const GState<D>& a, const GState<D>& b) const {
+        double worst = 0.0;
+        if (act) {
+            const double sj = mc.sd[j];
+            worst = ::fabs(a.m - b.m) * sj;
+            TGP_GU for (int i = 0; i < D; ++i) {
+                const double r = ::fabs(a.P[i] - b.P[i]) * (mc.sd[i] * sj);
+                worst = r > worst ? r : worst;      // (a NaN on either side compares false everywhere: caught by the caller's finite test)
+            }
+        }
+        return group_max(worst);
+    }
 };
 
 // One forward run of a group: `nrows` rows of 8 steps from step ts on (a multiple of 8, possibly negative); the rows that start in [lo, hi) are
@@ -483,12 +585,249 @@ __global__ __launch_bounds__(64) void k_sweep_group(const GArgs by_value) {
     }
 }
 
+// ---- the adjoint gradient: k_sweep_adjoint's algorithm (tgp_sweep.hip) in k_sweep_group<POST>'s geometry ------------------
+struct GAArgs {
+    GArgs ka;              // (ka.Wb holds the adjoint's warm-up Wa; mean / var unused)
+    double* gh_steps;      // [T] or null: d logpdf / d h_t, d logpdf / d R_t of every step
+    double* gR_steps;
+};
+static_assert(sizeof(GAArgs) <= 4096, "the kernel's argument segment");
+
+// One adjoint run of a group over the rows nrows - 1 .. 0 of its chunk (first step t0; backward_run's frame): the steps below hi are walked, from
+// `ad` = the adjoint behind step hi - 1; on return `ad` is the adjoint in front of step t0.  The filtering states of a block are recomputed from its
+// checkpoint into LDS (sF: [B][NS] of this group); step k reads the state in FRONT of it -- slot k holds the checkpoint for k = 0, step k - 1's
+// state otherwise -- so the block's last state is not computed.  ACC: the block gradients are summed into *acc, and gh_t / gR_t of the walked
+// steps are written where gh_steps / gR_steps are given, a 64-byte row per group.
+template <int D, int XS, int B, bool ACC>
+__device__ __forceinline__ void adjoint_run(const GArgs& ka, const Lane<D, XS, false>& ln, long long t0, int nrows, long long hi, GState<D>& ad, GAcc<D>* acc,
+                                            double* gh_steps, double* gR_steps, const double* ck, size_t ck_ld, double* sF, bool& ok) {
+    constexpr int NS = Lane<D, XS, false>::NS;
+    Row<XS> in, nx;
+    load_row<XS>(ka, t0 + 8ll * (nrows - 1), ln.j, in);
+    for (int r = nrows - 1; r >= 0; --r) {
+        const long long tb = t0 + 8ll * r;
+        load_row<XS>(ka, tb - 8, ln.j, nx);      // the next row (row r - 1): in flight through this one
+        double og = 0.0, oR = 0.0;
+#pragma nounroll
+        for (int s = 8 / B - 1; s >= 0; --s) {
+            const long long tsb = tb + s * B;
+            if (tsb < hi) {
+                // ---- the states in front of the block's steps, forwards from its checkpoint
+                GState<D> x;
+                ln.load_packed(ck + (size_t)((tsb - t0) / B) * ck_ld, x);
+                wave_sync();
+                ln.store_packed(sF, x);
+#pragma nounroll
+                for (int k = 0; k + 1 < B; ++k) {
+                    ln.fstep(x, in, s * B + k, tsb + k, ka.T, (LmlAcc*)nullptr, ok);
+                    ln.store_packed(sF + (k + 1) * NS, x);
+                }
+                wave_sync();
+                // ---- backwards through the block
+#pragma nounroll
+                for (int k = B - 1; k >= 0; --k) {
+                    const long long t = tsb + k;
+                    if (t < hi) {
+                        GState<D> xf;
+                        ln.load_packed(sF + k * NS, xf);
+                        const int q = s * B + k;
+                        const double y = __shfl(in.y, q, G);
+                        const double Rt = (XS & 1) ? __shfl(in.R, q, G) : ln.R;
+                        const double ht = (XS & 2) ? __shfl(in.hh, q, G) : ln.hh;
+                        const bool obs = t < ka.T && __shfl((int)in.mk, q, G) == 0;
+                        double gh_t, gR_t;
+                        ln.template adjoint_step<ACC>(xf, y, Rt, ht, obs, ad, acc, gh_t, gR_t);
+                        og = (ln.j == q) ? gh_t : og;
+                        oR = (ln.j == q) ? gR_t : oR;
+                    }
+                }
+            }
+        }
+        if (ACC && tb + ln.j < hi) {
+            if (gh_steps != nullptr) gh_steps[tb + ln.j] = og;
+            if (gR_steps != nullptr) gR_steps[tb + ln.j] = oR;
+        }
+        in = nx;
+    }
+}
+
+// part[wave]: [lml, bits, dist_f, dist_b | gA d*d | ga d | gQ packed | gH d | sum gh_t | sum gR_t | gx0m d | gx0P packed] -- k_sweep_adjoint's record
+// (the symmetric blocks leave as the upper triangle of the lanes' columns).  The register counts are in profiles/sweep_group_adjoint_resources.txt.
+template <int D, int XS>
+__global__ __launch_bounds__(64) void k_sweep_group_adjoint(const GAArgs by_value) {
+    (void)by_value;
+    const GAArgs& ar = *(const GAArgs*)__builtin_amdgcn_kernarg_segment_ptr();      // (read in place: tgp_sweep.hip k_sweep)
+    const GArgs& ka = ar.ka;
+    constexpr int B = tgp_sweep::group_block(D), NS = Lane<D, XS, false>::NS, DS = D * (D + 1) / 2, NG = tgp_sweep::kGroupsPerWave;
+    __shared__ __attribute__((aligned(16))) double sA[G * G];
+    __shared__ double tiles[NG * kTileLD];
+    __shared__ double sF[NG * B * NS];
+    const int lane = threadIdx.x, g = lane / G;
+    const long long wave = blockIdx.x;
+    sA[lane] = ka.mc.A[lane];
+    __syncthreads();
+
+    Lane<D, XS, false> ln;
+    ln.j = lane % G;
+    ln.act = ln.j < D;
+    ln.tile = tiles + g * kTileLD;
+    ln.sA = sA;
+    const int j = ln.j;
+    TGP_GU for (int i = 0; i < D; ++i) {
+        ln.Qc[i] = ln.act ? ka.mc.Q[i + G * j] : 0.0;
+        ln.H[i] = ka.mc.H[i];
+    }
+    ln.Hj = ln.act ? ka.mc.H[j] : 0.0;
+    ln.aj = ln.act ? ka.mc.a[j] : 0.0;
+    ln.hh = ka.mc.hh;
+    ln.R = ka.mc.R;
+
+    const long long T = ka.T;
+    const int C = ka.C;
+    const tgp_sweep::GroupSpan span = tgp_sweep::group_span(wave, g, ka.owned, ka.nchunks, C, T);
+    const long long t0 = span.t0, t1 = span.t1;
+    const long long t1r = (t1 + 7) & ~7ll;
+    const bool runs = span.runs;          // group 0 only warms up for group 1
+    const bool owned = span.owned;        // group 7 only warms up backwards for group 6
+    bool ok = true;
+
+    GState<D> gen, x0;
+    gen.m = ln.act ? ka.mc.gm[j] : 0.0;
+    x0.m = ln.act ? ka.mc.x0m[j] : 0.0;
+    TGP_GU for (int i = 0; i < D; ++i) {
+        gen.P[i] = ln.act ? ka.mc.gP[i + G * j] : 0.0;
+        x0.P[i] = ln.act ? ka.mc.x0P[i + G * j] : 0.0;
+    }
+    const size_t ck_ld = (size_t)NG * NS;
+    double* ck = ka.ckpt + (size_t)wave * (size_t)(C / B) * ck_ld + (size_t)g * NS;
+    double* sFg = sF + g * B * NS;
+
+    // ---- forwards: k_sweep_group<POST>'s two passes (warm-up, hand-over, the chunk with its checkpoints and the log marginal likelihood)
+    GState<D> x, e1;
+    LmlAcc acc;
+    {
+        const long long tw = t1r - ka.W;
+        x = tw <= 0 ? x0 : gen;
+        forward_run<D, XS, B, false>(ka, ln, tw, ka.W / 8, tw > 0 ? tw : 0, t1r, x, acc, false, (double*)nullptr, 0, 0, ok);
+        e1 = x;
+        x.m = __shfl_up(e1.m, G, 64);
+        TGP_GU for (int i = 0; i < D; ++i) x.P[i] = __shfl_up(e1.P[i], G, 64);
+        if (t0 == 0) x = x0;
+        acc = LmlAcc();
+        forward_run<D, XS, B, false>(ka, ln, t0, C / 8, t0, runs ? t1r : t0, x, acc, true, ck, t0, ck_ld, ok);
+    }
+    double dist_f = 0.0, dist_b = 0.0;
+    bool finite = true;
+    {
+        const double df = ln.distance(ka.mc, x, e1);
+        const bool fin = ln.finite(x) && ln.finite(e1);
+        if (owned) {
+            dist_f = df;
+            finite = fin;
+        }
+    }
+
+    // ---- backwards, the warm-up: the adjoint in front of the chunk's first step as its first Wa steps give it from zero (exact where they reach the
+    // series' last step) -- what the PREVIOUS group continues from
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // (the checkpoints are read back by other lanes of the group)
+    GState<D> b1;
+    b1.m = 0.0;
+    TGP_GU for (int i = 0; i < D; ++i) b1.P[i] = 0.0;
+    {
+        const long long te = (t0 + ka.Wb < t1) ? t0 + ka.Wb : t1;
+        adjoint_run<D, XS, B, false>(ka, ln, t0, ka.Wb / 8, runs ? te : t0, b1, (GAcc<D>*)nullptr, (double*)nullptr, (double*)nullptr, ck, ck_ld, sFg, ok);
+    }
+    // ---- backwards, the chunk: from the next group's adjoint in front of ITS first step (zero behind the series' last step)
+    GState<D> ad;
+    ad.m = __shfl_down(b1.m, G, 64);
+    TGP_GU for (int i = 0; i < D; ++i) ad.P[i] = __shfl_down(b1.P[i], G, 64);
+    if (t1 == T) {
+        ad.m = 0.0;
+        TGP_GU for (int i = 0; i < D; ++i) ad.P[i] = 0.0;
+    }
+    GAcc<D> ga;
+    ga.zero();
+    adjoint_run<D, XS, B, true>(ka, ln, t0, C / 8, owned ? t1 : t0, ad, &ga, ar.gh_steps, ar.gR_steps, ck, ck_ld, sFg, ok);
+    {
+        const double db = ln.adjoint_distance(ka.mc, ad, b1);
+        const bool fin = ln.finite(ad) && ln.finite(b1);
+        if (owned) {
+            dist_b = db;
+            finite = finite && fin;
+        }
+    }
+
+    // ---- the wave's share: the groups' sums added in a fixed order (lane j of every group holds column j), then lanes 0 .. d - 1 write their columns
+    const bool first = owned && span.t0 == 0;      // the adjoint in front of step 0 is the gradient of the series' prior
+    double gxm = first ? ad.m : 0.0, gxP[D];
+    TGP_GU for (int i = 0; i < D; ++i) gxP[i] = first ? ad.P[i] : 0.0;
+    {
+        double s = ::fabs(ga.ga) + ::fabs(ga.gH) + ::fabs(ga.gh) + ::fabs(ga.gR);
+        TGP_GU for (int i = 0; i < D; ++i) s += ::fabs(ga.gA[i]) + ::fabs(ga.gQ[i]);
+        finite = finite && (s < 1e300);
+    }
+    double lml = (owned && j == 0) ? acc.total() : 0.0;
+    finite = finite && (::fabs(lml) < 1e300);
+    unsigned bits = 0;
+    if (owned && !(dist_f <= ka.mc.tol)) bits |= 1u;
+    if (owned && !(dist_b <= ka.mc.tol_b)) bits |= 2u;
+    if (!ok) bits |= 4u;
+    if (!finite) bits |= 8u;
+#pragma unroll
+    for (int off = 8; off <= 32; off <<= 1) {
+        TGP_GU for (int i = 0; i < D; ++i) {
+            ga.gA[i] += __shfl_xor(ga.gA[i], off, 64);
+            ga.gQ[i] += __shfl_xor(ga.gQ[i], off, 64);
+            gxP[i] += __shfl_xor(gxP[i], off, 64);
+        }
+        ga.ga += __shfl_xor(ga.ga, off, 64);
+        ga.gH += __shfl_xor(ga.gH, off, 64);
+        ga.gh += __shfl_xor(ga.gh, off, 64);
+        ga.gR += __shfl_xor(ga.gR, off, 64);
+        gxm += __shfl_xor(gxm, off, 64);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        lml += __shfl_xor(lml, off, 64);
+        bits |= (unsigned)__shfl_xor((int)bits, off, 64);
+        const double of = __shfl_xor(dist_f, off, 64), ob = __shfl_xor(dist_b, off, 64);
+        dist_f = (of > dist_f) ? of : dist_f;
+        dist_b = (ob > dist_b) ? ob : dist_b;
+    }
+    double* p = ka.part + (size_t)wave * (4 + tgp_sweep::group_adjoint_sums(D));
+    if (lane == 0) {
+        p[0] = lml;
+        p[1] = (double)bits;
+        p[2] = dist_f;
+        p[3] = dist_b;
+        p[4 + D * D + D + DS + D] = ga.gh;
+        p[4 + D * D + D + DS + D + 1] = ga.gR;
+    }
+    if (lane < D) {
+        double* q = p + 4;
+        TGP_GU for (int i = 0; i < D; ++i) q[i + D * j] = ga.gA[i];
+        q += D * D;
+        q[j] = ga.ga;
+        q += D;
+        TGP_GU for (int i = 0; i < D; ++i)
+            if (i <= j) q[j * (j + 1) / 2 + i] = ga.gQ[i];
+        q += DS;
+        q[j] = ga.gH;
+        q += D + 2;
+        q[j] = gxm;
+        q += D;
+        TGP_GU for (int i = 0; i < D; ++i)
+            if (i <= j) q[j * (j + 1) / 2 + i] = gxP[i];
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------------ host side
 struct Engine {
     tgp_sweep::GroupPlan p;
     tgp_sweep::Forced forced;
     double* part = nullptr;      // pinned: the waves' shares
     size_t part_cap = 0;
+    int part_stride = 4;         // doubles per wave in `part`: 4, and the gradient's sums behind them in an adjoint call
     void* ckpt = nullptr;
     size_t ckpt_cap = 0;
 };
@@ -511,10 +850,11 @@ void geometry(const Engine* e, int* C, int* W, int* Wb, int64_t* nwaves) {
     if (Wb) *Wb = e->p.Wb;
     if (nwaves) *nwaves = e->p.nwaves;
 }
-bool plan(Engine* e, const tgp_sweep::ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why) {
-    return tgp_sweep::plan_group(&e->p, e->forced, m, T, w_hint, wb_hint, num_cu, post, why);
+bool plan(Engine* e, const tgp_sweep::ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why, bool adjoint) {
+    return tgp_sweep::plan_group(&e->p, e->forced, m, T, w_hint, wb_hint, num_cu, post || adjoint, why, adjoint);
 }
 const char* kernel_name(bool post) { return post ? "k_sweep_group<lti,posterior>" : "k_sweep_group<lti,logpdf>"; }
+const char* adjoint_kernel_name() { return "k_sweep_group_adjoint<lti>"; }
 
 namespace {
 
@@ -531,6 +871,16 @@ template <int D> void launch_d(const Engine* e, hipStream_t stream, const GArgs&
         default: launch_x<D, 3>(e, stream, ka, post); break;
     }
 }
+template <int D> void launch_adjoint_d(const Engine* e, hipStream_t stream, const GAArgs& ar) {
+    const dim3 grid((unsigned)e->p.nwaves), block(64);
+    const int xs = (ar.ka.st.R != nullptr ? 1 : 0) | (ar.ka.st.hh != nullptr ? 2 : 0);
+    switch (xs) {
+        case 0: hipLaunchKernelGGL((k_sweep_group_adjoint<D, 0>), grid, block, 0, stream, ar); break;
+        case 1: hipLaunchKernelGGL((k_sweep_group_adjoint<D, 1>), grid, block, 0, stream, ar); break;
+        case 2: hipLaunchKernelGGL((k_sweep_group_adjoint<D, 2>), grid, block, 0, stream, ar); break;
+        default: hipLaunchKernelGGL((k_sweep_group_adjoint<D, 3>), grid, block, 0, stream, ar); break;
+    }
+}
 
 }  // namespace
 
@@ -541,11 +891,16 @@ int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char*
     };
     const tgp_sweep::GroupPlan& p = e->p;
     const bool post = c.mean != nullptr;
-    if (post != p.post || c.T != p.T || (post && (c.var == nullptr || c.Rnew == nullptr))) {
+    if (c.adjoint ? (post || !p.adjoint) : p.adjoint) {
+        if (err) *err = "k_sweep_group_adjoint: the call does not match its plan (no other output in an adjoint call)";
+        return 1;
+    }
+    if ((post || c.adjoint) != p.post || c.T != p.T || (post && (c.var == nullptr || c.Rnew == nullptr))) {
         if (err) *err = "k_sweep_group: the call does not match its plan";
         return 1;
     }
-    const size_t need_part = (size_t)p.nwaves * 4 * sizeof(double);
+    e->part_stride = c.adjoint ? 4 + tgp_sweep::group_adjoint_sums(p.d) : 4;
+    const size_t need_part = (size_t)p.nwaves * e->part_stride * sizeof(double);
     if (need_part > e->part_cap) {
         if (e->part) (void)tgp_alloc::host_free(e->part);
         e->part = nullptr;
@@ -555,7 +910,7 @@ int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char*
         if (rc != hipSuccess) return fail("hipHostMalloc", rc);
         e->part_cap = cap;
     }
-    if (post) {
+    if (p.post) {      // (the adjoint keeps the posterior call's checkpoints)
         const int NS = p.d + p.d * (p.d + 1) / 2;
         const size_t need = (size_t)p.nwaves * (size_t)(p.C / p.B) * tgp_sweep::kGroupsPerWave * NS * sizeof(double);
         if (need > e->ckpt_cap) {
@@ -586,6 +941,22 @@ int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char*
     ka.var = c.var;
     ka.ckpt = static_cast<double*>(e->ckpt);
     ka.part = e->part;
+    if (c.adjoint) {
+        GAArgs ar;
+        ar.ka = ka;      // (ka.Wb: the plan's backward slot carries the adjoint's warm-up)
+        ar.gh_steps = c.gh_steps;
+        ar.gR_steps = c.gR_steps;
+        if (kname) *kname = adjoint_kernel_name();
+        switch (p.d) {
+            case 5: launch_adjoint_d<5>(e, stream, ar); break;
+            case 6: launch_adjoint_d<6>(e, stream, ar); break;
+            case 7: launch_adjoint_d<7>(e, stream, ar); break;
+            default: launch_adjoint_d<8>(e, stream, ar); break;
+        }
+        hipError_t rc = hipGetLastError();
+        if (rc != hipSuccess) return fail("k_sweep_group_adjoint launch", rc);
+        return 0;
+    }
     if (kname) *kname = kernel_name(post);
     switch (p.d) {
         case 5: launch_d<5>(e, stream, ka, post); break;
@@ -602,7 +973,7 @@ double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* d
     double lml = 0.0, df = 0.0, db = 0.0;
     unsigned bits = 0;
     for (int64_t i = 0; i < e->p.nwaves; ++i) {      // fixed order: the same sum for the same geometry
-        const double* q = e->part + (size_t)i * 4;
+        const double* q = e->part + (size_t)i * e->part_stride;
         lml += q[0];
         bits |= (unsigned)q[1];
         df = std::max(df, q[2]);
@@ -614,6 +985,10 @@ double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* d
     if (dist_f) *dist_f = df;
     if (dist_b) *dist_b = db;
     return lml;
+}
+
+void adjoint_blocks(const Engine* e, const tgp_sweep::AdjointOut& out) {
+    tgp_sweep::adjoint_blocks_from_parts(e->part, e->p.nwaves, e->part_stride, e->p.d, out);
 }
 
 }  // namespace tgp_sweep_group

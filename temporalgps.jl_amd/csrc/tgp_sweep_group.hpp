@@ -11,6 +11,11 @@
 // by block from the checkpoints into LDS.  Both hand-overs are checked to `tol` as in the lane sweep and the host repairs or declines the same way.
 // Group 0 of a wave only warms up for group 1, and in a posterior call group 7 only warms up (backwards) for group 6: waves are independent, 7 of 8
 // groups own output in a logpdf call, 6 of 8 in a posterior call.
+//
+// The gradient of the log marginal likelihood (k_sweep_group_adjoint) is the posterior call's geometry and forward half and, backwards, the
+// adjoint of the recursion (tgp_sweep.hpp) in the column layout: lane j holds l_j and column j of L; a group continues from the next group's
+// adjoint in front of ITS first step, which that group gets from a walk over its own first Wa steps from zero; the hand-over is checked on the adjoints.
+// A lane sums column j of the block gradients over its group's steps, the wave adds its six owned groups, the host the waves.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,12 +32,19 @@ void destroy(Engine* e);
 
 // The geometry for this model and series (tgp_sweep_plan.hpp plan_group); false: the engine declines (`why` says so).  post: the call asks for the
 // posterior marginals.
-bool plan(Engine* e, const tgp_sweep::ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why);
-// c: the lane sweep's call record; y, mask, R, hh, Rnew, mean, var are read (mean == null: logpdf only)
+// adjoint: the call asks for the gradient (k_sweep_group_adjoint) -- the posterior call's geometry with the adjoint's warm-up Wa in the backward
+// slot: wb_hint is a Wa that a previous call needed (0: the forward warm-up's value), and a forced Wb forces Wa.
+bool plan(Engine* e, const tgp_sweep::ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why, bool adjoint = false);
+// c: the lane sweep's call record; y, mask, R, hh, Rnew, mean, var are read (mean == null: logpdf only); c.adjoint: the gradient instead (gh_steps,
+// gR_steps: device [T] or null), on an adjoint plan
 int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char** kernel_name, std::string* err);
 const char* kernel_name(bool post);
-// After the stream has been synchronised: tgp_sweep::finish's status bits, warm-ups and distances.
+const char* adjoint_kernel_name();
+// After the stream has been synchronised: tgp_sweep::finish's status bits, warm-ups and distances.  An adjoint call: bit 2, *wb and *dist_b are the
+// adjoint warm-up's.
 double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* dist_b);
+// Behind finish of an adjoint call whose status is clean: the waves' sums, added in wave order (gQ and gx0P symmetric).
+void adjoint_blocks(const Engine* e, const tgp_sweep::AdjointOut& out);
 void geometry(const Engine* e, int* C, int* W, int* Wb, int64_t* nwaves);
 // test hook: force the geometry of the next plan (0: automatic)
 void force_geometry(Engine* e, int C, int W, int Wb);

@@ -364,6 +364,12 @@ constexpr int64_t kGroupMinT = 2048;           // shorter series stay on the gen
 constexpr int group_owned(bool post) { return post ? kGroupsPerWave - 2 : kGroupsPerWave - 1; }
 // steps per checkpoint block: the block's filtering states (d + d (d + 1) / 2 doubles per step and group) sit in LDS during the backward run
 constexpr int group_block(int d) { return d <= 6 ? 8 : 4; }
+// The adjoint call (k_sweep_group_adjoint) runs in the posterior call's geometry.  Doubles a wave leaves behind its 4 status words: gA d*d, ga d,
+// gQ packed, gH d, the sums of gh_t and gR_t, gx0m d, gx0P packed (the lane sweep's record).
+constexpr int group_adjoint_sums(int d) { return d * d + d + d * (d + 1) / 2 + d + 2 + d + d * (d + 1) / 2; }
+// waves resident per CU in an adjoint call, from the kernel's register counts as group_waves_per_cu's (profiles/sweep_group_adjoint_resources.txt):
+// 8 where it takes at most 256 registers (d = 5, 6: 220 .. 254), else 4 (d = 7, 8: 262 .. 290)
+constexpr int group_adjoint_waves_per_cu(int d) { return d <= 6 ? 8 : 4; }
 
 // The steps [t0, t1) of group g (0 .. 7) of a wave, as the kernel and the tests compute them: the wave's groups hold the chunks
 // wave * owned - 1 .. wave * owned + 6.  runs: the group runs its chunk (group 0 only warms up); owned: it writes output and sums.
@@ -399,12 +405,13 @@ struct GroupPlan {
     int C = 0, W = 0, Wb = 0;
     int64_t T = 0, nchunks = 0, nwaves = 0;
     GroupModelC mc;
+    bool adjoint = false;      // an adjoint call: post's geometry, Wb holds the adjoint's warm-up Wa
 };
 
 namespace plan_detail {
 
 template <int D> inline bool plan_group_d(GroupPlan* e, const Forced& f, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post,
-                                          std::string* why) {
+                                          std::string* why, bool adjoint = false) {
     double Aty[D * D], Qty[D * D], gm[D], Ps[D * D];
     if (!stationary_prior<D>(m, Aty, Qty, gm, Ps)) {
         if (why) *why = "the transition has no stationary covariance";
@@ -412,17 +419,21 @@ template <int D> inline bool plan_group_d(GroupPlan* e, const Forced& f, const M
     }
     int W = w_hint, Wb = wb_hint;
     if (!estimate_warmups<D>(Aty, Qty, m.H, m.R, W, Wb, why)) return false;
+    // the adjoint's warm-up: the forward warm-up's value is the first guess (plan_d: the adjoint forgets at the filter's rate); a call that found it
+    // short passes a longer one
+    if (adjoint && wb_hint <= 0) Wb = W;
     auto up = [](int v, int q) { return (v + q - 1) / q * q; };
     // chunk length: group_waves_per_cu waves per CU, every wave `owned` chunks of its own; a chunk holds the backward warm-up.  A multiple of 8 (the rows
     // of the observation stream), hence of the checkpoint block.
     const int owned = group_owned(post);
-    const int64_t slots = (int64_t)std::max(num_cu, 1) * group_waves_per_cu(D, post) * owned;
+    const int64_t slots = (int64_t)std::max(num_cu, 1) * (adjoint ? group_adjoint_waves_per_cu(D) : group_waves_per_cu(D, post)) * owned;
     int64_t C = up((int)std::min<int64_t>((T + slots - 1) / slots, 1 << 20), 8);
     C = std::max<int64_t>(C, 64);
     C = std::max<int64_t>(C, Wb);
     if (f.C > 0) C = up(f.C, 8);
     if (f.W > 0) W = up(f.W, 8);
     if (f.Wb > 0) Wb = up(f.Wb, 8);
+    else if (adjoint && wb_hint <= 0) Wb = W;      // (the first guess follows a forced forward warm-up)
     if (Wb > C) Wb = (int)C;
     if (W > kMaxWarm || (f.C == 0 && W > 4 * C)) {
         if (why) *why = "forward warm-up longer than four chunks";
@@ -437,6 +448,7 @@ template <int D> inline bool plan_group_d(GroupPlan* e, const Forced& f, const M
     e->B = group_block(D);
     e->owned = owned;
     e->post = post;
+    e->adjoint = adjoint;
     e->T = T;
     e->C = (int)C;
     e->W = W;
@@ -470,8 +482,10 @@ template <int D> inline bool plan_group_d(GroupPlan* e, const Forced& f, const M
 }  // namespace plan_detail
 
 // The geometry of a group-sweep call (LTI form); false: the engine declines (`why` says so).  post: a posterior call (6 of a wave's 8 groups own
-// output instead of 7).  w_hint / wb_hint as make_plan's.
-inline bool plan_group(GroupPlan* p, const Forced& f, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why) {
+// output instead of 7).  w_hint / wb_hint as make_plan's.  adjoint (with post): an adjoint call -- the backward slot carries the adjoint's warm-up Wa
+// (wb_hint: a Wa that a previous call needed, 0: the forward warm-up's value; a forced Wb forces Wa).
+inline bool plan_group(GroupPlan* p, const Forced& f, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why,
+                       bool adjoint = false) {
     if (m.d < kGroupMinD || m.d > kGroupMaxD || m.sde) {
         if (why) *why = "state dimension";
         return false;
@@ -481,10 +495,10 @@ inline bool plan_group(GroupPlan* p, const Forced& f, const ModelHost& m, int64_
         return false;
     }
     switch (m.d) {
-        case 5: return plan_detail::plan_group_d<5>(p, f, m, T, w_hint, wb_hint, num_cu, post, why);
-        case 6: return plan_detail::plan_group_d<6>(p, f, m, T, w_hint, wb_hint, num_cu, post, why);
-        case 7: return plan_detail::plan_group_d<7>(p, f, m, T, w_hint, wb_hint, num_cu, post, why);
-        default: return plan_detail::plan_group_d<8>(p, f, m, T, w_hint, wb_hint, num_cu, post, why);
+        case 5: return plan_detail::plan_group_d<5>(p, f, m, T, w_hint, wb_hint, num_cu, post, why, adjoint);
+        case 6: return plan_detail::plan_group_d<6>(p, f, m, T, w_hint, wb_hint, num_cu, post, why, adjoint);
+        case 7: return plan_detail::plan_group_d<7>(p, f, m, T, w_hint, wb_hint, num_cu, post, why, adjoint);
+        default: return plan_detail::plan_group_d<8>(p, f, m, T, w_hint, wb_hint, num_cu, post, why, adjoint);
     }
 }
 

@@ -608,12 +608,8 @@ def logpdf_adjoint(model, y):
     return lml.value, g
 
 
-def logpdf_adjoint_missing(model, y, per_step=False):
-    """logpdf_adjoint where the gains vary in time -- NaNs in y (or a (y, mask) tuple), a noise variance or an emission offset per step -- by ONE adjoint
-    pass on the sweep engine (tgp_logpdf_adjoint_missing, k_sweep_adjoint): Forward models with shared A, a, Q, H, scalar observations, d <= 4, T >= 2048.
-    Returns (lml, g) with g as logpdf_adjoint gives it; "h" and "R" are the sums of the per-step gradients over the observed steps, whether the stream is
-    shared or per step.  per_step: g also holds "h_steps" and "R_steps" (T,), d logpdf / d h_t and d logpdf / d R_t, zero at missing steps (torch tensors
-    on the model's device where y is one).  Raises Unsupported where the engine declines (use logpdf_and_grad)."""
+def _logpdf_adjoint_sweep(entry, model, y, per_step):
+    """tgp_logpdf_adjoint_missing / tgp_logpdf_adjoint_group: one argument list, one output convention"""
     _check_inputs(model, y[0] if isinstance(y, tuple) else y)
     hd = model.handle()
     yy, mm, dev = _obs(y, model)
@@ -622,14 +618,30 @@ def logpdf_adjoint_missing(model, y, per_step=False):
     steps = [_out(model, (model.T,), dev), _out(model, (model.T,), dev)] if per_step else [None, None]
     lml = ctypes.c_double()
     flags = (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0
-    hd.check(hd.lib.tgp_logpdf_adjoint_missing(hd.h, _lib.ptr(yy), _lib.ptr(mm), flags, ctypes.byref(lml),
-                                               *[_lib.ptr(g[k]) for k in ("A", "a", "Q", "H", "h", "R", "x0m", "x0P")], _lib.ptr(steps[0]), _lib.ptr(steps[1])))
+    hd.check(getattr(hd.lib, entry)(hd.h, _lib.ptr(yy), _lib.ptr(mm), flags, ctypes.byref(lml),
+                                    *[_lib.ptr(g[k]) for k in ("A", "a", "Q", "H", "h", "R", "x0m", "x0P")], _lib.ptr(steps[0]), _lib.ptr(steps[1])))
     for k in ("A", "Q", "x0P"):
         g[k] = g[k].T.copy()          # column-major blocks -> [i][k]
     g["h"], g["R"] = float(g["h"][0]), float(g["R"][0])
     if per_step:
         g["h_steps"], g["R_steps"] = steps
     return lml.value, g
+
+
+def logpdf_adjoint_missing(model, y, per_step=False):
+    """logpdf_adjoint where the gains vary in time -- NaNs in y (or a (y, mask) tuple), a noise variance or an emission offset per step -- by ONE adjoint
+    pass on the sweep engine (tgp_logpdf_adjoint_missing, k_sweep_adjoint): Forward models with shared A, a, Q, H, scalar observations, d <= 4, T >= 2048.
+    Returns (lml, g) with g as logpdf_adjoint gives it; "h" and "R" are the sums of the per-step gradients over the observed steps, whether the stream is
+    shared or per step.  per_step: g also holds "h_steps" and "R_steps" (T,), d logpdf / d h_t and d logpdf / d R_t, zero at missing steps (torch tensors
+    on the model's device where y is one).  Raises Unsupported where the engine declines (use logpdf_and_grad)."""
+    return _logpdf_adjoint_sweep("tgp_logpdf_adjoint_missing", model, y, per_step)
+
+
+def logpdf_adjoint_group(model, y, per_step=False):
+    """logpdf_adjoint_missing at state dimensions 5 <= d <= 8: ONE adjoint pass on the group sweep (tgp_logpdf_adjoint_group, k_sweep_group_adjoint,
+    DESIGN 4.11) -- Forward models with shared A, a, Q, H, scalar observations, T >= 2048; NaNs in y (or a (y, mask) tuple), a noise variance or an emission
+    offset per step.  Arguments and the returned (lml, g) as logpdf_adjoint_missing's.  Raises Unsupported where the engine declines (use logpdf_and_grad)."""
+    return _logpdf_adjoint_sweep("tgp_logpdf_adjoint_group", model, y, per_step)
 
 
 def logpdf_adjoint_sde(model, y, per_step=False):

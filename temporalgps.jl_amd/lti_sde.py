@@ -856,13 +856,15 @@ def _logpdf_and_gradient_adjoint(fx, y):
 
 
 def _logpdf_and_gradient_sweep(fx, y):
-    """One adjoint pass on the sweep engine (L.logpdf_adjoint_missing: missing observations and / or one noise variance per observation, d <= 4,
-    T >= 2048) contracted with the exact block tangents.  One variance per observation: no "noise" entry (as on the "fd" route)."""
+    """One adjoint pass on the sweep engine (L.logpdf_adjoint_missing at d <= 4, L.logpdf_adjoint_group at 5 <= d <= 8: missing observations and / or one
+    noise variance per observation, T >= 2048) contracted with the exact block tangents.  One variance per observation: no "noise" entry (as on the "fd"
+    route)."""
     if not (isinstance(fx.x, RegularSpacing) and isinstance(fx.f.f.mean, (ZeroMean, ConstMean))):
         raise NotImplementedError("logpdf_and_gradient(method='sweep'): RegularSpacing inputs with a ZeroMean or ConstMean only")
     plist = parameters(fx.f.f.kernel)
     names = [n for n, _, _ in plist] + (["noise"] if fx.sigma2.shape[0] == 1 else []) + (["mean.c"] if isinstance(fx.f.f.mean, ConstMean) else [])
-    lp, g = L.logpdf_adjoint_missing(fx.build_lgssm(), y)
+    model = fx.build_lgssm()
+    lp, g = (L.logpdf_adjoint_group if 5 <= model.dim <= 8 else L.logpdf_adjoint_missing)(model, y)
     grad = {}
     for name, t in zip(names, _shared_block_tangents(fx, names, plist)):
         grad[name] = float(sum(_contract(g[k], v) for k, v in t.items()))
@@ -1028,8 +1030,8 @@ def logpdf_and_gradient(fx, y, rel_step=None, method=None):
     method: None (default policy), "adjoint" (ONE reverse-time pass on the stationary-gain engine, exact block tangents on the host:
     regular spacing, homoscedastic noise, d <= 8, or the wide-state engine for 8 < d <= 63 where its plan applies -- cost independent of the
     number of parameters), "sweep" (ONE adjoint pass on the sweep engine: regular spacing with NaNs in y and / or one noise variance per
-    observation, or plain-array (irregularly spaced) inputs bound through their SDE; ZeroMean or ConstMean, d <= 4, T >= 2048; raises Unsupported where the
-    device declines), "tangent" (the forward-mode scans)
+    observation at d <= 8 -- the group sweep's kernel at 5 <= d <= 8 --, or plain-array (irregularly spaced) inputs bound through their SDE at d <= 4;
+    ZeroMean or ConstMean, T >= 2048; raises Unsupported where the device declines), "tangent" (the forward-mode scans)
     or "fd" (central differences of the device logpdf).
     Default: the adjoint pass where it applies -- on the stationary-gain engines, or on the sweep engine for d <= 4 and T >= 2048 with missing observations
     or one noise variance per observation (profiles/sweep_adjoint_time.txt) or with plain-array inputs and no rel_step given
