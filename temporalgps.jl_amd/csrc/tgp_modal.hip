@@ -1496,7 +1496,7 @@ bool plan(Engine* e, const tgp_plan::ModelHost& m, long long T, bool logpdf_only
     layout_tables(e);
     e->mh = m;
     e->hh_T = T;
-    if (logpdf_only && e->sf.ok && lml_stream_enabled() && stream_serves(e, T, kLmlMinT)) {
+    if (logpdf_only && e->sf.ok && e->sf.amp <= tgp_stream_form::kClosureAmpMax && lml_stream_enabled() && stream_serves(e, T, kLmlMinT)) {
         // the streaming logpdf kernel: no tables (the head runs on the host from build_core's gains), no wait inside the kernel
         e->lg = tgp_lml::choose_geometry(e->sf.md, T);
         if (!e->lpart) {

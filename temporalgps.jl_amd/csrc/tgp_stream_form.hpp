@@ -22,6 +22,13 @@ namespace tgp_stream_form {
 
 constexpr int kMaxD = tgp_plan::kMaxD;
 constexpr double kRelMin = 1e-8;
+// The streaming logpdf kernel closes its first tile on the host as a quadratic form in the head's end state: sum (r0_t - w_t . x)^2 expanded into
+// sum r0_t^2 - 2 x . sum r0_t w_t + x' W x.  Its rounding is eps times the size of the terms, not of the result.  With the input entering every block
+// with coefficient 1 a block settles at u / (1 - lambda_i), so the terms are (amp u)^2 with amp = sum_i |w~_i| / |1 - lambda_i|, while the innovations
+// are of the size of u or below: the closure loses amp^2.  Ordinary models have amp = 1 .. 6; a closed loop whose real modes nearly coincide has w~ in
+// the thousands with alternating signs (a Matern-5/2 model 1e-6 in the spacing from the point where its pair splits: amp = 1.9e3, logpdf off by 1.5e-9
+// absolute).  64^2 eps = 4.5e-13 leaves a factor 200 for u^2 / S and a small |logpdf| under the 1e-10 bar; beyond it k_steady_one serves logpdf.
+constexpr double kClosureAmpMax = 64.0;
 
 struct Form {
     bool ok = false;
@@ -29,6 +36,7 @@ struct Form {
     double bp[kMaxD], bq[kMaxD];        // B: the block [[p, q], [-q, p]] of a pair (both members carry it), p alone (q = 0) on a real mode
     double cp[kMaxD], cq[kMaxD];        // C likewise
     double s[kMaxD];                    // the forward shift, in the kernels' coordinates
+    double amp = 0.0;                   // sum_i |w~_i| / |1 - lambda_i|: what the logpdf kernel's quadratic closure amplifies rounding by (kClosureAmpMax)
 };
 
 namespace detail {
@@ -141,6 +149,8 @@ inline bool build(const tgp_plan::Modal& in, Form& f) {
             }
         if (!solve(d, A, b, f.s)) return false;
     }
+    f.amp = 0.0;
+    for (int i = 0; i < d; ++i) f.amp += std::fabs(md.fw[i]) / std::sqrt((1.0 - in.fd[i]) * (1.0 - in.fd[i]) + in.fo[i] * in.fo[i]);
     double hs = in.hh;
     for (int i = 0; i < d; ++i) hs += md.fw[i] * f.s[i];
     md.hh = hs;

@@ -5,7 +5,8 @@ offset and a non-zero transition offset throughout -- and runs the plan's recurs
     backward  the means, the left-edge state mapped back.
 Every deviation is taken relative to the largest entry of what is compared and must stay within 1e-12: the two recursions are the same linear map in
 two bases of one conditioning, so what separates them is rounding along a contracting recursion (a few hundred ulp at the spectral radii used here),
-not a property of the model.  The guard: a model one of whose input coefficients is 1e-12 of the others reports that the form declines."""
+not a property of the model.  The guard: a model one of whose input coefficients is 1e-12 of the others reports that the form declines.
+Given files, the same main reads a plan's modal form and a series from each and reports the case's largest deviation (tests/test_stream_envelope_host.py)."""
 import os
 import re
 import shutil
@@ -100,9 +101,11 @@ static void compare(const char* what, int d, int np, const std::vector<double>& 
     }
 }
 
-static void run(int d, int np, double hh, double offset) {
-    const int T = 4096;
-    const Modal md = make(d, np, hh, offset);
+// the two recursions side by side on one modal form over 4096 steps.  series == nullptr: a seeded series around hh and a start state of the plan's;
+// else the given series (4096 values) and a start state of unit size in the normal form's coordinates, mapped to the plan's by state_out
+static void run_modal(const Modal& md, const double* series) {
+    const int T = 4096, d = md.d, np = md.npair;
+    const double hh = md.hh;
     sf::Form f;
     if (!sf::build(md, f)) {
         std::printf("FAIL d %d npair %d: the form declined\n", d, np);
@@ -111,9 +114,14 @@ static void run(int d, int np, double hh, double offset) {
     }
     const Modal& nf = f.md;
     std::vector<double> y(T), r(T), rn(T), mean(T), meann(T);
-    for (int t = 0; t < T; ++t) y[t] = hh + 3.0 * sym();
+    for (int t = 0; t < T; ++t) y[t] = series ? series[t] : hh + 3.0 * sym();
     double z[8], x[8], nz[8];
-    for (int i = 0; i < d; ++i) z[i] = 2.0 * sym();
+    if (series) {
+        for (int i = 0; i < d; ++i) x[i] = sym();
+        sf::state_out(f, x, z);
+    } else {
+        for (int i = 0; i < d; ++i) z[i] = 2.0 * sym();
+    }
     sf::state_in(f, z, x);
     double q = 0.0, qn = 0.0;
     for (int t = 0; t < T; ++t) {
@@ -162,7 +170,36 @@ static void run(int d, int np, double hh, double offset) {
     compare("left-edge backward state", d, np, std::vector<double>(ze, ze + d), std::vector<double>(back, back + d));
 }
 
-int main() {
+static void run(int d, int np, double hh, double offset) { run_modal(make(d, np, hh, offset), nullptr); }
+
+// a plan's modal form and a series from a file: name, d, npair, hh, rS, then fd fo fb fa fw gd go gc gw (d values each), then 4096 observations.
+// Prints the case's largest deviation; the caller holds it against the bound.
+static int run_file(const char* path) {
+    std::FILE* fp = std::fopen(path, "r");
+    if (!fp) return 2;
+    char name[64];
+    Modal md{};
+    bool ok = std::fscanf(fp, "%63s %d %d %lf %lf", name, &md.d, &md.npair, &md.hh, &md.rS) == 5 && md.d >= 1 && md.d <= 8 && md.npair >= 0 && 2 * md.npair <= md.d;
+    double* arrs[9] = {md.fd, md.fo, md.fb, md.fa, md.fw, md.gd, md.go, md.gc, md.gw};
+    for (int k = 0; ok && k < 9; ++k)
+        for (int i = 0; ok && i < md.d; ++i) ok = std::fscanf(fp, "%lf", &arrs[k][i]) == 1;
+    std::vector<double> y(4096);
+    for (int t = 0; ok && t < 4096; ++t) ok = std::fscanf(fp, "%lf", &y[t]) == 1;
+    std::fclose(fp);
+    if (!ok) return 2;
+    worst = 0.0;
+    const int before = fails;
+    run_modal(md, y.data());
+    std::printf("case %s deviation %.3e%s\n", name, worst, fails == before ? "" : " FAIL");
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1) {      // plans from files: one line per case, the exit status says only whether the files could be read
+        for (int k = 1; k < argc; ++k)
+            if (run_file(argv[k])) return 2;
+        return 0;
+    }
     const int grid[][2] = {{1, 0}, {2, 0}, {2, 1}, {3, 0}, {3, 1}, {6, 0}, {6, 1}, {6, 2}, {6, 3}};
     for (const auto& g : grid) {
         run(g[0], g[1], 0.7, 0.5);       // emission and transition offset
@@ -193,8 +230,8 @@ int main() {
 """
 
 
-@pytest.mark.skipif(CXX is None, reason="needs a host C++ compiler")
-def test_normal_form_reproduces_the_plans_recursions_and_declines_a_weak_input(tmp_path):
+def build_harness(tmp_path):
+    """the main above, compiled for the host into tmp_path (tests/test_stream_envelope_host.py runs it on the plans of its table)"""
     src = tmp_path / "stream_form_main.cpp"
     exe = tmp_path / "stream_form_main"
     src.write_text(MAIN)
@@ -202,6 +239,12 @@ def test_normal_form_reproduces_the_plans_recursions_and_declines_a_weak_input(t
     build = subprocess.run([CXX, "-std=c++17", "-O1", "-g", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC,
                             str(src), "-o", str(exe)], capture_output=True, text=True)
     assert build.returncode == 0, build.stderr
+    return exe
+
+
+@pytest.mark.skipif(CXX is None, reason="needs a host C++ compiler")
+def test_normal_form_reproduces_the_plans_recursions_and_declines_a_weak_input(tmp_path):
+    exe = build_harness(tmp_path)
     run = subprocess.run([str(exe)], capture_output=True, text=True)
     print(run.stdout, run.stderr)
     assert run.returncode == 0, run.stdout + run.stderr
