@@ -152,16 +152,17 @@ typedef struct tgp_handle tgp_handle;
                            tgp_[logpdf_and_]posterior_marginals run on the GROUP sweep (tgp_sweep_group.hip) -- the same algorithm,
                            checks and repair with a chunk spread over 8 lanes, lane j holding column j of every matrix; kernels
                            k_sweep_group<lti,logpdf> / k_sweep_group<lti,posterior>; the gradient has an entry point of its own there,
-                           tgp_logpdf_adjoint_group (k_sweep_group_adjoint<lti>; served under 1 and 2 alike); the draw stays at d <= 4.  Under 1 the group
+                           tgp_logpdf_adjoint_group (k_sweep_group_adjoint<lti>; served under 1 and 2 alike), and so has the draw, tgp_posterior_rand_group
+                           (k_sweep_group_draw<lti>; likewise); tgp_posterior_rand_missing stays at d <= 4.  Under 1 the group
                            sweep takes only the (d, call) pairs that beat the general engine at T = 1e6 and 1e7 (profiles/sweep_group_time.txt):
                            tgp_logpdf at d = 6, 7, 8; 2: every pair, tgp_logpdf at d = 5 and the posterior calls included (tests, A/B timing;
                            the lane sweep is the same under 1 and 2).  Both step aside
                            on an explicit request for the general engine (TGP_REUSE_REDUCE, TGP_OPT_CHUNK, TGP_OPT_VARIANT, TGP_OPT_STEADY 0 / 1,
-                           TGP_OPT_GRAPH).  0: the general chunked-scan engine as before; tgp_posterior_rand_missing,
+                           TGP_OPT_GRAPH).  0: the general chunked-scan engine as before; tgp_posterior_rand_missing, tgp_posterior_rand_group,
                            tgp_logpdf_adjoint_missing and tgp_logpdf_adjoint_group answer TGP_EUNSUPPORTED for these models. */
 #define TGP_OPT_SWEEP_CHUNK 15       /* tests: steps per chunk of the sweep engine (0 automatic) */
 #define TGP_OPT_SWEEP_WARMUP 16      /* tests: forward warm-up steps (0 automatic); a forced geometry is never repaired by longer warm-ups */
-#define TGP_OPT_SWEEP_WARMUP_BACK 17 /* tests: backward warm-up steps (0 automatic); in tgp_posterior_rand_missing: the draw's warm-up; in
+#define TGP_OPT_SWEEP_WARMUP_BACK 17 /* tests: backward warm-up steps (0 automatic); in tgp_posterior_rand_missing / _group: the draw's warm-up; in
                                         tgp_logpdf_adjoint_missing / _group: the adjoint's */
 #define TGP_OPT_STREAM_MIN_T 18 /* series length from which the STREAMING kernels of the stationary-gain engine serve a call: persistent
                                    waves with ~7 us more fixed latency and 1.3 - 2.7 x the throughput of k_steady_one.  -1 (default): the measured
@@ -211,12 +212,13 @@ int64_t tgp_graph_replays(const tgp_handle* h);
    the stationary-gain engines, their one-launch kernels and the wide-state engine: T - n0 (n0: the head of steps with gains of their own);
    the general engine: the steps the forward pass of the last posterior-path call ran in the mean-only form. */
 int tgp_steady_steps(tgp_handle* h, int64_t* mean_only, int64_t* total);
-/* Diagnostics of TGP_OPT_SWEEP for the last tgp_logpdf / tgp_[logpdf_and_]posterior_marginals / tgp_posterior_rand_missing / tgp_logpdf_adjoint_missing /
-   tgp_logpdf_adjoint_group / tgp_logpdf_adjoint_sde call. info [8]: served by the sweep engine (0 / 1), steps per chunk, forward warm-up, backward warm-up (tgp_posterior_rand_missing: the draw's;
+/* Diagnostics of TGP_OPT_SWEEP for the last tgp_logpdf / tgp_[logpdf_and_]posterior_marginals / tgp_posterior_rand_missing / tgp_posterior_rand_group /
+   tgp_logpdf_adjoint_missing / tgp_logpdf_adjoint_group / tgp_logpdf_adjoint_sde call. info [8]: served by the sweep engine (0 / 1), steps per chunk,
+   forward warm-up, backward warm-up (tgp_posterior_rand_missing / _group: the draw's;
    tgp_logpdf_adjoint_missing / _group / _sde: the adjoint's, and dist[1] compares the adjoints of its hand-over), waves, attempts (launches),
    status bits of the last attempt (1 forward / 2 backward or draw warm-up too short, 4 not positive definite, 8 non-finite), state for the bound
    model (0 untried, 1 serves, -1 declined).  dist [2]: the largest relative distance between a warm-up's end state and the run that reproduces it,
-   forwards / backwards (the checks' 1e-12 / 1e-11; tgp_posterior_rand_missing: dist[1] compares the sample states of the draw's hand-over).
+   forwards / backwards (the checks' 1e-12 / 1e-11; tgp_posterior_rand_missing / _group: dist[1] compares the sample states of the draw's hand-over).
    A call the sweep engine was not asked for reports zeros beside the state.  State -1 holds for the bound model, whatever the series of a later
    call, until tgp_model_set or one of the options 14-17.  Either may be NULL. */
 int tgp_sweep_info(tgp_handle* h, int64_t* info, double* dist);
@@ -475,7 +477,8 @@ int tgp_marginals(tgp_handle* h, uint32_t flags, double* mean_out, double* var_o
  *      device scratch: T doubles).  eps_t [T][d], eps_e [T] where TGP_IN_DEVICE says (as y and Rnew),
  *      eps_0 [d] host; eps_t[t] / eps_e[t] drive the transition / emission of step t and eps_0 the draw of the
  *      final filtering state, exactly as tgp_rand on the evaluated posterior uses them. Rnew: one value
- *      (TGP_SHARED_R) or T. y_out [T]. TGP_EUNSUPPORTED: not a model of this path (d = 7, 8; a wide model whose
+ *      (TGP_SHARED_R) or T. y_out [T]. TGP_EUNSUPPORTED: not a model of this path (d = 7, 8 -- tgp_posterior_rand_group serves 5 <= d <= 8 at
+ *      T >= 2048 --; a wide model whose
  *      covariance does not settle or whose reverse-time transition does not forget) -- evaluate the posterior
  *      (tgp_posterior), bind it as a Reverse model and call tgp_rand (what the Python mirror does). */
 int tgp_posterior_rand(tgp_handle* h, const double* y, const double* Rnew, const double* eps_t, const double* eps_e,
@@ -497,11 +500,24 @@ int tgp_posterior_rand(tgp_handle* h, const double* y, const double* Rnew, const
  *      eps_e / y_out [T][p]; Rnew [p] with TGP_SHARED_R, else [T][p]; eps_0 [d] host; the others where TGP_IN_DEVICE /
  *      TGP_OUT_DEVICE say.  Draws are used as tgp_rand on the evaluated posterior uses them; emissions of p > 1 (or
  *      TGP_SMALL_OUTPUT) models add the reference's 1e-9 to Rnew.  TGP_EUNSUPPORTED (nothing written to y_out): another engine's
- *      handle, a Reverse model, TGP_OPT_SWEEP = 0 (d <= 4), a sweep-engine draw whose Cholesky pivots are not positive, whose values
+ *      handle, a Reverse model, TGP_OPT_SWEEP = 0 (d <= 4), 5 <= d <= 16 (5 .. 8: tgp_posterior_rand_group), a sweep-engine draw whose Cholesky pivots are not positive, whose values
  *      are not finite or whose forced warm-ups are too short, TGP_OPT_DENSE_CHUNKED = 0 or TGP_OPT_DENSE_FUSED = 0, or stores that do
  *      not fit -- take tgp_posterior_rand (LTI, d <= 16) or tgp_posterior + tgp_rand. */
 int tgp_posterior_rand_missing(tgp_handle* h, const double* y, const uint8_t* missing, const double* Rnew, const double* eps_t,
                                const double* eps_e, const double* eps_0, uint32_t flags, double* y_out);
+/* The same draw at state dimensions 5 <= d <= 8 by ONE kernel of the GROUP sweep (k_sweep_group_draw<lti>): a chunk spread over 8 lanes, lane j
+ * holding column j of every matrix and element j of the sample; k_sweep_group<lti,posterior>'s geometry (6 of a wave's 8 groups own output) and forward
+ * half, then the walk back over the chunk from the next group's sample of ITS first step, with the hand-over check (1e-11 on the samples) and repair of
+ * tgp_posterior_rand_missing.  Arguments, flags, the use of the draws and tgp_sweep_info exactly as there (p = 1); TGP_OPT_SWEEP_WARMUP_BACK forces the
+ * draw's warm-up.  An explicit call: served under TGP_OPT_SWEEP = 1 and 2 alike, whatever the default routing of the engine's other calls; a model without
+ * any gap is served too.  Never the reverse-time model (T (2 d^2 + d) doubles): T doubles of device scratch beside the checkpoints.  Two calls on the
+ * same series and draws give the same bits.
+ * TGP_EUNSUPPORTED, with nothing written to y_out (host or device): d < 5 (use tgp_posterior_rand_missing), d > 8, SDE-described models, p > 1, Reverse
+ * models, T < 2048, TGP_OPT_SWEEP = 0, an explicit request for the general engine (TGP_OPT_CHUNK, ...), an engine declined for the bound model, a forced
+ * geometry whose warm-ups are too short, a Cholesky pivot that is not positive, non-finite values.  The library does not fall back: take tgp_posterior +
+ * tgp_rand. */
+int tgp_posterior_rand_group(tgp_handle* h, const double* y, const uint8_t* missing, const double* Rnew, const double* eps_t, const double* eps_e,
+                             const double* eps_0, uint32_t flags, double* y_out);
 
 /* ---- logpdf(replace_observation_noise_cov(posterior(model, y), R_new), y_new) (posterior_lti_sde.jl:62-78 ->
  *      lgssm.jl:147-151 on the reverse-time model of lgssm.jl:193-221) without a posterior: two observations of

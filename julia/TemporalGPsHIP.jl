@@ -343,15 +343,23 @@ function AbstractGPs.rand(rng::AbstractRNG, m::DeviceLGSSM)
 end
 
 """`rand` of `replace_observation_noise_cov(posterior(model, y), Σs_new)` on supplied draws without evaluating the posterior
-(tgp_posterior_rand_missing: scalar observations, d <= 4, T >= 2048 on the sweep engine's draw kernel; 16 < d <= 64, p <= 16 on the dense engine).
+(tgp_posterior_rand_missing: scalar observations, d <= 4, T >= 2048 on the sweep engine's draw kernel; 16 < d <= 64, p <= 16 on the dense engine;
+tgp_posterior_rand_group on the group sweep at 5 <= d <= 8, scalar observations, T >= 2048).
 `nothing`: TGP_EUNSUPPORTED, take the evaluated route."""
 function posterior_rand_missing(m::DeviceLGSSM{Forward}, y::AbstractVector, Σs_new::AbstractVector, eps_t, eps_e, eps_0)
     yv, mp, mask = _split_missing(y)
     (R, shared) = m.p == 1 ? _flat(Σs_new) : _flat_diag(Σs_new)
     out = Vector{Float64}(undef, m.p * m.T)
-    rc = GC.@preserve yv mask R ccall((:tgp_posterior_rand_missing, libtgp), Cint,
-        (Ptr{Cvoid}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, UInt32, Ptr{Float64}),
-        m.h.ptr, yv, mp, R, eps_t, eps_e, eps_0, shared ? SHARED_R : UInt32(0), out)
+    # (5 <= d <= 8: the group sweep's entry point, the same argument list; a ccall's symbol must be a literal)
+    rc = GC.@preserve yv mask R if 5 <= m.d <= 8 && m.p == 1
+        ccall((:tgp_posterior_rand_group, libtgp), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, UInt32, Ptr{Float64}),
+            m.h.ptr, yv, mp, R, eps_t, eps_e, eps_0, shared ? SHARED_R : UInt32(0), out)
+    else
+        ccall((:tgp_posterior_rand_missing, libtgp), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, UInt32, Ptr{Float64}),
+            m.h.ptr, yv, mp, R, eps_t, eps_e, eps_0, shared ? SHARED_R : UInt32(0), out)
+    end
     rc == 4 && return nothing
     check(m.h, rc)
     return out

@@ -77,6 +77,7 @@ _SIGS = {
     "tgp_rand": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u32, _vp]),
     "tgp_posterior_rand": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "tgp_posterior_rand_missing": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "tgp_posterior_rand_group": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "tgp_logpdf_noise": (ctypes.c_int, [_vp, _vp, _u32, ctypes.c_double, _vp]),
     "tgp_pair_statistic": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "tgp_elem_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
@@ -229,8 +230,8 @@ class Handle:
         return dict(kernel_ms=k.value, h2d_ms=a.value, d2h_ms=b.value)
 
     def sweep_info(self):
-        """diagnostics of the sweep engine (TGP_OPT_SWEEP) for the last logpdf / posterior-marginals / posterior-draw / adjoint-gradient call (a draw:
-        Wb and dist_b are the draw warm-up's; logpdf_adjoint_missing / logpdf_adjoint_group / logpdf_adjoint_sde: the adjoint warm-up's)"""
+        """diagnostics of the sweep engine (TGP_OPT_SWEEP) for the last logpdf / posterior-marginals / posterior-draw / adjoint-gradient call (a draw,
+        posterior_rand_group's too: Wb and dist_b are the draw warm-up's; logpdf_adjoint_missing / logpdf_adjoint_group / logpdf_adjoint_sde: the adjoint warm-up's)"""
         import numpy as np
         info, dist = np.zeros(8, dtype=np.int64), np.zeros(2)
         self.check(self.lib.tgp_sweep_info(self.h, info.ctypes.data, dist.ctypes.data))

@@ -363,7 +363,7 @@ struct tgp_handle {
     tgp_sweep_group::Engine* sweep_group = nullptr;
     int sweep_state = 0;          // 0 untried for the bound model, 1 served the last call, -1 does not apply
     int sweep_W = 0, sweep_Wb = 0;     // warm-ups the bound model's last served call needed (0: estimate)
-    int sweep_Wd = 0;             // the same for the draw's warm-up (tgp_posterior_rand_missing; 0: the backward warm-up's estimate)
+    int sweep_Wd = 0;             // the same for the draw's warm-up (tgp_posterior_rand_missing / _group; 0: the backward warm-up's estimate)
     int sweep_Wa = 0;             // the same for the adjoint's warm-up (tgp_logpdf_adjoint_missing / _group; 0: the forward warm-up's value)
     int sweep_fC = 0, sweep_fW = 0, sweep_fWb = 0;   // TGP_OPT_SWEEP_CHUNK / _WARMUP / _WARMUP_BACK (tests; 0 automatic)
     int64_t sweep_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // tgp_sweep_info

@@ -329,30 +329,26 @@ int sweep_group_call(tgp_handle* h, const double* y, const uint8_t* missing, uin
     return sweep_run(h, eng, y, missing, flags, Rnew, mean_out, var_out, lml_out, served);
 }
 
-// rand of the posterior on the engine (k_sweep_draw, DESIGN 4.7): sweep_call's staging and repair loop around the draw kernel.  The draw pass sits in
-// the backward slots of tgp_sweep_info (its warm-up Wd is remembered apart from Wb; TGP_OPT_SWEEP_WARMUP_BACK forces it here).  *served = false with
-// *why set: the engine declined, nothing was written to y_out.
-int sweep_draw_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, const double* eps_t, const double* eps_e,
-                    const double* eps_0, double* y_out, bool* served, std::string* why) {
+// What sweep_draw_run needs of an engine: the lane sweep's draw kernel and the group sweep's behind one call sequence (SweepAdjointOps' twin; Wd: the draw's
+// warm-up, in the lane engine's draw slot and the group engine's backward slot).
+struct SweepDrawOps {
+    const char* tag;
+    const char* kname;
+    bool (*plan)(tgp_handle* h, const tgp_sweep::ModelHost& mh, int W, int Wd, std::string* why);      // (with the handle's forced geometry)
+    int (*enqueue)(tgp_handle* h, const tgp_sweep::Call& c, const char** kname, std::string* err);
+    void (*finish)(tgp_handle* h, int* status, int* w, int* wd, double* dist_f, double* dist_d);
+    void (*geometry)(tgp_handle* h, int* C, int64_t* nwaves);
+};
+
+// rand of the posterior on one of the sweep engines: sweep_run's staging and repair loop around a draw kernel.  The draw pass sits in the backward slots
+// of tgp_sweep_info (its warm-up Wd is remembered apart from Wb; TGP_OPT_SWEEP_WARMUP_BACK forces it here).  *served = false with *why set: the engine
+// declined, nothing was written to y_out.
+int sweep_draw_run(tgp_handle* h, const SweepDrawOps& eng, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, const double* eps_t,
+                   const double* eps_e, const double* eps_0, double* y_out, bool* served, std::string* why) {
     *served = false;
-    if (!h->sweep) h->sweep = tgp_sweep::create();
     static const bool dbg = getenv("TGP_STEADY_DEBUG") != nullptr;
     const int d = h->d;
-    const size_t dd = (size_t)d * d;
-    const double* q = h->sweepm.data();
-    tgp_sweep::ModelHost mh;
-    mh.d = d;
-    mh.sde = h->sde;
-    mh.A = h->sde ? h->sde_A1Q1_host.data() : q;
-    mh.a = q + dd;
-    mh.Q = h->sde ? h->sde_A1Q1_host.data() + dd : q + dd + d;
-    mh.H = q + 2 * dd + d;
-    mh.hh = q[2 * dd + 2 * d];
-    mh.R = h->sweep_Rrep;
-    mh.x0m = h->x0m.data();
-    mh.x0P = h->x0P.data();
-    mh.coef = h->sde ? h->sde_coef_host.data() : nullptr;
-    mh.tau_typ = h->sweep_tau;
+    const tgp_sweep::ModelHost mh = sweep_host_model(h);
     const bool idev = (flags & TGP_IN_DEVICE) != 0, odev = (flags & TGP_OUT_DEVICE) != 0;
     const bool rshared = (flags & TGP_SHARED_R) != 0;
     const size_t nT = (size_t)h->T * sizeof(double);
@@ -361,9 +357,8 @@ int sweep_draw_call(tgp_handle* h, const double* y, const uint8_t* missing, uint
     for (int64_t& v : h->sweep_info) v = 0;
     auto replan = [&]() {
         std::string w;
-        tgp_sweep::force_geometry(h->sweep, h->sweep_fC, h->sweep_fW, 0, h->sweep_fWb);
-        if (tgp_sweep::plan(h->sweep, mh, h->T, W, h->sweep_Wb, h->num_cu, &w, Wd)) return true;
-        if (dbg) fprintf(stderr, "[tgp sweep] does not apply: %s\n", w.c_str());
+        if (eng.plan(h, mh, W, Wd, &w)) return true;
+        if (dbg) fprintf(stderr, "[tgp %s] does not apply: %s\n", eng.tag, w.c_str());
         h->sweep_state = -1;
         *why = "the sweep engine's plan declines the model (" + w + ")";
         return false;
@@ -397,21 +392,21 @@ int sweep_draw_call(tgp_handle* h, const double* y, const uint8_t* missing, uint
         c.y_out = dy;
         {
             std::string err;
-            const char* kname = tgp_sweep::kernel_name(d, h->sde, true, true);
+            const char* kname = eng.kname;
             LaunchScope ls(h, kname);
-            if (tgp_sweep::enqueue(h->sweep, h->stream, c, &kname, &err) != 0) return h->fail(TGP_EHIP, err);
+            if (eng.enqueue(h, c, &kname, &err) != 0) return h->fail(TGP_EHIP, err);
         }
         tm.kernels_done();
         if (h->timing) (void)hipEventRecord(h->ev[3], h->stream);
         HIPCHK(hipStreamSynchronize(h->stream));
         resolve_profile(h);
         int status = 0, w = 0, wd = 0;
-        (void)tgp_sweep::finish(h->sweep, &status, &w, nullptr, &h->sweep_dist[0], &h->sweep_dist[1], &wd);
+        eng.finish(h, &status, &w, &wd, &h->sweep_dist[0], &h->sweep_dist[1]);
         int C = 0;
         int64_t nw = 0;
-        tgp_sweep::geometry(h->sweep, &C, nullptr, nullptr, &nw);
+        eng.geometry(h, &C, &nw);
         h->sweep_info[1] = C; h->sweep_info[2] = w; h->sweep_info[3] = wd; h->sweep_info[4] = nw; h->sweep_info[5] = attempt + 1; h->sweep_info[6] = status;
-        if (dbg) fprintf(stderr, "[tgp sweep draw] attempt %d: C %d W %d Wd %d waves %lld status %d dist %.3g / %.3g\n", attempt, C, w, wd, (long long)nw, status, h->sweep_dist[0], h->sweep_dist[1]);
+        if (dbg) fprintf(stderr, "[tgp %s] attempt %d: C %d W %d Wd %d waves %lld status %d dist %.3g / %.3g\n", eng.tag, attempt, C, w, wd, (long long)nw, status, h->sweep_dist[0], h->sweep_dist[1]);
         if (status & 12) {      // not positive definite / non-finite values: the evaluated route reports it the way it always has
             if (status & 4) h->sweep_state = -1;
             *why = (status & 4) ? "a Cholesky pivot of the draw is not positive" : "non-finite values in the draw";
@@ -441,6 +436,40 @@ int sweep_draw_call(tgp_handle* h, const double* y, const uint8_t* missing, uint
     h->sweep_state = -1;      // four attempts, warm-ups still too short: a model that mixes too slowly for this engine
     *why = "the warm-ups stayed too short over four attempts";
     return TGP_OK;
+}
+
+// The draw on the lane sweep (k_sweep_draw, DESIGN 4.7; LTI and SDE form)
+int sweep_draw_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, const double* eps_t, const double* eps_e,
+                    const double* eps_0, double* y_out, bool* served, std::string* why) {
+    *served = false;
+    if (!h->sweep) h->sweep = tgp_sweep::create();
+    const SweepDrawOps eng = {
+        "sweep draw", tgp_sweep::kernel_name(h->d, h->sde, true, true),
+        [](tgp_handle* hh, const tgp_sweep::ModelHost& m, int W, int Wd, std::string* w) {
+            tgp_sweep::force_geometry(hh->sweep, hh->sweep_fC, hh->sweep_fW, 0, hh->sweep_fWb);
+            return tgp_sweep::plan(hh->sweep, m, hh->T, W, hh->sweep_Wb, hh->num_cu, w, Wd);
+        },
+        [](tgp_handle* hh, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep::enqueue(hh->sweep, hh->stream, c, kname, err); },
+        [](tgp_handle* hh, int* status, int* w, int* wd, double* df, double* dd) { (void)tgp_sweep::finish(hh->sweep, status, w, nullptr, df, dd, wd); },
+        [](tgp_handle* hh, int* C, int64_t* nw) { tgp_sweep::geometry(hh->sweep, C, nullptr, nullptr, nw); }};
+    return sweep_draw_run(h, eng, y, missing, flags, Rnew, eps_t, eps_e, eps_0, y_out, served, why);
+}
+
+// The same at 5 <= d <= 8 on the group sweep (k_sweep_group_draw, DESIGN 4.12; LTI form): the posterior call's geometry with Wd in its backward slot.
+int sweep_group_draw_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, const double* eps_t,
+                          const double* eps_e, const double* eps_0, double* y_out, bool* served, std::string* why) {
+    *served = false;
+    if (!h->sweep_group) h->sweep_group = tgp_sweep_group::create();
+    const SweepDrawOps eng = {
+        "sweep group draw", tgp_sweep_group::draw_kernel_name(),
+        [](tgp_handle* hh, const tgp_sweep::ModelHost& m, int W, int Wd, std::string* w) {
+            tgp_sweep_group::force_geometry(hh->sweep_group, hh->sweep_fC, hh->sweep_fW, hh->sweep_fWb);
+            return tgp_sweep_group::plan(hh->sweep_group, m, hh->T, W, Wd, hh->num_cu, /*post=*/true, w, /*adjoint=*/false, /*draw=*/true);
+        },
+        [](tgp_handle* hh, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep_group::enqueue(hh->sweep_group, hh->stream, c, kname, err); },
+        [](tgp_handle* hh, int* status, int* w, int* wd, double* df, double* dd) { (void)tgp_sweep_group::finish(hh->sweep_group, status, w, wd, df, dd); },
+        [](tgp_handle* hh, int* C, int64_t* nw) { tgp_sweep_group::geometry(hh->sweep_group, C, nullptr, nullptr, nw); }};
+    return sweep_draw_run(h, eng, y, missing, flags, Rnew, eps_t, eps_e, eps_0, y_out, served, why);
 }
 
 // What sweep_adjoint_run needs of an engine: the lane sweep's adjoint kernels and the group sweep's behind one call sequence (SweepEngineOps' twin; Wa: the

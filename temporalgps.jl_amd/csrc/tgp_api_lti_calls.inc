@@ -451,6 +451,7 @@ int tgp_posterior_rand_missing(tgp_handle* h, const double* y, const uint8_t* mi
         if (served) return TGP_OK;
         return h->fail(TGP_EUNSUPPORTED, "tgp_posterior_rand_missing: the sweep engine declines the draw: " + why + " (take tgp_posterior + tgp_rand)");
     }
+    // (5 <= d <= 8 on the group sweep: tgp_posterior_rand_group, an entry point of its own -- this one declines there with no attempt made)
     if (!h->is_dense || h->ordering != 0 || h->d > 64 || h->p > 16 || !h->dense_fused || !h->dense_chunked)
         return h->fail(TGP_EUNSUPPORTED, "tgp_posterior_rand_missing: Forward models with scalar observations, d <= 4 and T >= 2048 on the sweep engine, or with "
                                          "16 < d <= 64 and p <= 16 on the dense engine's passes across the chip (else take tgp_posterior_rand, or "
@@ -472,6 +473,24 @@ int tgp_posterior_rand_missing(tgp_handle* h, const double* y, const uint8_t* mi
     tm.kernels_done();
     TRY(copy_back(h, y_out, dy, nT, odev));
     return dense_finish(h, tm, nullptr);
+}
+
+// The same draw at state dimensions 5 .. 8 by the group sweep's draw kernel (k_sweep_group_draw, DESIGN 4.12): what sweep_group_eligible accepts, whatever
+// the default routing of the engine's other calls (an explicit call; TGP_OPT_SWEEP >= 1).  tgp_posterior_rand_missing's arguments and flags.
+int tgp_posterior_rand_group(tgp_handle* h, const double* y, const uint8_t* missing, const double* Rnew, const double* eps_t, const double* eps_e,
+                             const double* eps_0, uint32_t flags, double* y_out) {
+    StreamGuard stream_guard_(h);
+    TRY(check_ready(h, /*general=*/false));
+    if (!y || !Rnew || !eps_t || !eps_e || !eps_0 || !y_out) return h->fail(TGP_EINVAL, "tgp_posterior_rand_group: null argument");
+    if (!sweep_group_eligible(h, flags, /*post=*/true, /*explicit_call=*/true))
+        return h->fail(TGP_EUNSUPPORTED, "tgp_posterior_rand_group: Forward models with shared A, a, Q, H (not SDE-described), scalar observations, 5 <= d <= 8 "
+                                         "and T >= 2048 on the group sweep (TGP_OPT_SWEEP >= 1, the engine not declined for the bound model); use "
+                                         "tgp_posterior_rand_missing at d <= 4 and tgp_posterior + tgp_rand otherwise");
+    bool served = false;
+    std::string why;
+    TRY(sweep_group_draw_call(h, y, missing, flags, Rnew, eps_t, eps_e, eps_0, y_out, &served, &why));
+    if (served) return TGP_OK;
+    return h->fail(TGP_EUNSUPPORTED, "tgp_posterior_rand_group: the group sweep declines the draw: " + why + " (take tgp_posterior + tgp_rand)");
 }
 
 // logpdf and its gradient with respect to the shared blocks, and to the noise variance and the emission offset of every step, where the gains vary in time

@@ -52,10 +52,10 @@ struct Call {
     int rnew_per_step = 0;
     double* mean = nullptr;               // device; null: logpdf only
     double* var = nullptr;
-    // a posterior draw instead (y_out set; mean / var null): k_sweep_draw
+    // a posterior draw instead (y_out set; mean / var null): k_sweep_draw, k_sweep_group_draw (5 <= d <= 8)
     const double* eps_t = nullptr;        // device [T][d]: row t drives the reverse-time transition out of step t (row 0 unused)
     const double* eps_e = nullptr;        // device [T]
-    double eps_0[4] = {0.0, 0.0, 0.0, 0.0};      // the start x_(T-1): travels in the kernel arguments
+    double eps_0[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};      // the start x_(T-1), d entries: travels in the kernel arguments
     double* y_out = nullptr;              // device [T]
     // the adjoint gradient instead (mean / var / y_out null): k_sweep_adjoint (LTI form), k_sweep_adjoint_sde (SDE form)
     bool adjoint = false;

@@ -179,18 +179,13 @@ template <int D, int XS, bool KEEP_A> struct Lane {
         update(x, y, Rt, ht, obs, acc, ok);
     }
 
-    // One step of the reverse-time recursion (lgssm.jl:231-238 + :111-115; tgp_sweep_body.hpp smooth_step in the column layout): xf = filtering
-    // state of step t, xs = smoothing state of step t + 1 on entry, of step t on return.  G = Pf A' (Pp + 1e-10 I)^-1 by the 8-lane Cholesky of
-    // tgp_group_smooth.hpp; gain form  ms = mf + G (ms+ - mp),  Ps = Pf + G (Ps+ - Pp - 1e-10 I) G'.
-    __device__ __forceinline__ void smooth_step(const GState<D>& xf, GState<D>& xs, bool& ok) const {
-        GState<D> xp = xf;
-        double AP[D];
-        predict(xp, AP);
-        // ---- upper Cholesky factor of Pp + jitter I, one row per step: lane i finishes U[i][i] and hands its column above the diagonal to everybody
-        double Uc[D], rinv[D];
+    // Upper Cholesky factor of M + jit I by the 8-lane scheme of tgp_group_smooth.hpp (Mc: column j of the symmetric M), one row per step: lane i finishes
+    // U[i][i] and hands its column above the diagonal to everybody.  Uc: column j of U (zero below the diagonal and in a padding lane), rinv: the
+    // reciprocal pivots (the same in every lane).
+    __device__ __forceinline__ void chol_cols(const double* Mc, double jit, double* Uc, double* rinv, bool& ok) const {
         TGP_GU for (int i = 0; i < D; ++i) Uc[i] = 0.0;
         TGP_GU for (int i = 0; i < D; ++i) {
-            double acc = xp.P[i] + ((i == j) ? kJitter : 0.0);
+            double acc = Mc[i] + ((i == j) ? jit : 0.0);
             wave_sync();
             if (j == i) {
                 double dg = acc;
@@ -209,9 +204,13 @@ template <int D, int XS, bool KEEP_A> struct Lane {
             TGP_GU for (int k = 0; k < i; ++k) acc = fma(-tile[V0 + k], Uc[k], acc);
             Uc[i] = (j == i) ? di : ((j > i && act) ? acc * rinv[i] : 0.0);
         }
-        // ---- column j of G' = (Pp + jitter I)^-1 (A Pf):  U' z = AP[:, j],  U w = z   (U published: tile[i + 8 k] = U[i][k])
+    }
+    // The gain of the reverse-time recursion, shared by smooth_step and draw_step: U = the upper factor of Pp + 1e-10 I, left PUBLISHED in the tile
+    // (tile[i + 8 k] = U[i][k]), and Xc = column j of G' = (Pp + jitter I)^-1 (A Pf):  U' z = AP[:, j],  U w = z  (zero in a padding lane).
+    __device__ __forceinline__ void gain_cols(const double* Ppc, const double* AP, double* Xc, bool& ok) const {
+        double Uc[D], rinv[D];
+        chol_cols(Ppc, kJitter, Uc, rinv, ok);
         publish(Uc);
-        double Xc[D];
         TGP_GU for (int i = 0; i < D; ++i) {
             double acc = AP[i];
             TGP_GU for (int k = 0; k < i; ++k) acc = fma(-tile[k + G * i], Xc[k], acc);
@@ -223,6 +222,17 @@ template <int D, int XS, bool KEEP_A> struct Lane {
             Xc[i] = acc * rinv[i];
         }
         if (!act) { TGP_GU for (int i = 0; i < D; ++i) Xc[i] = 0.0; }
+    }
+
+    // One step of the reverse-time recursion (lgssm.jl:231-238 + :111-115; tgp_sweep_body.hpp smooth_step in the column layout): xf = filtering
+    // state of step t, xs = smoothing state of step t + 1 on entry, of step t on return.  G = Pf A' (Pp + 1e-10 I)^-1 by the 8-lane Cholesky of
+    // tgp_group_smooth.hpp (gain_cols); gain form  ms = mf + G (ms+ - mp),  Ps = Pf + G (Ps+ - Pp - 1e-10 I) G'.
+    __device__ __forceinline__ void smooth_step(const GState<D>& xf, GState<D>& xs, bool& ok) const {
+        GState<D> xp = xf;
+        double AP[D];
+        predict(xp, AP);
+        double Xc[D];
+        gain_cols(xp.P, AP, Xc, ok);
         // ---- the mean: (G dm)_j = sum_k G'[k][j] dm_k
         double dm[D];
         gather(xs.m - xp.m, dm, V0);
@@ -251,6 +261,59 @@ template <int D, int XS, bool KEEP_A> struct Lane {
         TGP_GU for (int i = 0; i < D; ++i) pj = fma(xs.P[i], H[i], pj);
         mean = group_sum(Hj * xs.m) + ht;
         var = group_sum(Hj * pj);
+    }
+
+    // ---- a draw from the posterior (k_sweep_group_draw): tgp_sweep_body.hpp draw_start / draw_step_r in the column layout.  The sample
+    // state is ONE double per lane: lane j holds x_j (zero in a padding lane).  e[k] = draw k of the step, gathered (the same in every lane).
+    // (U' e)_j = sum_(k <= j) U[k][j] e_k: column j of the factor against the gathered draws, lane-local (Uc is zero below the diagonal)
+    __device__ __forceinline__ double mul_Ut(const double* Uc, const double* e) const {
+        double acc = 0.0;
+        TGP_GU for (int k = 0; k < D; ++k) acc = fma(Uc[k], e[k], acc);
+        return acc;
+    }
+    // x_(T-1) = mf + chol(Pf + 1e-12 I).U' eps_0
+    __device__ __forceinline__ double draw_start(const GState<D>& xf, const double* e0, bool& ok) const {
+        double Uc[D], rinv[D];
+        chol_cols(xf.P, tgp_sweep::kJitterStart, Uc, rinv, ok);
+        return xf.m + mul_Ut(Uc, e0);
+    }
+    // One step of the walk: xf = filtering state of step t, e = eps_t[t + 1]; x = x_(t+1) on entry, x_t on return:
+    // x_t = mf + G (x_(t+1) - mp) + chol(L + 1e-9 I).U' e,  L = Pf - (U G')'(U G') in the reference's form (lgc.jl:84-87).  The step does not look at the
+    // observation: a missing step needs no branch.
+    __device__ __forceinline__ void draw_step(const GState<D>& xf, double& x, const double* e, bool& ok) const {
+        GState<D> xp = xf;
+        double AP[D];
+        predict(xp, AP);      // (the filter's own predict, to the bit: both sides of the hand-over check see the same filtering states)
+        double Xc[D];
+        gain_cols(xp.P, AP, Xc, ok);
+        // ---- column j of Z = U G' from the published U (U[i][k] = tile[i + 8 k], k >= i)
+        double Z[D];
+        TGP_GU for (int i = 0; i < D; ++i) {
+            double acc = 0.0;
+            TGP_GU for (int k = i; k < D; ++k) acc = fma(tile[i + G * k], Xc[k], acc);
+            Z[i] = acc;
+        }
+        // ---- column j of L = Pf - Z' Z: ONE publication of Z (Z[k][i] = tile[k + 8 i])
+        publish(Z);
+        double Lc[D];
+        TGP_GU for (int i = 0; i < D; ++i) {
+            double acc = xf.P[i];
+            TGP_GU for (int k = 0; k < D; ++k) acc = fma(-tile[k + G * i], Z[k], acc);
+            Lc[i] = acc;
+        }
+        double UL[D], rinvL[D];
+        chol_cols(Lc, tgp_sweep::kJitterDraw, UL, rinvL, ok);
+        // ---- the mean: x_j = mf_j + nz_j + sum_k G'[k][j] (x+ - mp)_k
+        double dm[D];
+        gather(x - xp.m, dm, V0);
+        double acc = xf.m + mul_Ut(UL, e);
+        TGP_GU for (int k = 0; k < D; ++k) acc = fma(Xc[k], dm[k], acc);
+        x = act ? acc : 0.0;
+    }
+    // how far apart two sample states are: the mean part of `distance`, this lane's element, then the group's maximum
+    __device__ __forceinline__ double draw_distance(const GroupModelC& mc, double a, double b) const {
+        const double worst = act ? ::fabs(a - b) / (mc.sd[j] + ::fabs(a) + ::fabs(b)) : 0.0;
+        return group_max(worst);
     }
 
     // packed state records (checkpoints in HBM, a block's filtering states in LDS): [m d | upper triangle, column by column]
@@ -821,6 +884,206 @@ __global__ __launch_bounds__(64) void k_sweep_group_adjoint(const GAArgs by_valu
     }
 }
 
+// ---- a draw from the posterior: k_sweep_draw's walk (tgp_sweep.hip) in k_sweep_group<POST>'s geometry -----------------------
+struct GDArgs {
+    GArgs ka;               // (ka.Wb holds the draw's warm-up Wd; mean / var unused)
+    const double* eps_t;    // [T][d]: row t drives the reverse-time transition out of step t (row 0 unused)
+    const double* eps_e;    // [T]
+    double eps_0[G];        // the start x_(T-1)
+    double* y_out;          // [T]
+};
+static_assert(sizeof(GDArgs) <= 4096, "the kernel's argument segment");
+
+// the draws of the transition out of step t, one per lane of the group (lane k < d holds eps_t[t][k])
+template <int D> __device__ __forceinline__ double load_eps(const GDArgs& ar, long long t, int j) {
+    return j < D ? ar.eps_t[(size_t)tgp_sweep::clamp_t(t, ar.ka.T) * D + j] : 0.0;
+}
+
+// One run of the walk by a group over the rows nrows - 1 .. 0 of its chunk (first step t0; backward_run's frame): the steps below hi are walked.
+// start 0: x holds the sample of step hi (the next group's first step); 1: the run starts at step hi - 1 from that step's filtering mean (a warm-up);
+// 2: from the true x_(T-1) = mf + chol(Pf + 1e-12 I).U' eps_0 (step hi - 1 is the series' last).  On return x is the sample of step t0.
+// EMIT: y*_t = H x_t + h_t + sqrt(Rnew_t) eps_e[t] of the steps is written, a 64-byte row per group.  The draws of a step are asked for one step ahead
+// (a row of lanes, handed out by shuffle); the filtering states of a block are recomputed from its checkpoint into LDS (sF: [step][NS] of this group).
+template <int D, int XS, int B, bool EMIT>
+__device__ __forceinline__ void draw_run(const GDArgs& ar, const Lane<D, XS, false>& ln, long long t0, int nrows, long long hi, int start, double& x,
+                                         const double* ck, size_t ck_ld, double* sF, bool& ok) {
+    constexpr int NS = Lane<D, XS, false>::NS;
+    const GArgs& ka = ar.ka;
+    Row<XS> in, nx;
+    load_row<XS>(ka, t0 + 8ll * (nrows - 1), ln.j, in);
+    double en = load_eps<D>(ar, hi, ln.j);      // what step hi - 1 consumes (unused where the run starts there)
+    for (int r = nrows - 1; r >= 0; --r) {
+        const long long tb = t0 + 8ll * r;
+        load_row<XS>(ka, tb - 8, ln.j, nx);      // the next row (row r - 1): in flight through this one
+        double oy = 0.0, rn = 0.0, ee = 0.0;
+        if (EMIT) {
+            const long long tc = tgp_sweep::clamp_t(tb + ln.j, ka.T);
+            rn = ka.st.Rnew[ka.st.rnew_per_step ? tc : 0];
+            ee = ar.eps_e[tc];
+        }
+#pragma nounroll
+        for (int s = 8 / B - 1; s >= 0; --s) {
+            const long long tsb = tb + s * B;
+            if (tsb < hi) {
+                // ---- the block's filtering states, forwards from its checkpoint
+                GState<D> xw;
+                ln.load_packed(ck + (size_t)((tsb - t0) / B) * ck_ld, xw);
+                wave_sync();
+#pragma nounroll
+                for (int k = 0; k < B; ++k) {
+                    ln.fstep(xw, in, s * B + k, tsb + k, ka.T, (LmlAcc*)nullptr, ok);
+                    ln.store_packed(sF + k * NS, xw);
+                }
+                wave_sync();
+                // ---- backwards through the block
+#pragma nounroll
+                for (int k = B - 1; k >= 0; --k) {
+                    const long long t = tsb + k;
+                    if (t < hi) {
+                        GState<D> xf;
+                        ln.load_packed(sF + k * NS, xf);
+                        const double ec = en;
+                        en = load_eps<D>(ar, t, ln.j);      // step t - 1's draws: in flight through this step
+                        double e[D];
+                        if (start != 0 && t == hi - 1) {
+                            if (start == 2) {
+                                TGP_GU for (int i = 0; i < D; ++i) e[i] = ar.eps_0[i];
+                                x = ln.draw_start(xf, e, ok);
+                            } else {
+                                x = xf.m;
+                            }
+                        } else {
+                            TGP_GU for (int i = 0; i < D; ++i) e[i] = __shfl(ec, i, G);
+                            ln.draw_step(xf, x, e, ok);
+                        }
+                        if (EMIT) {
+                            const double hx = group_sum(ln.Hj * x) + ((XS & 2) ? __shfl(in.hh, s * B + k, G) : ln.hh);
+                            oy = (ln.j == s * B + k) ? hx : oy;
+                        }
+                    }
+                }
+            }
+        }
+        if (EMIT && tb + ln.j < hi) ar.y_out[tb + ln.j] = fma(::sqrt(rn), ee, oy);
+        in = nx;
+    }
+}
+
+// part[wave]: [0, bits, dist_f, dist_d].  The register counts are in profiles/sweep_group_draw_resources.txt.
+template <int D, int XS>
+__global__ __launch_bounds__(64) void k_sweep_group_draw(const GDArgs by_value) {
+    (void)by_value;
+    const GDArgs& ar = *(const GDArgs*)__builtin_amdgcn_kernarg_segment_ptr();      // (read in place: tgp_sweep.hip k_sweep)
+    const GArgs& ka = ar.ka;
+    constexpr int B = tgp_sweep::group_block(D), NS = Lane<D, XS, false>::NS, NG = tgp_sweep::kGroupsPerWave;
+    __shared__ __attribute__((aligned(16))) double sA[G * G];
+    __shared__ double tiles[NG * kTileLD];
+    __shared__ double sF[NG * B * NS];
+    const int lane = threadIdx.x, g = lane / G;
+    const long long wave = blockIdx.x;
+    sA[lane] = ka.mc.A[lane];
+    __syncthreads();
+
+    Lane<D, XS, false> ln;
+    ln.j = lane % G;
+    ln.act = ln.j < D;
+    ln.tile = tiles + g * kTileLD;
+    ln.sA = sA;
+    const int j = ln.j;
+    TGP_GU for (int i = 0; i < D; ++i) {
+        ln.Qc[i] = ln.act ? ka.mc.Q[i + G * j] : 0.0;
+        ln.H[i] = ka.mc.H[i];
+    }
+    ln.Hj = ln.act ? ka.mc.H[j] : 0.0;
+    ln.aj = ln.act ? ka.mc.a[j] : 0.0;
+    ln.hh = ka.mc.hh;
+    ln.R = ka.mc.R;
+
+    const long long T = ka.T;
+    const int C = ka.C;
+    const tgp_sweep::GroupSpan span = tgp_sweep::group_span(wave, g, ka.owned, ka.nchunks, C, T);
+    const long long t0 = span.t0, t1 = span.t1;
+    const long long t1r = (t1 + 7) & ~7ll;
+    const bool runs = span.runs;          // group 0 only warms up for group 1
+    const bool owned = span.owned;        // group 7 only warms up backwards for group 6
+    bool ok = true;
+
+    GState<D> gen, x0;
+    gen.m = ln.act ? ka.mc.gm[j] : 0.0;
+    x0.m = ln.act ? ka.mc.x0m[j] : 0.0;
+    TGP_GU for (int i = 0; i < D; ++i) {
+        gen.P[i] = ln.act ? ka.mc.gP[i + G * j] : 0.0;
+        x0.P[i] = ln.act ? ka.mc.x0P[i + G * j] : 0.0;
+    }
+    const size_t ck_ld = (size_t)NG * NS;
+    double* ck = ka.ckpt + (size_t)wave * (size_t)(C / B) * ck_ld + (size_t)g * NS;
+    double* sFg = sF + g * B * NS;
+
+    // ---- forwards: k_sweep_group<POST>'s two passes (warm-up, hand-over, the chunk with its checkpoints); no log marginal likelihood
+    GState<D> x, e1;
+    {
+        LmlAcc acc;
+        const long long tw = t1r - ka.W;
+        x = tw <= 0 ? x0 : gen;
+        forward_run<D, XS, B, false>(ka, ln, tw, ka.W / 8, tw > 0 ? tw : 0, t1r, x, acc, false, (double*)nullptr, 0, 0, ok);
+        e1 = x;
+        x.m = __shfl_up(e1.m, G, 64);
+        TGP_GU for (int i = 0; i < D; ++i) x.P[i] = __shfl_up(e1.P[i], G, 64);
+        if (t0 == 0) x = x0;
+        forward_run<D, XS, B, false>(ka, ln, t0, C / 8, t0, runs ? t1r : t0, x, acc, false, ck, t0, ck_ld, ok);
+    }
+    double dist_f = 0.0, dist_d = 0.0;
+    bool finite = true;
+    {
+        const double df = ln.distance(ka.mc, x, e1);
+        const bool fin = ln.finite(x) && ln.finite(e1);
+        if (owned) {
+            dist_f = df;
+            finite = fin;
+        }
+    }
+
+    // ---- backwards, the warm-up: the sample of the chunk's first step as the walk over its first Wd steps gives it from the filtering mean behind them,
+    // with the real draws (exact where they reach the series' last step: the true x_(T-1)) -- what the PREVIOUS group continues from
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // (the checkpoints are read back by other lanes of the group)
+    double b1 = 0.0;
+    {
+        const long long te = (t0 + ka.Wb < t1) ? t0 + ka.Wb : t1;
+        draw_run<D, XS, B, false>(ar, ln, t0, ka.Wb / 8, runs ? te : t0, te == T ? 2 : 1, b1, ck, ck_ld, sFg, ok);
+    }
+    // ---- backwards, the chunk: from the next group's sample of ITS first step; y* of every step
+    double xs = __shfl_down(b1, G, 64);
+    draw_run<D, XS, B, true>(ar, ln, t0, C / 8, owned ? t1 : t0, t1 == T ? 2 : 0, xs, ck, ck_ld, sFg, ok);
+    {
+        const double dd = ln.draw_distance(ka.mc, xs, b1);
+        const bool fin = group_sum(::fabs(xs) + ::fabs(b1)) < 1e300;
+        if (owned) {
+            dist_d = dd;
+            finite = finite && fin;
+        }
+    }
+
+    unsigned bits = 0;
+    if (owned && !(dist_f <= ka.mc.tol)) bits |= 1u;
+    if (owned && !(dist_d <= ka.mc.tol_b)) bits |= 2u;
+    if (!ok) bits |= 4u;
+    if (!finite) bits |= 8u;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        bits |= (unsigned)__shfl_xor((int)bits, off, 64);
+        const double of = __shfl_xor(dist_f, off, 64), ob = __shfl_xor(dist_d, off, 64);
+        dist_f = (of > dist_f) ? of : dist_f;
+        dist_d = (ob > dist_d) ? ob : dist_d;
+    }
+    if (lane == 0) {
+        double* p = ka.part + (size_t)wave * 4;
+        p[0] = 0.0;
+        p[1] = (double)bits;
+        p[2] = dist_f;
+        p[3] = dist_d;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------------ host side
 struct Engine {
     tgp_sweep::GroupPlan p;
@@ -850,11 +1113,12 @@ void geometry(const Engine* e, int* C, int* W, int* Wb, int64_t* nwaves) {
     if (Wb) *Wb = e->p.Wb;
     if (nwaves) *nwaves = e->p.nwaves;
 }
-bool plan(Engine* e, const tgp_sweep::ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why, bool adjoint) {
-    return tgp_sweep::plan_group(&e->p, e->forced, m, T, w_hint, wb_hint, num_cu, post || adjoint, why, adjoint);
+bool plan(Engine* e, const tgp_sweep::ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why, bool adjoint, bool draw) {
+    return tgp_sweep::plan_group(&e->p, e->forced, m, T, w_hint, wb_hint, num_cu, post || adjoint || draw, why, adjoint, draw);
 }
 const char* kernel_name(bool post) { return post ? "k_sweep_group<lti,posterior>" : "k_sweep_group<lti,logpdf>"; }
 const char* adjoint_kernel_name() { return "k_sweep_group_adjoint<lti>"; }
+const char* draw_kernel_name() { return "k_sweep_group_draw<lti>"; }
 
 namespace {
 
@@ -882,6 +1146,17 @@ template <int D> void launch_adjoint_d(const Engine* e, hipStream_t stream, cons
     }
 }
 
+template <int D> void launch_draw_d(const Engine* e, hipStream_t stream, const GDArgs& ar) {
+    const dim3 grid((unsigned)e->p.nwaves), block(64);
+    const int xs = (ar.ka.st.R != nullptr ? 1 : 0) | (ar.ka.st.hh != nullptr ? 2 : 0);
+    switch (xs) {
+        case 0: hipLaunchKernelGGL((k_sweep_group_draw<D, 0>), grid, block, 0, stream, ar); break;
+        case 1: hipLaunchKernelGGL((k_sweep_group_draw<D, 1>), grid, block, 0, stream, ar); break;
+        case 2: hipLaunchKernelGGL((k_sweep_group_draw<D, 2>), grid, block, 0, stream, ar); break;
+        default: hipLaunchKernelGGL((k_sweep_group_draw<D, 3>), grid, block, 0, stream, ar); break;
+    }
+}
+
 }  // namespace
 
 int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char** kname, std::string* err) {
@@ -895,7 +1170,12 @@ int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char*
         if (err) *err = "k_sweep_group_adjoint: the call does not match its plan (no other output in an adjoint call)";
         return 1;
     }
-    if ((post || c.adjoint) != p.post || c.T != p.T || (post && (c.var == nullptr || c.Rnew == nullptr))) {
+    const bool draw = c.y_out != nullptr;
+    if (draw ? (post || c.adjoint || !p.draw || c.eps_t == nullptr || c.eps_e == nullptr || c.Rnew == nullptr) : p.draw) {
+        if (err) *err = "k_sweep_group_draw: the call does not match its plan (no other output in a draw call)";
+        return 1;
+    }
+    if ((post || c.adjoint || draw) != p.post || c.T != p.T || (post && (c.var == nullptr || c.Rnew == nullptr))) {
         if (err) *err = "k_sweep_group: the call does not match its plan";
         return 1;
     }
@@ -955,6 +1235,24 @@ int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char*
         }
         hipError_t rc = hipGetLastError();
         if (rc != hipSuccess) return fail("k_sweep_group_adjoint launch", rc);
+        return 0;
+    }
+    if (draw) {
+        GDArgs ar;
+        ar.ka = ka;      // (ka.Wb: the plan's backward slot carries the draw's warm-up)
+        ar.eps_t = c.eps_t;
+        ar.eps_e = c.eps_e;
+        for (int k = 0; k < G; ++k) ar.eps_0[k] = k < p.d ? c.eps_0[k] : 0.0;
+        ar.y_out = c.y_out;
+        if (kname) *kname = draw_kernel_name();
+        switch (p.d) {
+            case 5: launch_draw_d<5>(e, stream, ar); break;
+            case 6: launch_draw_d<6>(e, stream, ar); break;
+            case 7: launch_draw_d<7>(e, stream, ar); break;
+            default: launch_draw_d<8>(e, stream, ar); break;
+        }
+        hipError_t rc = hipGetLastError();
+        if (rc != hipSuccess) return fail("k_sweep_group_draw launch", rc);
         return 0;
     }
     if (kname) *kname = kernel_name(post);

@@ -16,6 +16,10 @@
 // adjoint of the recursion (tgp_sweep.hpp) in the column layout: lane j holds l_j and column j of L; a group continues from the next group's
 // adjoint in front of ITS first step, which that group gets from a walk over its own first Wa steps from zero; the hand-over is checked on the adjoints.
 // A lane sums column j of the block gradients over its group's steps, the wave adds its six owned groups, the host the waves.
+//
+// A draw from the posterior (k_sweep_group_draw) is the same geometry and forward half and, backwards, the reverse-time model's sample path
+// (tgp_sweep.hpp) instead of its moments: the sample state is one double per lane; a group continues from the next group's sample of ITS first
+// step, which that group gets from a walk over its own first Wd steps from the filtering mean with the real draws; the hand-over is checked on the samples.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,14 +38,18 @@ void destroy(Engine* e);
 // posterior marginals.
 // adjoint: the call asks for the gradient (k_sweep_group_adjoint) -- the posterior call's geometry with the adjoint's warm-up Wa in the backward
 // slot: wb_hint is a Wa that a previous call needed (0: the forward warm-up's value), and a forced Wb forces Wa.
-bool plan(Engine* e, const tgp_sweep::ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why, bool adjoint = false);
+// draw: the call asks for a draw from the posterior (k_sweep_group_draw) -- the same with the draw's warm-up Wd in the backward slot: wb_hint
+// is a Wd that a previous call needed (0: the backward warm-up's estimate).
+bool plan(Engine* e, const tgp_sweep::ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why, bool adjoint = false,
+          bool draw = false);
 // c: the lane sweep's call record; y, mask, R, hh, Rnew, mean, var are read (mean == null: logpdf only); c.adjoint: the gradient instead (gh_steps,
-// gR_steps: device [T] or null), on an adjoint plan
+// gR_steps: device [T] or null), on an adjoint plan; c.y_out set: a draw instead (Rnew, eps_t, eps_e, eps_0), on a draw plan
 int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char** kernel_name, std::string* err);
 const char* kernel_name(bool post);
 const char* adjoint_kernel_name();
+const char* draw_kernel_name();
 // After the stream has been synchronised: tgp_sweep::finish's status bits, warm-ups and distances.  An adjoint call: bit 2, *wb and *dist_b are the
-// adjoint warm-up's.
+// adjoint warm-up's; a draw call: the draw warm-up's, and the returned value is 0.
 double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* dist_b);
 // Behind finish of an adjoint call whose status is clean: the waves' sums, added in wave order (gQ and gx0P symmetric).
 void adjoint_blocks(const Engine* e, const tgp_sweep::AdjointOut& out);

@@ -370,6 +370,9 @@ constexpr int group_adjoint_sums(int d) { return d * d + d + d * (d + 1) / 2 + d
 // waves resident per CU in an adjoint call, from the kernel's register counts as group_waves_per_cu's (profiles/sweep_group_adjoint_resources.txt):
 // 8 where it takes at most 256 registers (d = 5, 6: 220 .. 254), else 4 (d = 7, 8: 262 .. 290)
 constexpr int group_adjoint_waves_per_cu(int d) { return d <= 6 ? 8 : 4; }
+// waves resident per CU in a draw call (k_sweep_group_draw), from the kernel's register counts in the same way
+// (profiles/sweep_group_draw_resources.txt): 8 at d = 5 (237 .. 244 registers), else 4 (d = 6, 7, 8: 277 .. 412)
+constexpr int group_draw_waves_per_cu(int d) { return d <= 5 ? 8 : 4; }
 
 // The steps [t0, t1) of group g (0 .. 7) of a wave, as the kernel and the tests compute them: the wave's groups hold the chunks
 // wave * owned - 1 .. wave * owned + 6.  runs: the group runs its chunk (group 0 only warms up); owned: it writes output and sums.
@@ -406,12 +409,13 @@ struct GroupPlan {
     int64_t T = 0, nchunks = 0, nwaves = 0;
     GroupModelC mc;
     bool adjoint = false;      // an adjoint call: post's geometry, Wb holds the adjoint's warm-up Wa
+    bool draw = false;         // a draw call: post's geometry, Wb holds the draw's warm-up Wd
 };
 
 namespace plan_detail {
 
 template <int D> inline bool plan_group_d(GroupPlan* e, const Forced& f, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post,
-                                          std::string* why, bool adjoint = false) {
+                                          std::string* why, bool adjoint = false, bool draw = false) {
     double Aty[D * D], Qty[D * D], gm[D], Ps[D * D];
     if (!stationary_prior<D>(m, Aty, Qty, gm, Ps)) {
         if (why) *why = "the transition has no stationary covariance";
@@ -422,11 +426,12 @@ template <int D> inline bool plan_group_d(GroupPlan* e, const Forced& f, const M
     // the adjoint's warm-up: the forward warm-up's value is the first guess (plan_d: the adjoint forgets at the filter's rate); a call that found it
     // short passes a longer one
     if (adjoint && wb_hint <= 0) Wb = W;
+    // (the draw's warm-up: the backward warm-up's estimate is the first guess, as plan_d's -- the walk forgets through the same gains)
     auto up = [](int v, int q) { return (v + q - 1) / q * q; };
     // chunk length: group_waves_per_cu waves per CU, every wave `owned` chunks of its own; a chunk holds the backward warm-up.  A multiple of 8 (the rows
     // of the observation stream), hence of the checkpoint block.
     const int owned = group_owned(post);
-    const int64_t slots = (int64_t)std::max(num_cu, 1) * (adjoint ? group_adjoint_waves_per_cu(D) : group_waves_per_cu(D, post)) * owned;
+    const int64_t slots = (int64_t)std::max(num_cu, 1) * (adjoint ? group_adjoint_waves_per_cu(D) : draw ? group_draw_waves_per_cu(D) : group_waves_per_cu(D, post)) * owned;
     int64_t C = up((int)std::min<int64_t>((T + slots - 1) / slots, 1 << 20), 8);
     C = std::max<int64_t>(C, 64);
     C = std::max<int64_t>(C, Wb);
@@ -449,6 +454,7 @@ template <int D> inline bool plan_group_d(GroupPlan* e, const Forced& f, const M
     e->owned = owned;
     e->post = post;
     e->adjoint = adjoint;
+    e->draw = draw;
     e->T = T;
     e->C = (int)C;
     e->W = W;
@@ -483,9 +489,11 @@ template <int D> inline bool plan_group_d(GroupPlan* e, const Forced& f, const M
 
 // The geometry of a group-sweep call (LTI form); false: the engine declines (`why` says so).  post: a posterior call (6 of a wave's 8 groups own
 // output instead of 7).  w_hint / wb_hint as make_plan's.  adjoint (with post): an adjoint call -- the backward slot carries the adjoint's warm-up Wa
-// (wb_hint: a Wa that a previous call needed, 0: the forward warm-up's value; a forced Wb forces Wa).
+// (wb_hint: a Wa that a previous call needed, 0: the forward warm-up's value; a forced Wb forces Wa).  draw (with post): a draw call
+// (k_sweep_group_draw) -- the backward slot carries the draw's warm-up Wd (wb_hint: a Wd that a previous call needed, 0: the backward
+// warm-up's estimate; a forced Wb forces Wd; the chunk grows to hold it).
 inline bool plan_group(GroupPlan* p, const Forced& f, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why,
-                       bool adjoint = false) {
+                       bool adjoint = false, bool draw = false) {
     if (m.d < kGroupMinD || m.d > kGroupMaxD || m.sde) {
         if (why) *why = "state dimension";
         return false;
@@ -495,10 +503,10 @@ inline bool plan_group(GroupPlan* p, const Forced& f, const ModelHost& m, int64_
         return false;
     }
     switch (m.d) {
-        case 5: return plan_detail::plan_group_d<5>(p, f, m, T, w_hint, wb_hint, num_cu, post, why, adjoint);
-        case 6: return plan_detail::plan_group_d<6>(p, f, m, T, w_hint, wb_hint, num_cu, post, why, adjoint);
-        case 7: return plan_detail::plan_group_d<7>(p, f, m, T, w_hint, wb_hint, num_cu, post, why, adjoint);
-        default: return plan_detail::plan_group_d<8>(p, f, m, T, w_hint, wb_hint, num_cu, post, why, adjoint);
+        case 5: return plan_detail::plan_group_d<5>(p, f, m, T, w_hint, wb_hint, num_cu, post, why, adjoint, draw);
+        case 6: return plan_detail::plan_group_d<6>(p, f, m, T, w_hint, wb_hint, num_cu, post, why, adjoint, draw);
+        case 7: return plan_detail::plan_group_d<7>(p, f, m, T, w_hint, wb_hint, num_cu, post, why, adjoint, draw);
+        default: return plan_detail::plan_group_d<8>(p, f, m, T, w_hint, wb_hint, num_cu, post, why, adjoint, draw);
     }
 }
 

@@ -1016,13 +1016,12 @@ def _posterior_rand_one_launch(post, eps_t, eps_e, eps_0):
     return out
 
 
-def _posterior_rand_sweep(post, eps_t, eps_e, eps_0):
-    """rand of a posterior that has not been evaluated, on the sweep engine (tgp_posterior_rand_missing: Forward, scalar observations, d <= 4, T >= 2048;
-    shared blocks or closed-form SDE transitions, a mask / noise variance / emission offset per step -- one kernel, k_sweep_draw).  A NaN of a
-    host series is a missing step (the mask, with a finite value in y); a device series gets its mask from torch.isnan on the device.  None: not a
-    model of that path, or one the library declines -- the caller goes on to the evaluated route."""
+def _posterior_rand_sweep_entry(entry, post, eps_t, eps_e, eps_0):
+    """tgp_posterior_rand_missing on the sweep engine / tgp_posterior_rand_group: one argument list, one preparation of the buffers.  A NaN of a host
+    series is a missing step (the mask, with a finite value in y); a device series gets its mask from torch.isnan on the device.  None: not a posterior
+    these calls take, or buffers they cannot read (the library was not asked); raises Unsupported where the library declines."""
     prior = post._prior
-    if (post._model is not None or isinstance(prior, PosteriorLGSSM) or prior.ordering is not Forward or prior.p != 1 or prior.dim > 4
+    if (post._model is not None or isinstance(prior, PosteriorLGSSM) or prior.ordering is not Forward or prior.p != 1
             or prior._whiten is not None or isinstance(post._y, tuple)):
         return None
     y = post._y
@@ -1067,11 +1066,32 @@ def _posterior_rand_sweep(post, eps_t, eps_e, eps_0):
     hd = prior.handle()
     out = _out(prior, _osh(prior), dev)
     flags = ((_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0) | (_lib.SHARED_R if Rn.shape[0] == 1 else 0)
+    hd.check(getattr(hd.lib, entry)(hd.h, _lib.ptr(yy), _lib.ptr(mm), _lib.ptr(Rn), _lib.ptr(et), _lib.ptr(ee), _lib.ptr(e0), flags, _lib.ptr(out)))
+    return out
+
+
+def _posterior_rand_sweep(post, eps_t, eps_e, eps_0):
+    """rand of a posterior that has not been evaluated, on the sweep engine (tgp_posterior_rand_missing: Forward, scalar observations, d <= 4, T >= 2048;
+    shared blocks or closed-form SDE transitions, a mask / noise variance / emission offset per step -- one kernel, k_sweep_draw).  None: not a
+    model of that path, or one the library declines -- the caller goes on to the evaluated route."""
+    if not isinstance(post._prior, PosteriorLGSSM) and post._prior.dim > 4:
+        return None
     try:
-        hd.check(hd.lib.tgp_posterior_rand_missing(hd.h, _lib.ptr(yy), _lib.ptr(mm), _lib.ptr(Rn), _lib.ptr(et), _lib.ptr(ee), _lib.ptr(e0), flags,
-                                                   _lib.ptr(out)))
+        return _posterior_rand_sweep_entry("tgp_posterior_rand_missing", post, eps_t, eps_e, eps_0)
     except _lib.Unsupported:
         return None
+
+
+def posterior_rand_group(post, eps_t, eps_e, eps_0):
+    """rand of a posterior that has not been evaluated (posterior(model, y), optionally with its observation noise replaced) at state dimensions
+    5 <= d <= 8: ONE kernel of the group sweep (tgp_posterior_rand_group, k_sweep_group_draw) -- Forward models with shared A, a, Q, H, scalar
+    observations, T >= 2048; NaNs in y, a noise variance or an emission offset per step.  eps_t (T, d), eps_e (T,), eps_0 (d,) are used as rand on the
+    evaluated posterior uses them; host arrays, or torch tensors on the model's device together with y.  Raises Unsupported where the engine declines
+    (use rand)."""
+    out = None if not isinstance(post, PosteriorLGSSM) else _posterior_rand_sweep_entry("tgp_posterior_rand_group", post, eps_t, eps_e, eps_0)
+    if out is None:
+        raise _lib.Unsupported(_lib.EUNSUPPORTED, "posterior_rand_group: a lazy posterior of a Forward model with scalar observations, with y and the draws "
+                                                   "of matching sizes on one side (host or device)")
     return out
 
 
@@ -1136,14 +1156,27 @@ def _posterior_rand_dense(post, eps_t, eps_e, eps_0):
     return out
 
 
-def rand(rng_or_eps, model):
-    """lgssm.jl:65-69. `rng_or_eps` is a numpy Generator, or the explicit (eps_t (T,d), eps_e (T,), eps_0 (d,))."""
+def rand(rng_or_eps, model, method=None):
+    """lgssm.jl:65-69. `rng_or_eps` is a numpy Generator, or the explicit (eps_t (T,d), eps_e (T,), eps_0 (d,)).
+    method: None (default policy) or "sweep" -- a lazy posterior on the sweep engines' draw kernels alone: posterior_rand_group at 5 <= d <= 8
+    (k_sweep_group_draw), the lane sweep's k_sweep_draw at d <= 4; raises Unsupported where neither serves."""
+    if method not in (None, "sweep"):
+        raise ValueError(f"rand: unknown method {method!r}")
+    if method == "sweep" and not (isinstance(model, PosteriorLGSSM) and model._model is None):
+        raise _lib.Unsupported(_lib.EUNSUPPORTED, "rand(method='sweep'): a posterior that has not been evaluated")
     if isinstance(model, PosteriorLGSSM) and model._model is None:
         if isinstance(rng_or_eps, tuple):
             eps = rng_or_eps
         else:       # (the reference's order of draws: lgssm.jl:72-77, then x0's)
             et, ee = rng_or_eps.standard_normal((model.T, model.dim)), rng_or_eps.standard_normal((model.T,) if model.p == 1 else (model.T, model.p))
             eps = (et, ee, rng_or_eps.standard_normal(model.dim))
+        if method == "sweep":
+            if 5 <= model.dim <= 8:
+                return posterior_rand_group(model, *eps)
+            y1 = _posterior_rand_sweep(model, *eps)
+            if y1 is None:
+                raise _lib.Unsupported(_lib.EUNSUPPORTED, "rand(method='sweep'): the sweep engine does not serve this posterior (d <= 8, T >= 2048)")
+            return y1
         y1 = _posterior_rand_one_launch(model, *eps)
         if y1 is None:
             y1 = _posterior_rand_sweep(model, *eps)

@@ -473,10 +473,19 @@ def logpdf(fx, y):
     return L.logpdf(fx.build_lgssm(), y)
 
 
-def rand(rng, fx, N=None):
-    """lti_sde.jl:48-58 / posterior_lti_sde.jl:48-58."""
+def rand(rng, fx, N=None, method=None):
+    """lti_sde.jl:48-58 / posterior_lti_sde.jl:48-58.
+    method: None (default policy) or "sweep" -- ONE kernel of the sweep engines over the T training steps (L.rand(..., method="sweep"): the group sweep's
+    draw kernel at 5 <= d <= 8, the lane sweep's at d <= 4; T >= 2048) for a posterior queried at its training inputs on a RegularSpacing with NaNs in y;
+    other inputs raise NotImplementedError, and Unsupported is raised where the device declines."""
     if N is not None:
-        return np.stack([rand(rng, fx) for _ in range(N)], axis=1)
+        return np.stack([rand(rng, fx, method=method) for _ in range(N)], axis=1)
+    if method == "sweep":
+        if not isinstance(fx, FinitePosteriorLTISDE):
+            raise NotImplementedError("rand(method='sweep'): a posterior at its training inputs (RegularSpacing, NaNs in y) only")
+        return fx._rand_sweep(rng)
+    if method is not None:
+        raise ValueError(f"rand: unknown method {method!r}")
     if isinstance(fx, FinitePosteriorLTISDE):
         return fx._rand(rng)
     return L.rand(rng, fx.build_lgssm())
@@ -565,6 +574,18 @@ class FinitePosteriorLTISDE:
             S_new = _noise(self.sigma2, len(self.x)) if len(self.sigma2) > 1 else self.sigma2
             return L.rand(rng, L.replace_observation_noise_cov(L.posterior(model, d["y"]), S_new))
         return self._rand_merged(rng)
+
+    def _rand_sweep(self, rng):
+        """rand(method="sweep"): prediction inputs = training inputs on a regular grid with NaNs in y.  _rand's argument for the branch without NaNs holds
+        with them: each joined pair of steps shares one latent state, so the draw is that of the posterior over the T training steps with its observation
+        noise replaced -- a model with a missing mask, which the sweep engines' draw kernels serve in one launch.  Same distribution; the draws of one
+        rng are consumed in another order than over the 2T merged steps."""
+        d = self.f.data
+        if not (isinstance(self.x, RegularSpacing) and _same_sorted_inputs(self.x, d["x"]) and np.isnan(d["y"]).any()):
+            raise NotImplementedError("rand(method='sweep'): a posterior at its training inputs (RegularSpacing, NaNs in y) only")
+        model = self._posterior_model(d["x"], d["sigma2"], d["y"])
+        S_new = _noise(self.sigma2, len(self.x)) if len(self.sigma2) > 1 else self.sigma2
+        return L.rand(rng, L.replace_observation_noise_cov(L.posterior(model, d["y"]), S_new), method="sweep")
 
     def _rand_merged(self, rng):
         npr = len(self.x)
