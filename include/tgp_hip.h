@@ -156,7 +156,11 @@ typedef struct tgp_handle tgp_handle;
                            (k_sweep_group_draw<lti>; likewise); tgp_posterior_rand_missing stays at d <= 4.  Under 1 the group
                            sweep takes only the (d, call) pairs that beat the general engine at T = 1e6 and 1e7 (profiles/sweep_group_time.txt):
                            tgp_logpdf at d = 6, 7, 8; 2: every pair, tgp_logpdf at d = 5 and the posterior calls included (tests, A/B timing;
-                           the lane sweep is the same under 1 and 2).  Both step aside
+                           the lane sweep is the same under 1 and 2).  2 only: 5 <= d <= 8 bound by tgp_model_set_sde (irregular spacing, closed-form
+                           transitions, shared a and H), T >= 2048 -- tgp_logpdf / tgp_[logpdf_and_]posterior_marginals run on the group sweep's
+                           kernels for SDE-described models (tgp_sweep_group_sde.hip): k_sweep_group<sde,logpdf> /
+                           k_sweep_group<sde,posterior>, the transition of every step built from its gap; under 1 these models stay on the
+                           general engine, and their gradient and draw do so under every value.  Both step aside
                            on an explicit request for the general engine (TGP_REUSE_REDUCE, TGP_OPT_CHUNK, TGP_OPT_VARIANT, TGP_OPT_STEADY 0 / 1,
                            TGP_OPT_GRAPH).  0: the general chunked-scan engine as before; tgp_posterior_rand_missing, tgp_posterior_rand_group,
                            tgp_logpdf_adjoint_missing and tgp_logpdf_adjoint_group answer TGP_EUNSUPPORTED for these models. */

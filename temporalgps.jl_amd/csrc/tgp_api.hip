@@ -1917,7 +1917,7 @@ int tgp_model_set_sde(tgp_handle* h, int64_t T, int d, int ordering, uint32_t fl
     // what the sweep engine reads (tgp_sweep.hpp): the gaps as one plain array, the closed-form coefficients and the first transition on the host
     h->sde_coef_host.clear();
     h->sde_A1Q1_host.clear();
-    if (h->sde_closed && d <= tgp_sweep::kMaxD) {
+    if (h->sde_closed && d <= tgp_sweep::kGroupMaxD) {      // (d <= 4: the lane sweep; 5 .. 8: the group sweep)
         std::vector<double> coef;
         (void)sde_closed_form(d, F, x0P, nullptr, nullptr, coef);
         h->sde_coef_host = coef;
@@ -2016,7 +2016,7 @@ int tgp_logpdf(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t 
         TRY(sweep_call(h, y, missing, flags, nullptr, nullptr, nullptr, out, &served));
         if (served) return TGP_OK;
     }
-    if (sweep_group_eligible(h, flags, /*post=*/false)) {      // the same at 5 <= d <= 8 (tgp_sweep_group.hip)
+    if (sweep_group_eligible(h, flags, /*post=*/false) || sweep_group_sde_eligible(h, flags)) {      // the same at 5 <= d <= 8 (tgp_sweep_group.hip)
         bool served = false;
         TRY(sweep_group_call(h, y, missing, flags, nullptr, nullptr, nullptr, out, &served));
         if (served) return TGP_OK;
@@ -2352,7 +2352,7 @@ int tgp_posterior_marginals(tgp_handle* h, const double* y, const uint8_t* missi
         TRY(sweep_call(h, y, missing, flags, Rnew, mean_out, var_out, lml_out, &served));
         if (served) return TGP_OK;
     }
-    if (sweep_group_eligible(h, flags, /*post=*/true)) {      // the same at 5 <= d <= 8 (tgp_sweep_group.hip)
+    if (sweep_group_eligible(h, flags, /*post=*/true) || sweep_group_sde_eligible(h, flags)) {      // the same at 5 <= d <= 8 (tgp_sweep_group.hip)
         bool served = false;
         TRY(sweep_group_call(h, y, missing, flags, Rnew, mean_out, var_out, lml_out, &served));
         if (served) return TGP_OK;

@@ -171,6 +171,17 @@ bool sweep_group_eligible(const tgp_handle* h, uint32_t flags, bool post, bool e
     if (h->T < tgp_sweep::kGroupMinT || h->mv.T != h->T || h->mv.sH != 0 || h->sweepm.empty()) return false;
     return h->mv.sA == 0 && h->mv.sa == 0 && h->mv.sQ == 0;
 }
+// An SDE-described model at 5 <= d <= 8 (k_sweep_group_sde, DESIGN 4.13): sweep_eligible's SDE conditions (the closed form found and allowed, a and H
+// shared) with sweep_group_eligible's others.  tgp_logpdf and tgp_[logpdf_and_]posterior_marginals only (the gradient and the draw decline: the
+// predicate above), and under TGP_OPT_SWEEP = 2 only: no (d, call) pair is routed here by default (profiles/sweep_group_sde_time.txt has the measured medians
+// beside the general engine's: a routing change would rest on them).
+bool sweep_group_sde_eligible(const tgp_handle* h, uint32_t flags) {
+    if (h->opt_sweep < 2 || h->sweep_state < 0 || h->is_dense || h->p != 1 || h->ordering != 0 || !h->sde) return false;
+    if (h->d < tgp_sweep::kGroupMinD || h->d > tgp_sweep::kGroupMaxD) return false;
+    if ((flags & TGP_REUSE_REDUCE) || h->opt_chunk != 0 || h->variant_opt != 0 || !h->opt_steady2 || h->opt_graph != 0) return false;
+    if (h->T < tgp_sweep::kGroupMinT || h->mv.T != h->T || h->mv.sH != 0 || h->sweepm.empty()) return false;
+    return h->sde_closed && h->opt_sde_closed && !h->sde_coef_host.empty() && h->mv.sa == 0;
+}
 
 // The host model the plans of both engines read, from the staged blocks of the bound model
 tgp_sweep::ModelHost sweep_host_model(const tgp_handle* h) {
@@ -313,12 +324,12 @@ int sweep_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t 
     return sweep_run(h, eng, y, missing, flags, Rnew, mean_out, var_out, lml_out, served);
 }
 
-// The group sweep (5 <= d <= 8; LTI form)
+// The group sweep (5 <= d <= 8; LTI form, and SDE form where sweep_group_sde_eligible says so)
 int sweep_group_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, double* mean_out, double* var_out,
                      double* lml_out, bool* served) {
     if (!h->sweep_group) h->sweep_group = tgp_sweep_group::create();
     const SweepEngineOps eng = {
-        "sweep group", tgp_sweep_group::kernel_name(mean_out != nullptr), mean_out != nullptr,
+        "sweep group", tgp_sweep_group::kernel_name(mean_out != nullptr, h->sde), mean_out != nullptr,
         [](tgp_handle* hh, const tgp_sweep::ModelHost& mh, bool post, int W, int Wb, std::string* why) {
             tgp_sweep_group::force_geometry(hh->sweep_group, hh->sweep_fC, hh->sweep_fW, hh->sweep_fWb);
             return tgp_sweep_group::plan(hh->sweep_group, mh, hh->T, W, Wb, hh->num_cu, post, why);

@@ -45,7 +45,7 @@ bool plan(Engine* e, const tgp_sweep::ModelHost& m, int64_t T, int w_hint, int w
 // c: the lane sweep's call record; y, mask, R, hh, Rnew, mean, var are read (mean == null: logpdf only); c.adjoint: the gradient instead (gh_steps,
 // gR_steps: device [T] or null), on an adjoint plan; c.y_out set: a draw instead (Rnew, eps_t, eps_e, eps_0), on a draw plan
 int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char** kernel_name, std::string* err);
-const char* kernel_name(bool post);
+const char* kernel_name(bool post, bool sde = false);      // sde: the model is SDE-described (k_sweep_group_sde)
 const char* adjoint_kernel_name();
 const char* draw_kernel_name();
 // After the stream has been synchronised: tgp_sweep::finish's status bits, warm-ups and distances.  An adjoint call: bit 2, *wb and *dist_b are the

@@ -355,6 +355,7 @@ inline bool make_plan(Plan* p, const Forced& f, const ModelHost& m, int64_t T, i
 
 // ---- the group sweep (tgp_sweep_group.hip): the same algorithm at 5 <= d <= 8, a chunk spread over 8 lanes ---------------------------
 // A wave holds 8 groups = 8 consecutive chunks.  Group 0 only warms up for group 1; in a posterior call group 7 only warms up (backwards) for group 6.
+// Both forms of a model: LTI (k_sweep_group) and SDE-described on irregular inputs (k_sweep_group_sde).
 constexpr int kGroupMinD = 5, kGroupMaxD = 8;
 constexpr int kGroupLanes = 8, kGroupsPerWave = 8;
 // waves resident per CU: two per SIMD by LDS and registers, but one where the posterior kernel takes more than 256 registers (d >= 6:
@@ -373,6 +374,10 @@ constexpr int group_adjoint_waves_per_cu(int d) { return d <= 6 ? 8 : 4; }
 // waves resident per CU in a draw call (k_sweep_group_draw), from the kernel's register counts in the same way
 // (profiles/sweep_group_draw_resources.txt): 8 at d = 5 (237 .. 244 registers), else 4 (d = 6, 7, 8: 277 .. 412)
 constexpr int group_draw_waves_per_cu(int d) { return d <= 5 ? 8 : 4; }
+// waves resident per CU in a call on an SDE-described model (k_sweep_group_sde), from the kernel's register counts in the same way
+// (profiles/sweep_group_sde_resources.txt has the counts and tests/test_sweep_group_sde_resources.py holds this function to them): today every logpdf
+// kernel is within 256 registers and every posterior kernel above, whatever d
+constexpr int group_sde_waves_per_cu(int d, bool post) { return (void)d, post ? 4 : 8; }
 
 // The steps [t0, t1) of group g (0 .. 7) of a wave, as the kernel and the tests compute them: the wave's groups hold the chunks
 // wave * owned - 1 .. wave * owned + 6.  runs: the group runs its chunk (group 0 only warms up); owned: it writes output and sums.
@@ -402,7 +407,19 @@ struct GroupModelC {
     double hh, R, tol, tol_b;
 };
 
+// What an SDE-described model adds (k_sweep_group_sde): exp(F tau) = diag(e^(-lam tau)) (I + tau N1 + tau^2 N2) per block (ModelView::sde),
+// padded to 8 and row-major like GroupModelC::A.  The blocks of the closed form are contiguous and at most 3 wide (tgp_api.hip sde_closed_form), so
+// N1 and N2 are zero outside the band |i - k| <= 2, which is all the kernel multiplies (the plan checks it).  GroupModelC carries the rest: gP = Pinf,
+// (x0m, x0P) = the prior predicted through the first transition (the state in FRONT of update 0), A and Q unused.
+struct GroupSdeC {
+    double lam[8];
+    double N1[64], N2[64];      // [8 i + k]
+};
+constexpr int kGroupSdeBand = 2;
+
 struct GroupPlan {
+    bool sde = false;          // an SDE-described model: k_sweep_group_sde reads mc and sc
+    GroupSdeC sc;
     int d = 0, B = 0, owned = 0;
     bool post = false;
     int C = 0, W = 0, Wb = 0;
@@ -417,7 +434,57 @@ namespace plan_detail {
 template <int D> inline bool plan_group_d(GroupPlan* e, const Forced& f, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post,
                                           std::string* why, bool adjoint = false, bool draw = false) {
     double Aty[D * D], Qty[D * D], gm[D], Ps[D * D];
-    if (!stationary_prior<D>(m, Aty, Qty, gm, Ps)) {
+    double p0m[D], p0P[D * D];      // SDE: the prior predicted through the first transition
+    if (m.sde) {
+        // plan_d's SDE branch: the warm-up starts from (x0m, Pinf) (x0P where no Pinf is given); the first transition must be consistent with it
+        const double* Pg = m.Pinf ? m.Pinf : m.x0P;
+        for (int j = 0; j < D; ++j)
+            for (int i = 0; i < D; ++i) Ps[i + j * D] = 0.5 * (Pg[i + j * D] + Pg[j + i * D]);
+        double worst = 0.0, scale = 0.0;
+        for (int j = 0; j < D; ++j)
+            for (int i = 0; i < D; ++i) {
+                double a = 0.0;
+                for (int k = 0; k < D; ++k)
+                    for (int l = 0; l < D; ++l) a += m.A[i + k * D] * Ps[k + l * D] * m.A[j + l * D];
+                worst = std::max(worst, std::fabs(Ps[i + j * D] - a - m.Q[i + j * D]));
+                scale = std::max(scale, std::fabs(Ps[i + j * D]));
+            }
+        if (!(worst <= 1e-11 * scale)) {
+            if (why) *why = "first transition not of the form Q1 = Pinf - A1 Pinf A1'";
+            return false;
+        }
+        for (int j = 0; j < D; ++j)
+            for (int i = 0; i < D; ++i)
+                if (std::abs(i - j) > kGroupSdeBand && (m.coef[D + i + j * D] != 0.0 || m.coef[D + D * D + i + j * D] != 0.0)) {
+                    if (why) *why = "closed form wider than the band the kernel multiplies";
+                    return false;
+                }
+        for (int i = 0; i < D; ++i) gm[i] = m.x0m[i];
+        host_sde_A<D>(m.coef, m.tau_typ, Aty);
+        for (int j = 0; j < D; ++j)
+            for (int i = 0; i < D; ++i) {
+                double a = 0.0;
+                for (int k = 0; k < D; ++k)
+                    for (int l = 0; l < D; ++l) a += Aty[i + k * D] * Ps[k + l * D] * Aty[j + l * D];
+                Qty[i + j * D] = Ps[i + j * D] - a;
+            }
+        // step 0 on the host (A1 is not exp(F tau) of any tau once a term is stretched): m <- A1 x0m + a, P <- A1 Symmetric(x0P) A1' + Q1; the kernel
+        // keeps this state at t == 0 instead of predicting
+        for (int i = 0; i < D; ++i) {
+            double a = m.a[i];
+            for (int k = 0; k < D; ++k) a += m.A[i + k * D] * m.x0m[k];
+            p0m[i] = a;
+        }
+        for (int j = 0; j < D; ++j)
+            for (int i = 0; i < D; ++i) {
+                double a = 0.5 * (m.Q[i + j * D] + m.Q[j + i * D]);
+                for (int k = 0; k < D; ++k)
+                    for (int l = 0; l < D; ++l) a += m.A[i + k * D] * m.x0P[std::min(k, l) + std::max(k, l) * D] * m.A[j + l * D];
+                p0P[i + j * D] = a;
+            }
+        for (int j = 0; j < D; ++j)
+            for (int i = 0; i < j; ++i) p0P[i + j * D] = p0P[j + i * D] = 0.5 * (p0P[i + j * D] + p0P[j + i * D]);
+    } else if (!stationary_prior<D>(m, Aty, Qty, gm, Ps)) {
         if (why) *why = "the transition has no stationary covariance";
         return false;
     }
@@ -431,7 +498,8 @@ template <int D> inline bool plan_group_d(GroupPlan* e, const Forced& f, const M
     // chunk length: group_waves_per_cu waves per CU, every wave `owned` chunks of its own; a chunk holds the backward warm-up.  A multiple of 8 (the rows
     // of the observation stream), hence of the checkpoint block.
     const int owned = group_owned(post);
-    const int64_t slots = (int64_t)std::max(num_cu, 1) * (adjoint ? group_adjoint_waves_per_cu(D) : draw ? group_draw_waves_per_cu(D) : group_waves_per_cu(D, post)) * owned;
+    const int per_cu = m.sde ? group_sde_waves_per_cu(D, post) : adjoint ? group_adjoint_waves_per_cu(D) : draw ? group_draw_waves_per_cu(D) : group_waves_per_cu(D, post);
+    const int64_t slots = (int64_t)std::max(num_cu, 1) * per_cu * owned;
     int64_t C = up((int)std::min<int64_t>((T + slots - 1) / slots, 1 << 20), 8);
     C = std::max<int64_t>(C, 64);
     C = std::max<int64_t>(C, Wb);
@@ -482,20 +550,39 @@ template <int D> inline bool plan_group_d(GroupPlan* e, const Forced& f, const M
     mc.R = m.R;
     mc.tol = kTol;
     mc.tol_b = kTolBack;
+    e->sde = m.sde;
+    std::memset(&e->sc, 0, sizeof e->sc);
+    if (m.sde) {
+        std::memset(mc.A, 0, sizeof mc.A);
+        std::memset(mc.Q, 0, sizeof mc.Q);
+        for (int i = 0; i < D; ++i) {
+            mc.x0m[i] = p0m[i];
+            e->sc.lam[i] = m.coef[i];
+            for (int k = 0; k < D; ++k) {
+                mc.x0P[i + 8 * k] = p0P[i + k * D];
+                e->sc.N1[8 * i + k] = m.coef[D + i + k * D];
+                e->sc.N2[8 * i + k] = m.coef[D + D * D + i + k * D];
+            }
+        }
+    }
     return true;
 }
 
 }  // namespace plan_detail
 
-// The geometry of a group-sweep call (LTI form); false: the engine declines (`why` says so).  post: a posterior call (6 of a wave's 8 groups own
+// The geometry of a group-sweep call (LTI form, or SDE-described: m.sde); false: the engine declines (`why` says so).  post: a posterior call (6 of a wave's 8 groups own
 // output instead of 7).  w_hint / wb_hint as make_plan's.  adjoint (with post): an adjoint call -- the backward slot carries the adjoint's warm-up Wa
 // (wb_hint: a Wa that a previous call needed, 0: the forward warm-up's value; a forced Wb forces Wa).  draw (with post): a draw call
 // (k_sweep_group_draw) -- the backward slot carries the draw's warm-up Wd (wb_hint: a Wd that a previous call needed, 0: the backward
 // warm-up's estimate; a forced Wb forces Wd; the chunk grows to hold it).
 inline bool plan_group(GroupPlan* p, const Forced& f, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why,
                        bool adjoint = false, bool draw = false) {
-    if (m.d < kGroupMinD || m.d > kGroupMaxD || m.sde) {
+    if (m.d < kGroupMinD || m.d > kGroupMaxD) {
         if (why) *why = "state dimension";
+        return false;
+    }
+    if (m.sde && (adjoint || draw)) {      // (the gradient and the draw of an SDE-described model at these d: the general engine)
+        if (why) *why = "SDE-described model";
         return false;
     }
     if (T < kGroupMinT) {
