@@ -11,6 +11,15 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtgp_hip.so")
 
+# The out-of-line kernels of the scan engine (d = 8's dual-number block scans, everything at d = 9 .. 16) keep 18 .. 55 KB of private memory per lane
+# (csrc/tgp_api.hip choose_chunk).  The HSA runtime can serve such a kernel only by sizing the scratch for the waves of that one dispatch and taking it
+# back afterwards ("scratch reclaim", its default).  Under HSA_NO_SCRATCH_RECLAIM=1 it sizes every queue's arena for every wave slot of the device and
+# keeps it: 37 KB x 64 lanes x 8192 slots = 19 GB against a scratch aperture of 4 GB, so the first such dispatch aborts its queue
+# (HSA_STATUS_ERROR_OUT_OF_RESOURCES) and every later HIP call of the process fails.  The runtime reads the variable once, when it initialises, so the
+# package asks for the default here, at import -- which must therefore come before the process's first HIP call (torch.cuda's included).
+if os.environ.get("HSA_NO_SCRATCH_RECLAIM", "0") != "0":
+    os.environ["HSA_NO_SCRATCH_RECLAIM"] = "0"
+
 # flags / codes / options (mirror include/tgp_hip.h)
 SHARED_A, SHARED_a, SHARED_Q, SHARED_H, SHARED_h, SHARED_R = (1 << i for i in range(6))
 SHARED_ALL = 0x3F

@@ -5,6 +5,7 @@ import subprocess
 
 import numpy as np
 
+import temporalgps_jl_amd  # noqa: F401  (at collection, before anything asks torch for a GPU: the package states the runtime settings its kernels need, _lib.py)
 from oracle import components as oc
 from oracle import lgssm_ref as ref
 
