@@ -160,7 +160,8 @@ typedef struct tgp_handle tgp_handle;
                            transitions, shared a and H), T >= 2048 -- tgp_logpdf / tgp_[logpdf_and_]posterior_marginals run on the group sweep's
                            kernels for SDE-described models (tgp_sweep_group_sde.hip): k_sweep_group<sde,logpdf> /
                            k_sweep_group<sde,posterior>, the transition of every step built from its gap; under 1 these models stay on the
-                           general engine, and their gradient and draw do so under every value.  Both step aside
+                           general engine and their draw does so under every value; their gradient has an entry point of its own,
+                           tgp_logpdf_adjoint_group_sde (k_sweep_group_adjoint<sde>; served under 1 and 2 alike).  Both step aside
                            on an explicit request for the general engine (TGP_REUSE_REDUCE, TGP_OPT_CHUNK, TGP_OPT_VARIANT, TGP_OPT_STEADY 0 / 1,
                            TGP_OPT_GRAPH).  0: the general chunked-scan engine as before; tgp_posterior_rand_missing, tgp_posterior_rand_group,
                            tgp_logpdf_adjoint_missing and tgp_logpdf_adjoint_group answer TGP_EUNSUPPORTED for these models. */
@@ -349,6 +350,18 @@ int tgp_logpdf_adjoint_group(tgp_handle* h, const double* y, const uint8_t* miss
  * variance that is not positive, non-finite values.  The library does not fall back: use tgp_logpdf_grad_sde. */
 int tgp_logpdf_adjoint_sde(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, double* gF, double* gPinf, double* gA1,
                            double* ga, double* gH, double* ghh, double* gR, double* gx0m, double* gx0P, double* gh_steps, double* gR_steps);
+/* The same gradient of an SDE-described model at state dimensions 5 <= d <= 8 by one adjoint pass on the GROUP sweep (k_sweep_group_adjoint<sde>,
+ * DESIGN 4.14): tgp_logpdf_adjoint_group's geometry and walk with the transition of every step built from its gap as k_sweep_group<sde,*> builds it,
+ * lane j of a group contracting column j of d logpdf / d A_t into the coefficient sums.  The kernel never sees the first transition: the host pulls the
+ * adjoint in front of the first update back through A1 in O(d^3).  Arguments, outputs, TGP_IN_DEVICE / TGP_OUT_DEVICE, repair and tgp_sweep_info exactly
+ * as for tgp_logpdf_adjoint_sde; a prior replaced by tgp_model_set_x0 is served (gx0P apart from gPinf).  An explicit call: served under TGP_OPT_SWEEP = 1
+ * and 2 alike.  Two calls on the same series give the same bits.
+ * TGP_EUNSUPPORTED, with no output byte written (host or device): models in LTI form (use tgp_logpdf_adjoint_group), d < 5 (use tgp_logpdf_adjoint_sde),
+ * d > 8, p > 1, Reverse models, T < 2048, TGP_OPT_SWEEP = 0, no closed form, a closed form wider than the band |i - k| <= 2, an explicit request for the
+ * general engine (TGP_OPT_CHUNK, ...), an engine declined for the bound model, a forced geometry whose warm-ups are too short, an innovation variance
+ * that is not positive, non-finite values.  The library does not fall back: central differences of tgp_logpdf are what remains. */
+int tgp_logpdf_adjoint_group_sde(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, double* gF, double* gPinf,
+                                 double* gA1, double* ga, double* gH, double* ghh, double* gR, double* gx0m, double* gx0P, double* gh_steps, double* gR_steps);
 /* The plan of the stationary-gain engine's ONE-LAUNCH path (TGP_OPT_STEADY = 3, the default), a pure host function: what
  * tgp_logpdf / tgp_[logpdf_and_]posterior_marginals build inside every call of a Forward LTI model with one noise variance and scalar
  * observations (d <= 8) before their single kernel -- the covariance half of lgssm.jl:99-238 (predict lgc.jl:46-52, update lgc.jl:247-257,

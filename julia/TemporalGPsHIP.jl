@@ -443,8 +443,16 @@ function logpdf_and_block_gradients_missing(m::DeviceLGSSM{Forward}, y::Abstract
     return lml[], per_step ? merge(g, (h_steps = hs, R_steps = Rs)) : g
 end
 
+# tgp_logpdf_adjoint_sde (d <= 4) and tgp_logpdf_adjoint_group_sde (5 <= d <= 8, DESIGN 4.14) share one argument list; the symbol of a ccall is a literal
+for (fn, sym) in ((:_adjoint_sde_lane, :tgp_logpdf_adjoint_sde), (:_adjoint_sde_group, :tgp_logpdf_adjoint_group_sde))
+    @eval $fn(h, yv, mp, lml, gF, gPi, gA1, ga, gH, gh, gR, gm, gP, hs, Rs) = ccall(($(QuoteNode(sym)), libtgp), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{UInt8}, UInt32, Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64},
+         Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        h, yv, mp, UInt32(0), lml, gF, gPi, gA1, ga, gH, gh, gR, gm, gP, hs, Rs)
+end
+
 """The same for a model bound by its SDE and time stamps (tgp_logpdf_adjoint_sde: Forward, closed-form exp(F tau), scalar observations, d <= 4,
-T >= 2048). `F` is zero outside the connected components of the drift matrix, `Pinf` and `x0P` are separate (add them where x0P doubles as Pinf), `A1` is
+T >= 2048; tgp_logpdf_adjoint_group_sde at 5 <= d <= 8, picked here by the state dimension -- this wrapper has not been run). `F` is zero outside the connected components of the drift matrix, `Pinf` and `x0P` are separate (add them where x0P doubles as Pinf), `A1` is
 zero for a model bound without an explicit first transition. `nothing`: TGP_EUNSUPPORTED, take the tangent scans."""
 function logpdf_and_block_gradients_sde(m::DeviceLGSSM{Forward}, y::AbstractVector; per_step::Bool = false)
     d = m.d
@@ -454,10 +462,9 @@ function logpdf_and_block_gradients_sde(m::DeviceLGSSM{Forward}, y::AbstractVect
     ga, gH, gm = (Vector{Float64}(undef, d) for _ in 1:3)
     gh, gR = Ref{Float64}(0.0), Ref{Float64}(0.0)
     hs, Rs = per_step ? (Vector{Float64}(undef, m.T), Vector{Float64}(undef, m.T)) : (Float64[], Float64[])
-    rc = GC.@preserve yv mask hs Rs ccall((:tgp_logpdf_adjoint_sde, libtgp), Cint,
-        (Ptr{Cvoid}, Ptr{Float64}, Ptr{UInt8}, UInt32, Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64},
-         Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
-        m.h.ptr, yv, mp, UInt32(0), lml, gF, gPi, gA1, ga, gH, gh, gR, gm, gP, per_step ? pointer(hs) : C_NULL, per_step ? pointer(Rs) : C_NULL)
+    entry = d >= 5 ? _adjoint_sde_group : _adjoint_sde_lane
+    rc = GC.@preserve yv mask hs Rs entry(m.h.ptr, yv, mp, lml, gF, gPi, gA1, ga, gH, gh, gR, gm, gP, per_step ? pointer(hs) : C_NULL,
+                                          per_step ? pointer(Rs) : C_NULL)
     rc == 4 && return nothing
     check(m.h, rc)
     g = (F = gF, Pinf = gPi, A1 = gA1, a = ga, H = gH, h = gh[], R = gR[], x0m = gm, x0P = gP)

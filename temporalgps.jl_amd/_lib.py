@@ -66,6 +66,7 @@ _SIGS = {
     "tgp_logpdf_adjoint_missing": (ctypes.c_int, [_vp, _vp, _vp, _u32, _dp] + [_vp] * 10),
     "tgp_logpdf_adjoint_group": (ctypes.c_int, [_vp, _vp, _vp, _u32, _dp] + [_vp] * 10),
     "tgp_logpdf_adjoint_sde": (ctypes.c_int, [_vp, _vp, _vp, _u32, _dp] + [_vp] * 11),
+    "tgp_logpdf_adjoint_group_sde": (ctypes.c_int, [_vp, _vp, _vp, _u32, _dp] + [_vp] * 11),
     "tgp_adjoint_record_size": (ctypes.c_int, [ctypes.c_int]),
     "tgp_steady_plan": (ctypes.c_int, [ctypes.c_int] + [_vp] * 8 + [_i64, _vp, _vp, _vp, _vp]),
     "tgp_filter_plan": (ctypes.c_int, [ctypes.c_int] + [_vp] * 8 + [_i64, _vp]),

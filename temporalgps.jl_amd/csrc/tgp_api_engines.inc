@@ -172,11 +172,12 @@ bool sweep_group_eligible(const tgp_handle* h, uint32_t flags, bool post, bool e
     return h->mv.sA == 0 && h->mv.sa == 0 && h->mv.sQ == 0;
 }
 // An SDE-described model at 5 <= d <= 8 (k_sweep_group_sde, DESIGN 4.13): sweep_eligible's SDE conditions (the closed form found and allowed, a and H
-// shared) with sweep_group_eligible's others.  tgp_logpdf and tgp_[logpdf_and_]posterior_marginals only (the gradient and the draw decline: the
-// predicate above), and under TGP_OPT_SWEEP = 2 only: no (d, call) pair is routed here by default (profiles/sweep_group_sde_time.txt has the measured medians
+// shared) with sweep_group_eligible's others.  tgp_logpdf and tgp_[logpdf_and_]posterior_marginals (the draw declines: the
+// predicate above; the gradient has its explicit entry, below), and under TGP_OPT_SWEEP = 2 only: no (d, call) pair is routed here by default (profiles/sweep_group_sde_time.txt has the measured medians
 // beside the general engine's: a routing change would rest on them).
-bool sweep_group_sde_eligible(const tgp_handle* h, uint32_t flags) {
-    if (h->opt_sweep < 2 || h->sweep_state < 0 || h->is_dense || h->p != 1 || h->ordering != 0 || !h->sde) return false;
+// explicit_call: an entry point of the engine's own (tgp_logpdf_adjoint_group_sde, DESIGN 4.14), served under TGP_OPT_SWEEP >= 1 as sweep_group_eligible's.
+bool sweep_group_sde_eligible(const tgp_handle* h, uint32_t flags, bool explicit_call = false) {
+    if (h->opt_sweep < (explicit_call ? 1 : 2) || h->sweep_state < 0 || h->is_dense || h->p != 1 || h->ordering != 0 || !h->sde) return false;
     if (h->d < tgp_sweep::kGroupMinD || h->d > tgp_sweep::kGroupMaxD) return false;
     if ((flags & TGP_REUSE_REDUCE) || h->opt_chunk != 0 || h->variant_opt != 0 || !h->opt_steady2 || h->opt_graph != 0) return false;
     if (h->T < tgp_sweep::kGroupMinT || h->mv.T != h->T || h->mv.sH != 0 || h->sweepm.empty()) return false;
@@ -648,6 +649,28 @@ int sweep_group_adjoint_call(tgp_handle* h, const double* y, const uint8_t* miss
                              [&]() { tgp_sweep_group::adjoint_blocks(h->sweep_group, o); });
 }
 
+// The same on an SDE-described model (k_sweep_group_adjoint_sde, DESIGN 4.14): the sums over the closed form's coefficients go to *so, with step 0 pulled
+// back on the host through the first transition.  The stationary covariance is the one tgp_model_set_sde took (sweep_adjoint_call: tgp_model_set_x0 may
+// have replaced the prior since); tgp_logpdf and the posterior calls keep planning from sweep_host_model.
+int sweep_group_adjoint_sde_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, const tgp_sweep::AdjointSdeOut& so,
+                                 double* gh_steps, double* gR_steps, bool* served, std::string* why) {
+    *served = false;
+    if (!h->sweep_group) h->sweep_group = tgp_sweep_group::create();
+    tgp_sweep::ModelHost mh = sweep_host_model(h);
+    mh.Pinf = h->sde_coef_host.data() + h->d + 2 * (size_t)h->d * h->d;
+    const SweepAdjointOps eng = {
+        "sweep group adjoint sde", tgp_sweep_group::adjoint_sde_kernel_name(),
+        [](tgp_handle* hh, const tgp_sweep::ModelHost& m, int W, int Wa, std::string* w) {
+            tgp_sweep_group::force_geometry(hh->sweep_group, hh->sweep_fC, hh->sweep_fW, hh->sweep_fWb);
+            return tgp_sweep_group::plan(hh->sweep_group, m, hh->T, W, Wa, hh->num_cu, /*post=*/true, w, /*adjoint=*/true);
+        },
+        [](tgp_handle* hh, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep_group::enqueue(hh->sweep_group, hh->stream, c, kname, err); },
+        [](tgp_handle* hh, int* status, int* w, int* wa, double* df, double* db) { return tgp_sweep_group::finish(hh->sweep_group, status, w, wa, df, db); },
+        [](tgp_handle* hh, int* C, int64_t* nw) { tgp_sweep_group::geometry(hh->sweep_group, C, nullptr, nullptr, nw); }};
+    return sweep_adjoint_run(h, eng, mh, true, y, missing, flags, lml_out, gh_steps, gR_steps, served, why,
+                             [&]() { tgp_sweep_group::adjoint_blocks_sde(h->sweep_group, mh, so); });
+}
+
 // d logpdf / d F from the sums over the closed form's coefficients: the transpose of sde_closed_form's map.  coef = [lam d | N d*d | N^2 / 2 d*d | ...];
 // a connected component S of n rows has N = F_SS + lam I, lam = -tr F_SS / n:  gN = [n >= 2] gN1_SS + [n >= 3] (gN2_SS N' + N' gN2_SS) / 2,
 // gF_SS = gN - ((sum_S gl_i + tr gN) / n) I.  Entries outside the components are zero (the closed form does not read them).
@@ -683,6 +706,37 @@ void sde_coef_to_gF(int d, const double* coef, const double* gl, const double* g
         for (int jj = 0; jj < n; ++jj)
             for (int ii = 0; ii < n; ++ii) gF[S[ii] + S[jj] * d] = gN[ii + jj * n] - (ii == jj ? tr / n : 0.0);
     }
+}
+
+// The outputs of tgp_logpdf_adjoint_sde / tgp_logpdf_adjoint_group_sde from an engine's record (any output null).  A model bound without A1 took
+// A1 = E (I + N1 + N2), E = diag(e^(-lam_i)), at step 0: its G_0 (so.gA1) belongs to the coefficients, with tau = 1, and gA1 is zero.
+void sde_adjoint_outputs(const tgp_handle* h, const tgp_sweep::AdjointSdeOut& so, double* gF, double* gPinf, double* gA1, double* ga, double* gH, double* ghh,
+                         double* gR, double* gx0m, double* gx0P) {
+    const int d = h->d, dd = d * d;
+    const double* coef = h->sde_coef_host.data();
+    if (!h->have_AQ1) {
+        const double* A1 = h->sde_A1Q1_host.data();
+        for (int i = 0; i < d; ++i) {
+            const double e = std::exp(-coef[i]);
+            double s = 0.0;
+            for (int j = 0; j < d; ++j) {
+                s += so.gA1[i + j * d] * A1[i + j * d];
+                so.gN1[i + j * d] += e * so.gA1[i + j * d];
+                so.gN2[i + j * d] += e * so.gA1[i + j * d];
+            }
+            so.gl[i] -= s;
+        }
+        for (int i = 0; i < dd; ++i) so.gA1[i] = 0.0;
+    }
+    if (gF) sde_coef_to_gF(d, coef, so.gl, so.gN1, so.gN2, gF);
+    if (gPinf) std::memcpy(gPinf, so.gPinf, sizeof(double) * dd);
+    if (gA1) std::memcpy(gA1, so.gA1, sizeof(double) * dd);
+    if (ga) std::memcpy(ga, so.ga, sizeof(double) * d);
+    if (gH) std::memcpy(gH, so.gH, sizeof(double) * d);
+    if (ghh) *ghh = *so.ghh;
+    if (gR) *gR = *so.gR;
+    if (gx0m) std::memcpy(gx0m, so.gx0m, sizeof(double) * d);
+    if (gx0P) std::memcpy(gx0P, so.gx0P, sizeof(double) * dd);
 }
 
 bool steady2_served(tgp_handle* h) {

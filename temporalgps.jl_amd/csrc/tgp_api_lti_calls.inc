@@ -559,30 +559,34 @@ int tgp_logpdf_adjoint_sde(tgp_handle* h, const double* y, const uint8_t* missin
     std::string why;
     TRY(sweep_adjoint_call(h, y, missing, flags, lml_out, tgp_sweep::AdjointOut(), gh_steps, gR_steps, &served, &why, &so));
     if (!served) return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_sde: the sweep engine declines the gradient: " + why + " (use tgp_logpdf_grad_sde)");
-    const double* coef = h->sde_coef_host.data();
-    if (!h->have_AQ1) {      // step 0 took A1 = E (I + N1 + N2), E = diag(e^(-lam_i)): its G_0 belongs to the coefficients
-        const double* A1 = h->sde_A1Q1_host.data();
-        for (int i = 0; i < d; ++i) {
-            const double e = std::exp(-coef[i]);
-            double s = 0.0;
-            for (int j = 0; j < d; ++j) {
-                s += so.gA1[i + j * d] * A1[i + j * d];
-                so.gN1[i + j * d] += e * so.gA1[i + j * d];
-                so.gN2[i + j * d] += e * so.gA1[i + j * d];
-            }
-            so.gl[i] -= s;
-        }
-        for (int i = 0; i < dd; ++i) so.gA1[i] = 0.0;
-    }
-    if (gF) sde_coef_to_gF(d, coef, so.gl, so.gN1, so.gN2, gF);
-    if (gPinf) std::memcpy(gPinf, so.gPinf, sizeof(double) * dd);
-    if (gA1) std::memcpy(gA1, so.gA1, sizeof(double) * dd);
-    if (ga) std::memcpy(ga, so.ga, sizeof(double) * d);
-    if (gH) std::memcpy(gH, so.gH, sizeof(double) * d);
-    if (ghh) *ghh = *so.ghh;
-    if (gR) *gR = *so.gR;
-    if (gx0m) std::memcpy(gx0m, so.gx0m, sizeof(double) * d);
-    if (gx0P) std::memcpy(gx0P, so.gx0P, sizeof(double) * dd);
+    sde_adjoint_outputs(h, so, gF, gPinf, gA1, ga, gH, ghh, gR, gx0m, gx0P);
+    return TGP_OK;
+}
+
+// The same at state dimensions 5 .. 8 by the group sweep's k_sweep_group_adjoint_sde (DESIGN 4.14): what sweep_group_sde_eligible accepts, whatever the
+// default routing of the engine's other calls (an explicit call; TGP_OPT_SWEEP >= 1).  tgp_logpdf_adjoint_sde's arguments and outputs.  The kernel never
+// sees the first transition: the host pulls the adjoint in front of update 0 back through A1 (tgp_sweep_group.hip adjoint_blocks_sde).
+int tgp_logpdf_adjoint_group_sde(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, double* gF, double* gPinf, double* gA1,
+                                 double* ga, double* gH, double* ghh, double* gR, double* gx0m, double* gx0P, double* gh_steps, double* gR_steps) {
+    StreamGuard stream_guard_(h);
+    TRY(check_ready(h, /*general=*/false));
+    if (!y) return h->fail(TGP_EINVAL, "tgp_logpdf_adjoint_group_sde: null argument");
+    if (!sweep_group_sde_eligible(h, flags, /*explicit_call=*/true))
+        return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_group_sde: Forward SDE-described models (tgp_model_set_sde) with closed-form transitions "
+                                         "(TGP_OPT_SDE_CLOSED_FORM = 1), shared a and H, scalar observations, 5 <= d <= 8 and T >= 2048 on the group sweep "
+                                         "(TGP_OPT_SWEEP >= 1, the engine not declined for the bound model); use tgp_logpdf_adjoint_sde at d <= 4 and "
+                                         "tgp_logpdf_adjoint_group for models in LTI form");
+    constexpr int M = tgp_sweep::kGroupMaxD;
+    double buf[6 * M * M + 4 * M + 2];      // (sized for d = 8)
+    const int d = h->d, dd = d * d;
+    tgp_sweep::AdjointSdeOut so;
+    so.gl = buf; so.gN1 = so.gl + d; so.gN2 = so.gN1 + dd; so.gPinf = so.gN2 + dd; so.gA1 = so.gPinf + dd; so.ga = so.gA1 + dd; so.gH = so.ga + d;
+    so.ghh = so.gH + d; so.gR = so.ghh + 1; so.gx0m = so.gR + 1; so.gx0P = so.gx0m + d;
+    bool served = false;
+    std::string why;
+    TRY(sweep_group_adjoint_sde_call(h, y, missing, flags, lml_out, so, gh_steps, gR_steps, &served, &why));
+    if (!served) return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_group_sde: the group sweep declines the gradient: " + why);
+    sde_adjoint_outputs(h, so, gF, gPinf, gA1, ga, gH, ghh, gR, gx0m, gx0P);
     return TGP_OK;
 }
 

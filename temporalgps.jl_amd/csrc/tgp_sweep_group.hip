@@ -691,6 +691,7 @@ const char* kernel_name(bool post, bool sde) {
     return post ? "k_sweep_group<lti,posterior>" : "k_sweep_group<lti,logpdf>";
 }
 const char* adjoint_kernel_name() { return "k_sweep_group_adjoint<lti>"; }
+const char* adjoint_sde_kernel_name() { return "k_sweep_group_adjoint<sde>"; }
 const char* draw_kernel_name() { return "k_sweep_group_draw<lti>"; }
 
 namespace {
@@ -752,7 +753,7 @@ int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char*
         if (err) *err = "k_sweep_group: the call does not match its plan";
         return 1;
     }
-    e->part_stride = c.adjoint ? 4 + tgp_sweep::group_adjoint_sums(p.d) : 4;
+    e->part_stride = c.adjoint ? 4 + (p.sde ? tgp_sweep::group_adjoint_sde_sums(p.d) : tgp_sweep::group_adjoint_sums(p.d)) : 4;
     const size_t need_part = (size_t)p.nwaves * e->part_stride * sizeof(double);
     if (need_part > e->part_cap) {
         if (e->part) (void)tgp_alloc::host_free(e->part);
@@ -794,6 +795,14 @@ int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char*
     ka.var = c.var;
     ka.ckpt = static_cast<double*>(e->ckpt);
     ka.part = e->part;
+    if (c.adjoint && p.sde) {      // an SDE-described model: the transitions from the gaps (tgp_sweep_group_adjoint_sde.hip)
+        ka.st.tau = c.tau;
+        if (kname) *kname = adjoint_sde_kernel_name();
+        launch_adjoint_sde(p.d, (unsigned)p.nwaves, stream, ka, p.sc, c.gh_steps, c.gR_steps);
+        hipError_t rc = hipGetLastError();
+        if (rc != hipSuccess) return fail("k_sweep_group_adjoint_sde launch", rc);
+        return 0;
+    }
     if (c.adjoint) {
         GAArgs ar;
         ar.ka = ka;      // (ka.Wb: the plan's backward slot carries the adjoint's warm-up)
@@ -867,6 +876,58 @@ double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* d
 
 void adjoint_blocks(const Engine* e, const tgp_sweep::AdjointOut& out) {
     tgp_sweep::adjoint_blocks_from_parts(e->part, e->p.nwaves, e->part_stride, e->p.d, out);
+}
+
+// The record of an adjoint call on an SDE-described model (k_sweep_group_adjoint_sde): the waves' sums in wave order, then step 0 on the host.  The kernel
+// stops in front of update 0 with (mb, Pb) = d logpdf / d (m_p, P_p) of the state the plan predicted through the first transition A1:
+// G_0 = mb x0m' + 2 Pb A1 (x0P - Pinf) (left in gA1: the caller decides whether it belongs to A1 or to the coefficients), gx0m = A1' mb,
+// gx0P = A1' Pb A1, gPinf += Pb - A1' Pb A1, ga += mb.  m: the host model the plan was made from (A = A1; x0P read as Symmetric(upper triangle)).
+void adjoint_blocks_sde(const Engine* e, const tgp_sweep::ModelHost& m, const tgp_sweep::AdjointSdeOut& o) {
+    const int d = e->p.d, dd = d * d, ds = d * (d + 1) / 2, ng = e->part_stride - 4;
+    double g[tgp_sweep::group_adjoint_sde_sums(tgp_sweep::kGroupMaxD)] = {0.0};      // (the largest record: d = 8)
+    for (int64_t i = 0; i < e->p.nwaves; ++i) {      // fixed order: two calls on the same series give the same bits
+        const double* q = e->part + (size_t)i * e->part_stride + 4;
+        for (int k = 0; k < ng; ++k) g[k] += q[k];
+    }
+    const double *gl = g, *gN1 = gl + d, *gN2 = gN1 + dd, *gPi = gN2 + dd, *ga = gPi + ds, *gH = ga + d, *gs = gH + d, *mb = gs + 2, *Pbp = mb + d;
+    std::memcpy(o.gl, gl, sizeof(double) * d);
+    std::memcpy(o.gN1, gN1, sizeof(double) * dd);
+    std::memcpy(o.gN2, gN2, sizeof(double) * dd);
+    std::memcpy(o.gH, gH, sizeof(double) * d);
+    *o.ghh = gs[0];
+    *o.gR = gs[1];
+    constexpr int M = tgp_sweep::kGroupMaxD;
+    double Pb[M * M], X[M * M], PA[M * M];      // Pb full; X = A1 (x0P - Pinf); PA = Pb A1
+    const double* Pinf = m.Pinf ? m.Pinf : m.x0P;
+    for (int j = 0; j < d; ++j)
+        for (int i = 0; i < d; ++i) Pb[i + j * d] = Pbp[tgp_sweep::pidx(i, j)];
+    for (int j = 0; j < d; ++j)
+        for (int i = 0; i < d; ++i) {
+            double x = 0.0, pa = 0.0;
+            for (int k = 0; k < d; ++k) {
+                x += m.A[i + k * d] * (m.x0P[std::min(k, j) + std::max(k, j) * d] - 0.5 * (Pinf[k + j * d] + Pinf[j + k * d]));
+                pa += Pb[i + k * d] * m.A[k + j * d];
+            }
+            X[i + j * d] = x;
+            PA[i + j * d] = pa;
+        }
+    for (int j = 0; j < d; ++j)
+        for (int i = 0; i < d; ++i) {
+            double g0 = mb[i] * m.x0m[j], apa = 0.0;
+            for (int k = 0; k < d; ++k) {
+                g0 += 2.0 * Pb[i + k * d] * X[k + j * d];
+                apa += m.A[k + i * d] * PA[k + j * d];
+            }
+            o.gA1[i + j * d] = g0;
+            o.gx0P[i + j * d] = apa;
+            o.gPinf[i + j * d] = gPi[tgp_sweep::pidx(i, j)] + Pb[i + j * d] - apa;
+        }
+    for (int i = 0; i < d; ++i) {
+        double a = 0.0;
+        for (int k = 0; k < d; ++k) a += m.A[k + i * d] * mb[k];
+        o.gx0m[i] = a;
+        o.ga[i] = ga[i] + mb[i];
+    }
 }
 
 }  // namespace tgp_sweep_group

@@ -47,12 +47,16 @@ bool plan(Engine* e, const tgp_sweep::ModelHost& m, int64_t T, int w_hint, int w
 int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char** kernel_name, std::string* err);
 const char* kernel_name(bool post, bool sde = false);      // sde: the model is SDE-described (k_sweep_group_sde)
 const char* adjoint_kernel_name();
+const char* adjoint_sde_kernel_name();      // the model is SDE-described (k_sweep_group_adjoint_sde)
 const char* draw_kernel_name();
 // After the stream has been synchronised: tgp_sweep::finish's status bits, warm-ups and distances.  An adjoint call: bit 2, *wb and *dist_b are the
 // adjoint warm-up's; a draw call: the draw warm-up's, and the returned value is 0.
 double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* dist_b);
 // Behind finish of an adjoint call whose status is clean: the waves' sums, added in wave order (gQ and gx0P symmetric).
 void adjoint_blocks(const Engine* e, const tgp_sweep::AdjointOut& out);
+// The same for an SDE-described model (none of out's pointers null): the sums over the closed form's coefficients, and step 0 pulled back on the host through
+// the first transition of m, the host model the plan was made from -- gA1 holds G_0 = d logpdf / d A1, gx0m / gx0P / gPinf / ga carry step 0's shares.
+void adjoint_blocks_sde(const Engine* e, const tgp_sweep::ModelHost& m, const tgp_sweep::AdjointSdeOut& out);
 void geometry(const Engine* e, int* C, int* W, int* Wb, int64_t* nwaves);
 // test hook: force the geometry of the next plan (0: automatic)
 void force_geometry(Engine* e, int C, int W, int Wb);

@@ -437,5 +437,8 @@ template <int D, int XS, bool KEEP_A> struct Lane {
 
 // tgp_sweep_group_sde.hip: a call on an SDE-described model -- k_sweep_group_sde<d, XS, post> on nwaves workgroups; ka.st.tau holds the gaps
 void launch_sde(int d, unsigned nwaves, hipStream_t stream, const GArgs& ka, const tgp_sweep::GroupSdeC& sc, bool post);
+// tgp_sweep_group_adjoint_sde.hip: the adjoint gradient of such a model -- k_sweep_group_adjoint_sde<d, XS>; ka.Wb holds the adjoint's
+// warm-up, ka.part has 4 + tgp_sweep::group_adjoint_sde_sums(d) doubles per wave, gh_steps / gR_steps: device [T] or null
+void launch_adjoint_sde(int d, unsigned nwaves, hipStream_t stream, const GArgs& ka, const tgp_sweep::GroupSdeC& sc, double* gh_steps, double* gR_steps);
 
 }  // namespace tgp_sweep_group

@@ -378,6 +378,13 @@ constexpr int group_draw_waves_per_cu(int d) { return d <= 5 ? 8 : 4; }
 // (profiles/sweep_group_sde_resources.txt has the counts and tests/test_sweep_group_sde_resources.py holds this function to them): today every logpdf
 // kernel is within 256 registers and every posterior kernel above, whatever d
 constexpr int group_sde_waves_per_cu(int d, bool post) { return (void)d, post ? 4 : 8; }
+// The adjoint call on an SDE-described model (k_sweep_group_adjoint_sde) runs in the posterior call's geometry.  Doubles a wave leaves behind
+// its 4 status words: gl d, gN1 d*d, gN2 d*d (the sums over the closed form's coefficients), gPinf packed, ga d, gH d, the sums of gh_t and gR_t, and the
+// adjoint in front of update 0 (d, packed) -- the host pulls that one back through the first transition.
+constexpr int group_adjoint_sde_sums(int d) { return d + 2 * d * d + d * (d + 1) / 2 + 2 * d + 2 + d + d * (d + 1) / 2; }
+// waves resident per CU in that call, from the kernel's register counts as the others' (profiles/sweep_group_adjoint_sde_resources.txt): every
+// instantiation takes more than 256 registers, one wave per SIMD
+constexpr int group_adjoint_sde_waves_per_cu(int d) { return (void)d, 4; }
 
 // The steps [t0, t1) of group g (0 .. 7) of a wave, as the kernel and the tests compute them: the wave's groups hold the chunks
 // wave * owned - 1 .. wave * owned + 6.  runs: the group runs its chunk (group 0 only warms up); owned: it writes output and sums.
@@ -498,7 +505,8 @@ template <int D> inline bool plan_group_d(GroupPlan* e, const Forced& f, const M
     // chunk length: group_waves_per_cu waves per CU, every wave `owned` chunks of its own; a chunk holds the backward warm-up.  A multiple of 8 (the rows
     // of the observation stream), hence of the checkpoint block.
     const int owned = group_owned(post);
-    const int per_cu = m.sde ? group_sde_waves_per_cu(D, post) : adjoint ? group_adjoint_waves_per_cu(D) : draw ? group_draw_waves_per_cu(D) : group_waves_per_cu(D, post);
+    const int per_cu = m.sde ? (adjoint ? group_adjoint_sde_waves_per_cu(D) : group_sde_waves_per_cu(D, post))
+                             : adjoint ? group_adjoint_waves_per_cu(D) : draw ? group_draw_waves_per_cu(D) : group_waves_per_cu(D, post);
     const int64_t slots = (int64_t)std::max(num_cu, 1) * per_cu * owned;
     int64_t C = up((int)std::min<int64_t>((T + slots - 1) / slots, 1 << 20), 8);
     C = std::max<int64_t>(C, 64);
@@ -581,7 +589,7 @@ inline bool plan_group(GroupPlan* p, const Forced& f, const ModelHost& m, int64_
         if (why) *why = "state dimension";
         return false;
     }
-    if (m.sde && (adjoint || draw)) {      // (the gradient and the draw of an SDE-described model at these d: the general engine)
+    if (m.sde && draw) {      // (the draw of an SDE-described model at these d: the general engine)
         if (why) *why = "SDE-described model";
         return false;
     }

@@ -651,9 +651,21 @@ def logpdf_adjoint_sde(model, y, per_step=False):
     connected components of F --, Pinf (d,d) and x0P (d,d) (symmetrised, separate: a model whose x0P doubles as Pinf adds them), A1 (d,d) (zero for a model
     bound without an explicit first transition), a (d,), H (d,), h (), R () (sums over the observed steps), x0m (d,); per_step adds "h_steps" and "R_steps"
     (T,) as logpdf_adjoint_missing does.  Raises Unsupported where the engine declines (use logpdf_and_grad_sde)."""
+    return _logpdf_adjoint_sde("tgp_logpdf_adjoint_sde", model, y, per_step)
+
+
+def logpdf_adjoint_group_sde(model, y, per_step=False):
+    """logpdf_adjoint_sde at state dimensions 5 <= d <= 8: ONE adjoint pass on the group sweep (tgp_logpdf_adjoint_group_sde, k_sweep_group_adjoint<sde>,
+    DESIGN 4.14) -- e.g. Matern52 + Matern32 on irregular time stamps.  Arguments and the returned (lml, g) as logpdf_adjoint_sde's; a prior replaced
+    through tgp_model_set_x0 is served.  Raises Unsupported where the engine declines (central differences of logpdf are what remains at these d)."""
+    return _logpdf_adjoint_sde("tgp_logpdf_adjoint_group_sde", model, y, per_step)
+
+
+def _logpdf_adjoint_sde(entry, model, y, per_step):
+    """tgp_logpdf_adjoint_sde / tgp_logpdf_adjoint_group_sde: one argument list, one output convention"""
     _check_inputs(model, y[0] if isinstance(y, tuple) else y)
     if not isinstance(model.transitions, SDETransitions):
-        raise _lib.Unsupported(_lib.EUNSUPPORTED, "logpdf_adjoint_sde needs SDE-described transitions (use logpdf_adjoint_missing)")
+        raise _lib.Unsupported(_lib.EUNSUPPORTED, entry[4:] + " needs SDE-described transitions (use logpdf_adjoint_missing / logpdf_adjoint_group)")
     hd = model.handle()
     yy, mm, dev = _obs(y, model)
     d = model.dim
@@ -662,8 +674,8 @@ def logpdf_adjoint_sde(model, y, per_step=False):
     steps = [_out(model, (model.T,), dev), _out(model, (model.T,), dev)] if per_step else [None, None]
     lml = ctypes.c_double()
     flags = (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0
-    hd.check(hd.lib.tgp_logpdf_adjoint_sde(hd.h, _lib.ptr(yy), _lib.ptr(mm), flags, ctypes.byref(lml),
-                                           *[_lib.ptr(g[k]) for k in ("F", "Pinf", "A1", "a", "H", "h", "R", "x0m", "x0P")], _lib.ptr(steps[0]), _lib.ptr(steps[1])))
+    hd.check(getattr(hd.lib, entry)(hd.h, _lib.ptr(yy), _lib.ptr(mm), flags, ctypes.byref(lml),
+                                    *[_lib.ptr(g[k]) for k in ("F", "Pinf", "A1", "a", "H", "h", "R", "x0m", "x0P")], _lib.ptr(steps[0]), _lib.ptr(steps[1])))
     for k in ("F", "Pinf", "A1", "x0P"):
         g[k] = g[k].T.copy()          # column-major blocks -> [i][k]
     g["h"], g["R"] = float(g["h"][0]), float(g["R"][0])

@@ -894,19 +894,20 @@ def _logpdf_and_gradient_sweep(fx, y):
 
 def _logpdf_and_gradient_sweep_sde(fx, y):
     """Plain-array (irregularly spaced) inputs: the model is bound through its SDE as _logpdf_and_gradient_sde binds it, ONE adjoint pass on the sweep engine
-    (L.logpdf_adjoint_sde, k_sweep_adjoint<sde>: d <= 4, T >= 2048) gives d logpdf / d (F, H, Pinf, x0P, A1, h, R), contracted with the exact tangents of
-    those O(1) blocks.  x0P doubles as Pinf: the two gradients are added.  One variance per observation: no "noise" entry."""
+    (L.logpdf_adjoint_sde, k_sweep_adjoint<sde>: d <= 4; L.logpdf_adjoint_group_sde, k_sweep_group_adjoint<sde>: 5 <= d <= 8; T >= 2048) gives
+    d logpdf / d (F, H, Pinf, x0P, A1, h, R), contracted with the exact tangents of those O(1) blocks.  x0P doubles as Pinf: the two gradients are added.
+    One variance per observation: no "noise" entry."""
     kernel = fx.f.f.kernel
     if not isinstance(fx.f.f.mean, (ZeroMean, ConstMean)):
         raise NotImplementedError("logpdf_and_gradient(method='sweep'): a ZeroMean or ConstMean only")
-    if not hasattr(kernel, "sde_blocks") or kernel.sde_blocks()[0].shape[0] > 4:
-        raise NotImplementedError("logpdf_and_gradient(method='sweep') on irregular inputs: kernels with state dimension <= 4")
+    if not hasattr(kernel, "sde_blocks") or kernel.sde_blocks()[0].shape[0] > 8:
+        raise NotImplementedError("logpdf_and_gradient(method='sweep') on irregular inputs: kernels with state dimension <= 8")
     plist = parameters(kernel)
     names = [n for n, _, _ in plist] + (["noise"] if fx.sigma2.shape[0] == 1 else []) + (["mean.c"] if isinstance(fx.f.f.mean, ConstMean) else [])
     model = build_lgssm(kernel, fx.x, fx.sigma2, fx.f.f.mean, fx.f.storage.device, device_components=True)
     if not isinstance(model.transitions, L.SDETransitions):
         raise NotImplementedError("logpdf_and_gradient: could not bind the model through its SDE")
-    lp, g = L.logpdf_adjoint_sde(model, y)
+    lp, g = (L.logpdf_adjoint_group_sde if 5 <= model.dim <= 8 else L.logpdf_adjoint_sde)(model, y)
     gP = g["Pinf"] + g["x0P"]
     grad = {}
     for name, t in zip(names, _sde_param_tangents(fx, names, plist)):
@@ -1051,7 +1052,8 @@ def logpdf_and_gradient(fx, y, rel_step=None, method=None):
     method: None (default policy), "adjoint" (ONE reverse-time pass on the stationary-gain engine, exact block tangents on the host:
     regular spacing, homoscedastic noise, d <= 8, or the wide-state engine for 8 < d <= 63 where its plan applies -- cost independent of the
     number of parameters), "sweep" (ONE adjoint pass on the sweep engine: regular spacing with NaNs in y and / or one noise variance per
-    observation at d <= 8 -- the group sweep's kernel at 5 <= d <= 8 --, or plain-array (irregularly spaced) inputs bound through their SDE at d <= 4;
+    observation at d <= 8 -- the group sweep's kernel at 5 <= d <= 8 --, or plain-array (irregularly spaced) inputs bound through their SDE at d <= 8
+    -- likewise, e.g. Matern52 + Matern32: the only device gradient these have beside "fd", and never the default --;
     ZeroMean or ConstMean, T >= 2048; raises Unsupported where the device declines), "tangent" (the forward-mode scans)
     or "fd" (central differences of the device logpdf).
     Default: the adjoint pass where it applies -- on the stationary-gain engines, or on the sweep engine for d <= 4 and T >= 2048 with missing observations
