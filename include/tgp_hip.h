@@ -160,14 +160,15 @@ typedef struct tgp_handle tgp_handle;
                            transitions, shared a and H), T >= 2048 -- tgp_logpdf / tgp_[logpdf_and_]posterior_marginals run on the group sweep's
                            kernels for SDE-described models (tgp_sweep_group_sde.hip): k_sweep_group<sde,logpdf> /
                            k_sweep_group<sde,posterior>, the transition of every step built from its gap; under 1 these models stay on the
-                           general engine and their draw does so under every value; their gradient has an entry point of its own,
-                           tgp_logpdf_adjoint_group_sde (k_sweep_group_adjoint<sde>; served under 1 and 2 alike).  Both step aside
+                           general engine; their gradient has an entry point of its own, tgp_logpdf_adjoint_group_sde
+                           (k_sweep_group_adjoint<sde>; served under 1 and 2 alike), and so has their draw,
+                           tgp_posterior_rand_group_sde (k_sweep_group_draw<sde>; likewise).  Both step aside
                            on an explicit request for the general engine (TGP_REUSE_REDUCE, TGP_OPT_CHUNK, TGP_OPT_VARIANT, TGP_OPT_STEADY 0 / 1,
                            TGP_OPT_GRAPH).  0: the general chunked-scan engine as before; tgp_posterior_rand_missing, tgp_posterior_rand_group,
                            tgp_logpdf_adjoint_missing and tgp_logpdf_adjoint_group answer TGP_EUNSUPPORTED for these models. */
 #define TGP_OPT_SWEEP_CHUNK 15       /* tests: steps per chunk of the sweep engine (0 automatic) */
 #define TGP_OPT_SWEEP_WARMUP 16      /* tests: forward warm-up steps (0 automatic); a forced geometry is never repaired by longer warm-ups */
-#define TGP_OPT_SWEEP_WARMUP_BACK 17 /* tests: backward warm-up steps (0 automatic); in tgp_posterior_rand_missing / _group: the draw's warm-up; in
+#define TGP_OPT_SWEEP_WARMUP_BACK 17 /* tests: backward warm-up steps (0 automatic); in tgp_posterior_rand_missing / _group / _group_sde: the draw's warm-up; in
                                         tgp_logpdf_adjoint_missing / _group: the adjoint's */
 #define TGP_OPT_STREAM_MIN_T 18 /* series length from which the STREAMING kernels of the stationary-gain engine serve a call: persistent
                                    waves with ~7 us more fixed latency and 1.3 - 2.7 x the throughput of k_steady_one.  -1 (default): the measured
@@ -535,6 +536,17 @@ int tgp_posterior_rand_missing(tgp_handle* h, const double* y, const uint8_t* mi
  * tgp_rand. */
 int tgp_posterior_rand_group(tgp_handle* h, const double* y, const uint8_t* missing, const double* Rnew, const double* eps_t, const double* eps_e,
                              const double* eps_0, uint32_t flags, double* y_out);
+/* The same for a model bound by tgp_model_set_sde at 5 <= d <= 8 (irregular spacing, closed-form transitions, shared a and H) -- what
+ * rand(rng, posterior(fx, y)(x_new)) merges into on a plain array of inputs -- by ONE kernel, k_sweep_group_draw<sde> (tgp_sweep_group_draw_sde.hip,
+ * DESIGN 4.15): tgp_posterior_rand_group's geometry, checks and repair with the transition of every step built from its gap as k_sweep_group<sde,...>
+ * builds it; the step from x_(t+1) to x_t takes the gap in front of step t + 1; tied time stamps (a gap of 0) are steps like any other.  Arguments, flags,
+ * the use of the draws and tgp_sweep_info exactly as tgp_posterior_rand_group.  An explicit call: served under TGP_OPT_SWEEP = 1 and 2 alike.  A prior
+ * replaced by tgp_model_set_x0 is served.  TGP_EUNSUPPORTED, with nothing written to y_out (host or device): a model in LTI form (use
+ * tgp_posterior_rand_group), d < 5, d > 8, no closed form (or TGP_OPT_SDE_CLOSED_FORM = 0), p > 1, T < 2048, TGP_OPT_SWEEP = 0, an explicit request for
+ * the general engine, an engine declined for the bound model, a forced geometry whose warm-ups are too short, a Cholesky pivot that is not positive,
+ * non-finite values.  The library does not fall back: take tgp_posterior + tgp_rand. */
+int tgp_posterior_rand_group_sde(tgp_handle* h, const double* y, const uint8_t* missing, const double* Rnew, const double* eps_t, const double* eps_e,
+                                 const double* eps_0, uint32_t flags, double* y_out);
 
 /* ---- logpdf(replace_observation_noise_cov(posterior(model, y), R_new), y_new) (posterior_lti_sde.jl:62-78 ->
  *      lgssm.jl:147-151 on the reverse-time model of lgssm.jl:193-221) without a posterior: two observations of

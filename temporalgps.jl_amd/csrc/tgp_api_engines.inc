@@ -172,10 +172,10 @@ bool sweep_group_eligible(const tgp_handle* h, uint32_t flags, bool post, bool e
     return h->mv.sA == 0 && h->mv.sa == 0 && h->mv.sQ == 0;
 }
 // An SDE-described model at 5 <= d <= 8 (k_sweep_group_sde, DESIGN 4.13): sweep_eligible's SDE conditions (the closed form found and allowed, a and H
-// shared) with sweep_group_eligible's others.  tgp_logpdf and tgp_[logpdf_and_]posterior_marginals (the draw declines: the
-// predicate above; the gradient has its explicit entry, below), and under TGP_OPT_SWEEP = 2 only: no (d, call) pair is routed here by default (profiles/sweep_group_sde_time.txt has the measured medians
+// shared) with sweep_group_eligible's others.  tgp_logpdf and tgp_[logpdf_and_]posterior_marginals (the draw and the gradient have
+// explicit entries of their own, below), and under TGP_OPT_SWEEP = 2 only: no (d, call) pair is routed here by default (profiles/sweep_group_sde_time.txt has the measured medians
 // beside the general engine's: a routing change would rest on them).
-// explicit_call: an entry point of the engine's own (tgp_logpdf_adjoint_group_sde, DESIGN 4.14), served under TGP_OPT_SWEEP >= 1 as sweep_group_eligible's.
+// explicit_call: an entry point of the engine's own (tgp_logpdf_adjoint_group_sde, DESIGN 4.14; tgp_posterior_rand_group_sde, DESIGN 4.15), served under TGP_OPT_SWEEP >= 1 as sweep_group_eligible's.
 bool sweep_group_sde_eligible(const tgp_handle* h, uint32_t flags, bool explicit_call = false) {
     if (h->opt_sweep < (explicit_call ? 1 : 2) || h->sweep_state < 0 || h->is_dense || h->p != 1 || h->ordering != 0 || !h->sde) return false;
     if (h->d < tgp_sweep::kGroupMinD || h->d > tgp_sweep::kGroupMaxD) return false;
@@ -477,6 +477,27 @@ int sweep_group_draw_call(tgp_handle* h, const double* y, const uint8_t* missing
         [](tgp_handle* hh, const tgp_sweep::ModelHost& m, int W, int Wd, std::string* w) {
             tgp_sweep_group::force_geometry(hh->sweep_group, hh->sweep_fC, hh->sweep_fW, hh->sweep_fWb);
             return tgp_sweep_group::plan(hh->sweep_group, m, hh->T, W, Wd, hh->num_cu, /*post=*/true, w, /*adjoint=*/false, /*draw=*/true);
+        },
+        [](tgp_handle* hh, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep_group::enqueue(hh->sweep_group, hh->stream, c, kname, err); },
+        [](tgp_handle* hh, int* status, int* w, int* wd, double* df, double* dd) { (void)tgp_sweep_group::finish(hh->sweep_group, status, w, wd, df, dd); },
+        [](tgp_handle* hh, int* C, int64_t* nw) { tgp_sweep_group::geometry(hh->sweep_group, C, nullptr, nullptr, nw); }};
+    return sweep_draw_run(h, eng, y, missing, flags, Rnew, eps_t, eps_e, eps_0, y_out, served, why);
+}
+
+// The same for an SDE-described model on irregular inputs (k_sweep_group_draw_sde, DESIGN 4.15): the SDE posterior call's geometry with Wd in its
+// backward slot; Pinf from the closed-form record, so that a prior replaced by tgp_model_set_x0 is served (as the adjoint call's).  The plan callback is
+// a plain function pointer: it rebuilds the host model from the handle.
+int sweep_group_draw_sde_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, const double* eps_t,
+                              const double* eps_e, const double* eps_0, double* y_out, bool* served, std::string* why) {
+    *served = false;
+    if (!h->sweep_group) h->sweep_group = tgp_sweep_group::create();
+    const SweepDrawOps eng = {
+        "sweep group draw sde", tgp_sweep_group::draw_kernel_name(true),
+        [](tgp_handle* hh, const tgp_sweep::ModelHost& m, int W, int Wd, std::string* w) {
+            tgp_sweep::ModelHost mp = m;
+            mp.Pinf = hh->sde_coef_host.data() + hh->d + 2 * (size_t)hh->d * hh->d;
+            tgp_sweep_group::force_geometry(hh->sweep_group, hh->sweep_fC, hh->sweep_fW, hh->sweep_fWb);
+            return tgp_sweep_group::plan(hh->sweep_group, mp, hh->T, W, Wd, hh->num_cu, /*post=*/true, w, /*adjoint=*/false, /*draw=*/true);
         },
         [](tgp_handle* hh, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep_group::enqueue(hh->sweep_group, hh->stream, c, kname, err); },
         [](tgp_handle* hh, int* status, int* w, int* wd, double* df, double* dd) { (void)tgp_sweep_group::finish(hh->sweep_group, status, w, wd, df, dd); },

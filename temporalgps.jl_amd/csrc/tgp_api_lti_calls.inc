@@ -493,6 +493,26 @@ int tgp_posterior_rand_group(tgp_handle* h, const double* y, const uint8_t* miss
     return h->fail(TGP_EUNSUPPORTED, "tgp_posterior_rand_group: the group sweep declines the draw: " + why + " (take tgp_posterior + tgp_rand)");
 }
 
+// The same for a model described by its SDE and time stamps (tgp_model_set_sde: irregular spacing) -- what rand(rng, posterior(fx, y)(x_new)) merges into
+// -- by the group sweep's k_sweep_group_draw_sde (DESIGN 4.15): what sweep_group_sde_eligible accepts, whatever the default routing of the engine's other
+// calls (an explicit call; TGP_OPT_SWEEP >= 1).  tgp_posterior_rand_group's arguments and flags.
+int tgp_posterior_rand_group_sde(tgp_handle* h, const double* y, const uint8_t* missing, const double* Rnew, const double* eps_t, const double* eps_e,
+                                 const double* eps_0, uint32_t flags, double* y_out) {
+    StreamGuard stream_guard_(h);
+    TRY(check_ready(h, /*general=*/false));
+    if (!y || !Rnew || !eps_t || !eps_e || !eps_0 || !y_out) return h->fail(TGP_EINVAL, "tgp_posterior_rand_group_sde: null argument");
+    if (!sweep_group_sde_eligible(h, flags, /*explicit_call=*/true))
+        return h->fail(TGP_EUNSUPPORTED, "tgp_posterior_rand_group_sde: Forward SDE-described models (tgp_model_set_sde) with closed-form transitions "
+                                         "(TGP_OPT_SDE_CLOSED_FORM = 1), shared a and H, scalar observations, 5 <= d <= 8 and T >= 2048 on the group sweep "
+                                         "(TGP_OPT_SWEEP >= 1, the engine not declined for the bound model); use tgp_posterior_rand_missing at d <= 4, "
+                                         "tgp_posterior_rand_group for models in LTI form and tgp_posterior + tgp_rand otherwise");
+    bool served = false;
+    std::string why;
+    TRY(sweep_group_draw_sde_call(h, y, missing, flags, Rnew, eps_t, eps_e, eps_0, y_out, &served, &why));
+    if (served) return TGP_OK;
+    return h->fail(TGP_EUNSUPPORTED, "tgp_posterior_rand_group_sde: the group sweep declines the draw: " + why + " (take tgp_posterior + tgp_rand)");
+}
+
 // logpdf and its gradient with respect to the shared blocks, and to the noise variance and the emission offset of every step, where the gains vary in time
 // -- missing steps, a noise variance or an emission offset per step -- by ONE adjoint pass on the sweep engine (k_sweep_adjoint, DESIGN 4.8): what
 // sweep_eligible accepts in LTI form.  TGP_EUNSUPPORTED: no output was written, the caller takes tgp_logpdf_grad.

@@ -692,7 +692,7 @@ const char* kernel_name(bool post, bool sde) {
 }
 const char* adjoint_kernel_name() { return "k_sweep_group_adjoint<lti>"; }
 const char* adjoint_sde_kernel_name() { return "k_sweep_group_adjoint<sde>"; }
-const char* draw_kernel_name() { return "k_sweep_group_draw<lti>"; }
+const char* draw_kernel_name(bool sde) { return sde ? "k_sweep_group_draw<sde>" : "k_sweep_group_draw<lti>"; }
 
 namespace {
 
@@ -817,6 +817,14 @@ int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char*
         }
         hipError_t rc = hipGetLastError();
         if (rc != hipSuccess) return fail("k_sweep_group_adjoint launch", rc);
+        return 0;
+    }
+    if (draw && p.sde) {      // an SDE-described model: the transitions from the gaps (tgp_sweep_group_draw_sde.hip)
+        ka.st.tau = c.tau;
+        if (kname) *kname = draw_kernel_name(true);
+        launch_draw_sde(p.d, (unsigned)p.nwaves, stream, ka, p.sc, c.eps_t, c.eps_e, c.eps_0, c.y_out);
+        hipError_t rc = hipGetLastError();
+        if (rc != hipSuccess) return fail("k_sweep_group_draw_sde launch", rc);
         return 0;
     }
     if (draw) {

@@ -20,6 +20,10 @@
 // A draw from the posterior (k_sweep_group_draw) is the same geometry and forward half and, backwards, the reverse-time model's sample path
 // (tgp_sweep.hpp) instead of its moments: the sample state is one double per lane; a group continues from the next group's sample of ITS first
 // step, which that group gets from a walk over its own first Wd steps from the filtering mean with the real draws; the hand-over is checked on the samples.
+//
+// SDE-described models on irregular inputs (tgp_model_set_sde) run the same three calls and the draw in units of their own, the transition of every step
+// built per group from its gap: k_sweep_group_sde, k_sweep_group_adjoint_sde (4.14) and k_sweep_group_draw_sde (4.15; the walk's step from
+// x_(t+1) to x_t takes the gap in front of step t + 1).  plan() and enqueue() pick the unit by the plan's `sde`.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -48,7 +52,7 @@ int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char*
 const char* kernel_name(bool post, bool sde = false);      // sde: the model is SDE-described (k_sweep_group_sde)
 const char* adjoint_kernel_name();
 const char* adjoint_sde_kernel_name();      // the model is SDE-described (k_sweep_group_adjoint_sde)
-const char* draw_kernel_name();
+const char* draw_kernel_name(bool sde = false);      // sde: k_sweep_group_draw_sde
 // After the stream has been synchronised: tgp_sweep::finish's status bits, warm-ups and distances.  An adjoint call: bit 2, *wb and *dist_b are the
 // adjoint warm-up's; a draw call: the draw warm-up's, and the returned value is 0.
 double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* dist_b);

@@ -440,5 +440,9 @@ void launch_sde(int d, unsigned nwaves, hipStream_t stream, const GArgs& ka, con
 // tgp_sweep_group_adjoint_sde.hip: the adjoint gradient of such a model -- k_sweep_group_adjoint_sde<d, XS>; ka.Wb holds the adjoint's
 // warm-up, ka.part has 4 + tgp_sweep::group_adjoint_sde_sums(d) doubles per wave, gh_steps / gR_steps: device [T] or null
 void launch_adjoint_sde(int d, unsigned nwaves, hipStream_t stream, const GArgs& ka, const tgp_sweep::GroupSdeC& sc, double* gh_steps, double* gR_steps);
+// tgp_sweep_group_draw_sde.hip: a draw from the posterior of such a model -- k_sweep_group_draw_sde<d, XS>; ka.Wb holds the draw's warm-up,
+// eps_t [T][d] and eps_e [T] on the device, eps_0 [d] on the host (it travels in the kernel's arguments), y_out: device [T]
+void launch_draw_sde(int d, unsigned nwaves, hipStream_t stream, const GArgs& ka, const tgp_sweep::GroupSdeC& sc, const double* eps_t, const double* eps_e,
+                     const double* eps_0, double* y_out);
 
 }  // namespace tgp_sweep_group

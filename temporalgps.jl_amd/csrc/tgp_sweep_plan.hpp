@@ -385,6 +385,9 @@ constexpr int group_adjoint_sde_sums(int d) { return d + 2 * d * d + d * (d + 1)
 // waves resident per CU in that call, from the kernel's register counts as the others' (profiles/sweep_group_adjoint_sde_resources.txt): every
 // instantiation takes more than 256 registers, one wave per SIMD
 constexpr int group_adjoint_sde_waves_per_cu(int d) { return (void)d, 4; }
+// waves resident per CU in a draw call on an SDE-described model (k_sweep_group_draw_sde), from the kernel's register counts in the same way
+// (profiles/sweep_group_draw_sde_resources.txt): every instantiation takes more than 256 registers (301 .. 486), one wave per SIMD
+constexpr int group_draw_sde_waves_per_cu(int d) { return (void)d, 4; }
 
 // The steps [t0, t1) of group g (0 .. 7) of a wave, as the kernel and the tests compute them: the wave's groups hold the chunks
 // wave * owned - 1 .. wave * owned + 6.  runs: the group runs its chunk (group 0 only warms up); owned: it writes output and sums.
@@ -505,7 +508,7 @@ template <int D> inline bool plan_group_d(GroupPlan* e, const Forced& f, const M
     // chunk length: group_waves_per_cu waves per CU, every wave `owned` chunks of its own; a chunk holds the backward warm-up.  A multiple of 8 (the rows
     // of the observation stream), hence of the checkpoint block.
     const int owned = group_owned(post);
-    const int per_cu = m.sde ? (adjoint ? group_adjoint_sde_waves_per_cu(D) : group_sde_waves_per_cu(D, post))
+    const int per_cu = m.sde ? (adjoint ? group_adjoint_sde_waves_per_cu(D) : draw ? group_draw_sde_waves_per_cu(D) : group_sde_waves_per_cu(D, post))
                              : adjoint ? group_adjoint_waves_per_cu(D) : draw ? group_draw_waves_per_cu(D) : group_waves_per_cu(D, post);
     const int64_t slots = (int64_t)std::max(num_cu, 1) * per_cu * owned;
     int64_t C = up((int)std::min<int64_t>((T + slots - 1) / slots, 1 << 20), 8);
@@ -581,16 +584,12 @@ template <int D> inline bool plan_group_d(GroupPlan* e, const Forced& f, const M
 // The geometry of a group-sweep call (LTI form, or SDE-described: m.sde); false: the engine declines (`why` says so).  post: a posterior call (6 of a wave's 8 groups own
 // output instead of 7).  w_hint / wb_hint as make_plan's.  adjoint (with post): an adjoint call -- the backward slot carries the adjoint's warm-up Wa
 // (wb_hint: a Wa that a previous call needed, 0: the forward warm-up's value; a forced Wb forces Wa).  draw (with post): a draw call
-// (k_sweep_group_draw) -- the backward slot carries the draw's warm-up Wd (wb_hint: a Wd that a previous call needed, 0: the backward
+// (k_sweep_group_draw; SDE-described: k_sweep_group_draw_sde) -- the backward slot carries the draw's warm-up Wd (wb_hint: a Wd that a previous call needed, 0: the backward
 // warm-up's estimate; a forced Wb forces Wd; the chunk grows to hold it).
 inline bool plan_group(GroupPlan* p, const Forced& f, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why,
                        bool adjoint = false, bool draw = false) {
     if (m.d < kGroupMinD || m.d > kGroupMaxD) {
         if (why) *why = "state dimension";
-        return false;
-    }
-    if (m.sde && draw) {      // (the draw of an SDE-described model at these d: the general engine)
-        if (why) *why = "SDE-described model";
         return false;
     }
     if (T < kGroupMinT) {

@@ -1029,7 +1029,7 @@ def _posterior_rand_one_launch(post, eps_t, eps_e, eps_0):
 
 
 def _posterior_rand_sweep_entry(entry, post, eps_t, eps_e, eps_0):
-    """tgp_posterior_rand_missing on the sweep engine / tgp_posterior_rand_group: one argument list, one preparation of the buffers.  A NaN of a host
+    """tgp_posterior_rand_missing on the sweep engine / tgp_posterior_rand_group / tgp_posterior_rand_group_sde: one argument list, one preparation of the buffers.  A NaN of a host
     series is a missing step (the mask, with a finite value in y); a device series gets its mask from torch.isnan on the device.  None: not a posterior
     these calls take, or buffers they cannot read (the library was not asked); raises Unsupported where the library declines."""
     prior = post._prior
@@ -1107,6 +1107,17 @@ def posterior_rand_group(post, eps_t, eps_e, eps_0):
     return out
 
 
+def posterior_rand_group_sde(post, eps_t, eps_e, eps_0):
+    """posterior_rand_group for a prior bound through its SDE and time stamps (SDETransitions: irregularly spaced inputs, what
+    rand(rng, posterior(fx, y)(x_new)) merges into): ONE kernel of the group sweep (tgp_posterior_rand_group_sde, k_sweep_group_draw<sde>),
+    the transition of every step built from its gap.  Arguments and the use of the draws as there.  Raises Unsupported where the engine declines (use rand)."""
+    out = None if not isinstance(post, PosteriorLGSSM) else _posterior_rand_sweep_entry("tgp_posterior_rand_group_sde", post, eps_t, eps_e, eps_0)
+    if out is None:
+        raise _lib.Unsupported(_lib.EUNSUPPORTED, "posterior_rand_group_sde: a lazy posterior of a Forward model with scalar observations, with y and the "
+                                                   "draws of matching sizes on one side (host or device)")
+    return out
+
+
 def _posterior_rand_dense(post, eps_t, eps_e, eps_0):
     """rand of a posterior that has not been evaluated, on the dense engine (tgp_posterior_rand_missing: 16 < d <= 64, p <= 16, diagonal noise -- missing
     steps, per-step blocks and vector observations included; the persistent filter keeps its states and records, the draw pass walks back on them across
@@ -1171,7 +1182,7 @@ def _posterior_rand_dense(post, eps_t, eps_e, eps_0):
 def rand(rng_or_eps, model, method=None):
     """lgssm.jl:65-69. `rng_or_eps` is a numpy Generator, or the explicit (eps_t (T,d), eps_e (T,), eps_0 (d,)).
     method: None (default policy) or "sweep" -- a lazy posterior on the sweep engines' draw kernels alone: posterior_rand_group at 5 <= d <= 8
-    (k_sweep_group_draw), the lane sweep's k_sweep_draw at d <= 4; raises Unsupported where neither serves."""
+    (k_sweep_group_draw; posterior_rand_group_sde where the prior's transitions are SDETransitions), the lane sweep's k_sweep_draw at d <= 4; raises Unsupported where neither serves."""
     if method not in (None, "sweep"):
         raise ValueError(f"rand: unknown method {method!r}")
     if method == "sweep" and not (isinstance(model, PosteriorLGSSM) and model._model is None):
@@ -1184,6 +1195,8 @@ def rand(rng_or_eps, model, method=None):
             eps = (et, ee, rng_or_eps.standard_normal(model.dim))
         if method == "sweep":
             if 5 <= model.dim <= 8:
+                if isinstance(getattr(model._prior, "transitions", None), SDETransitions):
+                    return posterior_rand_group_sde(model, *eps)
                 return posterior_rand_group(model, *eps)
             y1 = _posterior_rand_sweep(model, *eps)
             if y1 is None:

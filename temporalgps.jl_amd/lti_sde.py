@@ -476,8 +476,10 @@ def logpdf(fx, y):
 def rand(rng, fx, N=None, method=None):
     """lti_sde.jl:48-58 / posterior_lti_sde.jl:48-58.
     method: None (default policy) or "sweep" -- ONE kernel of the sweep engines over the T training steps (L.rand(..., method="sweep"): the group sweep's
-    draw kernel at 5 <= d <= 8, the lane sweep's at d <= 4; T >= 2048) for a posterior queried at its training inputs on a RegularSpacing with NaNs in y;
-    other inputs raise NotImplementedError, and Unsupported is raised where the device declines."""
+    draw kernel at 5 <= d <= 8, the lane sweep's at d <= 4; T >= 2048) for a posterior queried at its training inputs on a RegularSpacing with NaNs in y
+    (other prediction inputs raise NotImplementedError there), or for a posterior whose training inputs are a plain array, at any prediction inputs (the
+    merged series; k_sweep_group_draw<sde> at 5 <= d <= 8); a prior raises NotImplementedError, and Unsupported is raised where the device
+    declines."""
     if N is not None:
         return np.stack([rand(rng, fx, method=method) for _ in range(N)], axis=1)
     if method == "sweep":
@@ -581,6 +583,20 @@ class FinitePosteriorLTISDE:
         noise replaced -- a model with a missing mask, which the sweep engines' draw kernels serve in one launch.  Same distribution; the draws of one
         rng are consumed in another order than over the 2T merged steps."""
         d = self.f.data
+        if not isinstance(d["x"], RegularSpacing):
+            # training inputs on a plain array: the model is bound through its SDE and time stamps, and the group sweep's draw kernel for such models
+            # (L.posterior_rand_group_sde, k_sweep_group_draw<sde>, DESIGN 4.15) takes irregular gaps, tied stamps and missing steps alike -- so any
+            # prediction inputs are served: the same-inputs model where they are the training inputs and y has NaNs, else _rand_merged's joined series
+            if _same_sorted_inputs(self.x, d["x"]) and np.isnan(d["y"]).any():
+                model = self._posterior_model(d["x"], d["sigma2"], d["y"])
+                S_new = _noise(self.sigma2, len(self.x)) if len(self.sigma2) > 1 else self.sigma2
+                return L.rand(rng, L.replace_observation_noise_cov(L.posterior(model, d["y"]), S_new), method="sweep")
+            npr = len(self.x)
+            x, S, y, _, pr = self._merge(np.full(npr, self.LARGE_VAR))
+            s_full = np.zeros(len(x))
+            s_full[pr] = _noise(self.sigma2, npr)
+            post = L.replace_observation_noise_cov(L.posterior(self._posterior_model(x, S, y), y), s_full)
+            return L.rand(rng, post, method="sweep")[pr]
         if not (isinstance(self.x, RegularSpacing) and _same_sorted_inputs(self.x, d["x"]) and np.isnan(d["y"]).any()):
             raise NotImplementedError("rand(method='sweep'): a posterior at its training inputs (RegularSpacing, NaNs in y) only")
         model = self._posterior_model(d["x"], d["sigma2"], d["y"])
