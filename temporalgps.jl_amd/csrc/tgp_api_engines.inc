@@ -184,8 +184,11 @@ bool sweep_group_sde_eligible(const tgp_handle* h, uint32_t flags, bool explicit
     return h->sde_closed && h->opt_sde_closed && !h->sde_coef_host.empty() && h->mv.sa == 0;
 }
 
-// The host model the plans of both engines read, from the staged blocks of the bound model
-tgp_sweep::ModelHost sweep_host_model(const tgp_handle* h) {
+// The host model the plans of both engines read, from the staged blocks of the bound model.  record_pinf: the stationary covariance of an SDE-described
+// model is the one tgp_model_set_sde took (the closed-form record; tgp_model_set_x0 may have replaced the prior since) -- the adjoint calls and the group
+// sweep's draw.  tgp_logpdf, the posterior calls and the lane sweep's draw pass none: the bound x0P stands for Pinf.  (The plans read Pinf, coef and
+// tau_typ of SDE-described models only: tgp_sweep_plan.hpp.)
+tgp_sweep::ModelHost sweep_host_model(const tgp_handle* h, bool record_pinf) {
     const int d = h->d;
     const size_t dd = (size_t)d * d;
     const double* q = h->sweepm.data();
@@ -201,495 +204,289 @@ tgp_sweep::ModelHost sweep_host_model(const tgp_handle* h) {
     mh.x0m = h->x0m.data();
     mh.x0P = h->x0P.data();
     mh.coef = h->sde ? h->sde_coef_host.data() : nullptr;
+    if (h->sde && record_pinf) mh.Pinf = h->sde_coef_host.data() + d + 2 * dd;
     mh.tau_typ = h->sweep_tau;
     return mh;
 }
 
-// What sweep_run needs of an engine: the lane sweep (tgp_sweep.hip) and the group sweep (tgp_sweep_group.hip) behind one call sequence.  Plain function
-// pointers on the handle (no allocation on the call path); `post`: the call asks for the posterior marginals.
-struct SweepEngineOps {
-    const char* tag;
-    const char* kname;
-    bool post;
-    bool (*plan)(tgp_handle* h, const tgp_sweep::ModelHost& mh, bool post, int W, int Wb, std::string* why);      // (with the handle's forced geometry)
+// The call kinds of the sweep engines.  Each has a second warm-up of its own beside the forward W -- the smoother's Wb, the draw's Wd, the adjoint's
+// Wa --, remembered apart on the handle, forced by TGP_OPT_SWEEP_WARMUP_BACK and reported in the backward slots of tgp_sweep_info.
+enum class SweepKind { marginals = 0, draw = 1, adjoint = 2 };      // (marginals: logpdf alone, or with the posterior marginals)
+int& sweep_back_slot(tgp_handle* h, SweepKind kind) { return kind == SweepKind::draw ? h->sweep_Wd : kind == SweepKind::adjoint ? h->sweep_Wa : h->sweep_Wb; }
+// per kind: the tag and the slot's name in the TGP_STEADY_DEBUG lines; why a call with status bit 4 / bit 8 is declined (null: a silent decline)
+const struct { const char *tag, *slot, *not_pd, *not_finite; } kSweepKindText[3] = {
+    {"", "Wb", nullptr, nullptr},
+    {" draw", "Wd", "a Cholesky pivot of the draw is not positive", "non-finite values in the draw"},
+    {" adjoint", "Wa", "an innovation variance is not positive", "non-finite values in the pass"}};
+
+// What sweep_attempts needs of an engine: the lane sweep (tgp_sweep.hip, d <= 4) and the group sweep (tgp_sweep_group.hip, 5 <= d <= 8) behind one call
+// sequence.  Plain function pointers on the handle, two static instances (no allocation on the call path).  Wk: the kind's second warm-up; post: a
+// marginals call asks for the posterior marginals.
+struct SweepOps {
+    const char* tag;       // in the TGP_STEADY_DEBUG lines
+    const char* name;      // in the entry points' error texts
+    const char* (*kname)(const tgp_handle* h, SweepKind kind, bool post);
+    // (creates the engine at the first call; with the handle's forced geometry)
+    bool (*plan)(tgp_handle* h, const tgp_sweep::ModelHost& mh, SweepKind kind, bool post, int W, int Wk, std::string* why);
     int (*enqueue)(tgp_handle* h, const tgp_sweep::Call& c, const char** kname, std::string* err);
-    double (*finish)(tgp_handle* h, int* status, int* w, int* wb, double* dist_f, double* dist_b);
+    double (*finish)(tgp_handle* h, SweepKind kind, int* status, int* w, int* wk, double* dist_f, double* dist_k);      // (a draw: returns 0)
     void (*geometry)(tgp_handle* h, int* C, int64_t* nwaves);
+    // behind finish of an adjoint call whose status is clean.  so (null: the LTI form, to o): the sums over the closed form's coefficients
+    void (*adjoint_blocks)(tgp_handle* h, const tgp_sweep::ModelHost& mh, const tgp_sweep::AdjointOut& o, const tgp_sweep::AdjointSdeOut* so);
 };
 
-// Runs a logpdf / posterior call on one of the sweep engines: staging ONCE, up to four attempts with doubled warm-ups, the engine switched off for the
-// bound model where it cannot serve it.  *served = false: it declined (nothing the caller must undo); the caller goes on to the general engine.
-int sweep_run(tgp_handle* h, const SweepEngineOps& eng, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, double* mean_out,
-              double* var_out, double* lml_out, bool* served) {
-    *served = false;
-    static const bool dbg = getenv("TGP_STEADY_DEBUG") != nullptr;
-    const tgp_sweep::ModelHost mh = sweep_host_model(h);
-    const bool idev = (flags & TGP_IN_DEVICE) != 0, odev = (flags & TGP_OUT_DEVICE) != 0;
-    const bool rshared = (flags & TGP_SHARED_R) != 0;
-    const size_t nT = (size_t)h->T * sizeof(double);
-    int W = h->sweep_W, Wb = h->sweep_Wb;
-    for (int64_t& v : h->sweep_info) v = 0;
-    // inputs and outputs are staged ONCE, in front of the attempts (round-5 advice: a host-resident series was uploaded again by every retry)
-    {
-        std::string why;
-        if (!eng.plan(h, mh, eng.post, W, Wb, &why)) {
-            if (dbg) fprintf(stderr, "[tgp %s] does not apply: %s\n", eng.tag, why.c_str());
-            h->sweep_state = -1;
-            return TGP_OK;
-        }
-    }
-    CallTimer tm(h, /*clear=*/false);
-    const void* pR = nullptr;
-    if (mean_out) TRY(stage_in(h, h->bRnew, Rnew, rshared ? sizeof(double) : nT, idev, &pR));
-    TRY(set_obs(h, y, missing, flags));
-    tm.inputs_done();
-    double *dm = nullptr, *dv = nullptr;
-    TRY(stage_out(h, h->bo1, mean_out, nT, odev, &dm));
-    TRY(stage_out(h, h->bo2, var_out, nT, odev, &dv));
-    for (int attempt = 0; attempt < 4; ++attempt) {
-        if (attempt > 0) {
-            std::string why;
-            if (!eng.plan(h, mh, eng.post, W, Wb, &why)) {
-                if (dbg) fprintf(stderr, "[tgp %s] does not apply: %s\n", eng.tag, why.c_str());
-                h->sweep_state = -1;
-                return TGP_OK;
-            }
-        }
-        tgp_sweep::Call c;
-        c.T = h->T;
-        c.y = h->mv.y;
-        c.mask = h->mv.missing;
-        c.R = h->mv.sR != 0 ? h->mv.R : nullptr;
-        c.hh = h->mv.sh != 0 ? h->mv.h : nullptr;
-        c.tau = h->sde ? h->btau.d() : nullptr;
-        c.Rnew = static_cast<const double*>(pR);
-        c.rnew_per_step = (mean_out && !rshared) ? 1 : 0;
-        c.mean = dm;
-        c.var = dv;
-        {
-            std::string err;
-            const char* kname = eng.kname;
-            LaunchScope ls(h, kname);
-            if (eng.enqueue(h, c, &kname, &err) != 0) return h->fail(TGP_EHIP, err);
-        }
-        tm.kernels_done();
-        if (h->timing) (void)hipEventRecord(h->ev[3], h->stream);
-        HIPCHK(hipStreamSynchronize(h->stream));
-        resolve_profile(h);
-        int status = 0, w = 0, wb = 0;
-        const double lml = eng.finish(h, &status, &w, &wb, &h->sweep_dist[0], &h->sweep_dist[1]);
-        int C = 0;
-        int64_t nw = 0;
-        eng.geometry(h, &C, &nw);
-        h->sweep_info[1] = C; h->sweep_info[2] = w; h->sweep_info[3] = wb; h->sweep_info[4] = nw; h->sweep_info[5] = attempt + 1; h->sweep_info[6] = status;
-        if (dbg) fprintf(stderr, "[tgp %s] attempt %d: C %d W %d Wb %d waves %lld status %d dist %.3g / %.3g\n", eng.tag, attempt, C, w, wb, (long long)nw, status, h->sweep_dist[0], h->sweep_dist[1]);
-        if (status & 12) {      // not positive definite / non-finite values: the general engine reports it the way it always has
-            if (status & 4) h->sweep_state = -1;      // (a property of the model, not of this series: later calls do not pay for a launch that cannot serve them)
-            return TGP_OK;
-        }
-        if (status & 3) {       // a warm-up was too short: longer ones (a forced geometry is a test's: report, do not repair)
-            if (h->sweep_fW || h->sweep_fWb || h->sweep_fC) return TGP_OK;
-            if (status & 1) W = 2 * w;
-            if (status & 2) Wb = 2 * wb;
-            continue;
-        }
-        TRY(copy_back(h, mean_out, dm, nT, odev));
-        TRY(copy_back(h, var_out, dv, nT, odev));
-        if ((mean_out && !odev)) HIPCHK(hipStreamSynchronize(h->stream));
-        read_timing(h);
-        note_served(h, Served::sweep, 0, lml, lml_out);
-        h->sweep_W = w;
-        h->sweep_Wb = wb;
-        h->sweep_state = 1;
-        h->sweep_info[0] = 1;
-        *served = true;
-        return TGP_OK;
-    }
-    h->sweep_state = -1;      // four attempts, warm-ups still too short: a model that mixes too slowly for this engine
-    return TGP_OK;
-}
-
-// The lane sweep (d <= 4; LTI and SDE form)
-int sweep_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, double* mean_out, double* var_out,
-               double* lml_out, bool* served) {
-    if (!h->sweep) h->sweep = tgp_sweep::create();
-    const SweepEngineOps eng = {
-        "sweep", tgp_sweep::kernel_name(h->d, h->sde, mean_out != nullptr), mean_out != nullptr,
-        [](tgp_handle* hh, const tgp_sweep::ModelHost& mh, bool, int W, int Wb, std::string* why) {
-            tgp_sweep::force_geometry(hh->sweep, hh->sweep_fC, hh->sweep_fW, hh->sweep_fWb);
-            return tgp_sweep::plan(hh->sweep, mh, hh->T, W, Wb, hh->num_cu, why);
-        },
-        [](tgp_handle* hh, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep::enqueue(hh->sweep, hh->stream, c, kname, err); },
-        [](tgp_handle* hh, int* status, int* w, int* wb, double* df, double* db) { return tgp_sweep::finish(hh->sweep, status, w, wb, df, db); },
-        [](tgp_handle* hh, int* C, int64_t* nw) { tgp_sweep::geometry(hh->sweep, C, nullptr, nullptr, nw); }};
-    return sweep_run(h, eng, y, missing, flags, Rnew, mean_out, var_out, lml_out, served);
-}
-
-// The group sweep (5 <= d <= 8; LTI form, and SDE form where sweep_group_sde_eligible says so)
-int sweep_group_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, double* mean_out, double* var_out,
-                     double* lml_out, bool* served) {
-    if (!h->sweep_group) h->sweep_group = tgp_sweep_group::create();
-    const SweepEngineOps eng = {
-        "sweep group", tgp_sweep_group::kernel_name(mean_out != nullptr, h->sde), mean_out != nullptr,
-        [](tgp_handle* hh, const tgp_sweep::ModelHost& mh, bool post, int W, int Wb, std::string* why) {
-            tgp_sweep_group::force_geometry(hh->sweep_group, hh->sweep_fC, hh->sweep_fW, hh->sweep_fWb);
-            return tgp_sweep_group::plan(hh->sweep_group, mh, hh->T, W, Wb, hh->num_cu, post, why);
-        },
-        [](tgp_handle* hh, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep_group::enqueue(hh->sweep_group, hh->stream, c, kname, err); },
-        [](tgp_handle* hh, int* status, int* w, int* wb, double* df, double* db) { return tgp_sweep_group::finish(hh->sweep_group, status, w, wb, df, db); },
-        [](tgp_handle* hh, int* C, int64_t* nw) { tgp_sweep_group::geometry(hh->sweep_group, C, nullptr, nullptr, nw); }};
-    return sweep_run(h, eng, y, missing, flags, Rnew, mean_out, var_out, lml_out, served);
-}
-
-// What sweep_draw_run needs of an engine: the lane sweep's draw kernel and the group sweep's behind one call sequence (SweepAdjointOps' twin; Wd: the draw's
-// warm-up, in the lane engine's draw slot and the group engine's backward slot).
-struct SweepDrawOps {
-    const char* tag;
-    const char* kname;
-    bool (*plan)(tgp_handle* h, const tgp_sweep::ModelHost& mh, int W, int Wd, std::string* why);      // (with the handle's forced geometry)
-    int (*enqueue)(tgp_handle* h, const tgp_sweep::Call& c, const char** kname, std::string* err);
-    void (*finish)(tgp_handle* h, int* status, int* w, int* wd, double* dist_f, double* dist_d);
-    void (*geometry)(tgp_handle* h, int* C, int64_t* nwaves);
-};
-
-// rand of the posterior on one of the sweep engines: sweep_run's staging and repair loop around a draw kernel.  The draw pass sits in the backward slots
-// of tgp_sweep_info (its warm-up Wd is remembered apart from Wb; TGP_OPT_SWEEP_WARMUP_BACK forces it here).  *served = false with *why set: the engine
-// declined, nothing was written to y_out.
-int sweep_draw_run(tgp_handle* h, const SweepDrawOps& eng, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, const double* eps_t,
-                   const double* eps_e, const double* eps_0, double* y_out, bool* served, std::string* why) {
-    *served = false;
-    static const bool dbg = getenv("TGP_STEADY_DEBUG") != nullptr;
-    const int d = h->d;
-    const tgp_sweep::ModelHost mh = sweep_host_model(h);
-    const bool idev = (flags & TGP_IN_DEVICE) != 0, odev = (flags & TGP_OUT_DEVICE) != 0;
-    const bool rshared = (flags & TGP_SHARED_R) != 0;
-    const size_t nT = (size_t)h->T * sizeof(double);
-    const bool forced = h->sweep_fW || h->sweep_fWb || h->sweep_fC;
-    int W = h->sweep_W, Wd = h->sweep_Wd;
-    for (int64_t& v : h->sweep_info) v = 0;
-    auto replan = [&]() {
-        std::string w;
-        if (eng.plan(h, mh, W, Wd, &w)) return true;
-        if (dbg) fprintf(stderr, "[tgp %s] does not apply: %s\n", eng.tag, w.c_str());
-        h->sweep_state = -1;
-        *why = "the sweep engine's plan declines the model (" + w + ")";
-        return false;
-    };
-    if (!replan()) return TGP_OK;
-    // inputs and the output are staged ONCE, in front of the attempts.  The draw goes to the handle's own buffer and reaches y_out behind the checks:
-    // a declined call leaves a device y_out untouched as well.
-    CallTimer tm(h, /*clear=*/false);
-    const void *pR = nullptr, *pet = nullptr, *pee = nullptr;
-    TRY(stage_in(h, h->bRnew, Rnew, rshared ? sizeof(double) : nT, idev, &pR));
-    TRY(set_obs(h, y, missing, flags));
-    TRY(stage_in(h, h->beps_t, eps_t, (size_t)h->T * d * sizeof(double), idev, &pet));
-    TRY(stage_in(h, h->beps_e, eps_e, nT, idev, &pee));
-    tm.inputs_done();
-    HIPCHK(h->bo1.ensure(nT));
-    double* dy = h->bo1.d();
-    for (int attempt = 0; attempt < 4; ++attempt) {
-        if (attempt > 0 && !replan()) return TGP_OK;
-        tgp_sweep::Call c;
-        c.T = h->T;
-        c.y = h->mv.y;
-        c.mask = h->mv.missing;
-        c.R = h->mv.sR != 0 ? h->mv.R : nullptr;
-        c.hh = h->mv.sh != 0 ? h->mv.h : nullptr;
-        c.tau = h->sde ? h->btau.d() : nullptr;
-        c.Rnew = static_cast<const double*>(pR);
-        c.rnew_per_step = rshared ? 0 : 1;
-        c.eps_t = static_cast<const double*>(pet);
-        c.eps_e = static_cast<const double*>(pee);
-        for (int k = 0; k < d; ++k) c.eps_0[k] = eps_0[k];
-        c.y_out = dy;
-        {
-            std::string err;
-            const char* kname = eng.kname;
-            LaunchScope ls(h, kname);
-            if (eng.enqueue(h, c, &kname, &err) != 0) return h->fail(TGP_EHIP, err);
-        }
-        tm.kernels_done();
-        if (h->timing) (void)hipEventRecord(h->ev[3], h->stream);
-        HIPCHK(hipStreamSynchronize(h->stream));
-        resolve_profile(h);
-        int status = 0, w = 0, wd = 0;
-        eng.finish(h, &status, &w, &wd, &h->sweep_dist[0], &h->sweep_dist[1]);
-        int C = 0;
-        int64_t nw = 0;
-        eng.geometry(h, &C, &nw);
-        h->sweep_info[1] = C; h->sweep_info[2] = w; h->sweep_info[3] = wd; h->sweep_info[4] = nw; h->sweep_info[5] = attempt + 1; h->sweep_info[6] = status;
-        if (dbg) fprintf(stderr, "[tgp %s] attempt %d: C %d W %d Wd %d waves %lld status %d dist %.3g / %.3g\n", eng.tag, attempt, C, w, wd, (long long)nw, status, h->sweep_dist[0], h->sweep_dist[1]);
-        if (status & 12) {      // not positive definite / non-finite values: the evaluated route reports it the way it always has
-            if (status & 4) h->sweep_state = -1;
-            *why = (status & 4) ? "a Cholesky pivot of the draw is not positive" : "non-finite values in the draw";
-            return TGP_OK;
-        }
-        if (status & 3) {       // a warm-up was too short: longer ones (a forced geometry is a test's: report, do not repair)
-            if (forced) {
-                *why = "a warm-up of the forced geometry is too short (tgp_sweep_info)";
-                return TGP_OK;
-            }
-            if (status & 1) W = 2 * w;
-            if (status & 2) Wd = 2 * wd;
-            continue;
-        }
-        if (odev) HIPCHK(hipMemcpyAsync(y_out, dy, nT, hipMemcpyDeviceToDevice, h->stream));
-        else HIPCHK(hipMemcpyAsync(y_out, dy, nT, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        read_timing(h);
-        note_served(h, Served::sweep, 0, 0.0, nullptr);
-        h->sweep_W = w;
-        h->sweep_Wd = wd;
-        h->sweep_state = 1;
-        h->sweep_info[0] = 1;
-        *served = true;
-        return TGP_OK;
-    }
-    h->sweep_state = -1;      // four attempts, warm-ups still too short: a model that mixes too slowly for this engine
-    *why = "the warm-ups stayed too short over four attempts";
-    return TGP_OK;
-}
-
-// The draw on the lane sweep (k_sweep_draw, DESIGN 4.7; LTI and SDE form)
-int sweep_draw_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, const double* eps_t, const double* eps_e,
-                    const double* eps_0, double* y_out, bool* served, std::string* why) {
-    *served = false;
-    if (!h->sweep) h->sweep = tgp_sweep::create();
-    const SweepDrawOps eng = {
-        "sweep draw", tgp_sweep::kernel_name(h->d, h->sde, true, true),
-        [](tgp_handle* hh, const tgp_sweep::ModelHost& m, int W, int Wd, std::string* w) {
-            tgp_sweep::force_geometry(hh->sweep, hh->sweep_fC, hh->sweep_fW, 0, hh->sweep_fWb);
-            return tgp_sweep::plan(hh->sweep, m, hh->T, W, hh->sweep_Wb, hh->num_cu, w, Wd);
-        },
-        [](tgp_handle* hh, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep::enqueue(hh->sweep, hh->stream, c, kname, err); },
-        [](tgp_handle* hh, int* status, int* w, int* wd, double* df, double* dd) { (void)tgp_sweep::finish(hh->sweep, status, w, nullptr, df, dd, wd); },
-        [](tgp_handle* hh, int* C, int64_t* nw) { tgp_sweep::geometry(hh->sweep, C, nullptr, nullptr, nw); }};
-    return sweep_draw_run(h, eng, y, missing, flags, Rnew, eps_t, eps_e, eps_0, y_out, served, why);
-}
-
-// The same at 5 <= d <= 8 on the group sweep (k_sweep_group_draw, DESIGN 4.12; LTI form): the posterior call's geometry with Wd in its backward slot.
-int sweep_group_draw_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, const double* eps_t,
-                          const double* eps_e, const double* eps_0, double* y_out, bool* served, std::string* why) {
-    *served = false;
-    if (!h->sweep_group) h->sweep_group = tgp_sweep_group::create();
-    const SweepDrawOps eng = {
-        "sweep group draw", tgp_sweep_group::draw_kernel_name(),
-        [](tgp_handle* hh, const tgp_sweep::ModelHost& m, int W, int Wd, std::string* w) {
-            tgp_sweep_group::force_geometry(hh->sweep_group, hh->sweep_fC, hh->sweep_fW, hh->sweep_fWb);
-            return tgp_sweep_group::plan(hh->sweep_group, m, hh->T, W, Wd, hh->num_cu, /*post=*/true, w, /*adjoint=*/false, /*draw=*/true);
-        },
-        [](tgp_handle* hh, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep_group::enqueue(hh->sweep_group, hh->stream, c, kname, err); },
-        [](tgp_handle* hh, int* status, int* w, int* wd, double* df, double* dd) { (void)tgp_sweep_group::finish(hh->sweep_group, status, w, wd, df, dd); },
-        [](tgp_handle* hh, int* C, int64_t* nw) { tgp_sweep_group::geometry(hh->sweep_group, C, nullptr, nullptr, nw); }};
-    return sweep_draw_run(h, eng, y, missing, flags, Rnew, eps_t, eps_e, eps_0, y_out, served, why);
-}
-
-// The same for an SDE-described model on irregular inputs (k_sweep_group_draw_sde, DESIGN 4.15): the SDE posterior call's geometry with Wd in its
-// backward slot; Pinf from the closed-form record, so that a prior replaced by tgp_model_set_x0 is served (as the adjoint call's).  The plan callback is
-// a plain function pointer: it rebuilds the host model from the handle.
-int sweep_group_draw_sde_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, const double* eps_t,
-                              const double* eps_e, const double* eps_0, double* y_out, bool* served, std::string* why) {
-    *served = false;
-    if (!h->sweep_group) h->sweep_group = tgp_sweep_group::create();
-    const SweepDrawOps eng = {
-        "sweep group draw sde", tgp_sweep_group::draw_kernel_name(true),
-        [](tgp_handle* hh, const tgp_sweep::ModelHost& m, int W, int Wd, std::string* w) {
-            tgp_sweep::ModelHost mp = m;
-            mp.Pinf = hh->sde_coef_host.data() + hh->d + 2 * (size_t)hh->d * hh->d;
-            tgp_sweep_group::force_geometry(hh->sweep_group, hh->sweep_fC, hh->sweep_fW, hh->sweep_fWb);
-            return tgp_sweep_group::plan(hh->sweep_group, mp, hh->T, W, Wd, hh->num_cu, /*post=*/true, w, /*adjoint=*/false, /*draw=*/true);
-        },
-        [](tgp_handle* hh, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep_group::enqueue(hh->sweep_group, hh->stream, c, kname, err); },
-        [](tgp_handle* hh, int* status, int* w, int* wd, double* df, double* dd) { (void)tgp_sweep_group::finish(hh->sweep_group, status, w, wd, df, dd); },
-        [](tgp_handle* hh, int* C, int64_t* nw) { tgp_sweep_group::geometry(hh->sweep_group, C, nullptr, nullptr, nw); }};
-    return sweep_draw_run(h, eng, y, missing, flags, Rnew, eps_t, eps_e, eps_0, y_out, served, why);
-}
-
-// What sweep_adjoint_run needs of an engine: the lane sweep's adjoint kernels and the group sweep's behind one call sequence (SweepEngineOps' twin; Wa: the
-// adjoint's warm-up, in the engines' backward slot).
-struct SweepAdjointOps {
-    const char* tag;
-    const char* kname;
-    bool (*plan)(tgp_handle* h, const tgp_sweep::ModelHost& mh, int W, int Wa, std::string* why);      // (with the handle's forced geometry)
-    int (*enqueue)(tgp_handle* h, const tgp_sweep::Call& c, const char** kname, std::string* err);
-    double (*finish)(tgp_handle* h, int* status, int* w, int* wa, double* dist_f, double* dist_b);
-    void (*geometry)(tgp_handle* h, int* C, int64_t* nwaves);
-};
-
-// The adjoint gradient on one of the sweep engines: sweep_run's staging and repair loop around an adjoint kernel.  The adjoint pass sits in the backward
-// slots of tgp_sweep_info (its warm-up Wa is remembered apart from Wb and Wd; TGP_OPT_SWEEP_WARMUP_BACK forces it here).  The per-step gradients go to the
-// handle's own buffers and reach gh_steps / gR_steps behind the checks, the block gradients are written behind them too (write_blocks):
-// *served = false with *why set: the engine declined, no output was written.
-template <class WriteBlocks>
-int sweep_adjoint_run(tgp_handle* h, const SweepAdjointOps& eng, const tgp_sweep::ModelHost& mh, bool sde, const double* y, const uint8_t* missing, uint32_t flags,
-                      double* lml_out, double* gh_steps, double* gR_steps, bool* served, std::string* why, WriteBlocks&& write_blocks) {
-    *served = false;
-    static const bool dbg = getenv("TGP_STEADY_DEBUG") != nullptr;
-    const bool odev = (flags & TGP_OUT_DEVICE) != 0;
-    const size_t nT = (size_t)h->T * sizeof(double);
-    const bool forced = h->sweep_fW || h->sweep_fWb || h->sweep_fC;
-    int W = h->sweep_W, Wa = h->sweep_Wa;
-    for (int64_t& v : h->sweep_info) v = 0;
-    auto replan = [&]() {
-        std::string w;
-        if (eng.plan(h, mh, W, Wa, &w)) return true;
-        if (dbg) fprintf(stderr, "[tgp %s] does not apply: %s\n", eng.tag, w.c_str());
-        h->sweep_state = -1;
-        *why = "the sweep engine's plan declines the model (" + w + ")";
-        return false;
-    };
-    if (!replan()) return TGP_OK;
-    CallTimer tm(h, /*clear=*/false);
-    TRY(set_obs(h, y, missing, flags));
-    tm.inputs_done();
-    double *dgh = nullptr, *dgR = nullptr;
-    if (gh_steps) {
-        HIPCHK(h->bo1.ensure(nT));
-        dgh = h->bo1.d();
-    }
-    if (gR_steps) {
-        HIPCHK(h->bo2.ensure(nT));
-        dgR = h->bo2.d();
-    }
-    for (int attempt = 0; attempt < 4; ++attempt) {
-        if (attempt > 0 && !replan()) return TGP_OK;
-        tgp_sweep::Call c;
-        c.T = h->T;
-        c.y = h->mv.y;
-        c.mask = h->mv.missing;
-        c.R = h->mv.sR != 0 ? h->mv.R : nullptr;
-        c.hh = h->mv.sh != 0 ? h->mv.h : nullptr;
-        c.tau = sde ? h->btau.d() : nullptr;
-        c.adjoint = true;
-        c.gh_steps = dgh;
-        c.gR_steps = dgR;
-        {
-            std::string err;
-            const char* kname = eng.kname;
-            LaunchScope ls(h, kname);
-            if (eng.enqueue(h, c, &kname, &err) != 0) return h->fail(TGP_EHIP, err);
-        }
-        tm.kernels_done();
-        if (h->timing) (void)hipEventRecord(h->ev[3], h->stream);
-        HIPCHK(hipStreamSynchronize(h->stream));
-        resolve_profile(h);
-        int status = 0, w = 0, wa = 0;
-        const double lml = eng.finish(h, &status, &w, &wa, &h->sweep_dist[0], &h->sweep_dist[1]);
-        int C = 0;
-        int64_t nw = 0;
-        eng.geometry(h, &C, &nw);
-        h->sweep_info[1] = C; h->sweep_info[2] = w; h->sweep_info[3] = wa; h->sweep_info[4] = nw; h->sweep_info[5] = attempt + 1; h->sweep_info[6] = status;
-        if (dbg) fprintf(stderr, "[tgp %s] attempt %d: C %d W %d Wa %d waves %lld status %d dist %.3g / %.3g\n", eng.tag, attempt, C, w, wa, (long long)nw, status, h->sweep_dist[0], h->sweep_dist[1]);
-        if (status & 12) {      // not positive definite / non-finite values: the tangent scans report it the way they always have
-            if (status & 4) h->sweep_state = -1;
-            *why = (status & 4) ? "an innovation variance is not positive" : "non-finite values in the pass";
-            return TGP_OK;
-        }
-        if (status & 3) {       // a warm-up was too short: longer ones (a forced geometry is a test's: report, do not repair)
-            if (forced) {
-                *why = "a warm-up of the forced geometry is too short (tgp_sweep_info)";
-                return TGP_OK;
-            }
-            if (status & 1) W = 2 * w;
-            if (status & 2) Wa = 2 * wa;
-            continue;
-        }
-        if (gh_steps) HIPCHK(hipMemcpyAsync(gh_steps, dgh, nT, odev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
-        if (gR_steps) HIPCHK(hipMemcpyAsync(gR_steps, dgR, nT, odev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
-        if (gh_steps || gR_steps) HIPCHK(hipStreamSynchronize(h->stream));
-        write_blocks();
-        read_timing(h);
-        note_served(h, Served::sweep, 0, lml, lml_out);
-        h->sweep_W = w;
-        h->sweep_Wa = wa;
-        h->sweep_state = 1;
-        h->sweep_info[0] = 1;
-        *served = true;
-        return TGP_OK;
-    }
-    h->sweep_state = -1;      // four attempts, warm-ups still too short: a model that mixes too slowly for this engine
-    *why = "the warm-ups stayed too short over four attempts";
-    return TGP_OK;
-}
-
-// The adjoint gradient on the lane sweep (k_sweep_adjoint, DESIGN 4.8; LTI form).
-// so (null: the LTI form): an SDE-described model -- k_sweep_adjoint_sde (DESIGN 4.9), the sums over the closed form's coefficients go to *so and `o` is unused.
-int sweep_adjoint_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, const tgp_sweep::AdjointOut& o,
-                       double* gh_steps, double* gR_steps, bool* served, std::string* why, const tgp_sweep::AdjointSdeOut* so = nullptr) {
-    *served = false;
-    if (!h->sweep) h->sweep = tgp_sweep::create();
-    const int d = h->d;
-    const size_t dd = (size_t)d * d;
-    const double* q = h->sweepm.data();
-    tgp_sweep::ModelHost mh;
-    mh.d = d;
-    mh.sde = so != nullptr;
-    mh.A = so ? h->sde_A1Q1_host.data() : q;
-    mh.a = q + dd;
-    mh.Q = so ? h->sde_A1Q1_host.data() + dd : q + dd + d;
-    mh.H = q + 2 * dd + d;
-    mh.hh = q[2 * dd + 2 * d];
-    mh.R = h->sweep_Rrep;
-    mh.x0m = h->x0m.data();
-    mh.x0P = h->x0P.data();
-    if (so) {      // (the stationary covariance as tgp_model_set_sde took it: tgp_model_set_x0 may have replaced the prior since)
-        mh.coef = h->sde_coef_host.data();
-        mh.Pinf = h->sde_coef_host.data() + d + 2 * dd;
-        mh.tau_typ = h->sweep_tau;
-    }
-    const SweepAdjointOps eng = {
-        "sweep adjoint", so ? tgp_sweep::adjoint_sde_kernel_name() : tgp_sweep::adjoint_kernel_name(),
-        [](tgp_handle* hh, const tgp_sweep::ModelHost& m, int W, int Wa, std::string* w) {
-            tgp_sweep::force_geometry(hh->sweep, hh->sweep_fC, hh->sweep_fW, 0, 0, hh->sweep_fWb);
-            return tgp_sweep::plan(hh->sweep, m, hh->T, W, hh->sweep_Wb, hh->num_cu, w, 0, Wa);
-        },
-        [](tgp_handle* hh, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep::enqueue(hh->sweep, hh->stream, c, kname, err); },
-        [](tgp_handle* hh, int* status, int* w, int* wa, double* df, double* db) { return tgp_sweep::finish(hh->sweep, status, w, nullptr, df, db, nullptr, wa); },
-        [](tgp_handle* hh, int* C, int64_t* nw) { tgp_sweep::geometry(hh->sweep, C, nullptr, nullptr, nw); }};
-    return sweep_adjoint_run(h, eng, mh, so != nullptr, y, missing, flags, lml_out, gh_steps, gR_steps, served, why, [&]() {
+// The lane sweep has a slot per kind in plan, finish and force_geometry: the forced and the repaired second warm-up go to the kind's own, and a draw or
+// an adjoint plans beside the Wb the bound model remembers.
+const SweepOps kLaneSweep = {
+    "sweep", "sweep engine",
+    [](const tgp_handle* h, SweepKind kind, bool post) {
+        if (kind == SweepKind::adjoint) return h->sde ? tgp_sweep::adjoint_sde_kernel_name() : tgp_sweep::adjoint_kernel_name();
+        return tgp_sweep::kernel_name(h->d, h->sde, post, kind == SweepKind::draw);
+    },
+    [](tgp_handle* h, const tgp_sweep::ModelHost& mh, SweepKind kind, bool, int W, int Wk, std::string* why) {
+        if (!h->sweep) h->sweep = tgp_sweep::create();
+        int forced[3] = {0, 0, 0}, hint[3] = {h->sweep_Wb, 0, 0};
+        forced[(int)kind] = h->sweep_fWb;
+        hint[(int)kind] = Wk;
+        tgp_sweep::force_geometry(h->sweep, h->sweep_fC, h->sweep_fW, forced[0], forced[1], forced[2]);
+        return tgp_sweep::plan(h->sweep, mh, h->T, W, hint[0], h->num_cu, why, hint[1], hint[2]);
+    },
+    [](tgp_handle* h, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep::enqueue(h->sweep, h->stream, c, kname, err); },
+    [](tgp_handle* h, SweepKind kind, int* status, int* w, int* wk, double* df, double* dk) {
+        int* ran[3] = {nullptr, nullptr, nullptr};
+        ran[(int)kind] = wk;
+        const double lml = tgp_sweep::finish(h->sweep, status, w, ran[0], df, dk, ran[1], ran[2]);
+        return kind == SweepKind::draw ? 0.0 : lml;
+    },
+    [](tgp_handle* h, int* C, int64_t* nw) { tgp_sweep::geometry(h->sweep, C, nullptr, nullptr, nw); },
+    [](tgp_handle* h, const tgp_sweep::ModelHost&, const tgp_sweep::AdjointOut& o, const tgp_sweep::AdjointSdeOut* so) {
         if (so) tgp_sweep::adjoint_blocks_sde(h->sweep, *so);
         else tgp_sweep::adjoint_blocks(h->sweep, o);
-    });
+    }};
+
+// The group sweep has one backward slot: a draw and an adjoint run on the posterior call's geometry with their warm-up in it, and say so by a flag.
+// Its SDE adjoint pulls step 0 back on the host through the first transition of the host model.
+const SweepOps kGroupSweep = {
+    "sweep group", "group sweep",
+    [](const tgp_handle* h, SweepKind kind, bool post) {
+        if (kind == SweepKind::adjoint) return h->sde ? tgp_sweep_group::adjoint_sde_kernel_name() : tgp_sweep_group::adjoint_kernel_name();
+        return kind == SweepKind::draw ? tgp_sweep_group::draw_kernel_name(h->sde) : tgp_sweep_group::kernel_name(post, h->sde);
+    },
+    [](tgp_handle* h, const tgp_sweep::ModelHost& mh, SweepKind kind, bool post, int W, int Wk, std::string* why) {
+        if (!h->sweep_group) h->sweep_group = tgp_sweep_group::create();
+        tgp_sweep_group::force_geometry(h->sweep_group, h->sweep_fC, h->sweep_fW, h->sweep_fWb);
+        return tgp_sweep_group::plan(h->sweep_group, mh, h->T, W, Wk, h->num_cu, post || kind != SweepKind::marginals, why, kind == SweepKind::adjoint,
+                                     kind == SweepKind::draw);
+    },
+    [](tgp_handle* h, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep_group::enqueue(h->sweep_group, h->stream, c, kname, err); },
+    [](tgp_handle* h, SweepKind kind, int* status, int* w, int* wk, double* df, double* dk) {
+        const double lml = tgp_sweep_group::finish(h->sweep_group, status, w, wk, df, dk);
+        return kind == SweepKind::draw ? 0.0 : lml;
+    },
+    [](tgp_handle* h, int* C, int64_t* nw) { tgp_sweep_group::geometry(h->sweep_group, C, nullptr, nullptr, nw); },
+    [](tgp_handle* h, const tgp_sweep::ModelHost& mh, const tgp_sweep::AdjointOut& o, const tgp_sweep::AdjointSdeOut* so) {
+        if (so) tgp_sweep_group::adjoint_blocks_sde(h->sweep_group, mh, *so);
+        else tgp_sweep_group::adjoint_blocks(h->sweep_group, o);
+    }};
+
+// Runs a call on one of the sweep engines: staging ONCE, up to four attempts with doubled warm-ups, the engine switched off for the bound model where it
+// cannot serve it.  What a kind brings:
+//   stage(tm)   inputs and outputs staged in front of the attempts (a host-resident series is not uploaded again by every retry); marks tm.inputs_done()
+//   fill(c)     the kind's fields of the engine's call record (the series, mask, per-step streams and gaps are filled here)
+//   deliver()   behind a clean status alone: the outputs reach the caller's memory, with the synchronisation they need
+// *served = false: the engine declined, nothing reached the caller's memory.  why == nullptr: declines are silent, the caller goes on to the general
+// engine; else *why says what a draw or a gradient was declined for.
+template <class Stage, class Fill, class Deliver>
+int sweep_attempts(tgp_handle* h, const SweepOps& eng, SweepKind kind, bool post, const tgp_sweep::ModelHost& mh, double* lml_out, bool* served, std::string* why,
+                   Stage&& stage, Fill&& fill, Deliver&& deliver) {
+    *served = false;
+    static const bool dbg = getenv("TGP_STEADY_DEBUG") != nullptr;
+    const auto& text = kSweepKindText[(int)kind];
+    auto decline = [&](const char* because) {
+        if (why) *why = because;
+        return TGP_OK;
+    };
+    const bool forced = h->sweep_fW || h->sweep_fWb || h->sweep_fC;
+    int& back = sweep_back_slot(h, kind);
+    int W = h->sweep_W, Wk = back;
+    for (int64_t& v : h->sweep_info) v = 0;
+    auto replan = [&]() {
+        std::string w;
+        if (eng.plan(h, mh, kind, post, W, Wk, &w)) return true;
+        if (dbg) fprintf(stderr, "[tgp %s%s] does not apply: %s\n", eng.tag, text.tag, w.c_str());
+        h->sweep_state = -1;
+        decline(("the sweep engine's plan declines the model (" + w + ")").c_str());
+        return false;
+    };
+    if (!replan()) return TGP_OK;
+    CallTimer tm(h, /*clear=*/false);
+    TRY(stage(tm));
+    const char* const kname0 = eng.kname(h, kind, post);
+    for (int attempt = 0; attempt < 4; ++attempt) {
+        if (attempt > 0 && !replan()) return TGP_OK;
+        tgp_sweep::Call c;
+        c.T = h->T;
+        c.y = h->mv.y;
+        c.mask = h->mv.missing;
+        c.R = h->mv.sR != 0 ? h->mv.R : nullptr;
+        c.hh = h->mv.sh != 0 ? h->mv.h : nullptr;
+        c.tau = h->sde ? h->btau.d() : nullptr;
+        fill(c);
+        {
+            std::string err;
+            const char* kname = kname0;
+            LaunchScope ls(h, kname);
+            if (eng.enqueue(h, c, &kname, &err) != 0) return h->fail(TGP_EHIP, err);
+        }
+        tm.kernels_done();
+        if (h->timing) (void)hipEventRecord(h->ev[3], h->stream);
+        HIPCHK(hipStreamSynchronize(h->stream));
+        resolve_profile(h);
+        int status = 0, w = 0, wk = 0;
+        const double lml = eng.finish(h, kind, &status, &w, &wk, &h->sweep_dist[0], &h->sweep_dist[1]);
+        int C = 0;
+        int64_t nw = 0;
+        eng.geometry(h, &C, &nw);
+        h->sweep_info[1] = C; h->sweep_info[2] = w; h->sweep_info[3] = wk; h->sweep_info[4] = nw; h->sweep_info[5] = attempt + 1; h->sweep_info[6] = status;
+        if (dbg)
+            fprintf(stderr, "[tgp %s%s] attempt %d: C %d W %d %s %d waves %lld status %d dist %.3g / %.3g\n", eng.tag, text.tag, attempt, C, w, text.slot, wk, (long long)nw,
+                    status, h->sweep_dist[0], h->sweep_dist[1]);
+        if (status & 12) {      // not positive definite / non-finite values: the general engine (the evaluated route, the tangent scans) reports it the way it always has
+            if (status & 4) h->sweep_state = -1;      // (a property of the model, not of this series: later calls do not pay for a launch that cannot serve them)
+            return decline((status & 4) ? text.not_pd : text.not_finite);
+        }
+        if (status & 3) {       // a warm-up was too short: longer ones (a forced geometry is a test's: report, do not repair)
+            if (forced) return decline("a warm-up of the forced geometry is too short (tgp_sweep_info)");
+            if (status & 1) W = 2 * w;
+            if (status & 2) Wk = 2 * wk;
+            continue;
+        }
+        TRY(deliver());
+        read_timing(h);
+        note_served(h, Served::sweep, 0, lml, lml_out);
+        h->sweep_W = w;
+        back = wk;
+        h->sweep_state = 1;
+        h->sweep_info[0] = 1;
+        *served = true;
+        return TGP_OK;
+    }
+    h->sweep_state = -1;      // four attempts, warm-ups still too short: a model that mixes too slowly for this engine
+    return decline("the warm-ups stayed too short over four attempts");
 }
 
-// The same at 5 <= d <= 8 on the group sweep (k_sweep_group_adjoint, DESIGN 4.11; LTI form): the posterior call's geometry with Wa in its backward slot.
-int sweep_group_adjoint_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, const tgp_sweep::AdjointOut& o,
-                             double* gh_steps, double* gR_steps, bool* served, std::string* why) {
-    *served = false;
-    if (!h->sweep_group) h->sweep_group = tgp_sweep_group::create();
-    const SweepAdjointOps eng = {
-        "sweep group adjoint", tgp_sweep_group::adjoint_kernel_name(),
-        [](tgp_handle* hh, const tgp_sweep::ModelHost& m, int W, int Wa, std::string* w) {
-            tgp_sweep_group::force_geometry(hh->sweep_group, hh->sweep_fC, hh->sweep_fW, hh->sweep_fWb);
-            return tgp_sweep_group::plan(hh->sweep_group, m, hh->T, W, Wa, hh->num_cu, /*post=*/true, w, /*adjoint=*/true);
+// logpdf / posterior marginals on the lane sweep (d <= 4; LTI and SDE form) or, sweep_group_call, on the group sweep (5 <= d <= 8; LTI form, and SDE form
+// where sweep_group_sde_eligible says so).  Rnew is staged only where the marginals are asked for; the kernel writes straight to the caller's device
+// arrays or their staging.  A decline is silent (nothing the caller must undo): the caller goes on to the general engine.
+int sweep_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, double* mean_out, double* var_out,
+               double* lml_out, bool* served, const SweepOps& eng = kLaneSweep) {
+    const bool idev = (flags & TGP_IN_DEVICE) != 0, odev = (flags & TGP_OUT_DEVICE) != 0, rshared = (flags & TGP_SHARED_R) != 0;
+    const size_t nT = (size_t)h->T * sizeof(double);
+    const void* pR = nullptr;
+    double *dm = nullptr, *dv = nullptr;
+    return sweep_attempts(
+        h, eng, SweepKind::marginals, mean_out != nullptr, sweep_host_model(h, /*record_pinf=*/false), lml_out, served, nullptr,
+        [&](CallTimer& tm) -> int {
+            if (mean_out) TRY(stage_in(h, h->bRnew, Rnew, rshared ? sizeof(double) : nT, idev, &pR));
+            TRY(set_obs(h, y, missing, flags));
+            tm.inputs_done();
+            TRY(stage_out(h, h->bo1, mean_out, nT, odev, &dm));
+            TRY(stage_out(h, h->bo2, var_out, nT, odev, &dv));
+            return TGP_OK;
         },
-        [](tgp_handle* hh, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep_group::enqueue(hh->sweep_group, hh->stream, c, kname, err); },
-        [](tgp_handle* hh, int* status, int* w, int* wa, double* df, double* db) { return tgp_sweep_group::finish(hh->sweep_group, status, w, wa, df, db); },
-        [](tgp_handle* hh, int* C, int64_t* nw) { tgp_sweep_group::geometry(hh->sweep_group, C, nullptr, nullptr, nw); }};
-    return sweep_adjoint_run(h, eng, sweep_host_model(h), false, y, missing, flags, lml_out, gh_steps, gR_steps, served, why,
-                             [&]() { tgp_sweep_group::adjoint_blocks(h->sweep_group, o); });
+        [&](tgp_sweep::Call& c) {
+            c.Rnew = static_cast<const double*>(pR);
+            c.rnew_per_step = (mean_out && !rshared) ? 1 : 0;
+            c.mean = dm;
+            c.var = dv;
+        },
+        [&]() -> int {
+            TRY(copy_back(h, mean_out, dm, nT, odev));
+            TRY(copy_back(h, var_out, dv, nT, odev));
+            if (mean_out && !odev) HIPCHK(hipStreamSynchronize(h->stream));
+            return TGP_OK;
+        });
+}
+int sweep_group_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, double* mean_out, double* var_out,
+                     double* lml_out, bool* served) {
+    return sweep_call(h, y, missing, flags, Rnew, mean_out, var_out, lml_out, served, kGroupSweep);
 }
 
-// The same on an SDE-described model (k_sweep_group_adjoint_sde, DESIGN 4.14): the sums over the closed form's coefficients go to *so, with step 0 pulled
-// back on the host through the first transition.  The stationary covariance is the one tgp_model_set_sde took (sweep_adjoint_call: tgp_model_set_x0 may
-// have replaced the prior since); tgp_logpdf and the posterior calls keep planning from sweep_host_model.
-int sweep_group_adjoint_sde_call(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, const tgp_sweep::AdjointSdeOut& so,
-                                 double* gh_steps, double* gR_steps, bool* served, std::string* why) {
-    *served = false;
-    if (!h->sweep_group) h->sweep_group = tgp_sweep_group::create();
-    tgp_sweep::ModelHost mh = sweep_host_model(h);
-    mh.Pinf = h->sde_coef_host.data() + h->d + 2 * (size_t)h->d * h->d;
-    const SweepAdjointOps eng = {
-        "sweep group adjoint sde", tgp_sweep_group::adjoint_sde_kernel_name(),
-        [](tgp_handle* hh, const tgp_sweep::ModelHost& m, int W, int Wa, std::string* w) {
-            tgp_sweep_group::force_geometry(hh->sweep_group, hh->sweep_fC, hh->sweep_fW, hh->sweep_fWb);
-            return tgp_sweep_group::plan(hh->sweep_group, m, hh->T, W, Wa, hh->num_cu, /*post=*/true, w, /*adjoint=*/true);
+// rand of the posterior on the lane sweep (k_sweep_draw, DESIGN 4.7; LTI and SDE form) or on the group sweep (k_sweep_group_draw, DESIGN 4.12;
+// k_sweep_group_draw_sde, 4.15).  The draw goes to the handle's own buffer and reaches y_out behind the checks: a declined call (*served = false, *why
+// set) leaves a device y_out untouched as well.  The lane sweep's draw plans an SDE-described model from the bound x0P, the group sweep's from the
+// record's Pinf, so that a prior replaced by tgp_model_set_x0 is served (as the adjoint calls').
+int sweep_draw_call(tgp_handle* h, const SweepOps& eng, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, const double* eps_t,
+                    const double* eps_e, const double* eps_0, double* y_out, bool* served, std::string* why) {
+    const int d = h->d;
+    const bool idev = (flags & TGP_IN_DEVICE) != 0, odev = (flags & TGP_OUT_DEVICE) != 0, rshared = (flags & TGP_SHARED_R) != 0;
+    const size_t nT = (size_t)h->T * sizeof(double);
+    const void *pR = nullptr, *pet = nullptr, *pee = nullptr;
+    double* dy = nullptr;
+    return sweep_attempts(
+        h, eng, SweepKind::draw, /*post=*/true, sweep_host_model(h, /*record_pinf=*/&eng == &kGroupSweep), nullptr, served, why,
+        [&](CallTimer& tm) -> int {
+            TRY(stage_in(h, h->bRnew, Rnew, rshared ? sizeof(double) : nT, idev, &pR));
+            TRY(set_obs(h, y, missing, flags));
+            TRY(stage_in(h, h->beps_t, eps_t, (size_t)h->T * d * sizeof(double), idev, &pet));
+            TRY(stage_in(h, h->beps_e, eps_e, nT, idev, &pee));
+            tm.inputs_done();
+            HIPCHK(h->bo1.ensure(nT));
+            dy = h->bo1.d();
+            return TGP_OK;
         },
-        [](tgp_handle* hh, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep_group::enqueue(hh->sweep_group, hh->stream, c, kname, err); },
-        [](tgp_handle* hh, int* status, int* w, int* wa, double* df, double* db) { return tgp_sweep_group::finish(hh->sweep_group, status, w, wa, df, db); },
-        [](tgp_handle* hh, int* C, int64_t* nw) { tgp_sweep_group::geometry(hh->sweep_group, C, nullptr, nullptr, nw); }};
-    return sweep_adjoint_run(h, eng, mh, true, y, missing, flags, lml_out, gh_steps, gR_steps, served, why,
-                             [&]() { tgp_sweep_group::adjoint_blocks_sde(h->sweep_group, mh, so); });
+        [&](tgp_sweep::Call& c) {
+            c.Rnew = static_cast<const double*>(pR);
+            c.rnew_per_step = rshared ? 0 : 1;
+            c.eps_t = static_cast<const double*>(pet);
+            c.eps_e = static_cast<const double*>(pee);
+            for (int k = 0; k < d; ++k) c.eps_0[k] = eps_0[k];
+            c.y_out = dy;
+        },
+        [&]() -> int {
+            HIPCHK(hipMemcpyAsync(y_out, dy, nT, odev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            return TGP_OK;
+        });
+}
+
+// The adjoint gradient on the lane sweep (k_sweep_adjoint, DESIGN 4.8; k_sweep_adjoint_sde, 4.9) or on the group sweep (k_sweep_group_adjoint, DESIGN 4.11;
+// k_sweep_group_adjoint_sde, 4.14).  The per-step gradients go to the handle's own buffers and reach gh_steps / gR_steps behind the checks, the block
+// gradients are written behind them too: *served = false with *why set: the engine declined, no output was written.
+// so (null: the LTI form, the block gradients go to o): an SDE-described model -- the sums over the closed form's coefficients go to *so, `o` is unused.
+int sweep_adjoint_call(tgp_handle* h, const SweepOps& eng, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, const tgp_sweep::AdjointOut& o,
+                       const tgp_sweep::AdjointSdeOut* so, double* gh_steps, double* gR_steps, bool* served, std::string* why) {
+    const bool odev = (flags & TGP_OUT_DEVICE) != 0;
+    const size_t nT = (size_t)h->T * sizeof(double);
+    const tgp_sweep::ModelHost mh = sweep_host_model(h, /*record_pinf=*/true);
+    double *dgh = nullptr, *dgR = nullptr;
+    return sweep_attempts(
+        h, eng, SweepKind::adjoint, /*post=*/true, mh, lml_out, served, why,
+        [&](CallTimer& tm) -> int {
+            TRY(set_obs(h, y, missing, flags));
+            tm.inputs_done();
+            if (gh_steps) {
+                HIPCHK(h->bo1.ensure(nT));
+                dgh = h->bo1.d();
+            }
+            if (gR_steps) {
+                HIPCHK(h->bo2.ensure(nT));
+                dgR = h->bo2.d();
+            }
+            return TGP_OK;
+        },
+        [&](tgp_sweep::Call& c) {
+            c.adjoint = true;
+            c.gh_steps = dgh;
+            c.gR_steps = dgR;
+        },
+        [&]() -> int {
+            if (gh_steps) HIPCHK(hipMemcpyAsync(gh_steps, dgh, nT, odev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+            if (gR_steps) HIPCHK(hipMemcpyAsync(gR_steps, dgR, nT, odev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+            if (gh_steps || gR_steps) HIPCHK(hipStreamSynchronize(h->stream));
+            eng.adjoint_blocks(h, mh, o, so);
+            return TGP_OK;
+        });
 }
 
 // d logpdf / d F from the sums over the closed form's coefficients: the transpose of sde_closed_form's map.  coef = [lam d | N d*d | N^2 / 2 d*d | ...];
@@ -731,8 +528,10 @@ void sde_coef_to_gF(int d, const double* coef, const double* gl, const double* g
 
 // The outputs of tgp_logpdf_adjoint_sde / tgp_logpdf_adjoint_group_sde from an engine's record (any output null).  A model bound without A1 took
 // A1 = E (I + N1 + N2), E = diag(e^(-lam_i)), at step 0: its G_0 (so.gA1) belongs to the coefficients, with tau = 1, and gA1 is zero.
-void sde_adjoint_outputs(const tgp_handle* h, const tgp_sweep::AdjointSdeOut& so, double* gF, double* gPinf, double* gA1, double* ga, double* gH, double* ghh,
-                         double* gR, double* gx0m, double* gx0P) {
+struct SdeGrads {      // (the entries' output arguments, in their order)
+    double *gF, *gPinf, *gA1, *ga, *gH, *ghh, *gR, *gx0m, *gx0P;
+};
+void sde_adjoint_outputs(const tgp_handle* h, const tgp_sweep::AdjointSdeOut& so, const SdeGrads& g) {
     const int d = h->d, dd = d * d;
     const double* coef = h->sde_coef_host.data();
     if (!h->have_AQ1) {
@@ -749,15 +548,15 @@ void sde_adjoint_outputs(const tgp_handle* h, const tgp_sweep::AdjointSdeOut& so
         }
         for (int i = 0; i < dd; ++i) so.gA1[i] = 0.0;
     }
-    if (gF) sde_coef_to_gF(d, coef, so.gl, so.gN1, so.gN2, gF);
-    if (gPinf) std::memcpy(gPinf, so.gPinf, sizeof(double) * dd);
-    if (gA1) std::memcpy(gA1, so.gA1, sizeof(double) * dd);
-    if (ga) std::memcpy(ga, so.ga, sizeof(double) * d);
-    if (gH) std::memcpy(gH, so.gH, sizeof(double) * d);
-    if (ghh) *ghh = *so.ghh;
-    if (gR) *gR = *so.gR;
-    if (gx0m) std::memcpy(gx0m, so.gx0m, sizeof(double) * d);
-    if (gx0P) std::memcpy(gx0P, so.gx0P, sizeof(double) * dd);
+    if (g.gF) sde_coef_to_gF(d, coef, so.gl, so.gN1, so.gN2, g.gF);
+    if (g.gPinf) std::memcpy(g.gPinf, so.gPinf, sizeof(double) * dd);
+    if (g.gA1) std::memcpy(g.gA1, so.gA1, sizeof(double) * dd);
+    if (g.ga) std::memcpy(g.ga, so.ga, sizeof(double) * d);
+    if (g.gH) std::memcpy(g.gH, so.gH, sizeof(double) * d);
+    if (g.ghh) *g.ghh = *so.ghh;
+    if (g.gR) *g.gR = *so.gR;
+    if (g.gx0m) std::memcpy(g.gx0m, so.gx0m, sizeof(double) * d);
+    if (g.gx0P) std::memcpy(g.gx0P, so.gx0P, sizeof(double) * dd);
 }
 
 bool steady2_served(tgp_handle* h) {

@@ -435,6 +435,65 @@ int tgp_posterior_rand(tgp_handle* h, const double* y, const double* Rnew, const
     return TGP_OK;
 }
 
+// An entry point of the sweep engines' own -- a draw or an adjoint gradient --: what its texts in tgp_last_error are made of.
+struct SweepEntry {
+    const char* name;            // the exported function
+    const SweepOps& eng;
+    int form;                    // the models it takes: 0 in LTI form, 1 SDE-described, -1 both
+    const char* wrong_form;      // TGP_EUNSUPPORTED for a model of the other form (null: `serves`)
+    const char* serves;          // TGP_EUNSUPPORTED where the engine's eligibility predicate says no: what the entry serves, what to take otherwise
+    const char* instead;         // behind the reason of a decline by the engine: what to take instead
+};
+// guard, null check, eligibility (an explicit call: the default routing of the group sweep's other calls does not filter it)
+static int sweep_entry_checks(tgp_handle* h, const SweepEntry& e, bool null_argument, uint32_t flags) {
+    TRY(check_ready(h, /*general=*/false));
+    if (null_argument) return h->fail(TGP_EINVAL, std::string(e.name) + ": null argument");
+    const bool form_ok = e.form < 0 || h->sde == (e.form == 1);
+    if (!form_ok && e.wrong_form) return h->fail(TGP_EUNSUPPORTED, std::string(e.name) + ": " + e.wrong_form);
+    const bool eligible = &e.eng == &kLaneSweep ? sweep_eligible(h, flags)
+                          : h->sde              ? sweep_group_sde_eligible(h, flags, /*explicit_call=*/true)
+                                                : sweep_group_eligible(h, flags, /*post=*/true, /*explicit_call=*/true);
+    if (!form_ok || !eligible) return h->fail(TGP_EUNSUPPORTED, std::string(e.name) + ": " + e.serves);
+    return TGP_OK;
+}
+// The draw of an eligible model: served, or TGP_EUNSUPPORTED with the engine's reason and nothing written to y_out
+static int sweep_draw_entry(tgp_handle* h, const SweepEntry& e, const double* y, const uint8_t* missing, const double* Rnew, const double* eps_t, const double* eps_e,
+                            const double* eps_0, uint32_t flags, double* y_out) {
+    bool served = false;
+    std::string why;
+    TRY(sweep_draw_call(h, e.eng, y, missing, flags, Rnew, eps_t, eps_e, eps_0, y_out, &served, &why));
+    if (served) return TGP_OK;
+    return h->fail(TGP_EUNSUPPORTED, std::string(e.name) + ": the " + e.eng.name + " declines the draw: " + why + e.instead);
+}
+// The group sweep's draw entries whole
+static int sweep_group_draw_entry(tgp_handle* h, const SweepEntry& e, const double* y, const uint8_t* missing, const double* Rnew, const double* eps_t,
+                                  const double* eps_e, const double* eps_0, uint32_t flags, double* y_out) {
+    StreamGuard stream_guard_(h);
+    TRY(sweep_entry_checks(h, e, !y || !Rnew || !eps_t || !eps_e || !eps_0 || !y_out, flags));
+    return sweep_draw_entry(h, e, y, missing, Rnew, eps_t, eps_e, eps_0, flags, y_out);
+}
+// The adjoint entries whole.  g (null: a model in LTI form, the block gradients go to o): an SDE-described model -- the engine's sums over the closed
+// form's coefficients are finished into *g (sde_adjoint_outputs).
+static int sweep_adjoint_entry(tgp_handle* h, const SweepEntry& e, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out,
+                               const tgp_sweep::AdjointOut& o, const SdeGrads* g, double* gh_steps, double* gR_steps) {
+    StreamGuard stream_guard_(h);
+    TRY(sweep_entry_checks(h, e, !y, flags));
+    constexpr int M = tgp_sweep::kGroupMaxD;
+    double buf[5 * M * M + 4 * M + 2];      // (AdjointSdeOut's five d x d blocks, four vectors and two sums at d = 8)
+    tgp_sweep::AdjointSdeOut so;
+    if (g) {
+        const int d = h->d, dd = d * d;
+        so.gl = buf; so.gN1 = so.gl + d; so.gN2 = so.gN1 + dd; so.gPinf = so.gN2 + dd; so.gA1 = so.gPinf + dd; so.ga = so.gA1 + dd; so.gH = so.ga + d;
+        so.ghh = so.gH + d; so.gR = so.ghh + 1; so.gx0m = so.gR + 1; so.gx0P = so.gx0m + d;
+    }
+    bool served = false;
+    std::string why;
+    TRY(sweep_adjoint_call(h, e.eng, y, missing, flags, lml_out, o, g ? &so : nullptr, gh_steps, gR_steps, &served, &why));
+    if (!served) return h->fail(TGP_EUNSUPPORTED, std::string(e.name) + ": the " + e.eng.name + " declines the gradient: " + why + e.instead);
+    if (g) sde_adjoint_outputs(h, so, *g);
+    return TGP_OK;
+}
+
 // The same draw where the series has missing steps, the transitions or the noise are per step, or the observations are vectors with diagonal noise --
 // what merge_datasets makes of rand(rng, posterior(fx, y)(x_new)) -- on the sweep engine's draw kernel (what sweep_eligible accepts: scalar observations,
 // d <= 4, T >= 2048; DESIGN 4.7, k_sweep_draw) or on the dense engine's persistent passes (16 < d <= 64, p <= 16; DESIGN 4.6, tgp_dense_draw.hpp).
@@ -444,13 +503,8 @@ int tgp_posterior_rand_missing(tgp_handle* h, const double* y, const uint8_t* mi
     StreamGuard stream_guard_(h);
     TRY(check_ready(h, /*general=*/false));
     if (!y || !Rnew || !eps_t || !eps_e || !eps_0 || !y_out) return h->fail(TGP_EINVAL, "tgp_posterior_rand_missing: null argument");
-    if (sweep_eligible(h, flags)) {
-        bool served = false;
-        std::string why;
-        TRY(sweep_draw_call(h, y, missing, flags, Rnew, eps_t, eps_e, eps_0, y_out, &served, &why));
-        if (served) return TGP_OK;
-        return h->fail(TGP_EUNSUPPORTED, "tgp_posterior_rand_missing: the sweep engine declines the draw: " + why + " (take tgp_posterior + tgp_rand)");
-    }
+    static const SweepEntry sweep_entry = {"tgp_posterior_rand_missing", kLaneSweep, -1, nullptr, nullptr, " (take tgp_posterior + tgp_rand)"};
+    if (sweep_eligible(h, flags)) return sweep_draw_entry(h, sweep_entry, y, missing, Rnew, eps_t, eps_e, eps_0, flags, y_out);
     // (5 <= d <= 8 on the group sweep: tgp_posterior_rand_group, an entry point of its own -- this one declines there with no attempt made)
     if (!h->is_dense || h->ordering != 0 || h->d > 64 || h->p > 16 || !h->dense_fused || !h->dense_chunked)
         return h->fail(TGP_EUNSUPPORTED, "tgp_posterior_rand_missing: Forward models with scalar observations, d <= 4 and T >= 2048 on the sweep engine, or with "
@@ -479,18 +533,12 @@ int tgp_posterior_rand_missing(tgp_handle* h, const double* y, const uint8_t* mi
 // the default routing of the engine's other calls (an explicit call; TGP_OPT_SWEEP >= 1).  tgp_posterior_rand_missing's arguments and flags.
 int tgp_posterior_rand_group(tgp_handle* h, const double* y, const uint8_t* missing, const double* Rnew, const double* eps_t, const double* eps_e,
                              const double* eps_0, uint32_t flags, double* y_out) {
-    StreamGuard stream_guard_(h);
-    TRY(check_ready(h, /*general=*/false));
-    if (!y || !Rnew || !eps_t || !eps_e || !eps_0 || !y_out) return h->fail(TGP_EINVAL, "tgp_posterior_rand_group: null argument");
-    if (!sweep_group_eligible(h, flags, /*post=*/true, /*explicit_call=*/true))
-        return h->fail(TGP_EUNSUPPORTED, "tgp_posterior_rand_group: Forward models with shared A, a, Q, H (not SDE-described), scalar observations, 5 <= d <= 8 "
-                                         "and T >= 2048 on the group sweep (TGP_OPT_SWEEP >= 1, the engine not declined for the bound model); use "
-                                         "tgp_posterior_rand_missing at d <= 4 and tgp_posterior + tgp_rand otherwise");
-    bool served = false;
-    std::string why;
-    TRY(sweep_group_draw_call(h, y, missing, flags, Rnew, eps_t, eps_e, eps_0, y_out, &served, &why));
-    if (served) return TGP_OK;
-    return h->fail(TGP_EUNSUPPORTED, "tgp_posterior_rand_group: the group sweep declines the draw: " + why + " (take tgp_posterior + tgp_rand)");
+    static const SweepEntry entry = {"tgp_posterior_rand_group", kGroupSweep, 0, nullptr,
+                                     "Forward models with shared A, a, Q, H (not SDE-described), scalar observations, 5 <= d <= 8 "
+                                     "and T >= 2048 on the group sweep (TGP_OPT_SWEEP >= 1, the engine not declined for the bound model); use "
+                                     "tgp_posterior_rand_missing at d <= 4 and tgp_posterior + tgp_rand otherwise",
+                                     " (take tgp_posterior + tgp_rand)"};
+    return sweep_group_draw_entry(h, entry, y, missing, Rnew, eps_t, eps_e, eps_0, flags, y_out);
 }
 
 // The same for a model described by its SDE and time stamps (tgp_model_set_sde: irregular spacing) -- what rand(rng, posterior(fx, y)(x_new)) merges into
@@ -498,19 +546,13 @@ int tgp_posterior_rand_group(tgp_handle* h, const double* y, const uint8_t* miss
 // calls (an explicit call; TGP_OPT_SWEEP >= 1).  tgp_posterior_rand_group's arguments and flags.
 int tgp_posterior_rand_group_sde(tgp_handle* h, const double* y, const uint8_t* missing, const double* Rnew, const double* eps_t, const double* eps_e,
                                  const double* eps_0, uint32_t flags, double* y_out) {
-    StreamGuard stream_guard_(h);
-    TRY(check_ready(h, /*general=*/false));
-    if (!y || !Rnew || !eps_t || !eps_e || !eps_0 || !y_out) return h->fail(TGP_EINVAL, "tgp_posterior_rand_group_sde: null argument");
-    if (!sweep_group_sde_eligible(h, flags, /*explicit_call=*/true))
-        return h->fail(TGP_EUNSUPPORTED, "tgp_posterior_rand_group_sde: Forward SDE-described models (tgp_model_set_sde) with closed-form transitions "
-                                         "(TGP_OPT_SDE_CLOSED_FORM = 1), shared a and H, scalar observations, 5 <= d <= 8 and T >= 2048 on the group sweep "
-                                         "(TGP_OPT_SWEEP >= 1, the engine not declined for the bound model); use tgp_posterior_rand_missing at d <= 4, "
-                                         "tgp_posterior_rand_group for models in LTI form and tgp_posterior + tgp_rand otherwise");
-    bool served = false;
-    std::string why;
-    TRY(sweep_group_draw_sde_call(h, y, missing, flags, Rnew, eps_t, eps_e, eps_0, y_out, &served, &why));
-    if (served) return TGP_OK;
-    return h->fail(TGP_EUNSUPPORTED, "tgp_posterior_rand_group_sde: the group sweep declines the draw: " + why + " (take tgp_posterior + tgp_rand)");
+    static const SweepEntry entry = {"tgp_posterior_rand_group_sde", kGroupSweep, 1, nullptr,
+                                     "Forward SDE-described models (tgp_model_set_sde) with closed-form transitions "
+                                     "(TGP_OPT_SDE_CLOSED_FORM = 1), shared a and H, scalar observations, 5 <= d <= 8 and T >= 2048 on the group sweep "
+                                     "(TGP_OPT_SWEEP >= 1, the engine not declined for the bound model); use tgp_posterior_rand_missing at d <= 4, "
+                                     "tgp_posterior_rand_group for models in LTI form and tgp_posterior + tgp_rand otherwise",
+                                     " (take tgp_posterior + tgp_rand)"};
+    return sweep_group_draw_entry(h, entry, y, missing, Rnew, eps_t, eps_e, eps_0, flags, y_out);
 }
 
 // logpdf and its gradient with respect to the shared blocks, and to the noise variance and the emission offset of every step, where the gains vary in time
@@ -518,40 +560,28 @@ int tgp_posterior_rand_group_sde(tgp_handle* h, const double* y, const uint8_t* 
 // sweep_eligible accepts in LTI form.  TGP_EUNSUPPORTED: no output was written, the caller takes tgp_logpdf_grad.
 int tgp_logpdf_adjoint_missing(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, double* gA, double* ga, double* gQ,
                                double* gH, double* ghh, double* gR, double* gx0m, double* gx0P, double* gh_steps, double* gR_steps) {
-    StreamGuard stream_guard_(h);
-    TRY(check_ready(h, /*general=*/false));
-    if (!y) return h->fail(TGP_EINVAL, "tgp_logpdf_adjoint_missing: null argument");
-    if (h->sde || !sweep_eligible(h, flags))
-        return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_missing: Forward models with shared A, a, Q, H (not SDE-described), scalar observations, d <= 4 and "
-                                         "T >= 2048 on the sweep engine (TGP_OPT_SWEEP = 1, the engine not declined for the bound model); use tgp_logpdf_grad "
-                                         "otherwise");
+    static const SweepEntry entry = {"tgp_logpdf_adjoint_missing", kLaneSweep, 0, nullptr,
+                                     "Forward models with shared A, a, Q, H (not SDE-described), scalar observations, d <= 4 and "
+                                     "T >= 2048 on the sweep engine (TGP_OPT_SWEEP = 1, the engine not declined for the bound model); use tgp_logpdf_grad "
+                                     "otherwise",
+                                     " (use tgp_logpdf_grad)"};
     tgp_sweep::AdjointOut o;
     o.gA = gA; o.ga = ga; o.gQ = gQ; o.gH = gH; o.ghh = ghh; o.gR = gR; o.gx0m = gx0m; o.gx0P = gx0P;
-    bool served = false;
-    std::string why;
-    TRY(sweep_adjoint_call(h, y, missing, flags, lml_out, o, gh_steps, gR_steps, &served, &why));
-    if (served) return TGP_OK;
-    return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_missing: the sweep engine declines the gradient: " + why + " (use tgp_logpdf_grad)");
+    return sweep_adjoint_entry(h, entry, y, missing, flags, lml_out, o, nullptr, gh_steps, gR_steps);
 }
 
 // The same at state dimensions 5 .. 8 by the group sweep's adjoint kernel (k_sweep_group_adjoint, DESIGN 4.11): what sweep_group_eligible accepts, whatever
 // the default routing of the engine's other calls (an explicit call; TGP_OPT_SWEEP >= 1).  tgp_logpdf_adjoint_missing's arguments and outputs.
 int tgp_logpdf_adjoint_group(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, double* gA, double* ga, double* gQ,
                              double* gH, double* ghh, double* gR, double* gx0m, double* gx0P, double* gh_steps, double* gR_steps) {
-    StreamGuard stream_guard_(h);
-    TRY(check_ready(h, /*general=*/false));
-    if (!y) return h->fail(TGP_EINVAL, "tgp_logpdf_adjoint_group: null argument");
-    if (!sweep_group_eligible(h, flags, /*post=*/true, /*explicit_call=*/true))
-        return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_group: Forward models with shared A, a, Q, H (not SDE-described), scalar observations, 5 <= d <= 8 "
-                                         "and T >= 2048 on the group sweep (TGP_OPT_SWEEP >= 1, the engine not declined for the bound model); use "
-                                         "tgp_logpdf_adjoint_missing at d <= 4 and tgp_logpdf_grad otherwise");
+    static const SweepEntry entry = {"tgp_logpdf_adjoint_group", kGroupSweep, 0, nullptr,
+                                     "Forward models with shared A, a, Q, H (not SDE-described), scalar observations, 5 <= d <= 8 "
+                                     "and T >= 2048 on the group sweep (TGP_OPT_SWEEP >= 1, the engine not declined for the bound model); use "
+                                     "tgp_logpdf_adjoint_missing at d <= 4 and tgp_logpdf_grad otherwise",
+                                     " (use tgp_logpdf_grad)"};
     tgp_sweep::AdjointOut o;
     o.gA = gA; o.ga = ga; o.gQ = gQ; o.gH = gH; o.ghh = ghh; o.gR = gR; o.gx0m = gx0m; o.gx0P = gx0P;
-    bool served = false;
-    std::string why;
-    TRY(sweep_group_adjoint_call(h, y, missing, flags, lml_out, o, gh_steps, gR_steps, &served, &why));
-    if (served) return TGP_OK;
-    return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_group: the group sweep declines the gradient: " + why + " (use tgp_logpdf_grad)");
+    return sweep_adjoint_entry(h, entry, y, missing, flags, lml_out, o, nullptr, gh_steps, gR_steps);
 }
 
 // The same for a model described by its SDE and time stamps (tgp_model_set_sde: irregular spacing) -- what sweep_eligible accepts in SDE form -- by the
@@ -560,27 +590,15 @@ int tgp_logpdf_adjoint_group(tgp_handle* h, const double* y, const uint8_t* miss
 // (tgp_model_set_sde): that step's G_0 is contracted into the coefficient sums with tau = 1 and gA1 is zero.
 int tgp_logpdf_adjoint_sde(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, double* gF, double* gPinf, double* gA1,
                            double* ga, double* gH, double* ghh, double* gR, double* gx0m, double* gx0P, double* gh_steps, double* gR_steps) {
-    StreamGuard stream_guard_(h);
-    TRY(check_ready(h, /*general=*/false));
-    if (!y) return h->fail(TGP_EINVAL, "tgp_logpdf_adjoint_sde: null argument");
-    if (!h->sde)
-        return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_sde: the model is not SDE-described (tgp_model_set_sde); use tgp_logpdf_adjoint_missing for models in "
-                                         "LTI form");
-    if (!sweep_eligible(h, flags))
-        return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_sde: Forward SDE-described models with closed-form transitions (TGP_OPT_SDE_CLOSED_FORM = 1), shared a "
-                                         "and H, scalar observations, d <= 4 and T >= 2048 on the sweep engine (TGP_OPT_SWEEP = 1, the engine not declined for the "
-                                         "bound model); use tgp_logpdf_grad_sde otherwise");
-    const int d = h->d, dd = d * d;
-    double buf[4 * 16 + 3 * 4 + 2 + 2 * 16];
-    tgp_sweep::AdjointSdeOut so;
-    so.gl = buf; so.gN1 = so.gl + d; so.gN2 = so.gN1 + dd; so.gPinf = so.gN2 + dd; so.gA1 = so.gPinf + dd; so.ga = so.gA1 + dd; so.gH = so.ga + d;
-    so.ghh = so.gH + d; so.gR = so.ghh + 1; so.gx0m = so.gR + 1; so.gx0P = so.gx0m + d;
-    bool served = false;
-    std::string why;
-    TRY(sweep_adjoint_call(h, y, missing, flags, lml_out, tgp_sweep::AdjointOut(), gh_steps, gR_steps, &served, &why, &so));
-    if (!served) return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_sde: the sweep engine declines the gradient: " + why + " (use tgp_logpdf_grad_sde)");
-    sde_adjoint_outputs(h, so, gF, gPinf, gA1, ga, gH, ghh, gR, gx0m, gx0P);
-    return TGP_OK;
+    static const SweepEntry entry = {"tgp_logpdf_adjoint_sde", kLaneSweep, 1,
+                                     "the model is not SDE-described (tgp_model_set_sde); use tgp_logpdf_adjoint_missing for models in "
+                                     "LTI form",
+                                     "Forward SDE-described models with closed-form transitions (TGP_OPT_SDE_CLOSED_FORM = 1), shared a "
+                                     "and H, scalar observations, d <= 4 and T >= 2048 on the sweep engine (TGP_OPT_SWEEP = 1, the engine not declined for the "
+                                     "bound model); use tgp_logpdf_grad_sde otherwise",
+                                     " (use tgp_logpdf_grad_sde)"};
+    const SdeGrads g = {gF, gPinf, gA1, ga, gH, ghh, gR, gx0m, gx0P};
+    return sweep_adjoint_entry(h, entry, y, missing, flags, lml_out, tgp_sweep::AdjointOut(), &g, gh_steps, gR_steps);
 }
 
 // The same at state dimensions 5 .. 8 by the group sweep's k_sweep_group_adjoint_sde (DESIGN 4.14): what sweep_group_sde_eligible accepts, whatever the
@@ -588,26 +606,14 @@ int tgp_logpdf_adjoint_sde(tgp_handle* h, const double* y, const uint8_t* missin
 // sees the first transition: the host pulls the adjoint in front of update 0 back through A1 (tgp_sweep_group.hip adjoint_blocks_sde).
 int tgp_logpdf_adjoint_group_sde(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, double* gF, double* gPinf, double* gA1,
                                  double* ga, double* gH, double* ghh, double* gR, double* gx0m, double* gx0P, double* gh_steps, double* gR_steps) {
-    StreamGuard stream_guard_(h);
-    TRY(check_ready(h, /*general=*/false));
-    if (!y) return h->fail(TGP_EINVAL, "tgp_logpdf_adjoint_group_sde: null argument");
-    if (!sweep_group_sde_eligible(h, flags, /*explicit_call=*/true))
-        return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_group_sde: Forward SDE-described models (tgp_model_set_sde) with closed-form transitions "
-                                         "(TGP_OPT_SDE_CLOSED_FORM = 1), shared a and H, scalar observations, 5 <= d <= 8 and T >= 2048 on the group sweep "
-                                         "(TGP_OPT_SWEEP >= 1, the engine not declined for the bound model); use tgp_logpdf_adjoint_sde at d <= 4 and "
-                                         "tgp_logpdf_adjoint_group for models in LTI form");
-    constexpr int M = tgp_sweep::kGroupMaxD;
-    double buf[6 * M * M + 4 * M + 2];      // (sized for d = 8)
-    const int d = h->d, dd = d * d;
-    tgp_sweep::AdjointSdeOut so;
-    so.gl = buf; so.gN1 = so.gl + d; so.gN2 = so.gN1 + dd; so.gPinf = so.gN2 + dd; so.gA1 = so.gPinf + dd; so.ga = so.gA1 + dd; so.gH = so.ga + d;
-    so.ghh = so.gH + d; so.gR = so.ghh + 1; so.gx0m = so.gR + 1; so.gx0P = so.gx0m + d;
-    bool served = false;
-    std::string why;
-    TRY(sweep_group_adjoint_sde_call(h, y, missing, flags, lml_out, so, gh_steps, gR_steps, &served, &why));
-    if (!served) return h->fail(TGP_EUNSUPPORTED, "tgp_logpdf_adjoint_group_sde: the group sweep declines the gradient: " + why);
-    sde_adjoint_outputs(h, so, gF, gPinf, gA1, ga, gH, ghh, gR, gx0m, gx0P);
-    return TGP_OK;
+    static const SweepEntry entry = {"tgp_logpdf_adjoint_group_sde", kGroupSweep, 1, nullptr,
+                                     "Forward SDE-described models (tgp_model_set_sde) with closed-form transitions "
+                                     "(TGP_OPT_SDE_CLOSED_FORM = 1), shared a and H, scalar observations, 5 <= d <= 8 and T >= 2048 on the group sweep "
+                                     "(TGP_OPT_SWEEP >= 1, the engine not declined for the bound model); use tgp_logpdf_adjoint_sde at d <= 4 and "
+                                     "tgp_logpdf_adjoint_group for models in LTI form",
+                                     ""};
+    const SdeGrads g = {gF, gPinf, gA1, ga, gH, ghh, gR, gx0m, gx0P};
+    return sweep_adjoint_entry(h, entry, y, missing, flags, lml_out, tgp_sweep::AdjointOut(), &g, gh_steps, gR_steps);
 }
 
 // Two observations per step of ONE latent value with independent noise are one observation of it:

@@ -85,16 +85,19 @@ Mutations (one scratch build each, never committed, run on the device against th
      forgets a start state (and every GP model's x0 is the stationary prior the other branch starts from).  B-x0-not-stationary-d3 was added for the
      branch itself (a prior that is not the stationary one, chunks of 64 steps): with `x = gen` for every warm-up B-x0-not-stationary-d3 fails,
      and nothing else.
-  C  the repair loop takes a pass with bit 2 set (`status & 3` -> `status & 1` in sweep_call): C-behind350-d3-short and C-behind400-d4-short fail (served
+  C  the repair loop takes a pass with bit 2 set (`status & 3` -> `status & 1` in sweep_attempts): C-behind350-d3-short and C-behind400-d4-short fail (served
      where the table says declined), and both test_a_draw_repairs_its_own_warm_up cases (the posterior call behind the draw fails backwards alone under
      default options and is taken at attempt 1).  The C-*-auto cases pass: their first attempt fails forwards as well.
   A  load_inputs gives every step of a block the noise variance of the block's first step (`R[tc[0]]`): 36 fail -- all 32 XS = 1 and XS = 3 cases of
      group A (k_sweep and the draw, every d, both forms), the negative-variance cases in the middle of a chunk (the variance is no longer where the table
      put it), the rebind sequence (two of its models have a noise per step) and the GP-level prediction; every XS = 0 and XS = 2 case passes.
   D  load_inputs turns a gap of exactly 0 into 1e-6: all five test_ties cases and test_prediction_at_training_inputs fail, nothing else.
-  E  sweep_call leaves sweep_state alone behind bit 4: E-negR-mid-d3 and E-negR-edge-d3 fail (state 0 where the table says -1), nothing else.
+  E  sweep_attempts leaves sweep_state alone behind bit 4: E-negR-mid-d3 and E-negR-edge-d3 fail (state 0 where the table says -1), nothing else.
   F  tgp_model_set keeps sweep_W / sweep_Wb / sweep_Wd of the previous model: test_one_handle_bound_to_one_model_after_the_other fails (the geometry
      is not a fresh handle's), nothing else.
+  G  sweep_attempts remembers every kind's second warm-up in sweep_Wb (`back = wk` -> `h->sweep_Wb = wk`): both d = 5 cases of
+     tests/test_gpu_sweep_group_edges.py test_the_call_kinds_in_turn_on_one_handle fail at the logpdf call (Wb = 200, the adjoint's, where the marginals
+     call reported 184); the two d = 2 cases here pass.
   A  c.R and c.hh swapped in fill_args: NOT RUN -- the kernel is chosen from the unswapped pointers, so at XS = 1 / 2 it would read through a null pointer.
   F  need_part never regrown: NOT RUN -- 2050 waves would write their records behind the end of a pinned host buffer.
   (A memory fault on a shared device is not a test outcome.  The XS = 1 / 2 cases of group A compare per-step noise and offset against the oracle with
@@ -450,3 +453,61 @@ def test_the_record_buffer_grows_beyond_2048_waves(tgp):
         out, info, kn = call(tgp, dm2, big, post)
         assert info["waves"] == 2050
         as_the_host(big, post, info, kn, values=out)
+
+
+# ------------------------------------------------------------------------------------------------------------ G: the call kinds in turn on one handle
+def kinds_in_turn(marginals, draw, adjoint, logpdf):
+    """marginals, draw, adjoint, logpdf, the draw again on ONE bound handle.  Each argument runs its call, holds its values to its file's bars and returns
+    the call's tgp_sweep_info.  Every call is served; from the second call of a kind on (logpdf shares the marginals' warm-ups) the engine needs one attempt
+    and reports in the backward slot what that kind's first call reported: the kinds share one call loop (tgp_api_engines.inc sweep_attempts), and no
+    kind's warm-up may leak into another's slot"""
+    first = {}
+    for kind, fn in (("marginals", marginals), ("draw", draw), ("adjoint", adjoint), ("marginals", logpdf), ("draw", draw)):
+        info = fn()
+        print(kind, info)
+        assert info["served"] == 1 and info["status"] == 0 and info["state"] == 1, (kind, info)
+        if kind in first:
+            assert info["attempts"] == 1 and info["Wb"] == first[kind]["Wb"], (kind, info, first[kind])
+        first.setdefault(kind, info)
+
+
+def sde_adjoint_reference(k, t, i):
+    """(lp, g) of tests/_sweep_adjoint_sde.restated for a GP kernel at time stamps t, as build_lgssm binds it; i: the inputs (model, y, mk)"""
+    from tests import _sweep_adjoint_sde as SS
+    F, Pinf, A1, a, H, x0m = SS.gp_blocks(k, t)
+    return SS.restated(F=F, Pinf=Pinf, A1=A1, a=a, H=H, h=float(np.atleast_1d(i["model"]["h"])[0]), R=float(np.atleast_1d(i["model"]["R"])[0]), x0m=x0m,
+                       x0P=Pinf, times=t, y=i["y"], missing=i["mk"])
+
+
+@pytest.mark.parametrize("form", ["lti", "sde"])
+def test_the_call_kinds_in_turn_on_one_handle(tgp, form):
+    """d = 2, T = 4096, 10 % missing, TGP_OPT_SWEEP = 2: k_sweep<posterior>, k_sweep_draw, k_sweep_adjoint, k_sweep<logpdf>, k_sweep_draw on one handle"""
+    from tests import _sweep_adjoint as SA
+    from tests import test_gpu_sweep_adjoint as TA
+    from tests import test_gpu_sweep_adjoint_sde as TS
+    c = E.case("G-kinds-d2-" + form, "G", 2, 4096, what="draw", sde=form == "sde")
+    i = E.inputs(c)
+    dm = device_model(tgp, c)
+    dm.handle_options[tgp._lib.OPT_SWEEP] = 2
+    few = lambda a: a <= 4      # noqa: E731 (a first call may repair its warm-ups)
+
+    def k_call(post):
+        out, info, kn = call(tgp, dm, c, post)
+        assert kn == {kname(c, post)}, kn
+        at_the_bars(c, out)
+        return info
+
+    def draw():
+        rc, out, info, kn = draw_call(tgp, dm, i["y"], i["mk"], i["Rn"], i["eps"])
+        assert rc == 0 and kn == {"k_sweep_draw<%s>" % form}, (rc, kn)
+        assert err(out, E.draw_reference(c)) <= BAR
+        return info
+
+    def adjoint():
+        if c.sde:
+            lp, g = sde_adjoint_reference(E.MODELS[c.d], i["t"], i)
+            return TS.served(tgp, dm, dict(y=i["y"], missing=i["mk"], lp=lp, g=g), attempts=few)[1]
+        lp, g = SA.restated(i["model"], i["y"], i["mk"])
+        return TA.served(tgp, dm, i["y"], i["mk"], lp, g, attempts=few)[1]
+
+    kinds_in_turn(lambda: k_call(True), draw, adjoint, lambda: k_call(False))

@@ -135,7 +135,7 @@ def test_a_slowly_forgetting_series_is_handed_over_by_the_plan(tgp):
 
 def test_sparse_observations_fail_the_first_hand_over_check_unforced(tgp):
     """one step in sixteen observed: the filter forgets far more slowly, in steps, than the plan's estimate for a series observed at every step, so the first
-    attempt's hand-over check fails without any forced geometry and sweep_run doubles the warm-ups: served after >= 2 attempts, or -- warm-ups beyond four
+    attempt's hand-over check fails without any forced geometry and sweep_attempts doubles the warm-ups: served after >= 2 attempts, or -- warm-ups beyond four
     chunks / still short after four attempts -- declined after at least one launch, the engine off for the bound model"""
     T = 8192
     k, dt, s2 = SG.KERNELS[5]
@@ -233,3 +233,55 @@ def test_the_served_flag_is_cleared_by_a_later_call_of_a_stationary_engine(tgp, 
     assert hd.sweep_info()["served"] == 0 and hd.sweep_info()["attempts"] == 0
     want = sk.logpdf(c["model"], c["y"])
     assert abs(got - want) <= 1e-10 * abs(want)
+
+
+@pytest.mark.parametrize("form", ["lti", "sde"])
+def test_the_call_kinds_in_turn_on_one_handle(tgp, form):
+    """d = 5, T = 4096, 10 % missing, TGP_OPT_SWEEP = 2: k_sweep_group<posterior>, k_sweep_group_draw, k_sweep_group_adjoint, k_sweep_group<logpdf>,
+    k_sweep_group_draw on one handle (tests/test_gpu_sweep_edges.py kinds_in_turn); every call at its own file's bars"""
+    from tests import _sweep_adjoint as SA
+    from tests import _sweep_group_draw as GD
+    from tests import _sweepdraw as SD
+    from tests import test_gpu_sweep_group_adjoint as TA
+    from tests import test_gpu_sweep_group_adjoint_sde as TS
+    from tests.test_gpu_sweep_edges import kinds_in_turn, sde_adjoint_reference
+    from tests.test_gpu_sweep_group_draw import BAR, draw_call
+    from tests.test_gpu_sweep_group_sde import _bind
+    d, T, sde = 5, 4096, form == "sde"
+    k, dt, s2 = SG.KERNELS[d]
+    rng = np.random.default_rng(70 + sde)
+    t = np.cumsum(rng.uniform(0.5 * dt, 1.5 * dt, T)) if sde else ("regular", 0.0, dt, T)
+    model, y, _ = U.gp_case(k, t, s2, seed=71 + sde)
+    mk = rng.random(T) < 0.1
+    mk[0] = mk[T - 1] = True
+    Rn = rng.random(T) * 0.05
+    eps = (rng.standard_normal((T, d)), rng.standard_normal(T), rng.standard_normal(d))
+    c = dict(zip(("lp", "pm", "pv"), _reference(model, y, mk, Rn, fast=True)), yin=np.where(mk, np.nan, y))
+    dm = _bind(tgp, k, t, s2) if sde else SG.device_model(tgp, model)
+    hd = dm.handle()
+    few = lambda a: a <= 4      # noqa: E731 (a first call may repair its warm-ups)
+
+    def k_call(post):
+        hd.set_option(tgp._lib.OPT_PROFILE, 1)
+        hd.profile_reset()
+        out = tgp.logpdf_and_posterior_marginals(dm, c["yin"], Rn) if post else (tgp.logpdf(dm, c["yin"]),)
+        info, names = hd.sweep_info(), set(hd.profile())
+        hd.set_option(tgp._lib.OPT_PROFILE, 0)
+        assert names == {"k_sweep_group<%s,%s>" % (form, "posterior" if post else "logpdf")}, names
+        _values_ok(c, *out)
+        return info
+
+    def draw():
+        rc, out, info, names = draw_call(tgp, dm, y, mk, Rn, eps, entry="tgp_posterior_rand_group_sde" if sde else "tgp_posterior_rand_group")
+        assert rc == 0 and names == {"k_sweep_group_draw<%s>" % form}, (rc, names)
+        assert GD.err(out, SD.draw_restated(model, y, mk, Rn, eps)) <= BAR
+        return info
+
+    def adjoint():
+        if sde:
+            lp, g = sde_adjoint_reference(k, t, dict(model=model, y=y, mk=mk))
+            return TS.served(tgp, dm, dict(y=y, missing=mk, lp=lp, g=g), attempts=few)[1]
+        lp, g = SA.restated(model, y, mk)
+        return TA.served(tgp, dm, y, mk, lp, g, attempts=few)[1]
+
+    kinds_in_turn(lambda: k_call(True), draw, adjoint, lambda: k_call(False))

@@ -230,7 +230,7 @@ def test_the_whole_walk_in_the_plans_geometry_matches_the_reference(exe, tmp_pat
 
 def test_the_repair_case(exe, tmp_path):
     """tests/test_gpu_sweep_group_sde.py's repair case, gaps and seed: the forward hand-over distance is above the check's 1e-12 at the plan's first
-    guess W and below it at 2 W (one doubling of sweep_run's repair loop), and the unstretched series passes at W"""
+    guess W and below it at 2 W (one doubling of sweep_attempts' repair loop), and the unstretched series passes at W"""
     d = SS.REPAIR_D
     k, dt, s2 = SG.KERNELS[d]
     t0 = np.cumsum(SS.repair_gaps(dt, 0, 0, stretched=False))
