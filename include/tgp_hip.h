@@ -162,7 +162,12 @@ typedef struct tgp_handle tgp_handle;
                            k_sweep_group<sde,posterior>, the transition of every step built from its gap; under 1 these models stay on the
                            general engine; their gradient has an entry point of its own, tgp_logpdf_adjoint_group_sde
                            (k_sweep_group_adjoint<sde>; served under 1 and 2 alike), and so has their draw,
-                           tgp_posterior_rand_group_sde (k_sweep_group_draw<sde>; likewise).  Both step aside
+                           tgp_posterior_rand_group_sde (k_sweep_group_draw<sde>; likewise).  2 only: 9 <= d <= 16 in LTI form
+                           (shared A, a, Q, H; not tgp_model_set_sde), T >= 2048, with a mask, a noise variance or an emission offset per step --
+                           tgp_logpdf / tgp_[logpdf_and_]posterior_marginals run on the TILE sweep (tgp_sweep_tile.hip): a chunk per
+                           wave, the covariance one fp64 MFMA tile, the backward pass a Bryson-Frazier recursion on a record of 20 doubles per
+                           step; kernels k_sweep_tile<logpdf> / k_sweep_tile<posterior>; fully observed models with one noise variance stay on
+                           the wide engine, and under 1 all of these stay where they were (profiles/sweep_tile_time.txt).  All step aside
                            on an explicit request for the general engine (TGP_REUSE_REDUCE, TGP_OPT_CHUNK, TGP_OPT_VARIANT, TGP_OPT_STEADY 0 / 1,
                            TGP_OPT_GRAPH).  0: the general chunked-scan engine as before; tgp_posterior_rand_missing, tgp_posterior_rand_group,
                            tgp_logpdf_adjoint_missing and tgp_logpdf_adjoint_group answer TGP_EUNSUPPORTED for these models. */

@@ -26,6 +26,7 @@
 #include "tgp_powers.hpp"
 #include "tgp_sweep.hpp"
 #include "tgp_sweep_group.hpp"
+#include "tgp_sweep_tile.hpp"
 #include "tgp_wide.hpp"
 #include "tgp_adjoint_host.hpp"
 #include "tgp_alloc.hpp"
@@ -356,12 +357,14 @@ struct tgp_handle {
     // variance or an emission offset per step, irregular spacing.  One launch; a call whose warm-ups prove too short is repeated with longer
     // ones (remembered for the bound model), a model it does not serve goes on to the general engine.  5 <= d <= 8 in LTI form: the group sweep
     // (tgp_sweep_group.hip), the same algorithm with a chunk spread over 8 lanes; it shares the state, hints and forced geometry below.
-    // 1: the group sweep takes the measured winners only (sweep_group_default_route); 2: every (d, call) pair.
+    // 1: the group sweep takes the measured winners only (sweep_group_default_route); 2: every (d, call) pair.  9 <= d <= 16 in LTI form, under 2
+    // only: the tile sweep (tgp_sweep_tile.hip), a chunk per wave with the covariance in one fp64 MFMA tile; the same state and hints.
     int opt_sweep = 1;
     long long opt_stream_min_T = -1;      // TGP_OPT_STREAM_MIN_T
     tgp_sweep::Engine* sweep = nullptr;
     tgp_sweep_group::Engine* sweep_group = nullptr;
-    int sweep_state = 0;          // 0 untried for the bound model, 1 served the last call, -1 does not apply
+    tgp_sweep_tile::Engine* sweep_tile = nullptr;
+    int sweep_state = 0;         // 0 untried for the bound model, 1 served the last call, -1 does not apply
     int sweep_W = 0, sweep_Wb = 0;     // warm-ups the bound model's last served call needed (0: estimate)
     int sweep_Wd = 0;             // the same for the draw's warm-up (tgp_posterior_rand_missing / _group; 0: the backward warm-up's estimate)
     int sweep_Wa = 0;             // the same for the adjoint's warm-up (tgp_logpdf_adjoint_missing / _group; 0: the forward warm-up's value)
@@ -1325,6 +1328,7 @@ int tgp_destroy(tgp_handle* h) {
     if (h->modal) tgp_modal::destroy(h->modal);
     if (h->sweep) tgp_sweep::destroy(h->sweep);
     if (h->sweep_group) tgp_sweep_group::destroy(h->sweep_group);
+    if (h->sweep_tile) tgp_sweep_tile::destroy(h->sweep_tile);
     if (h->host_result) (void)tgp_alloc::host_free(h->host_result);
     if (h->adj_host) (void)tgp_alloc::host_free(h->adj_host);
     if (h->flt_host) (void)tgp_alloc::host_free(h->flt_host);
@@ -1744,7 +1748,9 @@ int tgp_model_set(tgp_handle* h, int64_t T, int d, int p, int ordering, uint32_t
     const uint32_t host_bits = TGP_SHARED_A | TGP_SHARED_a | TGP_SHARED_Q | TGP_SHARED_H;
     const bool one_launch_model = h->lti && !h->binding_sde && p == 1 && (flags & TGP_SHARED_R) && tgp_steady::supports(d);      // what `hostm` stands for
     h->sweepm.clear();
-    if ((flags & host_bits) == host_bits && p == 1 && tgp_steady::supports(d)) {
+    // (d <= 8: the lane and the group sweep; 9 <= d <= 16 in LTI form: the tile sweep, tgp_sweep_tile.hip)
+    const bool tile_d = d >= tgp_sweep::kTileMinD && d <= tgp_sweep::kTileMaxD && !h->binding_sde;
+    if ((flags & host_bits) == host_bits && p == 1 && (tgp_steady::supports(d) || tile_d)) {
         TRY(pack_host_blocks(h, h->sweepm, d, dev, /*skip_hh=*/false, A, a, Q, H, hh, R));
         // a representative noise variance (the sweep engine's warm-up estimate): the median of a sample of the per-step values below the
         // "missing" level of missings.jl:43
@@ -2024,6 +2030,11 @@ int tgp_logpdf(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t 
     if (wide_eligible(h, y, missing)) {      // wide LTI models (8 < d <= 63): the stationary closed loop across the chip (tgp_wide.hip)
         bool served = false;
         TRY(wide_call(h, y, flags, nullptr, nullptr, nullptr, out, &served));
+        if (served) return TGP_OK;
+    }
+    if (sweep_tile_eligible(h, flags, missing)) {      // 9 <= d <= 16 with gains that vary in time, TGP_OPT_SWEEP = 2 (tgp_sweep_tile.hip)
+        bool served = false;
+        TRY(sweep_call(h, y, missing, flags, nullptr, nullptr, nullptr, out, &served, kTileSweep));
         if (served) return TGP_OK;
     }
     resolve_table(h);
@@ -2360,6 +2371,11 @@ int tgp_posterior_marginals(tgp_handle* h, const double* y, const uint8_t* missi
     if (wide_eligible(h, y, missing)) {      // wide LTI models: tgp_wide.hip
         bool served = false;
         TRY(wide_call(h, y, flags, Rnew, mean_out, var_out, lml_out, &served));
+        if (served) return TGP_OK;
+    }
+    if (sweep_tile_eligible(h, flags, missing)) {      // 9 <= d <= 16 with gains that vary in time, TGP_OPT_SWEEP = 2 (tgp_sweep_tile.hip)
+        bool served = false;
+        TRY(sweep_call(h, y, missing, flags, Rnew, mean_out, var_out, lml_out, &served, kTileSweep));
         if (served) return TGP_OK;
     }
     resolve_table(h);

@@ -184,6 +184,18 @@ bool sweep_group_sde_eligible(const tgp_handle* h, uint32_t flags, bool explicit
     return h->sde_closed && h->opt_sde_closed && !h->sde_coef_host.empty() && h->mv.sa == 0;
 }
 
+// The tile sweep (tgp_sweep_tile.hip, DESIGN 4.16): sweep_group_eligible's conditions at 9 <= d <= 16, LTI form, under TGP_OPT_SWEEP = 2 only -- no (d, call)
+// pair is routed here by default (profiles/sweep_tile_time.txt has the medians beside the general engine's: a routing change would rest on them).  A
+// fully observed series with one noise variance is the wide engine's (tgp_wide.hip) and, where that declines, the general engine's as before.
+bool sweep_tile_eligible(const tgp_handle* h, uint32_t flags, const uint8_t* missing) {
+    if (h->opt_sweep < 2 || h->sweep_state < 0 || h->is_dense || h->p != 1 || h->ordering != 0 || h->sde) return false;
+    if (h->d < tgp_sweep::kTileMinD || h->d > tgp_sweep::kTileMaxD) return false;
+    if (missing == nullptr && h->mv.sR == 0) return false;
+    if ((flags & TGP_REUSE_REDUCE) || h->opt_chunk != 0 || h->variant_opt != 0 || !h->opt_steady2 || h->opt_graph != 0) return false;
+    if (h->T < tgp_sweep::kTileMinT || h->mv.T != h->T || h->mv.sH != 0 || h->sweepm.empty()) return false;
+    return h->mv.sA == 0 && h->mv.sa == 0 && h->mv.sQ == 0;
+}
+
 // The host model the plans of both engines read, from the staged blocks of the bound model.  record_pinf: the stationary covariance of an SDE-described
 // model is the one tgp_model_set_sde took (the closed-form record; tgp_model_set_x0 may have replaced the prior since) -- the adjoint calls and the group
 // sweep's draw.  tgp_logpdf, the posterior calls and the lane sweep's draw pass none: the bound x0P stands for Pinf.  (The plans read Pinf, coef and
@@ -219,8 +231,8 @@ const struct { const char *tag, *slot, *not_pd, *not_finite; } kSweepKindText[3]
     {" draw", "Wd", "a Cholesky pivot of the draw is not positive", "non-finite values in the draw"},
     {" adjoint", "Wa", "an innovation variance is not positive", "non-finite values in the pass"}};
 
-// What sweep_attempts needs of an engine: the lane sweep (tgp_sweep.hip, d <= 4) and the group sweep (tgp_sweep_group.hip, 5 <= d <= 8) behind one call
-// sequence.  Plain function pointers on the handle, two static instances (no allocation on the call path).  Wk: the kind's second warm-up; post: a
+// What sweep_attempts needs of an engine: the lane sweep (tgp_sweep.hip, d <= 4), the group sweep (tgp_sweep_group.hip, 5 <= d <= 8) and the tile sweep
+// (tgp_sweep_tile.hip, 9 <= d <= 16) behind one call sequence.  Plain function pointers on the handle, three static instances (no allocation on the call path).  Wk: the kind's second warm-up; post: a
 // marginals call asks for the posterior marginals.
 struct SweepOps {
     const char* tag;       // in the TGP_STEADY_DEBUG lines
@@ -288,6 +300,24 @@ const SweepOps kGroupSweep = {
         if (so) tgp_sweep_group::adjoint_blocks_sde(h->sweep_group, mh, *so);
         else tgp_sweep_group::adjoint_blocks(h->sweep_group, o);
     }};
+
+// The tile sweep serves marginals calls only (logpdf, posterior marginals): one backward slot, no draw, no gradient.
+const SweepOps kTileSweep = {
+    "sweep tile", "tile sweep",
+    [](const tgp_handle*, SweepKind, bool post) { return tgp_sweep_tile::kernel_name(post); },
+    [](tgp_handle* h, const tgp_sweep::ModelHost& mh, SweepKind kind, bool post, int W, int Wk, std::string* why) {
+        if (kind != SweepKind::marginals) {
+            if (why) *why = "the tile sweep has no draw and no gradient";
+            return false;
+        }
+        if (!h->sweep_tile) h->sweep_tile = tgp_sweep_tile::create();
+        tgp_sweep_tile::force_geometry(h->sweep_tile, h->sweep_fC, h->sweep_fW, h->sweep_fWb);
+        return tgp_sweep_tile::plan(h->sweep_tile, mh, h->T, W, Wk, h->num_cu, post, why);
+    },
+    [](tgp_handle* h, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep_tile::enqueue(h->sweep_tile, h->stream, c, kname, err); },
+    [](tgp_handle* h, SweepKind, int* status, int* w, int* wk, double* df, double* dk) { return tgp_sweep_tile::finish(h->sweep_tile, status, w, wk, df, dk); },
+    [](tgp_handle* h, int* C, int64_t* nw) { tgp_sweep_tile::geometry(h->sweep_tile, C, nullptr, nullptr, nw); },
+    [](tgp_handle*, const tgp_sweep::ModelHost&, const tgp_sweep::AdjointOut&, const tgp_sweep::AdjointSdeOut*) {}};
 
 // Runs a call on one of the sweep engines: staging ONCE, up to four attempts with doubled warm-ups, the engine switched off for the bound model where it
 // cannot serve it.  What a kind brings:

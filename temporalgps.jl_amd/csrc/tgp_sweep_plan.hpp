@@ -604,4 +604,117 @@ inline bool plan_group(GroupPlan* p, const Forced& f, const ModelHost& m, int64_
     }
 }
 
+// ---- the tile sweep (tgp_sweep_tile.hip): the same algorithm at 9 <= d <= 16, a chunk per wave, the covariance one fp64 MFMA tile --------
+// LTI form only.  A wave owns one chunk: it warms up over the W steps in front of it, and checks the warm-up its neighbour starts from (the last W steps
+// of its own chunk) against its own run; a posterior call filters Wb steps beyond the chunk for the backward warm-up.
+constexpr int kTileMinD = 9, kTileMaxD = 16, kTileDP = 16;
+constexpr int kTileRec = kTileDP + 4;         // doubles a posterior call's forward run leaves per step: w (16), H P- H', H m-, v, s (0: a missing step)
+constexpr int kTileWavesPerCU = 8;            // two per SIMD: registers (profiles/sweep_tile_resources.txt) and LDS allow it
+constexpr int64_t kTileMinT = 2048;           // shorter series stay on the general engine
+
+// The model's shared blocks as the tile kernels read them (device memory: larger than a kernel's argument segment): padded to 16 with zeros, A row-major,
+// the symmetric blocks full.
+struct TileModelC {
+    double A[256];                       // [16 i + k]
+    double Q[256], x0P[256], gP[256];    // [i + 16 j]
+    double a[16], H[16], x0m[16], gm[16];
+    double sd[16], isd[16];              // sqrt(gP[i][i]) and its reciprocal, zero in the padding: the scale of a state's element i (the hand-over checks)
+    double hh, R, tol, tol_b;
+};
+
+struct TilePlan {
+    int d = 0;
+    bool post = false;
+    int C = 0, W = 0, Wb = 0;
+    int64_t T = 0, nchunks = 0;
+    TileModelC mc;
+};
+
+namespace plan_detail {
+
+template <int D> inline bool plan_tile_d(TilePlan* e, const Forced& f, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why) {
+    double Aty[D * D], Qty[D * D], gm[D], Ps[D * D];
+    if (!stationary_prior<D>(m, Aty, Qty, gm, Ps)) {
+        if (why) *why = "the transition has no stationary covariance";
+        return false;
+    }
+    int W = w_hint, Wb = wb_hint;
+    if (!estimate_warmups<D>(Aty, Qty, m.H, m.R, W, Wb, why)) return false;
+    auto up = [](int v, int q) { return (v + q - 1) / q * q; };
+    // chunk length: kTileWavesPerCU waves per CU, a chunk each; a chunk holds the backward warm-up (the check runs over its first Wb steps)
+    const int64_t slots = (int64_t)std::max(num_cu, 1) * kTileWavesPerCU;
+    int64_t C = up((int)std::min<int64_t>((T + slots - 1) / slots, 1 << 20), 8);
+    C = std::max<int64_t>(C, 64);
+    C = std::max<int64_t>(C, Wb);
+    if (f.C > 0) C = up(f.C, 8);
+    if (f.W > 0) W = up(f.W, 8);
+    if (f.Wb > 0) Wb = up(f.Wb, 8);
+    if (Wb > C) Wb = (int)C;
+    if (W > kMaxWarm || (f.C == 0 && W > 4 * C)) {
+        if (why) *why = "forward warm-up longer than four chunks";
+        return false;
+    }
+    const int64_t nchunks = (T + C - 1) / C;
+    if (nchunks < 2) {
+        if (why) *why = "fewer than two chunks";
+        return false;
+    }
+    e->d = D;
+    e->post = post;
+    e->T = T;
+    e->C = (int)C;
+    e->W = W;
+    e->Wb = Wb;
+    e->nchunks = nchunks;
+    TileModelC& mc = e->mc;
+    std::memset(&mc, 0, sizeof mc);
+    for (int i = 0; i < D; ++i) {
+        mc.a[i] = m.a[i];
+        mc.H[i] = m.H[i];
+        mc.x0m[i] = m.x0m[i];
+        mc.gm[i] = gm[i];
+        for (int k = 0; k < D; ++k) mc.A[16 * i + k] = m.A[i + k * D];
+    }
+    for (int j = 0; j < D; ++j)
+        for (int i = 0; i < D; ++i) {
+            const int lo = std::min(i, j), hi = std::max(i, j);
+            mc.Q[i + 16 * j] = Qty[i + j * D];
+            mc.x0P[i + 16 * j] = m.x0P[lo + hi * D];      // Symmetric(P): the upper triangle is what the reference reads (lgc.jl:50)
+            mc.gP[i + 16 * j] = 0.5 * (Ps[i + j * D] + Ps[j + i * D]);
+        }
+    for (int i = 0; i < D; ++i) {
+        mc.sd[i] = std::sqrt(mc.gP[i + 16 * i]);
+        mc.isd[i] = mc.sd[i] > 0.0 ? 1.0 / mc.sd[i] : 0.0;
+    }
+    mc.hh = m.hh;
+    mc.R = m.R;
+    mc.tol = kTol;
+    mc.tol_b = kTolBack;
+    return true;
+}
+
+}  // namespace plan_detail
+
+// The geometry of a tile-sweep call; false: the engine declines (`why` says so).  w_hint / wb_hint as make_plan's.
+inline bool plan_tile(TilePlan* p, const Forced& f, const ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why) {
+    if (m.d < kTileMinD || m.d > kTileMaxD || m.sde) {
+        if (why) *why = "state dimension";
+        return false;
+    }
+    if (T < kTileMinT) {
+        if (why) *why = "series shorter than 2048 steps";
+        return false;
+    }
+    switch (m.d) {
+        case 9: return plan_detail::plan_tile_d<9>(p, f, m, T, w_hint, wb_hint, num_cu, post, why);
+        case 10: return plan_detail::plan_tile_d<10>(p, f, m, T, w_hint, wb_hint, num_cu, post, why);
+        case 11: return plan_detail::plan_tile_d<11>(p, f, m, T, w_hint, wb_hint, num_cu, post, why);
+        case 12: return plan_detail::plan_tile_d<12>(p, f, m, T, w_hint, wb_hint, num_cu, post, why);
+        case 13: return plan_detail::plan_tile_d<13>(p, f, m, T, w_hint, wb_hint, num_cu, post, why);
+        case 14: return plan_detail::plan_tile_d<14>(p, f, m, T, w_hint, wb_hint, num_cu, post, why);
+        case 15: return plan_detail::plan_tile_d<15>(p, f, m, T, w_hint, wb_hint, num_cu, post, why);
+        default: return plan_detail::plan_tile_d<16>(p, f, m, T, w_hint, wb_hint, num_cu, post, why);
+    }
+}
+
 }  // namespace tgp_sweep

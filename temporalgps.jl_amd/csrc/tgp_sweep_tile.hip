@@ -1,0 +1,494 @@
+// The tile sweep: see tgp_sweep_tile.hpp (what and why) and DESIGN 4.16 (geometry, operand layouts, LDS and register budget, the record).  gfx950 only.
+// One wave per workgroup; a wave's LDS: one padded 16 x 17 tile (2176 B), the transpose of A P (forwards) and of A' N (backwards).
+//
+// Layouts of v_mfma_f64_16x16x4_f64 as tgp_dense_fused.hpp uses them, lane = (lr = lane % 16, lq = lane / 16):
+//   A-operand (16 x 4):  lane holds X[lr][lq]         B-operand (4 x 16):  lane holds Y[lq][lr]
+//   accumulator (16 x 16, 4 doubles):  register r of a lane holds Z[lq + 4 r][lr]
+// so register r of an accumulator-layout tile S is the B-operand "rows lq + 4 r of S", and with xf[r] = X[lr][lq + 4 r] the four MFMAs
+// sum_r mfma(xf[r], S[r]) give X S: the k-index of the product runs over lq + 4 r in another order, nothing else.
+// A vector lives in "column form" (lane holds v[lr], the same in the four row groups); its "row form" v[lq + 4 r] comes by four shuffles.
+// The padding (rows and columns >= d) is zero in every block of the model, stays zero in P, m, N, r and adds exact zeros to every sum.
+#include "tgp_sweep_tile.hpp"
+#include "tgp_alloc.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+namespace tgp_sweep_tile {
+
+using tgp_sweep::fast_rcp;
+using tgp_sweep::LmlAcc;
+using tgp_sweep::TileModelC;
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+constexpr int DP = tgp_sweep::kTileDP, REC = tgp_sweep::kTileRec;
+constexpr int kTLD = DP + 1;      // the transpose tile's leading dimension: rows written by 16 consecutive lanes, columns read at stride 17
+
+struct TArgs {
+    const TileModelC* mc;      // device
+    tgp_sweep::Streams st;
+    long long T;
+    int C, W, Wb, d;
+    double* mean;
+    double* var;
+    double* rec;       // [chunk][C + Wb][REC]: the forward run's record of the chunk's steps and of the Wb steps behind them (posterior calls)
+    double* part;      // [chunk][4]: share of the log marginal likelihood, status bits, forward / backward distance (pinned host memory)
+};
+
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+template <int CTRL> __device__ __forceinline__ double dpp_move(double x) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xF, 0xF, false);
+    return __hiloint2double(hi, lo);
+}
+// sum over the 16 lanes of a row (one DPP row), every lane ending with the same bits
+__device__ __forceinline__ double row_sum(double x) {
+    x += dpp_move<0xB1>(x);       // quad_perm:[1,0,3,2]
+    x += dpp_move<0x4E>(x);       // quad_perm:[2,3,0,1]
+    x += dpp_move<0x141>(x);      // row_half_mirror
+    x += dpp_move<0x140>(x);      // row_mirror
+    return x;
+}
+// sum over the four row groups (lanes lr, lr + 16, lr + 32, lr + 48), every lane ending with the same bits
+__device__ __forceinline__ double cross_sum(double x) {
+    x += __shfl_xor(x, 16, 64);
+    x += __shfl_xor(x, 32, 64);
+    return x;
+}
+__device__ __forceinline__ double wave_max(double x) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double o = __shfl_xor(x, off, 64);
+        x = o > x ? o : x;
+    }
+    return x;
+}
+__device__ __forceinline__ double rdlane(double v, int l) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ d4 mfma(double a, double b, d4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+
+// a lane's view of the wave's tile
+struct Lane {
+    int lr, lq;
+    double* sT;        // the wave's transpose tile
+
+    // X S X' + init for a symmetric S in the accumulator layout, xf[r] = X[lr][lq + 4 r]: T = X S (four MFMAs), T' through LDS, X T' on top of init
+    __device__ __forceinline__ d4 sandwich(const d4& xf, const d4& S, const d4& init) const {
+        d4 t = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) t = mfma(xf[r], S[r], t);
+        wave_sync();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sT[(lq + 4 * r) * kTLD + lr] = t[r];
+        wave_sync();
+        d4 out = init;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) out = mfma(xf[r], sT[lr * kTLD + lq + 4 * r], out);
+        return out;
+    }
+    // (X v)[lr] in column form from v in column form
+    __device__ __forceinline__ double matvec(const d4& xf, double vC) const {
+        double p = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) p = fma(xf[r], __shfl(vC, lq + 4 * r, 64), p);
+        return cross_sum(p);
+    }
+    // S v for a symmetric S in the accumulator layout: row form (register r: element lq + 4 r) by row sums, column form by symmetry
+    __device__ __forceinline__ void symvec(const d4& S, double vC, const d4& vR, d4& outR, double& outC) const {
+        double p = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            outR[r] = row_sum(S[r] * vC);
+            p = fma(S[r], vR[r], p);
+        }
+        outC = cross_sum(p);
+    }
+};
+
+// the blocks of the model a lane keeps in registers
+struct Blocks {
+    d4 af;         // A[lr][lq + 4 r]: the A-operands of the forward sandwich
+    d4 atf;        // A[lq + 4 r][lr]: those of the backward one (A')
+    d4 Q;          // accumulator layout
+    d4 HR;         // H in row form
+    double HC, aC; // H, a in column form
+    double hh, R;
+};
+
+// 64 steps of the observation streams, one per lane (ascending from tb forwards, descending from tb backwards), handed out by v_readlane.
+// XS bit 0: the noise variance is per step, bit 1: the emission offset is.
+struct Row {
+    double y, R, hh, rn;
+    unsigned mk;
+};
+template <int XS, bool BACK> __device__ __forceinline__ void load_row(const TArgs& ka, long long tb, int lane, Row& r) {
+    const long long t = tgp_sweep::clamp_t(BACK ? tb - lane : tb + lane, ka.T);
+    r.y = BACK ? 0.0 : ka.st.y[t];
+    r.R = ((XS & 1) && !BACK) ? ka.st.R[t] : 0.0;
+    r.hh = (XS & 2) ? ka.st.hh[t] : 0.0;
+    r.rn = BACK ? ka.st.Rnew[ka.st.rnew_per_step ? t : 0] : 0.0;
+    r.mk = (!BACK && ka.st.mask != nullptr) ? (unsigned)ka.st.mask[t] : 0u;
+}
+
+// One step of the filter (lgc.jl:46-52, :247-257; a missing step predicts only).  rec (null: none): the step's record for the backward run.
+__device__ __forceinline__ void fstep(const Lane& ln, const Blocks& b, d4& P, double& mC, double y, double Rt, double ht, bool obs, LmlAcc& acc, bool lml, bool& ok, double* rec) {
+    const d4 Pm = ln.sandwich(b.af, P, b.Q);
+    const double mp = ln.matvec(b.af, mC) + b.aC;
+    d4 wR;
+    double wC;
+    ln.symvec(Pm, b.HC, b.HR, wR, wC);
+    const double hph = row_sum(b.HC * wC), hm = row_sum(b.HC * mp);
+    const double S = obs ? hph + Rt : 1.0;
+    ok = ok && (S > 0.0);
+    const double iS = obs ? fast_rcp(S) : 0.0;
+    const double v = obs ? (y - (hm + ht)) : 0.0;
+    const double viS = v * iS;
+    mC = fma(wC, viS, mp);
+    const double wi = wC * iS;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) P[r] = fma(-wR[r], wi, Pm[r]);
+    if (lml) {
+        acc.q = fma(v, viS, acc.q);
+        acc.prod *= S;
+        acc.n += obs ? 1.0 : 0.0;
+    }
+    if (rec != nullptr) {
+        if (ln.lq == 0) rec[ln.lr] = wC;
+        if (ln.lr == 0 && ln.lq == 1) {
+            rec[DP] = hph;
+            rec[DP + 1] = hm;
+            rec[DP + 2] = v;
+            rec[DP + 3] = obs ? S : 0.0;
+        }
+    }
+}
+
+// One step of the Bryson-Frazier recursion, backwards over step t with its record: (r, N) behind the step on entry, in front of it on return --
+// m_s = m- + P- r, P_s = P- - P- N P- -- and the step's marginals without the replaced noise: mean = H m- + w' r + h_t, var = H P- H' - w' N w.
+__device__ __forceinline__ void bstep(const Lane& ln, const Blocks& b, d4& N, double& rC, const double* rec, double ht, double& mean, double& var) {
+    const double wC = rec[ln.lr];
+    d4 wR;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) wR[r] = rec[ln.lq + 4 * r];
+    const double hph = rec[DP], hm = rec[DP + 1], v = rec[DP + 2], s = rec[DP + 3];
+    const d4 zero = {0.0, 0.0, 0.0, 0.0};
+    const d4 Np = ln.sandwich(b.atf, N, zero);      // A' N A
+    const double rp = ln.matvec(b.atf, rC);         // A' r
+    d4 uR;
+    double uC;
+    ln.symvec(Np, wC, wR, uR, uC);                  // u = (A' N A) w
+    const double q = row_sum(wC * uC), rho = row_sum(wC * rp);
+    const double iS = s > 0.0 ? fast_rcp(s) : 0.0;  // (a missing step: (r, N) pass through the transition alone)
+    const double c = fma(-hph, iS, 1.0);            // 1 - H K = R / s
+    mean = fma(rho, c, hph * v * iS) + (hm + ht);
+    var = fma(-q * c, c, hph * c);
+    rC = fma(b.HC, (v - rho) * iS, rp);
+    const double k2 = fma(q * iS, iS, iS);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) N[r] = fma(b.HR[r] * b.HC, k2, fma(-iS, fma(b.HR[r], uC, uR[r] * b.HC), Np[r]));
+}
+
+// (two waves per SIMD: the register counts are in profiles/sweep_tile_resources.txt)
+template <int XS, bool POST>
+__global__ __launch_bounds__(64) void k_sweep_tile(const TArgs ka) {
+    __shared__ double sT[DP * kTLD];
+    const int lane = threadIdx.x;
+    Lane ln;
+    ln.lr = lane & 15;
+    ln.lq = lane >> 4;
+    ln.sT = sT;
+    const int lr = ln.lr, lq = ln.lq;
+    const TileModelC& mc = *ka.mc;
+    Blocks b;
+    d4 gP, x0P, sdR, isdR;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int i = lq + 4 * r;
+        b.af[r] = mc.A[DP * lr + i];
+        b.atf[r] = mc.A[DP * i + lr];
+        b.Q[r] = mc.Q[i + DP * lr];
+        b.HR[r] = mc.H[i];
+        gP[r] = mc.gP[i + DP * lr];
+        x0P[r] = mc.x0P[i + DP * lr];
+        sdR[r] = mc.sd[i];
+        isdR[r] = mc.isd[i];
+    }
+    b.HC = mc.H[lr];
+    b.aC = mc.a[lr];
+    b.hh = mc.hh;
+    b.R = mc.R;
+    const double gmC = mc.gm[lr], x0mC = mc.x0m[lr], sdC = mc.sd[lr], isdC = mc.isd[lr];
+
+    const long long T = ka.T, chunk = blockIdx.x;
+    const long long t0 = chunk * ka.C, t1 = (t0 + ka.C < T) ? t0 + ka.C : T;
+    double* const slab = POST ? ka.rec + (size_t)chunk * (size_t)(ka.C + ka.Wb) * REC : nullptr;
+    bool ok = true, finite = true;
+    double dist_f = 0.0, dist_b = 0.0;
+    LmlAcc acc;
+
+    // ---- forwards, four runs of the same loop.  0: the W steps in front of the chunk from the stationary prior (from the series' prior where they reach
+    // step 0).  1: the chunk (record, log marginal likelihood).  2 (posterior calls): the Wb steps behind the chunk, record only.  3: the last W steps
+    // of the chunk from the stationary prior -- what the NEXT wave starts from -- against run 1's end state.
+    d4 P, Pend;
+    double mC, mend;
+    for (int run = 0; run < 4; ++run) {
+        long long ta, tb;
+        if (run == 0) { ta = t0 - ka.W; tb = t0; }
+        else if (run == 1) { ta = t0; tb = t1; }
+        else if (run == 2) { ta = t1; tb = POST ? ((t1 + ka.Wb < T) ? t1 + ka.Wb : T) : t1; }
+        else { ta = t1 - ka.W; tb = t1 < T ? t1 : ta; }      // (the last chunk hands nothing over)
+        if (run == 0 || run == 3) {
+            const bool head = ta <= 0;      // the run reaches the series' first step: exact
+#pragma unroll
+            for (int r = 0; r < 4; ++r) P[r] = head ? x0P[r] : gP[r];
+            mC = head ? x0mC : gmC;
+            ta = head ? 0 : ta;
+        }
+        double* const rec = (POST && (run == 1 || run == 2)) ? slab : nullptr;
+        Row in, nx;
+        load_row<XS, false>(ka, ta, lane, in);
+        for (long long tr = ta; tr < tb; tr += 64) {
+            load_row<XS, false>(ka, tr + 64, lane, nx);      // in flight while this row computes (behind the last row: clamped, unused)
+            const int n = (int)((tb - tr < 64) ? tb - tr : 64);
+#pragma nounroll
+            for (int k = 0; k < n; ++k) {
+                const double y = rdlane(in.y, k);
+                const double Rt = (XS & 1) ? rdlane(in.R, k) : b.R;
+                const double ht = (XS & 2) ? rdlane(in.hh, k) : b.hh;
+                const bool obs = __builtin_amdgcn_readlane((int)in.mk, k) == 0;
+                fstep(ln, b, P, mC, y, Rt, ht, obs, acc, run == 1, ok, rec != nullptr ? rec + (size_t)(tr + k - t0) * REC : nullptr);
+                if (run == 1 && (k & 7) == 7) acc.flush();
+            }
+            if (run == 1) acc.flush();
+            in = nx;
+        }
+        if (run == 1) {
+            Pend = P;
+            mend = mC;
+        }
+        if (run == 3 && t1 < T) {
+            double worst = (lr < ka.d) ? ::fabs(mend - mC) / (sdC + ::fabs(mend) + ::fabs(mC)) : 0.0, s = ::fabs(mend) + ::fabs(mC);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const double e = ::fabs(Pend[r] - P[r]) * (isdR[r] * isdC);
+                worst = e > worst ? e : worst;
+                s += ::fabs(Pend[r]) + ::fabs(P[r]);
+            }
+            dist_f = wave_max(worst);
+            finite = finite && (cross_sum(row_sum(s)) < 1e300);      // (false for NaN as well)
+        }
+    }
+
+    if (POST) {
+        // ---- backwards, three runs of the same loop.  0: the Wb steps behind the chunk from zero (exact where they reach the series' last step): the
+        // (r, N) behind the chunk's last step.  1: the chunk, mean and variance of every step.  2: the chunk's own first Wb steps from zero -- what the
+        // PREVIOUS wave continues from -- against run 1's result.
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");      // (the record is read back by other lanes)
+        d4 N, Nown;
+        double rC, rown;
+        for (int run = 0; run < 3; ++run) {
+            long long ta, tb;      // the steps tb - 1 .. ta
+            if (run == 0) { ta = t1; tb = (t1 + ka.Wb < T) ? t1 + ka.Wb : T; }
+            else if (run == 1) { ta = t0; tb = t1; }
+            else { ta = t0; tb = t0 > 0 ? ((t0 + ka.Wb < t1) ? t0 + ka.Wb : t1) : t0; }      // (nobody continues from the first chunk)
+            if (run != 1) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) N[r] = 0.0;
+                rC = 0.0;
+            }
+            Row in, nx;
+            load_row<XS, true>(ka, tb - 1, lane, in);
+            for (long long tr = tb - 1; tr >= ta; tr -= 64) {
+                load_row<XS, true>(ka, tr - 64, lane, nx);      // the next row: in flight through this one
+                const int n = (int)((tr - ta + 1 < 64) ? tr - ta + 1 : 64);
+                double om = 0.0, ov = 0.0;
+#pragma nounroll
+                for (int k = 0; k < n; ++k) {
+                    const double ht = (XS & 2) ? rdlane(in.hh, k) : b.hh;
+                    double mu, vr;
+                    bstep(ln, b, N, rC, slab + (size_t)(tr - k - t0) * REC, ht, mu, vr);
+                    om = (lane == k) ? mu : om;
+                    ov = (lane == k) ? vr : ov;
+                }
+                if (run == 1 && lane < n) {
+                    ka.mean[tr - lane] = om;
+                    ka.var[tr - lane] = ov + in.rn;
+                }
+                in = nx;
+            }
+            if (run == 1) {
+                Nown = N;
+                rown = rC;
+            }
+            if (run == 2 && t0 > 0) {
+                double worst = ::fabs(rown - rC) * sdC, s = ::fabs(rown) + ::fabs(rC);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double e = ::fabs(Nown[r] - N[r]) * (sdR[r] * sdC);
+                    worst = e > worst ? e : worst;
+                    s += ::fabs(Nown[r]) + ::fabs(N[r]);
+                }
+                dist_b = wave_max(worst);
+                finite = finite && (cross_sum(row_sum(s)) < 1e300);
+            }
+        }
+    }
+
+    // ---- the wave's share (every lane holds the same sums)
+    const double lml = acc.total();
+    finite = finite && (::fabs(lml) < 1e300);
+    unsigned bits = 0;
+    if (!(dist_f <= mc.tol)) bits |= 1u;
+    if (POST && !(dist_b <= mc.tol_b)) bits |= 2u;
+    if (!ok) bits |= 4u;
+    if (!finite) bits |= 8u;
+    if (lane == 0) {
+        double* p = ka.part + (size_t)chunk * 4;
+        p[0] = lml;
+        p[1] = (double)bits;
+        p[2] = dist_f;
+        p[3] = dist_b;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------ host side
+struct Engine {
+    tgp_sweep::TilePlan p;
+    tgp_sweep::Forced forced;
+    double* part = nullptr;      // pinned: the waves' shares
+    size_t part_cap = 0;
+    void* mc = nullptr;          // device: the plan's TileModelC
+    void* rec = nullptr;         // device: the posterior call's record
+    size_t rec_cap = 0;
+};
+
+Engine* create() { return new Engine(); }
+void destroy(Engine* e) {
+    if (!e) return;
+    if (e->part) (void)tgp_alloc::host_free(e->part);
+    if (e->mc) (void)tgp_alloc::dev_free(e->mc);
+    if (e->rec) (void)tgp_alloc::dev_free(e->rec);
+    delete e;
+}
+void force_geometry(Engine* e, int C, int W, int Wb) {
+    e->forced.C = C;
+    e->forced.W = W;
+    e->forced.Wb = Wb;
+}
+void geometry(const Engine* e, int* C, int* W, int* Wb, int64_t* nwaves) {
+    if (C) *C = e->p.C;
+    if (W) *W = e->p.W;
+    if (Wb) *Wb = e->p.Wb;
+    if (nwaves) *nwaves = e->p.nchunks;
+}
+bool plan(Engine* e, const tgp_sweep::ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why) {
+    return tgp_sweep::plan_tile(&e->p, e->forced, m, T, w_hint, wb_hint, num_cu, post, why);
+}
+const char* kernel_name(bool post) { return post ? "k_sweep_tile<posterior>" : "k_sweep_tile<logpdf>"; }
+
+namespace {
+
+template <int XS> void launch_x(const Engine* e, hipStream_t stream, const TArgs& ka, bool post) {
+    if (post) hipLaunchKernelGGL((k_sweep_tile<XS, true>), dim3((unsigned)e->p.nchunks), dim3(64), 0, stream, ka);
+    else hipLaunchKernelGGL((k_sweep_tile<XS, false>), dim3((unsigned)e->p.nchunks), dim3(64), 0, stream, ka);
+}
+
+}  // namespace
+
+int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char** kname, std::string* err) {
+    auto fail = [&](const char* what, hipError_t rc) {
+        if (err) *err = std::string(what) + ": " + hipGetErrorString(rc);
+        return 1;
+    };
+    const tgp_sweep::TilePlan& p = e->p;
+    const bool post = c.mean != nullptr;
+    if (c.adjoint || c.y_out != nullptr || post != p.post || c.T != p.T || (post && (c.var == nullptr || c.Rnew == nullptr))) {
+        if (err) *err = "k_sweep_tile: the call does not match its plan";
+        return 1;
+    }
+    const size_t need_part = (size_t)p.nchunks * 4 * sizeof(double);
+    if (need_part > e->part_cap) {
+        if (e->part) (void)tgp_alloc::host_free(e->part);
+        e->part = nullptr;
+        e->part_cap = 0;
+        const size_t cap = std::max<size_t>(need_part, 1 << 16);
+        hipError_t rc = tgp_alloc::host_malloc((void**)&e->part, cap, hipHostMallocDefault);
+        if (rc != hipSuccess) return fail("hipHostMalloc", rc);
+        e->part_cap = cap;
+    }
+    if (!e->mc) {
+        hipError_t rc = tgp_alloc::dev_malloc(&e->mc, sizeof(TileModelC));
+        if (rc != hipSuccess) return fail("hipMalloc", rc);
+    }
+    if (post) {
+        const size_t need = (size_t)p.nchunks * (size_t)(p.C + p.Wb) * REC * sizeof(double);
+        if (need > e->rec_cap) {
+            if (e->rec) (void)tgp_alloc::dev_free(e->rec);
+            e->rec = nullptr;
+            e->rec_cap = 0;
+            hipError_t rc = tgp_alloc::dev_malloc(&e->rec, need);
+            if (rc != hipSuccess) return fail("hipMalloc", rc);
+            e->rec_cap = need;
+        }
+    }
+    {      // (the plan's blocks: 9 KB, staged by the runtime before the call returns; the kernel behind it on the same stream reads them)
+        hipError_t rc = hipMemcpyAsync(e->mc, &p.mc, sizeof(TileModelC), hipMemcpyHostToDevice, stream);
+        if (rc != hipSuccess) return fail("hipMemcpyAsync", rc);
+    }
+    TArgs ka;
+    ka.mc = static_cast<const TileModelC*>(e->mc);
+    ka.st.y = c.y;
+    ka.st.mask = c.mask;
+    ka.st.R = c.R;
+    ka.st.hh = c.hh;
+    ka.st.tau = nullptr;
+    ka.st.Rnew = c.Rnew;
+    ka.st.rnew_per_step = c.rnew_per_step;
+    ka.T = p.T;
+    ka.C = p.C;
+    ka.W = p.W;
+    ka.Wb = p.Wb;
+    ka.d = p.d;
+    ka.mean = c.mean;
+    ka.var = c.var;
+    ka.rec = static_cast<double*>(e->rec);
+    ka.part = e->part;
+    if (kname) *kname = kernel_name(post);
+    const int xs = (c.R != nullptr ? 1 : 0) | (c.hh != nullptr ? 2 : 0);
+    switch (xs) {
+        case 0: launch_x<0>(e, stream, ka, post); break;
+        case 1: launch_x<1>(e, stream, ka, post); break;
+        case 2: launch_x<2>(e, stream, ka, post); break;
+        default: launch_x<3>(e, stream, ka, post); break;
+    }
+    hipError_t rc = hipGetLastError();
+    if (rc != hipSuccess) return fail("k_sweep_tile launch", rc);
+    return 0;
+}
+
+double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* dist_b) {
+    double lml = 0.0, df = 0.0, db = 0.0;
+    unsigned bits = 0;
+    for (int64_t i = 0; i < e->p.nchunks; ++i) {      // fixed order: the same sum for the same geometry
+        const double* q = e->part + (size_t)i * 4;
+        lml += q[0];
+        bits |= (unsigned)q[1];
+        df = std::max(df, q[2]);
+        db = std::max(db, q[3]);
+    }
+    if (status) *status = (int)bits;
+    if (w) *w = e->p.W;
+    if (wb) *wb = e->p.Wb;
+    if (dist_f) *dist_f = df;
+    if (dist_b) *dist_b = db;
+    return lml;
+}
+
+}  // namespace tgp_sweep_tile

@@ -1,0 +1,46 @@
+// The tile sweep: the sweep engines' algorithm (tgp_sweep.hpp) for state dimensions 9 .. 16 -- logpdf and posterior marginals of Forward
+// models in LTI form (shared A, a, Q, H; scalar observations) whose gains vary in time: a missing-data mask, a noise variance per step, an emission
+// offset per step.  At these d a covariance is exactly ONE tile of v_mfma_f64_16x16x4_f64: the state is zero-padded to 16, d is a run-time argument and
+// one instantiation set (XS = 0 .. 3, logpdf / posterior) serves every d.
+//
+// One launch, one wave per workgroup, a wave = one chunk of C consecutive steps.  P lives in the MFMA accumulator layout (lane (lr, lq), register r:
+// row lq + 4 r, column lr), and A in registers as the four A-operands A[lr][lq + 4 r]: register r of P IS the B-operand of MFMA r, so A P costs four
+// MFMAs and no data movement; P- = A (A P)' + Q four more, with Q as the accumulator's initial value, behind one transpose of A P through a padded
+// LDS tile.  The scalar update runs in plain fp64 on the accumulator registers: P- H' by DPP sums inside the 16-lane rows and by sums across the four
+// row groups, the rank-one downdate four FMAs per lane; m sits one component per lane.
+//
+// Forwards a wave warms up over the W steps in front of its chunk from the stationary prior, runs its chunk (log s and v^2 / s of its observed steps)
+// and, for the check, repeats the warm-up its neighbour starts from -- the last W steps of its own chunk -- and compares it with its own run's end
+// state (kTol).  Waves never wait for each other.  Posterior calls keep no covariance per step: the forward run leaves a record of 16 + 4 doubles per
+// step (w = P- H', H P- H', H m-, v, s) and the backward run is the Bryson-Frazier recursion on (r, N), N a second accumulator-layout tile:
+// N <- A' N A by the same eight MFMAs and one transpose, the observed step's (I - K H)' N (I - K H) + H' H / s as rank-one corrections;
+// mean_t = H m- + w' r + h_t, var_t = H P- H' - w' N w + Rnew_t.  The (r, N) behind a chunk's last step come from a backward run over the Wb steps
+// behind it from zero, on records the wave filters itself beyond its chunk; the check is the same run over the chunk's own first Wb steps against the
+// chunk's own result (kTolBack).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+
+#include "tgp_sweep.hpp"
+
+namespace tgp_sweep_tile {
+
+struct Engine;
+Engine* create();
+void destroy(Engine* e);
+
+// The geometry for this model and series (tgp_sweep_plan.hpp plan_tile); false: the engine declines (`why` says so).  post: the call asks for the
+// posterior marginals.  w_hint / wb_hint: warm-ups a previous call on the bound model needed (0: estimate).
+bool plan(Engine* e, const tgp_sweep::ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why);
+// c: the lane sweep's call record; y, mask, R, hh, Rnew, mean, var are read (mean == null: logpdf only)
+int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char** kernel_name, std::string* err);
+const char* kernel_name(bool post);
+// After the stream has been synchronised: tgp_sweep::finish's status bits, warm-ups and distances.
+double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* dist_b);
+void geometry(const Engine* e, int* C, int* W, int* Wb, int64_t* nwaves);
+// test hook: force the geometry of the next plan (0: automatic)
+void force_geometry(Engine* e, int C, int W, int Wb);
+
+}  // namespace tgp_sweep_tile
