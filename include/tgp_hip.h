@@ -228,7 +228,7 @@ int tgp_steady_steps(tgp_handle* h, int64_t* mean_only, int64_t* total);
    forward warm-up, backward warm-up (tgp_posterior_rand_missing / _group: the draw's;
    tgp_logpdf_adjoint_missing / _group / _sde: the adjoint's, and dist[1] compares the adjoints of its hand-over), waves, attempts (launches),
    status bits of the last attempt (1 forward / 2 backward or draw warm-up too short, 4 not positive definite, 8 non-finite), state for the bound
-   model (0 untried, 1 serves, -1 declined).  dist [2]: the largest relative distance between a warm-up's end state and the run that reproduces it,
+   model (0 untried, 1 serves, -1 declined; tgp_logpdf_adjoint_group at 9 <= d <= 16 reports the tile sweep's adjoint call in the same slots).  dist [2]: the largest relative distance between a warm-up's end state and the run that reproduces it,
    forwards / backwards (the checks' 1e-12 / 1e-11; tgp_posterior_rand_missing / _group: dist[1] compares the sample states of the draw's hand-over).
    A call the sweep engine was not asked for reports zeros beside the state.  State -1 holds for the bound model, whatever the series of a later
    call, until tgp_model_set or one of the options 14-17.  Either may be NULL. */
@@ -331,7 +331,11 @@ int tgp_logpdf_adjoint_missing(tgp_handle* h, const double* y, const uint8_t* mi
  * Arguments, outputs, TGP_IN_DEVICE / TGP_OUT_DEVICE and tgp_sweep_info exactly as there; TGP_OPT_SWEEP_WARMUP_BACK forces the adjoint's warm-up.  An
  * explicit call: served under TGP_OPT_SWEEP = 1 and 2 alike, whatever the default routing of the engine's other calls; a model without any gap is
  * served too.  Two calls on the same series give the same bits.
- * TGP_EUNSUPPORTED, with no output byte written (host or device): d < 5 (use tgp_logpdf_adjoint_missing), d > 8, SDE-described models, p > 1, Reverse
+ * 9 <= d <= 16: the same entry runs the TILE sweep's adjoint kernel (k_sweep_tile_adjoint<lti>) for what tgp_logpdf runs on the tile sweep --
+ * TGP_OPT_SWEEP = 2, LTI form, Forward, p = 1, T >= 2048, and a mask pointer (an all-false mask serves a gap-free series) or a noise variance per step:
+ * a chunk per wave, a checkpoint (m, P) every 8 steps, the adjoint (l, L) with L a second fp64 MFMA tile, the waves' sums added in wave order by a
+ * second small kernel.  Arguments, outputs, flags, tgp_sweep_info, hand-over check and repair as at 5 <= d <= 8; under TGP_OPT_SWEEP = 1 these d decline.
+ * TGP_EUNSUPPORTED, with no output byte written (host or device): d < 5 (use tgp_logpdf_adjoint_missing), d > 16, SDE-described models, p > 1, Reverse
  * models, T < 2048, TGP_OPT_SWEEP = 0, an explicit request for the general engine (TGP_OPT_CHUNK, ...), an engine declined for the bound model, a
  * forced geometry whose warm-ups are too short, an innovation variance that is not positive, non-finite values.  The library does not fall back: use
  * tgp_logpdf_grad. */

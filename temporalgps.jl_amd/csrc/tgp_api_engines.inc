@@ -301,23 +301,24 @@ const SweepOps kGroupSweep = {
         else tgp_sweep_group::adjoint_blocks(h->sweep_group, o);
     }};
 
-// The tile sweep serves marginals calls only (logpdf, posterior marginals): one backward slot, no draw, no gradient.
+// The tile sweep serves marginals calls (logpdf, posterior marginals) and the adjoint gradient (DESIGN 4.17): one backward slot -- an adjoint runs on the
+// posterior call's geometry with its warm-up Wa in it --, no draw.
 const SweepOps kTileSweep = {
     "sweep tile", "tile sweep",
-    [](const tgp_handle*, SweepKind, bool post) { return tgp_sweep_tile::kernel_name(post); },
+    [](const tgp_handle*, SweepKind kind, bool post) { return kind == SweepKind::adjoint ? tgp_sweep_tile::adjoint_kernel_name() : tgp_sweep_tile::kernel_name(post); },
     [](tgp_handle* h, const tgp_sweep::ModelHost& mh, SweepKind kind, bool post, int W, int Wk, std::string* why) {
-        if (kind != SweepKind::marginals) {
-            if (why) *why = "the tile sweep has no draw and no gradient";
+        if (kind == SweepKind::draw) {
+            if (why) *why = "the tile sweep has no draw";
             return false;
         }
         if (!h->sweep_tile) h->sweep_tile = tgp_sweep_tile::create();
         tgp_sweep_tile::force_geometry(h->sweep_tile, h->sweep_fC, h->sweep_fW, h->sweep_fWb);
-        return tgp_sweep_tile::plan(h->sweep_tile, mh, h->T, W, Wk, h->num_cu, post, why);
+        return tgp_sweep_tile::plan(h->sweep_tile, mh, h->T, W, Wk, h->num_cu, post || kind == SweepKind::adjoint, why);
     },
     [](tgp_handle* h, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep_tile::enqueue(h->sweep_tile, h->stream, c, kname, err); },
     [](tgp_handle* h, SweepKind, int* status, int* w, int* wk, double* df, double* dk) { return tgp_sweep_tile::finish(h->sweep_tile, status, w, wk, df, dk); },
     [](tgp_handle* h, int* C, int64_t* nw) { tgp_sweep_tile::geometry(h->sweep_tile, C, nullptr, nullptr, nw); },
-    [](tgp_handle*, const tgp_sweep::ModelHost&, const tgp_sweep::AdjointOut&, const tgp_sweep::AdjointSdeOut*) {}};
+    [](tgp_handle* h, const tgp_sweep::ModelHost&, const tgp_sweep::AdjointOut& o, const tgp_sweep::AdjointSdeOut*) { tgp_sweep_tile::adjoint_blocks(h->sweep_tile, o); }};
 
 // Runs a call on one of the sweep engines: staging ONCE, up to four attempts with doubled warm-ups, the engine switched off for the bound model where it
 // cannot serve it.  What a kind brings:

@@ -445,14 +445,16 @@ struct SweepEntry {
     const char* instead;         // behind the reason of a decline by the engine: what to take instead
 };
 // guard, null check, eligibility (an explicit call: the default routing of the group sweep's other calls does not filter it)
-static int sweep_entry_checks(tgp_handle* h, const SweepEntry& e, bool null_argument, uint32_t flags) {
+// missing: the call's mask (the tile sweep's predicate reads whether there is one)
+static int sweep_entry_checks(tgp_handle* h, const SweepEntry& e, bool null_argument, uint32_t flags, const uint8_t* missing = nullptr) {
     TRY(check_ready(h, /*general=*/false));
     if (null_argument) return h->fail(TGP_EINVAL, std::string(e.name) + ": null argument");
     const bool form_ok = e.form < 0 || h->sde == (e.form == 1);
     if (!form_ok && e.wrong_form) return h->fail(TGP_EUNSUPPORTED, std::string(e.name) + ": " + e.wrong_form);
-    const bool eligible = &e.eng == &kLaneSweep ? sweep_eligible(h, flags)
-                          : h->sde              ? sweep_group_sde_eligible(h, flags, /*explicit_call=*/true)
-                                                : sweep_group_eligible(h, flags, /*post=*/true, /*explicit_call=*/true);
+    const bool eligible = &e.eng == &kLaneSweep   ? sweep_eligible(h, flags)
+                          : &e.eng == &kTileSweep ? sweep_tile_eligible(h, flags, missing)
+                          : h->sde                ? sweep_group_sde_eligible(h, flags, /*explicit_call=*/true)
+                                                  : sweep_group_eligible(h, flags, /*post=*/true, /*explicit_call=*/true);
     if (!form_ok || !eligible) return h->fail(TGP_EUNSUPPORTED, std::string(e.name) + ": " + e.serves);
     return TGP_OK;
 }
@@ -477,7 +479,7 @@ static int sweep_group_draw_entry(tgp_handle* h, const SweepEntry& e, const doub
 static int sweep_adjoint_entry(tgp_handle* h, const SweepEntry& e, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out,
                                const tgp_sweep::AdjointOut& o, const SdeGrads* g, double* gh_steps, double* gR_steps) {
     StreamGuard stream_guard_(h);
-    TRY(sweep_entry_checks(h, e, !y, flags));
+    TRY(sweep_entry_checks(h, e, !y, flags, missing));
     constexpr int M = tgp_sweep::kGroupMaxD;
     double buf[5 * M * M + 4 * M + 2];      // (AdjointSdeOut's five d x d blocks, four vectors and two sums at d = 8)
     tgp_sweep::AdjointSdeOut so;
@@ -572,16 +574,20 @@ int tgp_logpdf_adjoint_missing(tgp_handle* h, const double* y, const uint8_t* mi
 
 // The same at state dimensions 5 .. 8 by the group sweep's adjoint kernel (k_sweep_group_adjoint, DESIGN 4.11): what sweep_group_eligible accepts, whatever
 // the default routing of the engine's other calls (an explicit call; TGP_OPT_SWEEP >= 1).  tgp_logpdf_adjoint_missing's arguments and outputs.
+// At state dimensions 9 .. 16 the tile sweep's adjoint kernel (k_sweep_tile_adjoint, DESIGN 4.17) serves what sweep_tile_eligible accepts: TGP_OPT_SWEEP = 2
+// and a mask (all-false for a gap-free series) or a noise variance per step.
 int tgp_logpdf_adjoint_group(tgp_handle* h, const double* y, const uint8_t* missing, uint32_t flags, double* lml_out, double* gA, double* ga, double* gQ,
                              double* gH, double* ghh, double* gR, double* gx0m, double* gx0P, double* gh_steps, double* gR_steps) {
-    static const SweepEntry entry = {"tgp_logpdf_adjoint_group", kGroupSweep, 0, nullptr,
-                                     "Forward models with shared A, a, Q, H (not SDE-described), scalar observations, 5 <= d <= 8 "
-                                     "and T >= 2048 on the group sweep (TGP_OPT_SWEEP >= 1, the engine not declined for the bound model); use "
-                                     "tgp_logpdf_adjoint_missing at d <= 4 and tgp_logpdf_grad otherwise",
-                                     " (use tgp_logpdf_grad)"};
+    static const char* const serves =
+        "Forward models with shared A, a, Q, H (not SDE-described), scalar observations and T >= 2048: 5 <= d <= 8 on the group sweep "
+        "(TGP_OPT_SWEEP >= 1), or 9 <= d <= 16 with a missing-data mask or a noise variance per step on the tile sweep (TGP_OPT_SWEEP = 2); the engine "
+        "not declined for the bound model; use tgp_logpdf_adjoint_missing at d <= 4 and tgp_logpdf_grad otherwise";
+    static const SweepEntry group = {"tgp_logpdf_adjoint_group", kGroupSweep, 0, nullptr, serves, " (use tgp_logpdf_grad)"};
+    static const SweepEntry tile = {"tgp_logpdf_adjoint_group", kTileSweep, 0, nullptr, serves, " (use tgp_logpdf_grad)"};
     tgp_sweep::AdjointOut o;
     o.gA = gA; o.ga = ga; o.gQ = gQ; o.gH = gH; o.ghh = ghh; o.gR = gR; o.gx0m = gx0m; o.gx0P = gx0P;
-    return sweep_adjoint_entry(h, entry, y, missing, flags, lml_out, o, nullptr, gh_steps, gR_steps);
+    const bool tile_d = h && h->d >= tgp_sweep::kTileMinD && h->d <= tgp_sweep::kTileMaxD;
+    return sweep_adjoint_entry(h, tile_d ? tile : group, y, missing, flags, lml_out, o, nullptr, gh_steps, gR_steps);
 }
 
 // The same for a model described by its SDE and time stamps (tgp_model_set_sde: irregular spacing) -- what sweep_eligible accepts in SDE form -- by the

@@ -25,6 +25,11 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 
 constexpr int DP = tgp_sweep::kTileDP, REC = tgp_sweep::kTileRec;
 constexpr int kTLD = DP + 1;      // the transpose tile's leading dimension: rows written by 16 consecutive lanes, columns read at stride 17
+// The adjoint call.  kAdjB: steps between two checkpoints = states of a block recomputed into LDS: 8 x 2176 B beside the transpose tile's
+// 2176 B are 19 584 B, within the 20 480 B that keep eight workgroups on a CU (9 states would be 21 760 B).
+constexpr int kAdjB = 8;
+constexpr int kAdjState = DP * DP + DP;                  // a filtering state: P in the accumulator layout [r][lane], then m
+constexpr int kAdjSums = 3 * DP * DP + 3 * DP + 2;      // a wave's record: gA | gQ | gx0P (16 x 16, [i + 16 j]) | ga | gH | gx0m (16) | sum gh_t | sum gR_t
 
 struct TArgs {
     const TileModelC* mc;      // device
@@ -35,6 +40,11 @@ struct TArgs {
     double* var;
     double* rec;       // [chunk][C + Wb][REC]: the forward run's record of the chunk's steps and of the Wb steps behind them (posterior calls)
     double* part;      // [chunk][4]: share of the log marginal likelihood, status bits, forward / backward distance (pinned host memory)
+    // an adjoint call (k_sweep_tile_adjoint; Wb carries the adjoint's warm-up Wa)
+    double* gh;        // [T] or null: d logpdf / d h_t, d logpdf / d R_t of every step
+    double* gR;
+    double* ckpt;      // [chunk][(C + Wa) / kAdjB][kAdjState]: the filtering state in front of every kAdjB-th step of the chunk and of the Wa steps behind it
+    double* sums;      // [chunk][kAdjSums]: the wave's sums of the block gradients
 };
 
 __device__ __forceinline__ void wave_sync() {
@@ -358,6 +368,307 @@ __global__ __launch_bounds__(64) void k_sweep_tile(const TArgs ka) {
     }
 }
 
+// ---- the adjoint of the filter on the tile (the recursion: DESIGN 4.8, tests/_sweep_adjoint.py restated) ------------------------------
+// A filtering state in LDS or in a checkpoint: every lane's four registers of P where it reads them back, m behind them (written by row group 0).
+__device__ __forceinline__ void put_state(double* q, const Lane& ln, const d4& P, double mC) {
+    const int lane = ln.lr + 16 * ln.lq;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) q[64 * r + lane] = P[r];
+    if (ln.lq == 0) q[DP * DP + ln.lr] = mC;
+}
+__device__ __forceinline__ void get_state(const double* q, const Lane& ln, d4& P, double& mC) {
+    const int lane = ln.lr + 16 * ln.lq;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) P[r] = q[64 * r + lane];
+    mC = q[DP * DP + ln.lr];
+}
+
+// a wave's sums over its chunk: gA and gQ in the accumulator layout, ga and gH in column form
+struct AdjSums {
+    d4 gA, gQ;
+    double ga, gH, gh, gR;
+};
+
+// One step of the adjoint, backwards over step t: (lam, Lam) = d logpdf / d (m, P) behind the step on entry, in front of it on return; (m, P): the
+// filtering state in front of the step.  A missing step (iS = 0, v = 0) passes the adjoint through the transition alone and leaves zeros in gh, gR.
+// sum: the step belongs to the wave's chunk (the warm-up walks add nothing).  20 MFMAs with `sum`, 16 without.
+__device__ __forceinline__ void astep(const Lane& ln, const Blocks& b, const d4& P, double mC, double y, double Rt, double ht, bool obs, d4& Lam, double& lamC,
+                                      AdjSums& s, bool sum, double& gh, double& gR) {
+    const int lr = ln.lr, lq = ln.lq;
+    d4 AP = {0.0, 0.0, 0.0, 0.0};      // A P: register r is the B-operand "rows lq + 4 r of A P" of the gA product below
+#pragma unroll
+    for (int r = 0; r < 4; ++r) AP = mfma(b.af[r], P[r], AP);
+    wave_sync();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ln.sT[(lq + 4 * r) * kTLD + lr] = AP[r];
+    wave_sync();
+    d4 Pm = b.Q;                       // P- = A (A P)' + Q
+#pragma unroll
+    for (int r = 0; r < 4; ++r) Pm = mfma(b.af[r], ln.sT[lr * kTLD + lq + 4 * r], Pm);
+    const double mp = ln.matvec(b.af, mC) + b.aC;
+    d4 VR, LVR, lamR, VbR, Pb;
+    double VC, LVC;
+    ln.symvec(Pm, b.HC, b.HR, VR, VC);      // V = P- H'
+    ln.symvec(Lam, VC, VR, LVR, LVC);       // Lam V
+    const double S = obs ? row_sum(b.HC * VC) + Rt : 1.0;
+    const double iS = obs ? fast_rcp(S) : 0.0;
+    const double v = obs ? (y - (row_sum(b.HC * mp) + ht)) : 0.0;
+    const double lV = row_sum(lamC * VC), VLV = row_sum(VC * LVC), viS = v * iS;
+    const double vb = (lV - v) * iS;
+    const double Sb = fma(fma(-lV, v, VLV) * iS, iS, -0.5 * fma(-viS, viS, iS));
+    const double VbC = fma(Sb, b.HC, fma(lamC, viS, -2.0 * iS * LVC));
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        lamR[r] = __shfl(lamC, lq + 4 * r, 64);
+        VbR[r] = fma(Sb, b.HR[r], fma(lamR[r], viS, -2.0 * iS * LVR[r]));
+        Pb[r] = fma(0.5, fma(VbR[r], b.HC, b.HR[r] * VbC), Lam[r]);      // Lam + (Vb H + H' Vb') / 2
+    }
+    gh = -vb;
+    gR = Sb;
+    const double mbC = fma(-vb, b.HC, lamC);      // lam - vb H'
+    if (sum) {
+        double pv = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pv = fma(Pm[r], VbR[r], pv);
+        s.gH += cross_sum(pv) + fma(Sb, VC, -vb * mp);      // P- Vb + Sb V - vb m-
+        s.ga += mbC;
+        s.gh += gh;
+        s.gR += gR;
+        // gA += mb m' + 2 Pb (A P): the symmetric Pb in the accumulator layout is its own A-operand (register r: Pb[lr][lq + 4 r])
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            s.gQ[r] += Pb[r];
+            s.gA[r] = fma(fma(-vb, b.HR[r], lamR[r]), mC, s.gA[r]);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s.gA = mfma(2.0 * Pb[r], AP[r], s.gA);
+    }
+    const d4 zero = {0.0, 0.0, 0.0, 0.0};
+    lamC = ln.matvec(b.atf, mbC);          // A' mb
+    Lam = ln.sandwich(b.atf, Pb, zero);    // A' Pb A
+}
+
+// (two waves per SIMD: the register counts are in profiles/sweep_tile_adjoint_resources.txt)
+template <int XS>
+__global__ __launch_bounds__(64) void k_sweep_tile_adjoint(const TArgs ka) {
+    __shared__ double sT[DP * kTLD];
+    __shared__ double sX[kAdjB * kAdjState];      // the filtering states in front of a block's steps
+    const int lane = threadIdx.x;
+    Lane ln;
+    ln.lr = lane & 15;
+    ln.lq = lane >> 4;
+    ln.sT = sT;
+    const int lr = ln.lr, lq = ln.lq;
+    const TileModelC& mc = *ka.mc;
+    Blocks b;
+    d4 gP, x0P, sdR, isdR;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int i = lq + 4 * r;
+        b.af[r] = mc.A[DP * lr + i];
+        b.atf[r] = mc.A[DP * i + lr];
+        b.Q[r] = mc.Q[i + DP * lr];
+        b.HR[r] = mc.H[i];
+        gP[r] = mc.gP[i + DP * lr];
+        x0P[r] = mc.x0P[i + DP * lr];
+        sdR[r] = mc.sd[i];
+        isdR[r] = mc.isd[i];
+    }
+    b.HC = mc.H[lr];
+    b.aC = mc.a[lr];
+    b.hh = mc.hh;
+    b.R = mc.R;
+    const double gmC = mc.gm[lr], x0mC = mc.x0m[lr], sdC = mc.sd[lr], isdC = mc.isd[lr];
+
+    const long long T = ka.T, chunk = blockIdx.x;
+    const int Wa = ka.Wb;
+    const long long t0 = chunk * ka.C, t1 = (t0 + ka.C < T) ? t0 + ka.C : T;
+    const long long te = (t1 + Wa < T) ? t1 + Wa : T;      // the filter runs Wa steps beyond the chunk: the states of the adjoint's warm-up
+    double* const slab = ka.ckpt + (size_t)chunk * (size_t)((ka.C + Wa) / kAdjB) * kAdjState;
+    bool ok = true, finite = true;
+    double dist_f = 0.0, dist_b = 0.0;
+    LmlAcc acc;
+
+    // ---- forwards: k_sweep_tile's four runs; runs 1 and 2 leave a checkpoint in front of every kAdjB-th step in place of the record
+    d4 P, Pend;
+    double mC, mend;
+    for (int run = 0; run < 4; ++run) {
+        long long ta, tb;
+        if (run == 0) { ta = t0 - ka.W; tb = t0; }
+        else if (run == 1) { ta = t0; tb = t1; }
+        else if (run == 2) { ta = t1; tb = te; }
+        else { ta = t1 - ka.W; tb = t1 < T ? t1 : ta; }
+        if (run == 0 || run == 3) {
+            const bool head = ta <= 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) P[r] = head ? x0P[r] : gP[r];
+            mC = head ? x0mC : gmC;
+            ta = head ? 0 : ta;
+        }
+        const bool keep = run == 1 || run == 2;
+        Row in, nx;
+        load_row<XS, false>(ka, ta, lane, in);
+        for (long long tr = ta; tr < tb; tr += 64) {
+            load_row<XS, false>(ka, tr + 64, lane, nx);
+            const int n = (int)((tb - tr < 64) ? tb - tr : 64);
+#pragma nounroll
+            for (int k = 0; k < n; ++k) {
+                const double y = rdlane(in.y, k);
+                const double Rt = (XS & 1) ? rdlane(in.R, k) : b.R;
+                const double ht = (XS & 2) ? rdlane(in.hh, k) : b.hh;
+                const bool obs = __builtin_amdgcn_readlane((int)in.mk, k) == 0;
+                const long long s = tr + k - t0;
+                if (keep && (s & (kAdjB - 1)) == 0) put_state(slab + (size_t)(s / kAdjB) * kAdjState, ln, P, mC);
+                fstep(ln, b, P, mC, y, Rt, ht, obs, acc, run == 1, ok, nullptr);
+                if (run == 1 && (k & 7) == 7) acc.flush();
+            }
+            if (run == 1) acc.flush();
+            in = nx;
+        }
+        if (run == 1) {
+            Pend = P;
+            mend = mC;
+        }
+        if (run == 3 && t1 < T) {
+            double worst = (lr < ka.d) ? ::fabs(mend - mC) / (sdC + ::fabs(mend) + ::fabs(mC)) : 0.0, s = ::fabs(mend) + ::fabs(mC);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const double e = ::fabs(Pend[r] - P[r]) * (isdR[r] * isdC);
+                worst = e > worst ? e : worst;
+                s += ::fabs(Pend[r]) + ::fabs(P[r]);
+            }
+            dist_f = wave_max(worst);
+            finite = finite && (cross_sum(row_sum(s)) < 1e300);
+        }
+    }
+
+    // ---- backwards, three walks of the same loop.  0: the Wa steps behind the chunk from a zero adjoint (exact where they reach the series' last step).
+    // 1: the chunk, summing.  2: the chunk's own first Wa steps from zero -- what the PREVIOUS wave continues from -- against walk 1's result.
+    // A walk goes over rows of 64 steps (the streams, one step per lane) and in a row over blocks of kAdjB steps: the block's states forwards from its
+    // checkpoint into LDS, then the adjoint backwards over them.
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");      // (a checkpoint's m is read back by other lanes)
+    AdjSums sm;
+    d4 Lam, Lown;
+    double lamC = 0.0, lown = 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) sm.gA[r] = sm.gQ[r] = Lam[r] = Lown[r] = 0.0;
+    sm.ga = sm.gH = sm.gh = sm.gR = 0.0;
+    for (int run = 0; run < 3; ++run) {
+        long long ta, tb;      // the steps tb - 1 .. ta
+        if (run == 0) { ta = t1; tb = te; }
+        else if (run == 1) { ta = t0; tb = t1; }
+        else { ta = t0; tb = t0 > 0 ? ((t0 + Wa < t1) ? t0 + Wa : t1) : t0; }      // (nobody continues from the first chunk)
+        if (run != 1) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Lam[r] = 0.0;
+            lamC = 0.0;
+        }
+        const long long nrow = (tb - ta + 63) / 64;
+        Row in, nx;
+        load_row<XS, false>(ka, ta + (nrow - 1) * 64, lane, in);
+        for (long long j = nrow - 1; j >= 0; --j) {
+            const long long tr = ta + j * 64;
+            load_row<XS, false>(ka, tr - 64, lane, nx);      // the row walked next: in flight through this one (in front of the first: clamped, unused)
+            const int n = (int)((tb - tr < 64) ? tb - tr : 64);
+            double oh = 0.0, oR = 0.0;
+            for (int k0 = ((n - 1) / kAdjB) * kAdjB; k0 >= 0; k0 -= kAdjB) {
+                const int nb = (n - k0 < kAdjB) ? n - k0 : kAdjB;
+                get_state(slab + (size_t)((tr + k0 - t0) / kAdjB) * kAdjState, ln, P, mC);
+                bool okr = true;
+#pragma nounroll
+                for (int k = 0; k < nb; ++k) {
+                    put_state(sX + k * kAdjState, ln, P, mC);
+                    if (k + 1 < nb) {
+                        const int kk = k0 + k;
+                        fstep(ln, b, P, mC, rdlane(in.y, kk), (XS & 1) ? rdlane(in.R, kk) : b.R, (XS & 2) ? rdlane(in.hh, kk) : b.hh,
+                              __builtin_amdgcn_readlane((int)in.mk, kk) == 0, acc, false, okr, nullptr);
+                    }
+                }
+                wave_sync();
+#pragma nounroll
+                for (int k = nb - 1; k >= 0; --k) {
+                    const int kk = k0 + k;
+                    get_state(sX + k * kAdjState, ln, P, mC);
+                    double gh, gR;
+                    astep(ln, b, P, mC, rdlane(in.y, kk), (XS & 1) ? rdlane(in.R, kk) : b.R, (XS & 2) ? rdlane(in.hh, kk) : b.hh,
+                          __builtin_amdgcn_readlane((int)in.mk, kk) == 0, Lam, lamC, sm, run == 1, gh, gR);
+                    oh = (lane == kk) ? gh : oh;
+                    oR = (lane == kk) ? gR : oR;
+                }
+                wave_sync();      // (the next block overwrites the slots)
+            }
+            if (run == 1 && lane < n) {
+                if (ka.gh != nullptr) ka.gh[tr + lane] = oh;
+                if (ka.gR != nullptr) ka.gR[tr + lane] = oR;
+            }
+            in = nx;
+        }
+        if (run == 1) {
+            Lown = Lam;
+            lown = lamC;
+        }
+        if (run == 2 && t0 > 0) {
+            double worst = ::fabs(lown - lamC) * sdC, s = ::fabs(lown) + ::fabs(lamC);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const double e = ::fabs(Lown[r] - Lam[r]) * (sdR[r] * sdC);
+                worst = e > worst ? e : worst;
+                s += ::fabs(Lown[r]) + ::fabs(Lam[r]);
+            }
+            dist_b = wave_max(worst);
+            finite = finite && (cross_sum(row_sum(s)) < 1e300);
+        }
+    }
+
+    // ---- the wave's record (device memory: k_sweep_tile_adjoint_sum adds the waves) and its share (pinned, every lane holds the same values)
+    {
+        double* q = ka.sums + (size_t)chunk * kAdjSums;
+        const bool first = chunk == 0;      // the adjoint in front of step 0 is the gradient with respect to the prior
+        double s = ::fabs(sm.ga) + ::fabs(sm.gH) + ::fabs(lown);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int at = (lq + 4 * r) + DP * lr;
+            q[at] = sm.gA[r];
+            q[DP * DP + at] = sm.gQ[r];
+            q[2 * DP * DP + at] = first ? Lown[r] : 0.0;
+            s += ::fabs(sm.gA[r]) + ::fabs(sm.gQ[r]) + ::fabs(Lown[r]);
+        }
+        if (lq == 0) {
+            q[3 * DP * DP + lr] = sm.ga;
+            q[3 * DP * DP + DP + lr] = sm.gH;
+            q[3 * DP * DP + 2 * DP + lr] = first ? lown : 0.0;
+        }
+        if (lane == 0) {
+            q[3 * DP * DP + 3 * DP] = sm.gh;
+            q[3 * DP * DP + 3 * DP + 1] = sm.gR;
+        }
+        finite = finite && (cross_sum(row_sum(s)) < 1e300);
+    }
+    const double lml = acc.total();
+    finite = finite && (::fabs(lml) < 1e300);
+    unsigned bits = 0;
+    if (!(dist_f <= mc.tol)) bits |= 1u;
+    if (!(dist_b <= mc.tol_b)) bits |= 2u;
+    if (!ok) bits |= 4u;
+    if (!finite) bits |= 8u;
+    if (lane == 0) {
+        double* p = ka.part + (size_t)chunk * 4;
+        p[0] = lml;
+        p[1] = (double)bits;
+        p[2] = dist_f;
+        p[3] = dist_b;
+    }
+}
+
+// The waves' records added in index order, one entry per thread, into pinned host memory: no atomics, the same bits for the same geometry.
+__global__ __launch_bounds__(64) void k_sweep_tile_adjoint_sum(const double* __restrict__ sums, long long nwaves, double* __restrict__ out) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= kAdjSums) return;
+    double a = 0.0;
+    for (long long w = 0; w < nwaves; ++w) a += sums[(size_t)w * kAdjSums + i];
+    out[i] = a;
+}
+
 // ------------------------------------------------------------------------------------------------------------------------ host side
 struct Engine {
     tgp_sweep::TilePlan p;
@@ -367,6 +678,10 @@ struct Engine {
     void* mc = nullptr;          // device: the plan's TileModelC
     void* rec = nullptr;         // device: the posterior call's record
     size_t rec_cap = 0;
+    void* ckpt = nullptr;        // device: the adjoint call's checkpoints
+    size_t ckpt_cap = 0;
+    void* sums = nullptr;        // device: the adjoint call's records, one per wave
+    size_t sums_cap = 0;
 };
 
 Engine* create() { return new Engine(); }
@@ -375,6 +690,8 @@ void destroy(Engine* e) {
     if (e->part) (void)tgp_alloc::host_free(e->part);
     if (e->mc) (void)tgp_alloc::dev_free(e->mc);
     if (e->rec) (void)tgp_alloc::dev_free(e->rec);
+    if (e->ckpt) (void)tgp_alloc::dev_free(e->ckpt);
+    if (e->sums) (void)tgp_alloc::dev_free(e->sums);
     delete e;
 }
 void force_geometry(Engine* e, int C, int W, int Wb) {
@@ -392,8 +709,16 @@ bool plan(Engine* e, const tgp_sweep::ModelHost& m, int64_t T, int w_hint, int w
     return tgp_sweep::plan_tile(&e->p, e->forced, m, T, w_hint, wb_hint, num_cu, post, why);
 }
 const char* kernel_name(bool post) { return post ? "k_sweep_tile<posterior>" : "k_sweep_tile<logpdf>"; }
+const char* adjoint_kernel_name() { return "k_sweep_tile_adjoint<lti>"; }
 
 namespace {
+
+// (the walk and, behind it on the stream, the sum of its records into the pinned block behind the waves' shares)
+template <int XS> void launch_adjoint(const Engine* e, hipStream_t stream, const TArgs& ka) {
+    hipLaunchKernelGGL((k_sweep_tile_adjoint<XS>), dim3((unsigned)e->p.nchunks), dim3(64), 0, stream, ka);
+    hipLaunchKernelGGL(k_sweep_tile_adjoint_sum, dim3((kAdjSums + 63) / 64), dim3(64), 0, stream, ka.sums, (long long)e->p.nchunks,
+                       e->part + (size_t)e->p.nchunks * 4);
+}
 
 template <int XS> void launch_x(const Engine* e, hipStream_t stream, const TArgs& ka, bool post) {
     if (post) hipLaunchKernelGGL((k_sweep_tile<XS, true>), dim3((unsigned)e->p.nchunks), dim3(64), 0, stream, ka);
@@ -409,11 +734,21 @@ int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char*
     };
     const tgp_sweep::TilePlan& p = e->p;
     const bool post = c.mean != nullptr;
-    if (c.adjoint || c.y_out != nullptr || post != p.post || c.T != p.T || (post && (c.var == nullptr || c.Rnew == nullptr))) {
+    if (c.y_out != nullptr || (post || c.adjoint) != p.post || (post && c.adjoint) || c.T != p.T || (post && (c.var == nullptr || c.Rnew == nullptr))) {
         if (err) *err = "k_sweep_tile: the call does not match its plan";
         return 1;
     }
-    const size_t need_part = (size_t)p.nchunks * 4 * sizeof(double);
+    auto grow = [&](void** buf, size_t* cap, size_t need) {      // a device buffer of the engine's, at least `need` bytes
+        if (need <= *cap) return hipSuccess;
+        if (*buf) (void)tgp_alloc::dev_free(*buf);
+        *buf = nullptr;
+        *cap = 0;
+        const hipError_t rc = tgp_alloc::dev_malloc(buf, need);
+        if (rc == hipSuccess) *cap = need;
+        return rc;
+    };
+    // (an adjoint call: the summed record sits behind the waves' shares in the same pinned block)
+    const size_t need_part = ((size_t)p.nchunks * 4 + (c.adjoint ? kAdjSums : 0)) * sizeof(double);
     if (need_part > e->part_cap) {
         if (e->part) (void)tgp_alloc::host_free(e->part);
         e->part = nullptr;
@@ -428,15 +763,13 @@ int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char*
         if (rc != hipSuccess) return fail("hipMalloc", rc);
     }
     if (post) {
-        const size_t need = (size_t)p.nchunks * (size_t)(p.C + p.Wb) * REC * sizeof(double);
-        if (need > e->rec_cap) {
-            if (e->rec) (void)tgp_alloc::dev_free(e->rec);
-            e->rec = nullptr;
-            e->rec_cap = 0;
-            hipError_t rc = tgp_alloc::dev_malloc(&e->rec, need);
-            if (rc != hipSuccess) return fail("hipMalloc", rc);
-            e->rec_cap = need;
-        }
+        hipError_t rc = grow(&e->rec, &e->rec_cap, (size_t)p.nchunks * (size_t)(p.C + p.Wb) * REC * sizeof(double));
+        if (rc != hipSuccess) return fail("hipMalloc", rc);
+    }
+    if (c.adjoint) {      // (C and Wa are multiples of 8 = kAdjB: plan_tile)
+        hipError_t rc = grow(&e->ckpt, &e->ckpt_cap, (size_t)p.nchunks * (size_t)((p.C + p.Wb) / kAdjB) * kAdjState * sizeof(double));
+        if (rc == hipSuccess) rc = grow(&e->sums, &e->sums_cap, (size_t)p.nchunks * kAdjSums * sizeof(double));
+        if (rc != hipSuccess) return fail("hipMalloc", rc);
     }
     {      // (the plan's blocks: 9 KB, staged by the runtime before the call returns; the kernel behind it on the same stream reads them)
         hipError_t rc = hipMemcpyAsync(e->mc, &p.mc, sizeof(TileModelC), hipMemcpyHostToDevice, stream);
@@ -460,17 +793,48 @@ int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char*
     ka.var = c.var;
     ka.rec = static_cast<double*>(e->rec);
     ka.part = e->part;
-    if (kname) *kname = kernel_name(post);
+    ka.gh = c.gh_steps;
+    ka.gR = c.gR_steps;
+    ka.ckpt = static_cast<double*>(e->ckpt);
+    ka.sums = static_cast<double*>(e->sums);
+    if (kname) *kname = c.adjoint ? adjoint_kernel_name() : kernel_name(post);
     const int xs = (c.R != nullptr ? 1 : 0) | (c.hh != nullptr ? 2 : 0);
-    switch (xs) {
-        case 0: launch_x<0>(e, stream, ka, post); break;
-        case 1: launch_x<1>(e, stream, ka, post); break;
-        case 2: launch_x<2>(e, stream, ka, post); break;
-        default: launch_x<3>(e, stream, ka, post); break;
+    if (c.adjoint) {
+        switch (xs) {
+            case 0: launch_adjoint<0>(e, stream, ka); break;
+            case 1: launch_adjoint<1>(e, stream, ka); break;
+            case 2: launch_adjoint<2>(e, stream, ka); break;
+            default: launch_adjoint<3>(e, stream, ka); break;
+        }
+    } else {
+        switch (xs) {
+            case 0: launch_x<0>(e, stream, ka, post); break;
+            case 1: launch_x<1>(e, stream, ka, post); break;
+            case 2: launch_x<2>(e, stream, ka, post); break;
+            default: launch_x<3>(e, stream, ka, post); break;
+        }
     }
     hipError_t rc = hipGetLastError();
     if (rc != hipSuccess) return fail("k_sweep_tile launch", rc);
     return 0;
+}
+
+void adjoint_blocks(const Engine* e, const tgp_sweep::AdjointOut& o) {
+    const int d = e->p.d;
+    const double *g = e->part + (size_t)e->p.nchunks * 4, *gv = g + 3 * DP * DP;
+    auto block = [d](const double* tile, double* out, bool sym) {      // the d x d corner of a 16 x 16 tile, column-major
+        if (!out) return;
+        for (int j = 0; j < d; ++j)
+            for (int i = 0; i < d; ++i) out[i + j * d] = sym ? 0.5 * (tile[i + DP * j] + tile[j + DP * i]) : tile[i + DP * j];
+    };
+    block(g, o.gA, false);
+    block(g + DP * DP, o.gQ, true);
+    block(g + 2 * DP * DP, o.gx0P, true);
+    if (o.ga) std::memcpy(o.ga, gv, sizeof(double) * d);
+    if (o.gH) std::memcpy(o.gH, gv + DP, sizeof(double) * d);
+    if (o.gx0m) std::memcpy(o.gx0m, gv + 2 * DP, sizeof(double) * d);
+    if (o.ghh) *o.ghh = gv[3 * DP];
+    if (o.gR) *o.gR = gv[3 * DP + 1];
 }
 
 double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* dist_b) {

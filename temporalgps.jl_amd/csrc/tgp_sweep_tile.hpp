@@ -17,6 +17,13 @@
 // mean_t = H m- + w' r + h_t, var_t = H P- H' - w' N w + Rnew_t.  The (r, N) behind a chunk's last step come from a backward run over the Wb steps
 // behind it from zero, on records the wave filters itself beyond its chunk; the check is the same run over the chunk's own first Wb steps against the
 // chunk's own result (kTolBack).
+//
+// The gradient of the log marginal likelihood (k_sweep_tile_adjoint) is the same forward half with a checkpoint (m, P) every 8 steps in place
+// of the record and, backwards, the adjoint of the recursion: (l, L) = d logpdf / d (m, P), L a second accumulator-layout tile.  A block's
+// states are recomputed from its checkpoint into LDS; a step rebuilds A P and P- (eight MFMAs), takes its scalars from DPP sums, adds
+// gA += mb m' + 2 Pb (A P) by four MFMAs whose operands are the registers Pb and A P already sit in, and hands back L <- A' Pb A by the backward
+// sandwich.  The adjoint behind a chunk comes from a walk over the Wa steps behind it from zero; the check is the same walk over the chunk's own first Wa
+// steps against the chunk's own result (kTolBack).  Every wave leaves one record of its sums; k_sweep_tile_adjoint_sum adds them in wave order.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,11 +39,15 @@ Engine* create();
 void destroy(Engine* e);
 
 // The geometry for this model and series (tgp_sweep_plan.hpp plan_tile); false: the engine declines (`why` says so).  post: the call asks for the
-// posterior marginals.  w_hint / wb_hint: warm-ups a previous call on the bound model needed (0: estimate).
+// posterior marginals.  w_hint / wb_hint: warm-ups a previous call on the bound model needed (0: estimate).  An adjoint call plans with post = true and
+// its warm-up Wa in the backward slot (0: the backward warm-up's estimate).
 bool plan(Engine* e, const tgp_sweep::ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why);
-// c: the lane sweep's call record; y, mask, R, hh, Rnew, mean, var are read (mean == null: logpdf only)
+// c: the lane sweep's call record; y, mask, R, hh, Rnew, mean, var are read (mean == null: logpdf only); c.adjoint: gh_steps, gR_steps instead of mean, var
 int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char** kernel_name, std::string* err);
 const char* kernel_name(bool post);
+const char* adjoint_kernel_name();
+// Behind finish of an adjoint call whose status is clean: the gradient with respect to the shared blocks (Q and x0P symmetrised).
+void adjoint_blocks(const Engine* e, const tgp_sweep::AdjointOut& out);
 // After the stream has been synchronised: tgp_sweep::finish's status bits, warm-ups and distances.
 double finish(Engine* e, int* status, int* w, int* wb, double* dist_f, double* dist_b);
 void geometry(const Engine* e, int* C, int* W, int* Wb, int64_t* nwaves);

@@ -640,7 +640,9 @@ def logpdf_adjoint_missing(model, y, per_step=False):
 def logpdf_adjoint_group(model, y, per_step=False):
     """logpdf_adjoint_missing at state dimensions 5 <= d <= 8: ONE adjoint pass on the group sweep (tgp_logpdf_adjoint_group, k_sweep_group_adjoint,
     DESIGN 4.11) -- Forward models with shared A, a, Q, H, scalar observations, T >= 2048; NaNs in y (or a (y, mask) tuple), a noise variance or an emission
-    offset per step.  Arguments and the returned (lml, g) as logpdf_adjoint_missing's.  Raises Unsupported where the engine declines (use logpdf_and_grad)."""
+    offset per step.  At 9 <= d <= 16 the same entry runs the tile sweep's adjoint kernel (k_sweep_tile_adjoint) where TGP_OPT_SWEEP = 2 is set
+    on the model and the call has a mask (NaNs in y, or a (y, mask) tuple: an all-false mask serves a gap-free series) or a noise variance per step.
+    Arguments and the returned (lml, g) as logpdf_adjoint_missing's.  Raises Unsupported where the engine declines (use logpdf_and_grad)."""
     return _logpdf_adjoint_sweep("tgp_logpdf_adjoint_group", model, y, per_step)
 
 
