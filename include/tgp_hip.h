@@ -167,7 +167,9 @@ typedef struct tgp_handle tgp_handle;
                            tgp_logpdf / tgp_[logpdf_and_]posterior_marginals run on the TILE sweep (tgp_sweep_tile.hip): a chunk per
                            wave, the covariance one fp64 MFMA tile, the backward pass a Bryson-Frazier recursion on a record of 20 doubles per
                            step; kernels k_sweep_tile<logpdf> / k_sweep_tile<posterior>; fully observed models with one noise variance stay on
-                           the wide engine, and under 1 all of these stay where they were (profiles/sweep_tile_time.txt).  All step aside
+                           the wide engine, and under 1 all of these stay where they were (profiles/sweep_tile_time.txt).  The same models
+                           under 2 have tgp_logpdf_adjoint_group served by k_sweep_tile_adjoint<lti> and tgp_posterior_rand_group by
+                           k_sweep_tile_draw<lti>, given a mask pointer or a noise variance per step.  All step aside
                            on an explicit request for the general engine (TGP_REUSE_REDUCE, TGP_OPT_CHUNK, TGP_OPT_VARIANT, TGP_OPT_STEADY 0 / 1,
                            TGP_OPT_GRAPH).  0: the general chunked-scan engine as before; tgp_posterior_rand_missing, tgp_posterior_rand_group,
                            tgp_logpdf_adjoint_missing and tgp_logpdf_adjoint_group answer TGP_EUNSUPPORTED for these models. */
@@ -527,7 +529,7 @@ int tgp_posterior_rand(tgp_handle* h, const double* y, const double* Rnew, const
  *      eps_e / y_out [T][p]; Rnew [p] with TGP_SHARED_R, else [T][p]; eps_0 [d] host; the others where TGP_IN_DEVICE /
  *      TGP_OUT_DEVICE say.  Draws are used as tgp_rand on the evaluated posterior uses them; emissions of p > 1 (or
  *      TGP_SMALL_OUTPUT) models add the reference's 1e-9 to Rnew.  TGP_EUNSUPPORTED (nothing written to y_out): another engine's
- *      handle, a Reverse model, TGP_OPT_SWEEP = 0 (d <= 4), 5 <= d <= 16 (5 .. 8: tgp_posterior_rand_group), a sweep-engine draw whose Cholesky pivots are not positive, whose values
+ *      handle, a Reverse model, TGP_OPT_SWEEP = 0 (d <= 4), 5 <= d <= 16 (tgp_posterior_rand_group: the group sweep at 5 .. 8, the tile sweep at 9 .. 16 under TGP_OPT_SWEEP = 2), a sweep-engine draw whose Cholesky pivots are not positive, whose values
  *      are not finite or whose forced warm-ups are too short, TGP_OPT_DENSE_CHUNKED = 0 or TGP_OPT_DENSE_FUSED = 0, or stores that do
  *      not fit -- take tgp_posterior_rand (LTI, d <= 16) or tgp_posterior + tgp_rand. */
 int tgp_posterior_rand_missing(tgp_handle* h, const double* y, const uint8_t* missing, const double* Rnew, const double* eps_t,
@@ -539,7 +541,12 @@ int tgp_posterior_rand_missing(tgp_handle* h, const double* y, const uint8_t* mi
  * draw's warm-up.  An explicit call: served under TGP_OPT_SWEEP = 1 and 2 alike, whatever the default routing of the engine's other calls; a model without
  * any gap is served too.  Never the reverse-time model (T (2 d^2 + d) doubles): T doubles of device scratch beside the checkpoints.  Two calls on the
  * same series and draws give the same bits.
- * TGP_EUNSUPPORTED, with nothing written to y_out (host or device): d < 5 (use tgp_posterior_rand_missing), d > 8, SDE-described models, p > 1, Reverse
+ * 9 <= d <= 16: the same entry runs the TILE sweep's draw kernel (k_sweep_tile_draw<lti>) for what tgp_logpdf runs on the tile sweep --
+ * TGP_OPT_SWEEP = 2, LTI form, Forward, p = 1, T >= 2048, and a mask pointer (an all-false mask serves a gap-free series) or a noise variance per step:
+ * a chunk per wave, a checkpoint (m, P) every 8 steps, the step's two Cholesky factorisations on the fp64 MFMA tile's registers with G (x - m-) and L
+ * from one forward substitution (no back-substitution, no G).  Arguments, flags, the use of the draws, tgp_sweep_info, hand-over check and repair as at
+ * 5 <= d <= 8; under TGP_OPT_SWEEP = 1 these d decline.  Device scratch: the checkpoints, (T + chunks * Wd) * 34 doubles.
+ * TGP_EUNSUPPORTED, with nothing written to y_out (host or device): d < 5 (use tgp_posterior_rand_missing), d > 16, SDE-described models, p > 1, Reverse
  * models, T < 2048, TGP_OPT_SWEEP = 0, an explicit request for the general engine (TGP_OPT_CHUNK, ...), an engine declined for the bound model, a forced
  * geometry whose warm-ups are too short, a Cholesky pivot that is not positive, non-finite values.  The library does not fall back: take tgp_posterior +
  * tgp_rand. */

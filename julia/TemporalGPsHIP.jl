@@ -344,7 +344,8 @@ end
 
 """`rand` of `replace_observation_noise_cov(posterior(model, y), Σs_new)` on supplied draws without evaluating the posterior
 (tgp_posterior_rand_missing: scalar observations, d <= 4, T >= 2048 on the sweep engine's draw kernel; 16 < d <= 64, p <= 16 on the dense engine;
-tgp_posterior_rand_group / tgp_posterior_rand_group_sde on the group sweep at 5 <= d <= 8, scalar observations, T >= 2048).
+tgp_posterior_rand_group / tgp_posterior_rand_group_sde on the group sweep at 5 <= d <= 8, scalar observations, T >= 2048; tgp_posterior_rand_group on
+the tile sweep at 9 <= d <= 16 in LTI form under TGP_OPT_SWEEP = 2, with missing steps or a noise variance per step).
 `nothing`: TGP_EUNSUPPORTED, take the evaluated route."""
 function posterior_rand_missing(m::DeviceLGSSM{Forward}, y::AbstractVector, Σs_new::AbstractVector, eps_t, eps_e, eps_0)
     yv, mp, mask = _split_missing(y)
@@ -356,7 +357,7 @@ function posterior_rand_missing(m::DeviceLGSSM{Forward}, y::AbstractVector, Σs_
         ccall((:tgp_posterior_rand_group_sde, libtgp), Cint,
             (Ptr{Cvoid}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, UInt32, Ptr{Float64}),
             m.h.ptr, yv, mp, R, eps_t, eps_e, eps_0, shared ? SHARED_R : UInt32(0), out)
-    elseif 5 <= m.d <= 8 && m.p == 1
+    elseif 5 <= m.d <= 16 && m.p == 1      # (the tile sweep behind the entry from d = 9, DESIGN 4.18, under TGP_OPT_SWEEP = 2: this range has not been run)
         ccall((:tgp_posterior_rand_group, libtgp), Cint,
             (Ptr{Cvoid}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, UInt32, Ptr{Float64}),
             m.h.ptr, yv, mp, R, eps_t, eps_e, eps_0, shared ? SHARED_R : UInt32(0), out)

@@ -302,21 +302,23 @@ const SweepOps kGroupSweep = {
     }};
 
 // The tile sweep serves marginals calls (logpdf, posterior marginals) and the adjoint gradient (DESIGN 4.17): one backward slot -- an adjoint runs on the
-// posterior call's geometry with its warm-up Wa in it --, no draw.
+// posterior call's geometry with its warm-up Wa in it -- and the draw (DESIGN 4.18) the same way with its warm-up Wd.
 const SweepOps kTileSweep = {
     "sweep tile", "tile sweep",
-    [](const tgp_handle*, SweepKind kind, bool post) { return kind == SweepKind::adjoint ? tgp_sweep_tile::adjoint_kernel_name() : tgp_sweep_tile::kernel_name(post); },
+    [](const tgp_handle*, SweepKind kind, bool post) {
+        if (kind == SweepKind::draw) return tgp_sweep_tile::draw_kernel_name();
+        return kind == SweepKind::adjoint ? tgp_sweep_tile::adjoint_kernel_name() : tgp_sweep_tile::kernel_name(post);
+    },
     [](tgp_handle* h, const tgp_sweep::ModelHost& mh, SweepKind kind, bool post, int W, int Wk, std::string* why) {
-        if (kind == SweepKind::draw) {
-            if (why) *why = "the tile sweep has no draw";
-            return false;
-        }
         if (!h->sweep_tile) h->sweep_tile = tgp_sweep_tile::create();
         tgp_sweep_tile::force_geometry(h->sweep_tile, h->sweep_fC, h->sweep_fW, h->sweep_fWb);
-        return tgp_sweep_tile::plan(h->sweep_tile, mh, h->T, W, Wk, h->num_cu, post || kind == SweepKind::adjoint, why);
+        return tgp_sweep_tile::plan(h->sweep_tile, mh, h->T, W, Wk, h->num_cu, post || kind != SweepKind::marginals, why);
     },
     [](tgp_handle* h, const tgp_sweep::Call& c, const char** kname, std::string* err) { return tgp_sweep_tile::enqueue(h->sweep_tile, h->stream, c, kname, err); },
-    [](tgp_handle* h, SweepKind, int* status, int* w, int* wk, double* df, double* dk) { return tgp_sweep_tile::finish(h->sweep_tile, status, w, wk, df, dk); },
+    [](tgp_handle* h, SweepKind kind, int* status, int* w, int* wk, double* df, double* dk) {
+        const double lml = tgp_sweep_tile::finish(h->sweep_tile, status, w, wk, df, dk);
+        return kind == SweepKind::draw ? 0.0 : lml;
+    },
     [](tgp_handle* h, int* C, int64_t* nw) { tgp_sweep_tile::geometry(h->sweep_tile, C, nullptr, nullptr, nw); },
     [](tgp_handle* h, const tgp_sweep::ModelHost&, const tgp_sweep::AdjointOut& o, const tgp_sweep::AdjointSdeOut*) { tgp_sweep_tile::adjoint_blocks(h->sweep_tile, o); }};
 
@@ -444,7 +446,7 @@ int sweep_group_call(tgp_handle* h, const double* y, const uint8_t* missing, uin
 }
 
 // rand of the posterior on the lane sweep (k_sweep_draw, DESIGN 4.7; LTI and SDE form) or on the group sweep (k_sweep_group_draw, DESIGN 4.12;
-// k_sweep_group_draw_sde, 4.15).  The draw goes to the handle's own buffer and reaches y_out behind the checks: a declined call (*served = false, *why
+// k_sweep_group_draw_sde, 4.15) or on the tile sweep (k_sweep_tile_draw, DESIGN 4.18).  The draw goes to the handle's own buffer and reaches y_out behind the checks: a declined call (*served = false, *why
 // set) leaves a device y_out untouched as well.  The lane sweep's draw plans an SDE-described model from the bound x0P, the group sweep's from the
 // record's Pinf, so that a prior replaced by tgp_model_set_x0 is served (as the adjoint calls').
 int sweep_draw_call(tgp_handle* h, const SweepOps& eng, const double* y, const uint8_t* missing, uint32_t flags, const double* Rnew, const double* eps_t,

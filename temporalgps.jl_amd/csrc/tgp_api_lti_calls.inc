@@ -467,11 +467,11 @@ static int sweep_draw_entry(tgp_handle* h, const SweepEntry& e, const double* y,
     if (served) return TGP_OK;
     return h->fail(TGP_EUNSUPPORTED, std::string(e.name) + ": the " + e.eng.name + " declines the draw: " + why + e.instead);
 }
-// The group sweep's draw entries whole
+// The group sweep's draw entries whole (and the tile sweep's behind tgp_posterior_rand_group)
 static int sweep_group_draw_entry(tgp_handle* h, const SweepEntry& e, const double* y, const uint8_t* missing, const double* Rnew, const double* eps_t,
                                   const double* eps_e, const double* eps_0, uint32_t flags, double* y_out) {
     StreamGuard stream_guard_(h);
-    TRY(sweep_entry_checks(h, e, !y || !Rnew || !eps_t || !eps_e || !eps_0 || !y_out, flags));
+    TRY(sweep_entry_checks(h, e, !y || !Rnew || !eps_t || !eps_e || !eps_0 || !y_out, flags, missing));
     return sweep_draw_entry(h, e, y, missing, Rnew, eps_t, eps_e, eps_0, flags, y_out);
 }
 // The adjoint entries whole.  g (null: a model in LTI form, the block gradients go to o): an SDE-described model -- the engine's sums over the closed
@@ -533,14 +533,18 @@ int tgp_posterior_rand_missing(tgp_handle* h, const double* y, const uint8_t* mi
 
 // The same draw at state dimensions 5 .. 8 by the group sweep's draw kernel (k_sweep_group_draw, DESIGN 4.12): what sweep_group_eligible accepts, whatever
 // the default routing of the engine's other calls (an explicit call; TGP_OPT_SWEEP >= 1).  tgp_posterior_rand_missing's arguments and flags.
+// At state dimensions 9 .. 16 the tile sweep's draw kernel (k_sweep_tile_draw, DESIGN 4.18) serves what sweep_tile_eligible accepts: TGP_OPT_SWEEP = 2
+// and a mask (all-false for a gap-free series) or a noise variance per step.
 int tgp_posterior_rand_group(tgp_handle* h, const double* y, const uint8_t* missing, const double* Rnew, const double* eps_t, const double* eps_e,
                              const double* eps_0, uint32_t flags, double* y_out) {
-    static const SweepEntry entry = {"tgp_posterior_rand_group", kGroupSweep, 0, nullptr,
-                                     "Forward models with shared A, a, Q, H (not SDE-described), scalar observations, 5 <= d <= 8 "
-                                     "and T >= 2048 on the group sweep (TGP_OPT_SWEEP >= 1, the engine not declined for the bound model); use "
-                                     "tgp_posterior_rand_missing at d <= 4 and tgp_posterior + tgp_rand otherwise",
-                                     " (take tgp_posterior + tgp_rand)"};
-    return sweep_group_draw_entry(h, entry, y, missing, Rnew, eps_t, eps_e, eps_0, flags, y_out);
+    static const char* const serves =
+        "Forward models with shared A, a, Q, H (not SDE-described), scalar observations and T >= 2048: 5 <= d <= 8 on the group sweep "
+        "(TGP_OPT_SWEEP >= 1), or 9 <= d <= 16 with a missing-data mask or a noise variance per step on the tile sweep (TGP_OPT_SWEEP = 2); the engine "
+        "not declined for the bound model; use tgp_posterior_rand_missing at d <= 4 and tgp_posterior + tgp_rand otherwise";
+    static const SweepEntry group = {"tgp_posterior_rand_group", kGroupSweep, 0, nullptr, serves, " (take tgp_posterior + tgp_rand)"};
+    static const SweepEntry tile = {"tgp_posterior_rand_group", kTileSweep, 0, nullptr, serves, " (take tgp_posterior + tgp_rand)"};
+    const bool tile_d = h && h->d >= tgp_sweep::kTileMinD && h->d <= tgp_sweep::kTileMaxD;
+    return sweep_group_draw_entry(h, tile_d ? tile : group, y, missing, Rnew, eps_t, eps_e, eps_0, flags, y_out);
 }
 
 // The same for a model described by its SDE and time stamps (tgp_model_set_sde: irregular spacing) -- what rand(rng, posterior(fx, y)(x_new)) merges into

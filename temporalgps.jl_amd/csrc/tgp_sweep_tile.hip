@@ -1,5 +1,6 @@
 // The tile sweep: see tgp_sweep_tile.hpp (what and why) and DESIGN 4.16 (geometry, operand layouts, LDS and register budget, the record).  gfx950 only.
-// One wave per workgroup; a wave's LDS: one padded 16 x 17 tile (2176 B), the transpose of A P (forwards) and of A' N (backwards).
+// One wave per workgroup; a wave's LDS: one padded 16 x 17 tile (2176 B), the transpose of A P (forwards) and of A' N (backwards); the adjoint and the
+// draw keep the eight filtering states of a block beside it.
 //
 // Layouts of v_mfma_f64_16x16x4_f64 as tgp_dense_fused.hpp uses them, lane = (lr = lane % 16, lq = lane / 16):
 //   A-operand (16 x 4):  lane holds X[lr][lq]         B-operand (4 x 16):  lane holds Y[lq][lr]
@@ -669,6 +670,270 @@ __global__ __launch_bounds__(64) void k_sweep_tile_adjoint_sum(const double* __r
     out[i] = a;
 }
 
+// ---- a draw from the posterior on the tile (the walk: tests/_sweepdraw.py draw_restated) ----------------------------------------------
+// The draw's arguments beside TArgs (Wb carries the draw's warm-up Wd; ckpt: a chunk's checkpoints and, in the last slot, the state its filter ends on).
+struct DArgs {
+    TArgs t;
+    const double* eps_t;      // [T][d]
+    const double* eps_e;      // [T]
+    double* y_out;            // [T]
+    double eps_0[DP];         // the start, zero in the padding
+};
+
+// Right-looking Cholesky M + jit I_d + I_pad = U' U on an accumulator-layout tile, a pivot at a time (k is a compile-time index: row k sits in register
+// k / 4 of row group k % 4).  Row k of U goes to every row group by two shuffles; the multipliers U[k][lq + 4 r] of a lane's own rows are that row in
+// row form; rows above the pivot see zeros and stay.  U is never stored: what needs it is summed while its rows pass.
+//   RHS:  the augmented right-hand side [B | c] (B a tile, c in column form) is forward-substituted in the same sweep: B <- Z = U^-T B in place,
+//         q = U^-T c a scalar per pivot, g += Z' q.
+//   else: nz += U' e for e in column form.
+// The padding (k >= d) is the identity and meets zeros in B, c and e: skipped.  A pivot that is not positive clears ok.
+template <bool RHS>
+__device__ __forceinline__ void factor(const Lane& ln, int d, d4& M, double jit, d4& B, double& cC, double& gC, double eC, double& nzC, bool& ok) {
+    const int lr = ln.lr, lq = ln.lq;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) M[r] += (lq + 4 * r == lr) ? (lr < d ? jit : 1.0) : 0.0;
+#pragma unroll
+    for (int k = 0; k < DP; ++k) {
+        const int kr = k >> 2, kq = k & 3;
+        if (k < tgp_sweep::kTileMinD || k < d) {
+            const double piv = rdlane(M[kr], k + 16 * kq);
+            ok = ok && (piv > 0.0);
+            const double is = 1.0 / ::sqrt(piv);
+            double u = __shfl(M[kr], lr + 16 * kq, 64) * is;      // U[k][lr]
+            u = lr < k ? 0.0 : u;
+            double z = 0.0;
+            if (RHS) {
+                z = __shfl(B[kr], lr + 16 * kq, 64) * is;         // Z[k][lr]
+                const double q = rdlane(cC, k) * is;
+                cC = fma(-u, q, cC);
+                gC = fma(z, q, gC);
+            } else {
+                nzC = fma(u, rdlane(eC, k), nzC);
+            }
+            if (k + 1 < DP) {
+#pragma unroll
+                for (int r = kr; r < 4; ++r) {
+                    const double mu = __shfl(u, lq + 4 * r, 64);  // U[k][lq + 4 r]: zero in the rows above the pivot
+                    M[r] = fma(-mu, u, M[r]);
+                    if (RHS) B[r] = fma(-mu, z, B[r]);
+                }
+            }
+            if (RHS) B[kr] = (lq == kq) ? z : B[kr];
+        }
+    }
+}
+
+// One step of the walk, backwards over step t: x = x_t on entry, x_(t-1) on return; (m, P): the filtering state in front of step t, e = eps_t[t] in
+// column form.  With Z = U^-T (A P) and q = U^-T (x - m-), U'U = P- + 1e-10 I:  G (x - m-) = Z' q and L = P - Z' Z -- no back-substitution, no G.
+// 12 MFMAs: A P, P- = A (A P)' + Q, and L = P - sum_r Z[r]' Z[r] on the registers Z sits in (register r is rows 4 r .. 4 r + 3 of Z: A- and B-operand at once).
+__device__ __forceinline__ void dstep(const Lane& ln, const Blocks& b, int d, const d4& P, double mC, double eC, double& xC, bool& ok) {
+    const int lr = ln.lr, lq = ln.lq;
+    d4 Z = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) Z = mfma(b.af[r], P[r], Z);      // A P
+    wave_sync();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ln.sT[(lq + 4 * r) * kTLD + lr] = Z[r];
+    wave_sync();
+    d4 M = b.Q;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) M = mfma(b.af[r], ln.sT[lr * kTLD + lq + 4 * r], M);
+    double cC = xC - (ln.matvec(b.af, mC) + b.aC), gC = 0.0, nzC = 0.0;
+    factor<true>(ln, d, M, 1e-10, Z, cC, gC, 0.0, nzC, ok);
+    d4 L = P;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) L = mfma(-Z[r], Z[r], L);
+    factor<false>(ln, d, L, 1e-9, Z, cC, gC, eC, nzC, ok);      // (Z, c, g: not touched without a right-hand side)
+    xC = mC + gC + nzC;
+}
+
+template <int XS>
+__global__ __launch_bounds__(64) void k_sweep_tile_draw(const DArgs da) {
+    __shared__ double sT[DP * kTLD];
+    __shared__ double sX[kAdjB * kAdjState];      // the filtering states in front of a block's steps
+    const TArgs& ka = da.t;
+    const int lane = threadIdx.x;
+    Lane ln;
+    ln.lr = lane & 15;
+    ln.lq = lane >> 4;
+    ln.sT = sT;
+    const int lr = ln.lr, lq = ln.lq, d = ka.d;
+    const TileModelC& mc = *ka.mc;
+    Blocks b;
+    d4 gP, x0P, isdR;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int i = lq + 4 * r;
+        b.af[r] = mc.A[DP * lr + i];
+        b.atf[r] = 0.0;      // (the walk has no backward sandwich)
+        b.Q[r] = mc.Q[i + DP * lr];
+        b.HR[r] = mc.H[i];
+        gP[r] = mc.gP[i + DP * lr];
+        x0P[r] = mc.x0P[i + DP * lr];
+        isdR[r] = mc.isd[i];
+    }
+    b.HC = mc.H[lr];
+    b.aC = mc.a[lr];
+    b.hh = mc.hh;
+    b.R = mc.R;
+    const double gmC = mc.gm[lr], x0mC = mc.x0m[lr], sdC = mc.sd[lr], isdC = mc.isd[lr];
+
+    const long long T = ka.T, chunk = blockIdx.x;
+    const int Wd = ka.Wb, nslots = (ka.C + Wd) / kAdjB;
+    const long long t0 = chunk * ka.C, t1 = (t0 + ka.C < T) ? t0 + ka.C : T;
+    const long long te = (t1 + Wd < T) ? t1 + Wd : T;      // the filter runs Wd steps beyond the chunk: the states of the walk's warm-up
+    double* const slab = ka.ckpt + (size_t)chunk * (size_t)(nslots + 1) * kAdjState;
+    bool ok = true, finite = true;
+    double dist_f = 0.0, dist_b = 0.0;
+    LmlAcc acc;
+
+    // ---- forwards: k_sweep_tile_adjoint's four runs (the loop is repeated here: sharing it would move the existing kernels' code); the state behind
+    // step te - 1 goes to the slab's last slot
+    d4 P, Pend;
+    double mC, mend;
+    for (int run = 0; run < 4; ++run) {
+        long long ta, tb;
+        if (run == 0) { ta = t0 - ka.W; tb = t0; }
+        else if (run == 1) { ta = t0; tb = t1; }
+        else if (run == 2) { ta = t1; tb = te; }
+        else { ta = t1 - ka.W; tb = t1 < T ? t1 : ta; }
+        if (run == 0 || run == 3) {
+            const bool head = ta <= 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) P[r] = head ? x0P[r] : gP[r];
+            mC = head ? x0mC : gmC;
+            ta = head ? 0 : ta;
+        }
+        const bool keep = run == 1 || run == 2;
+        Row in, nx;
+        load_row<XS, false>(ka, ta, lane, in);
+        for (long long tr = ta; tr < tb; tr += 64) {
+            load_row<XS, false>(ka, tr + 64, lane, nx);
+            const int n = (int)((tb - tr < 64) ? tb - tr : 64);
+#pragma nounroll
+            for (int k = 0; k < n; ++k) {
+                const double y = rdlane(in.y, k);
+                const double Rt = (XS & 1) ? rdlane(in.R, k) : b.R;
+                const double ht = (XS & 2) ? rdlane(in.hh, k) : b.hh;
+                const bool obs = __builtin_amdgcn_readlane((int)in.mk, k) == 0;
+                const long long s = tr + k - t0;
+                if (keep && (s & (kAdjB - 1)) == 0) put_state(slab + (size_t)(s / kAdjB) * kAdjState, ln, P, mC);
+                fstep(ln, b, P, mC, y, Rt, ht, obs, acc, false, ok, nullptr);
+            }
+            in = nx;
+        }
+        if (run == 1) {
+            Pend = P;
+            mend = mC;
+        }
+        if (run == 2) put_state(slab + (size_t)nslots * kAdjState, ln, P, mC);
+        if (run == 3 && t1 < T) {
+            double worst = (lr < d) ? ::fabs(mend - mC) / (sdC + ::fabs(mend) + ::fabs(mC)) : 0.0, s = ::fabs(mend) + ::fabs(mC);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const double e = ::fabs(Pend[r] - P[r]) * (isdR[r] * isdC);
+                worst = e > worst ? e : worst;
+                s += ::fabs(Pend[r]) + ::fabs(P[r]);
+            }
+            dist_f = wave_max(worst);
+            finite = finite && (cross_sum(row_sum(s)) < 1e300);
+        }
+    }
+
+    // ---- backwards, three walks of the same loop.  0: the Wd steps behind the chunk, from x = m_f behind them (from the true x_(T-1) where they reach the
+    // series' end), on the real draws: the x behind the chunk's last step.  1: the chunk, y* of every step.  2: the chunk's own first Wd steps from
+    // x = m_f -- what the PREVIOUS wave continues from -- against walk 1's x in front of the chunk.  A walk goes over rows of 64 steps and in a row over
+    // blocks of kAdjB steps, as the adjoint's: the block's states forwards from its checkpoint into LDS, then the walk backwards over them.
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");      // (a checkpoint's m is read back by other lanes)
+    double xC = 0.0, xown = 0.0, ysum = 0.0;
+    for (int run = 0; run < 3; ++run) {
+        long long ta, tb;      // the steps tb - 1 .. ta
+        if (run == 0) { ta = t1; tb = te; }
+        else if (run == 1) { ta = t0; tb = t1; }
+        else { ta = t0; tb = t0 > 0 ? ((t0 + Wd < t1) ? t0 + Wd : t1) : t0; }      // (nobody continues from the first chunk)
+        if (run == 2 && t0 == 0) break;
+        if (run != 1) {      // the walk's start: the state behind step tb - 1
+            get_state(slab + (size_t)(tb == te ? nslots : (tb - t0) / kAdjB) * kAdjState, ln, P, mC);
+            xC = mC;
+            if (tb == T) {      // x_(T-1) = m_f + chol(P_f + 1e-12 I).U' eps_0
+                double c0 = 0.0, g0 = 0.0, nz = 0.0;
+                d4 none = {0.0, 0.0, 0.0, 0.0};
+                factor<false>(ln, d, P, 1e-12, none, c0, g0, da.eps_0[lr], nz, ok);
+                xC = mC + nz;
+            }
+        }
+        // eps_t[t] in column form, loaded a step ahead of its use
+        auto load_e = [&](long long t) { return lr < d ? da.eps_t[(size_t)tgp_sweep::clamp_t(t, T) * d + lr] : 0.0; };
+        double eC = load_e(tb - 1);
+        const long long nrow = (tb - ta + 63) / 64;
+        Row in, nx;
+        load_row<XS, false>(ka, ta + (nrow - 1) * 64, lane, in);
+        for (long long j = nrow - 1; j >= 0; --j) {
+            const long long tr = ta + j * 64;
+            load_row<XS, false>(ka, tr - 64, lane, nx);      // the row walked next: in flight through this one (in front of the first: clamped, unused)
+            const int n = (int)((tb - tr < 64) ? tb - tr : 64);
+            const long long tl = tgp_sweep::clamp_t(tr + lane, T);      // the lane's own step of the row: what rides with the output
+            const double ee = da.eps_e[tl], rn = ka.st.Rnew[ka.st.rnew_per_step ? tl : 0];
+            double oy = 0.0;
+            for (int k0 = ((n - 1) / kAdjB) * kAdjB; k0 >= 0; k0 -= kAdjB) {
+                const int nb = (n - k0 < kAdjB) ? n - k0 : kAdjB;
+                get_state(slab + (size_t)((tr + k0 - t0) / kAdjB) * kAdjState, ln, P, mC);
+                bool okr = true;
+#pragma nounroll
+                for (int k = 0; k < nb; ++k) {
+                    put_state(sX + k * kAdjState, ln, P, mC);
+                    if (k + 1 < nb) {
+                        const int kk = k0 + k;
+                        fstep(ln, b, P, mC, rdlane(in.y, kk), (XS & 1) ? rdlane(in.R, kk) : b.R, (XS & 2) ? rdlane(in.hh, kk) : b.hh,
+                              __builtin_amdgcn_readlane((int)in.mk, kk) == 0, acc, false, okr, nullptr);
+                    }
+                }
+                wave_sync();
+#pragma nounroll
+                for (int k = nb - 1; k >= 0; --k) {
+                    const int kk = k0 + k;
+                    const long long t = tr + kk;
+                    const double hx = row_sum(b.HC * xC) + ((XS & 2) ? rdlane(in.hh, kk) : b.hh);      // H x_t + h_t
+                    oy = (lane == kk) ? hx : oy;
+                    const double en = load_e(t - 1);      // the next step's draws: in flight through this step
+                    if (t > 0) {
+                        get_state(sX + k * kAdjState, ln, P, mC);
+                        dstep(ln, b, d, P, mC, eC, xC, ok);
+                    }
+                    eC = en;
+                }
+                wave_sync();      // (the next block overwrites the slots)
+            }
+            if (run == 1 && lane < n) {
+                const double yo = fma(::sqrt(rn), ee, oy);
+                da.y_out[tr + lane] = yo;
+                ysum += ::fabs(yo);
+            }
+            in = nx;
+        }
+        if (run == 1) xown = xC;
+        if (run == 2) {
+            const double worst = (lr < d) ? ::fabs(xown - xC) / (sdC + ::fabs(xown) + ::fabs(xC)) : 0.0;
+            dist_b = wave_max(worst);
+        }
+        finite = finite && (cross_sum(row_sum(::fabs(xC))) < 1e300);      // (false for NaN as well)
+    }
+    finite = finite && (cross_sum(row_sum(ysum)) < 1e300);
+
+    unsigned bits = 0;
+    if (!(dist_f <= mc.tol)) bits |= 1u;
+    if (!(dist_b <= mc.tol_b)) bits |= 2u;
+    if (!ok) bits |= 4u;
+    if (!finite) bits |= 8u;
+    if (lane == 0) {
+        double* p = ka.part + (size_t)chunk * 4;
+        p[0] = 0.0;
+        p[1] = (double)bits;
+        p[2] = dist_f;
+        p[3] = dist_b;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------------ host side
 struct Engine {
     tgp_sweep::TilePlan p;
@@ -678,7 +943,7 @@ struct Engine {
     void* mc = nullptr;          // device: the plan's TileModelC
     void* rec = nullptr;         // device: the posterior call's record
     size_t rec_cap = 0;
-    void* ckpt = nullptr;        // device: the adjoint call's checkpoints
+    void* ckpt = nullptr;        // device: the adjoint call's and the draw's checkpoints
     size_t ckpt_cap = 0;
     void* sums = nullptr;        // device: the adjoint call's records, one per wave
     size_t sums_cap = 0;
@@ -710,6 +975,7 @@ bool plan(Engine* e, const tgp_sweep::ModelHost& m, int64_t T, int w_hint, int w
 }
 const char* kernel_name(bool post) { return post ? "k_sweep_tile<posterior>" : "k_sweep_tile<logpdf>"; }
 const char* adjoint_kernel_name() { return "k_sweep_tile_adjoint<lti>"; }
+const char* draw_kernel_name() { return "k_sweep_tile_draw<lti>"; }
 
 namespace {
 
@@ -718,6 +984,10 @@ template <int XS> void launch_adjoint(const Engine* e, hipStream_t stream, const
     hipLaunchKernelGGL((k_sweep_tile_adjoint<XS>), dim3((unsigned)e->p.nchunks), dim3(64), 0, stream, ka);
     hipLaunchKernelGGL(k_sweep_tile_adjoint_sum, dim3((kAdjSums + 63) / 64), dim3(64), 0, stream, ka.sums, (long long)e->p.nchunks,
                        e->part + (size_t)e->p.nchunks * 4);
+}
+
+template <int XS> void launch_draw(const Engine* e, hipStream_t stream, const DArgs& da) {
+    hipLaunchKernelGGL((k_sweep_tile_draw<XS>), dim3((unsigned)e->p.nchunks), dim3(64), 0, stream, da);
 }
 
 template <int XS> void launch_x(const Engine* e, hipStream_t stream, const TArgs& ka, bool post) {
@@ -733,8 +1003,9 @@ int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char*
         return 1;
     };
     const tgp_sweep::TilePlan& p = e->p;
-    const bool post = c.mean != nullptr;
-    if (c.y_out != nullptr || (post || c.adjoint) != p.post || (post && c.adjoint) || c.T != p.T || (post && (c.var == nullptr || c.Rnew == nullptr))) {
+    const bool post = c.mean != nullptr, draw = c.y_out != nullptr;
+    if ((post || c.adjoint || draw) != p.post || (int)post + (int)c.adjoint + (int)draw > 1 || c.T != p.T || (post && (c.var == nullptr || c.Rnew == nullptr)) ||
+        (draw && (c.Rnew == nullptr || c.eps_t == nullptr || c.eps_e == nullptr))) {
         if (err) *err = "k_sweep_tile: the call does not match its plan";
         return 1;
     }
@@ -771,6 +1042,10 @@ int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char*
         if (rc == hipSuccess) rc = grow(&e->sums, &e->sums_cap, (size_t)p.nchunks * kAdjSums * sizeof(double));
         if (rc != hipSuccess) return fail("hipMalloc", rc);
     }
+    if (draw) {           // (a slot more per chunk: the state the chunk's filter ends on)
+        hipError_t rc = grow(&e->ckpt, &e->ckpt_cap, (size_t)p.nchunks * (size_t)((p.C + p.Wb) / kAdjB + 1) * kAdjState * sizeof(double));
+        if (rc != hipSuccess) return fail("hipMalloc", rc);
+    }
     {      // (the plan's blocks: 9 KB, staged by the runtime before the call returns; the kernel behind it on the same stream reads them)
         hipError_t rc = hipMemcpyAsync(e->mc, &p.mc, sizeof(TileModelC), hipMemcpyHostToDevice, stream);
         if (rc != hipSuccess) return fail("hipMemcpyAsync", rc);
@@ -797,9 +1072,22 @@ int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char*
     ka.gR = c.gR_steps;
     ka.ckpt = static_cast<double*>(e->ckpt);
     ka.sums = static_cast<double*>(e->sums);
-    if (kname) *kname = c.adjoint ? adjoint_kernel_name() : kernel_name(post);
+    if (kname) *kname = draw ? draw_kernel_name() : c.adjoint ? adjoint_kernel_name() : kernel_name(post);
     const int xs = (c.R != nullptr ? 1 : 0) | (c.hh != nullptr ? 2 : 0);
-    if (c.adjoint) {
+    if (draw) {
+        DArgs da;
+        da.t = ka;
+        da.eps_t = c.eps_t;
+        da.eps_e = c.eps_e;
+        da.y_out = c.y_out;
+        for (int k = 0; k < DP; ++k) da.eps_0[k] = k < p.d ? c.eps_0[k] : 0.0;
+        switch (xs) {
+            case 0: launch_draw<0>(e, stream, da); break;
+            case 1: launch_draw<1>(e, stream, da); break;
+            case 2: launch_draw<2>(e, stream, da); break;
+            default: launch_draw<3>(e, stream, da); break;
+        }
+    } else if (c.adjoint) {
         switch (xs) {
             case 0: launch_adjoint<0>(e, stream, ka); break;
             case 1: launch_adjoint<1>(e, stream, ka); break;

@@ -24,6 +24,13 @@
 // gA += mb m' + 2 Pb (A P) by four MFMAs whose operands are the registers Pb and A P already sit in, and hands back L <- A' Pb A by the backward
 // sandwich.  The adjoint behind a chunk comes from a walk over the Wa steps behind it from zero; the check is the same walk over the chunk's own first Wa
 // steps against the chunk's own result (kTolBack).  Every wave leaves one record of its sums; k_sweep_tile_adjoint_sum adds them in wave order.
+//
+// A draw from the posterior (k_sweep_tile_draw) is the same forward half with the same checkpoints and, backwards, the reverse-time model's
+// sample path on supplied draws: x_(t-1) = m_f + G (x_t - m-) + chol(L + 1e-9 I).U' eps_t.  A step rebuilds A P and P- (eight MFMAs), factorises
+// P- + 1e-10 I on the accumulator registers a pivot at a time and forward-substitutes [A P | x_t - m-] into [Z | q] in the same sweep, so that
+// G (x_t - m-) = Z' q and L = P - Z' Z (four MFMAs on the registers Z sits in) need no back-substitution and no G; a second factorisation gives the noise.
+// The x behind a chunk comes from a walk over the Wd steps behind it from x = m_f on the real draws; the check is the same walk over the chunk's own
+// first Wd steps against the chunk's own x (kTolBack).  Nothing of size T x d^2 but the checkpoints.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,12 +47,14 @@ void destroy(Engine* e);
 
 // The geometry for this model and series (tgp_sweep_plan.hpp plan_tile); false: the engine declines (`why` says so).  post: the call asks for the
 // posterior marginals.  w_hint / wb_hint: warm-ups a previous call on the bound model needed (0: estimate).  An adjoint call plans with post = true and
-// its warm-up Wa in the backward slot (0: the backward warm-up's estimate).
+// its warm-up Wa in the backward slot (0: the backward warm-up's estimate); a draw the same with its warm-up Wd.
 bool plan(Engine* e, const tgp_sweep::ModelHost& m, int64_t T, int w_hint, int wb_hint, int num_cu, bool post, std::string* why);
-// c: the lane sweep's call record; y, mask, R, hh, Rnew, mean, var are read (mean == null: logpdf only); c.adjoint: gh_steps, gR_steps instead of mean, var
+// c: the lane sweep's call record; y, mask, R, hh, Rnew, mean, var are read (mean == null: logpdf only); c.adjoint: gh_steps, gR_steps instead of mean, var;
+// c.y_out set: a draw instead (Rnew, eps_t, eps_e, eps_0)
 int enqueue(Engine* e, hipStream_t stream, const tgp_sweep::Call& c, const char** kernel_name, std::string* err);
 const char* kernel_name(bool post);
 const char* adjoint_kernel_name();
+const char* draw_kernel_name();
 // Behind finish of an adjoint call whose status is clean: the gradient with respect to the shared blocks (Q and x0P symmetrised).
 void adjoint_blocks(const Engine* e, const tgp_sweep::AdjointOut& out);
 // After the stream has been synchronised: tgp_sweep::finish's status bits, warm-ups and distances.

@@ -1099,7 +1099,9 @@ def _posterior_rand_sweep(post, eps_t, eps_e, eps_0):
 def posterior_rand_group(post, eps_t, eps_e, eps_0):
     """rand of a posterior that has not been evaluated (posterior(model, y), optionally with its observation noise replaced) at state dimensions
     5 <= d <= 8: ONE kernel of the group sweep (tgp_posterior_rand_group, k_sweep_group_draw) -- Forward models with shared A, a, Q, H, scalar
-    observations, T >= 2048; NaNs in y, a noise variance or an emission offset per step.  eps_t (T, d), eps_e (T,), eps_0 (d,) are used as rand on the
+    observations, T >= 2048; NaNs in y, a noise variance or an emission offset per step.  At 9 <= d <= 16 the same entry runs ONE kernel of the tile sweep
+    (k_sweep_tile_draw) where the bound model has TGP_OPT_SWEEP = 2 set and the series has NaNs or a noise variance per step; a fully observed
+    host series with one noise variance is declined there (no mask is passed).  eps_t (T, d), eps_e (T,), eps_0 (d,) are used as rand on the
     evaluated posterior uses them; host arrays, or torch tensors on the model's device together with y.  Raises Unsupported where the engine declines
     (use rand)."""
     out = None if not isinstance(post, PosteriorLGSSM) else _posterior_rand_sweep_entry("tgp_posterior_rand_group", post, eps_t, eps_e, eps_0)
@@ -1183,8 +1185,9 @@ def _posterior_rand_dense(post, eps_t, eps_e, eps_0):
 
 def rand(rng_or_eps, model, method=None):
     """lgssm.jl:65-69. `rng_or_eps` is a numpy Generator, or the explicit (eps_t (T,d), eps_e (T,), eps_0 (d,)).
-    method: None (default policy) or "sweep" -- a lazy posterior on the sweep engines' draw kernels alone: posterior_rand_group at 5 <= d <= 8
-    (k_sweep_group_draw; posterior_rand_group_sde where the prior's transitions are SDETransitions), the lane sweep's k_sweep_draw at d <= 4; raises Unsupported where neither serves."""
+    method: None (default policy) or "sweep" -- a lazy posterior on the sweep engines' draw kernels alone: posterior_rand_group at 5 <= d <= 16
+    (k_sweep_group_draw at d <= 8, posterior_rand_group_sde there where the prior's transitions are SDETransitions; k_sweep_tile_draw at 9 <= d <= 16, LTI
+    form under TGP_OPT_SWEEP = 2), the lane sweep's k_sweep_draw at d <= 4; raises Unsupported where none serves."""
     if method not in (None, "sweep"):
         raise ValueError(f"rand: unknown method {method!r}")
     if method == "sweep" and not (isinstance(model, PosteriorLGSSM) and model._model is None):
@@ -1196,13 +1199,15 @@ def rand(rng_or_eps, model, method=None):
             et, ee = rng_or_eps.standard_normal((model.T, model.dim)), rng_or_eps.standard_normal((model.T,) if model.p == 1 else (model.T, model.p))
             eps = (et, ee, rng_or_eps.standard_normal(model.dim))
         if method == "sweep":
-            if 5 <= model.dim <= 8:
-                if isinstance(getattr(model._prior, "transitions", None), SDETransitions):
-                    return posterior_rand_group_sde(model, *eps)
+            sde = isinstance(getattr(model._prior, "transitions", None), SDETransitions)
+            if 5 <= model.dim <= 8 and sde:
+                return posterior_rand_group_sde(model, *eps)
+            if 5 <= model.dim <= 16 and not sde:
                 return posterior_rand_group(model, *eps)
             y1 = _posterior_rand_sweep(model, *eps)
             if y1 is None:
-                raise _lib.Unsupported(_lib.EUNSUPPORTED, "rand(method='sweep'): the sweep engine does not serve this posterior (d <= 8, T >= 2048)")
+                raise _lib.Unsupported(_lib.EUNSUPPORTED, "rand(method='sweep'): the sweep engines do not serve this posterior (d <= 16 in LTI form, d <= 8 "
+                                                           "SDE-described; T >= 2048)")
             return y1
         y1 = _posterior_rand_one_launch(model, *eps)
         if y1 is None:

@@ -476,7 +476,8 @@ def logpdf(fx, y):
 def rand(rng, fx, N=None, method=None):
     """lti_sde.jl:48-58 / posterior_lti_sde.jl:48-58.
     method: None (default policy) or "sweep" -- ONE kernel of the sweep engines over the T training steps (L.rand(..., method="sweep"): the group sweep's
-    draw kernel at 5 <= d <= 8, the lane sweep's at d <= 4; T >= 2048) for a posterior queried at its training inputs on a RegularSpacing with NaNs in y
+    draw kernel at 5 <= d <= 8, the lane sweep's at d <= 4, the tile sweep's k_sweep_tile_draw at 9 <= d <= 16 where the bound model has TGP_OPT_SWEEP = 2
+    set; T >= 2048) for a posterior queried at its training inputs on a RegularSpacing with NaNs in y
     (other prediction inputs raise NotImplementedError there), or for a posterior whose training inputs are a plain array, at any prediction inputs (the
     merged series; k_sweep_group_draw<sde> at 5 <= d <= 8); a prior raises NotImplementedError, and Unsupported is raised where the device
     declines."""
